@@ -88,7 +88,12 @@ def parse_args():
     ap.add_argument("--no-genome-like", action="store_true", help="N=1: skip the genome-like leg")
     ap.add_argument("--detail", type=str, default=os.path.join(ROOT, "bench_detail.json"),
                     help="file that receives the FULL result (every leg, every stage); stdout carries the contract line only")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write the hit rows of the LAST timed step as DIR/<field>.npy (float64; identity float32)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def git_head():
@@ -453,6 +458,14 @@ def weak_scaling(ctx):
         strong = strong_core(ctx, args.saturated_steps, 1)
     if rank != 0:
         return None
+    if args.dump_outputs:
+        last = args.steps - 1
+        if ctx["dist_on"]:                       # the last step of every rank, rank-major (query ids are rank-local)
+            g = gathered.cpu().numpy()
+            parts = [g[w, last, 1: g[w, last, 0, 0] + 1].reshape(-1).view(ROW_DTYPE) for w in range(world)]
+            dump_outputs(args.dump_outputs, np.concatenate(parts), rank=np.repeat(np.arange(world), [len(p) for p in parts]))
+        else:
+            dump_outputs(args.dump_outputs, table[last, 1: counts[last] + 1].cpu().numpy().reshape(-1).view(ROW_DTYPE))
 
     value = world * n_pairs_step * args.steps / elapsed
     # ---- roofline of the dominant kernel, from the stage times taken inside the timed region (device stamps of the
@@ -968,7 +981,7 @@ def oracle_legs(args, anc, names, refs, mapper, rot_queries, timed_rows):
     }
 
 
-def strong_core(ctx, steps, warmup):
+def strong_core(ctx, steps, warmup, dump=None):
     """BASELINE config 3 (families x members genomes of --length, all-vs-all) with the QUERIES dealt to the ranks balanced by
     fragment count, the index replicated, and ONE all-gather of the device-resident hit table per step
     (`sharding.ResidentHitTable`: rows written into a preallocated HBM table, query ids remapped by a device gather, no
@@ -1020,6 +1033,8 @@ def strong_core(ctx, steps, warmup):
     if rank != 0:
         return None
     rows = sharding.ResidentHitTable.rows_of(tables)          # (outside the timed region: the table stays in HBM inside it)
+    if dump:
+        dump_outputs(dump, rows)
     from_files = None
     if world == 1 and not ctx["dist_on"] and not args.no_fasta_leg:
         del batch, exchange, tables
@@ -1163,6 +1178,28 @@ def fasta_to_table_leg(ctx, genomes, chunk=24, ref_chunk=125):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+DUMP_LIMIT = 64 << 20          # bytes of --dump-outputs at most
+
+
+def dump_outputs(path, rows, rank=None, limit=DUMP_LIMIT):
+    """--dump-outputs: the hit rows (ROW_DTYPE) of the last timed step, one `<field>.npy` per field -- the integer fields as
+    float64 (exact), `identity` as the float32 the kernels wrote -- in (rank, query, reference) order, so that two builds can
+    be compared array for array.  A table larger than `limit` bytes is cut to a fixed, seeded sample of its rows."""
+    keys = (rows["ref_genome_id"], rows["query_id"]) + (() if rank is None else (rank,))
+    order = np.lexsort(keys)
+    per_row = 4 * 8 + 4 + (0 if rank is None else 8)
+    if len(order) * per_row + 4096 > limit:                 # (4 KB: the .npy headers)
+        pick = np.random.default_rng(20240).choice(len(order), (limit - 4096) // per_row, replace=False)
+        order = order[np.sort(pick)]
+    os.makedirs(path, exist_ok=True)
+    out = {name: rows[name][order].astype(np.float32 if name == "identity" else np.float64) for name in rows.dtype.names}
+    if rank is not None:
+        out["rank"] = np.asarray(rank)[order].astype(np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    print(f"[bench] --dump-outputs: {len(order)} of {len(rows)} rows of the last timed step -> {path}", file=sys.stderr)
+
+
 def _sha256_rows(rows):
     """Digest of the hit table in (query, reference) order: equal tables at N = 1 and N > 1 have equal digests."""
     import hashlib
@@ -1172,7 +1209,7 @@ def _sha256_rows(rows):
 
 def strong_scaling(ctx):
     args, world = ctx["args"], ctx["world"]
-    r = strong_core(ctx, args.steps, args.warmup)
+    r = strong_core(ctx, args.steps, args.warmup, dump=args.dump_outputs)
     if r is None:
         return None
     config = {k: r[k] for k in ("workload", "pairs_per_step", "rows_per_step", "parallelism", "exchange", "fragments_per_rank", "index_minimizers",

@@ -1,5 +1,5 @@
-import sys, warnings
-sys.path.insert(0, '/root/repo')
+import os, sys, warnings
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', '..'))
 import pyfastani_amd as pf
 from pyfastani_amd import synthetic as syn
 from oracle.oracle import OracleSketch

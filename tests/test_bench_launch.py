@@ -165,3 +165,47 @@ def test_emit_prints_the_contract_line_last_and_writes_the_detail(tmp_path, caps
         detail = json.load(f)
     assert detail["saturated"]["config3"]["fasta_to_table"]["rows"] > 0 and len(detail["config5_cells"]["cells"]) == 9
     assert "[bench detail]" in err
+
+
+def test_steps_must_be_positive_and_dump_outputs_is_an_option():
+    import pytest
+    bench = _load_bench()
+    old = sys.argv
+    try:
+        sys.argv = ["bench.py", "--steps", "7", "--dump-outputs", "out"]
+        args = bench.parse_args()
+        assert args.steps == 7 and args.dump_outputs == "out"
+        sys.argv = ["bench.py", "--steps", "0"]
+        with pytest.raises(SystemExit):
+            bench.parse_args()
+    finally:
+        sys.argv = old
+
+
+def test_dump_outputs_writes_every_field_sorted_and_bounded(tmp_path):
+    """`--dump-outputs DIR`: one .npy per row field (integers as float64, identity as float32), rows in (query, reference)
+    order whatever order the device wrote them in; over the size limit, the same seeded sample every time."""
+    import numpy as np
+    from pyfastani_amd._batch import ROW_DTYPE
+    bench = _load_bench()
+    g = np.random.default_rng(3)
+    rows = np.zeros(500, ROW_DTYPE)
+    rows["query_id"] = g.integers(0, 5, 500)
+    rows["ref_genome_id"] = g.permutation(500)
+    rows["count_seq"] = g.integers(1, 2000, 500)
+    rows["total_query_fragments"] = 1666
+    rows["identity"] = g.uniform(75, 100, 500).astype(np.float32)
+    bench.dump_outputs(str(tmp_path / "all"), rows)
+    got = {n: np.load(tmp_path / "all" / f"{n}.npy") for n in ROW_DTYPE.names}
+    assert got["identity"].dtype == np.float32 and all(got[n].dtype == np.float64 for n in ROW_DTYPE.names if n != "identity")
+    order = np.lexsort((rows["ref_genome_id"], rows["query_id"]))
+    for n in ROW_DTYPE.names:
+        assert np.array_equal(got[n], rows[n][order])
+    limit = 4096 + 100 * 36
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), rows[::-1], limit=limit)
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ROW_DTYPE.names}
+    b = {n: np.load(tmp_path / "b" / f"{n}.npy") for n in ROW_DTYPE.names}
+    assert all(len(a[n]) == 100 and np.array_equal(a[n], b[n]) for n in ROW_DTYPE.names)
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= limit
+    assert np.all(np.diff(a["query_id"] * 1000 + a["ref_genome_id"]) > 0)

@@ -103,6 +103,40 @@ def test_bench_weak_two_ranks_sharing_one_gpu():
     assert "strong" not in line
 
 
+def test_bench_dump_outputs_is_the_last_timed_step(tmp_path):
+    """`--dump-outputs DIR` at N = 1: the hit rows of the LAST timed step, one .npy per field in (query, reference) order.  The
+    bench uploads its four rotated queries as one batch and step 2 (the last of three) maps genome 2 of it: the dump must be
+    the rows the mapper returns for that genome of the same batch outside the bench.  A second run with the same arguments
+    writes the same arrays, and `steps` / `ms_per_step` are those of the three timed steps."""
+    import numpy as np
+    import pyfastani_amd as pf
+    from pyfastani_amd import workloads
+    from pyfastani_amd._batch import ROW_DTYPE
+    args = ["--refs", "6", "--length", "400000", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-saturated",
+            "--no-boundary", "--clients", "0", "--detail", str(tmp_path / "detail.json")]
+    dumps = []
+    for run in range(2):
+        out = tmp_path / f"run{run}"
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + ["--dump-outputs", str(out)],
+                             capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert res.returncode == 0, res.stdout + res.stderr
+        short, line = _line_and_detail(res.stdout)
+        assert short["steps"] == 3 and short["ms_per_step"] > 0
+        dumps.append({n: np.load(out / f"{n}.npy") for n in ROW_DTYPE.names})
+    anc, names, refs = workloads.config2_references(6, 400_000)
+    sk = pf.Sketch()
+    sk.add_drafts(names, refs)
+    mapper = sk.index()
+    rotated = mapper.upload_genomes([q for j in range(4) for q in workloads.config2_query(anc, j, 1)])
+    want = rotated.query_rows(2, 1)
+    want = want[np.lexsort((want["ref_genome_id"], want["query_id"]))]
+    assert len(want) >= 4
+    for n in ROW_DTYPE.names:
+        assert dumps[0][n].dtype == (np.float32 if n == "identity" else np.float64)
+        assert np.array_equal(dumps[0][n], want[n].astype(dumps[0][n].dtype)), n
+        assert np.array_equal(dumps[1][n], dumps[0][n]), n
+
+
 def test_bench_launches_its_own_ranks_and_carries_the_strong_leg():
     """`python bench.py --gpus 2` with NO launcher around it (the command a scaling run issues): the process starts its two
     ranks as a child `torch.distributed.run` before it imports torch, relays rank 0's line and exits with the child's status.
