@@ -244,8 +244,7 @@ int fa_debug_sketch_sequence(const fa_params *params, const void *data, int64_t 
 
 /* development probe: workgroups of 128 threads with `lds_bytes` of dynamic LDS the chip holds at once */
 int fa_debug_probe_occupancy(int lds_bytes, int *peak_alive);
-/* raw bytes of the last call's event arena (two-kernel L2 form: the slide events; FA_FUSED_DEBUG=8: per-workgroup time
- * stamps of k_l2_fused) -- development aid */
+/* raw bytes of the last call's event arena (the slide events) -- development aid */
 int fa_mapper_debug_items(fa_mapper *m, void *out, int64_t bytes);
 /* the query-independent slide geometry the index build derives per reference record: rec_prev,
  * rec_fwd, rec_bwd (4 bytes each) and the flag byte, `cap` records at most; *n = records of the index.  Checked against the

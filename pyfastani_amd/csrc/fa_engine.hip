@@ -127,9 +127,6 @@ struct StageTrace {
 };
 
 // `clear` (a query pass): ranges zeroed by extra workgroups of the first launch, beside the hashing
-static uint64_t env_u64(const char *name, uint64_t dflt);
-static uint64_t exp_u64(const char *name, uint64_t dflt);     // the same in builds with -DFA_EXPERIMENTS, else `dflt`
-
 // `fuse` (a query pass, F fragments): K1 and the per-fragment sketch in one launch (k_query_fused) where the pass qualifies
 // -- returns true then, and the caller skips k_query_sketch
 static bool launch_sketch_tiles(const fa_params &P, const StoreView &store, const Tile *d_tiles, int ntiles, uint32_t *stage_hash,
@@ -161,10 +158,9 @@ static bool launch_sketch_tiles(const fa_params &P, const StoreView &store, cons
   size_t lds = sketch_lds_bytes(P.kmer_size, P.window_size);
   size_t image = lds - ((size_t)a.npos_cap * 16 + ((size_t)a.npos_cap / 64 + 1) * 8 + (TILE / 64) * 8 + (TILE / 64 + 1) * 4 + 16 + 4 * 256 * 8);
   a.code_words = (int32_t)(image / 4);
-  static const size_t lds_pad = (size_t)exp_u64("FA_K1_LDS_PAD", 0);     // experiment: unused LDS, i.e. fewer workgroups per CU
   auto launch = [&](auto kernel) {
-    if (lds + lds_pad > 64 * 1024) FA_HIP(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds + lds_pad)));
-    hipLaunchKernelGGL(kernel, dim3(ntiles + extra), dim3(SK_THREADS), lds + lds_pad, st, a);
+    if (lds > 64 * 1024) FA_HIP(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kernel, dim3(ntiles + extra), dim3(SK_THREADS), lds, st, a);
     extra = 0; a.clear.count = 0; a.clear.stamp = nullptr;          // (only the first launch zeroes)
   };
   // plain-ACGT tiles from the 2-bit image; protein tiles and tiles with other bytes through the byte image
@@ -184,7 +180,7 @@ static bool launch_sketch_tiles(const fa_params &P, const StoreView &store, cons
     static const bool fuse_on = !(getenv("FA_QUERY_FUSED") && atoi(getenv("FA_QUERY_FUSED")) == 0);
     const bool may_fuse = fuse && fuse_on && (int64_t)5 * P.fragment_length / (P.window_size + 1) <= QF_CAP;
     auto launch_fast = [&](auto kernel) {
-      hipLaunchKernelGGL(kernel, dim3(ntiles + extra), dim3(SK_THREADS), flds + lds_pad, st, a);
+      hipLaunchKernelGGL(kernel, dim3(ntiles + extra), dim3(SK_THREADS), flds, st, a);
       extra = 0; a.clear.count = 0; a.clear.stamp = nullptr;
     };
     bool served = false;
@@ -196,7 +192,7 @@ static bool launch_sketch_tiles(const fa_params &P, const StoreView &store, cons
         qa.exc_tiles = store.n_exc > 0 ? 1 : 0;                                                                                   \
         if (store.n_exc > 0) launch(k_sketch_tiles<0, true>);                                                                     \
         const size_t qlds = flds + (size_t)QF_CAP * 4;                                                                            \
-        hipLaunchKernelGGL((k_query_fused<K, W>), dim3((unsigned)F + extra), dim3(SK_THREADS), qlds + lds_pad, st, a, qa, (int)F);  \
+        hipLaunchKernelGGL((k_query_fused<K, W>), dim3((unsigned)F + extra), dim3(SK_THREADS), qlds, st, a, qa, (int)F);            \
         FA_HIP(hipGetLastError());                                                                                                \
         return true;                                                                                                              \
       }                                                                                                                           \
@@ -496,7 +492,7 @@ struct Workspace {
   const int32_t *lut_min_hits = nullptr, *lut_pass = nullptr;
   const float *lut_ident = nullptr;
   // last-pass bookkeeping for the debug getters
-  int64_t last_F = 0, last_f0 = 0;
+  int64_t last_F = 0;
   uint32_t last_loci = 0;             // loci of the last accepted part (all regions)
   uint32_t loci_n = 1, loci_shift = 0;                    // regions of the locus numbering of the part in flight / last accepted
   bool l1_pf = false, l1_small_class = false;             // the part in flight ran k_l1 with the pre-filter / with the 256-thread class next to others
@@ -505,19 +501,13 @@ struct Workspace {
   const fa_genomes *last_genomes = nullptr;
   float last_ms[24] = {0};
   hipEvent_t ev[6] = {nullptr};
-  // the parts of a pass are pipelined over this workspace and two more *lanes* (run_query_pass): sub-workspaces with their
-  // own stream and per-part buffers; `serial` tells the debug getters which lanes took part in the last call
-  std::unique_ptr<Workspace> sub[2];
-  hipEvent_t ev_bins = nullptr;
-  uint64_t serial = 0;
-  int64_t pass_f0 = 0, pass_F = 0;    // first fragment and number of fragments of the last pass
+  int64_t pass_F = 0;                 // fragments of the last pass
   // the one-query-at-a-time call (fa_mapper_query) recycles its batch object -- no device allocation per call -- and
   // builds the upload image in pinned memory; its rows come back through a pinned block too
   std::unique_ptr<fa_genomes> query_batch;
   PinnedBuf pin_image, pin_rows;
   ~Workspace() {
     for (auto &e : ev) if (e) (void)hipEventDestroy(e);
-    if (ev_bins) (void)hipEventDestroy(ev_bins);
     if (stream) (void)hipStreamDestroy(stream);
     if (h_status) (void)hipHostFree(h_status);
   }
@@ -540,11 +530,10 @@ struct fa_mapper {
   DevBuf<uint16_t> rec_prev16;
   DevBuf<uint32_t> rec_gpos, wrap_rec;   // padded global coordinate of every record (low word) + its 2^32 boundaries, for k_l1
   int32_t n_wraps = 0, gpos_bits = 32;
-#ifdef FA_EXPERIMENTS
-  DevBuf<uint32_t> ev_bits;       // merged admit / drop order of the slide (k_event_bits), 2 bits per record
-  DevBuf<uint2> rec_hf;           // hash + flags + distance to the previous record of the hash (k_pack_hf), for k_l2_fused
-#endif
   bool packed_geo = false;
+  // k_l2_events reads the packed record layout (rec_hg, rec_prev16) when the index has one; FA_NO_PACKED_GEO=1 takes the
+  // plain arrays on any index (the tests reach the unpacked form on small indices that way)
+  bool events_packed() const { return packed_geo && !getenv("FA_NO_PACKED_GEO"); }
   int64_t N = 0, U = 0;
   int32_t C = 0, G = 0, table_bits = 4, freq_threshold = INT_MAX, total_bins = 0;
   std::vector<uint64_t> lengths;
@@ -592,9 +581,6 @@ struct fa_mapper {
     IndexView v;
     v.rec_hash = rec_hash.p; v.rec_seq = rec_seq.p; v.rec_wpos = rec_wpos.p; v.rec_prev = rec_prev.p; v.rec_fwd = rec_fwd.p; v.rec_bwd = rec_bwd.p; v.rec_flags = rec_flags.p;
     v.rec_hg = packed_geo ? rec_hg.p : nullptr; v.rec_prev16 = packed_geo ? rec_prev16.p : nullptr; v.rec_gpos = rec_gpos.p; v.wrap_rec = wrap_rec.p; v.n_wraps = n_wraps; v.gpos_bits = gpos_bits;
-#ifdef FA_EXPERIMENTS
-    v.ev_bits = ev_bits.p; v.rec_hf = rec_hf.p;
-#endif
     v.uniq_hash = uniq_hash.p; v.uniq_off = uniq_off.p; v.pos_ridx = pos_ridx.p; v.table = table.p;
     v.contig_rec = contig_rec.p; v.contig_genome = contig_genome.p; v.contig_bin = contig_bin.p; v.genome_bin = genome_bin.p;
     v.N = N; v.U = U; v.C = C; v.G = G; v.table_bits = table_bits; v.freq_threshold = freq_threshold; v.total_bins = total_bins;
@@ -612,19 +598,6 @@ __global__ void k_contig_bins(const int32_t *contig_rec, const int32_t *rec_wpos
   }
   nbins[c] = n;
 }
-
-// Knobs that only ever served A/B measurements (LDS padding, forced workgroup shapes, the fused L2 kernel) exist in builds
-// with -DFA_EXPERIMENTS only (scripts/experiments/README.md); the product library ignores them.
-#ifdef FA_EXPERIMENTS
-static uint64_t exp_u64(const char *name, uint64_t dflt) { return env_u64(name, dflt); }
-// FA_L2_FUSED=1: build the extra index arrays of the fused L2 kernel and use it (see run_query_pass)
-static bool fused_l2_enabled() {
-  static const bool on = getenv("FA_L2_FUSED") && atoi(getenv("FA_L2_FUSED")) != 0;
-  return on;
-}
-#else
-static uint64_t exp_u64(const char *, uint64_t dflt) { return dflt; }
-#endif
 
 // Sketch_t::index() + computeFreqHist() on the device
 static void build_index(fa_mapper &m) {
@@ -811,16 +784,6 @@ static void build_index(fa_mapper &m) {
       FA_REQUIRE(m.n_wraps <= GPOS_MAX_WRAPS, FA_ERR_UNSUPPORTED, m.gpos_bits == 32 ? "the index spans more than 2^40 bases (shard the references)"
                                                                                        : "FA_GPOS_BITS: more than 256 boundaries in this index");
     }
-#ifdef FA_EXPERIMENTS
-    if (fused_l2_enabled()) {
-      const size_t words = ((size_t)2 * (size_t)N + 31) / 32 + 4;
-      m.ev_bits.ensure(words);
-      FA_HIP(hipMemsetAsync(m.ev_bits.p, 0, words * sizeof(uint32_t), st));
-      hipLaunchKernelGGL(k_event_bits, dim3(ceil_div(N, 256)), dim3(256), 0, st, m.rec_seq.p, m.rec_bwd.p, m.contig_rec.p, N, m.ev_bits.p);
-      m.rec_hf.ensure((size_t)N + 4);
-      hipLaunchKernelGGL(k_pack_hf, dim3(ceil_div(N, 256)), dim3(256), 0, st, m.rec_hash.p, m.rec_flags.p, m.rec_prev.p, N, m.rec_hf.p);
-    }
-#endif
     m.packed_geo = m.cmw + 1 < (1 << GEO_BITS);
     if (m.packed_geo) {
       m.rec_hg.ensure((size_t)N + 4); m.rec_prev16.ensure((size_t)N + 4);
@@ -974,11 +937,11 @@ static uint32_t build_frag_order(const fa_genomes &g, int32_t g0, int64_t f0, in
 // atomicMax, so it simply accumulates) and the rows are formed after the last part.
 //
 // The pass as an object: what the stages share are its members, and the seams are its methods -- speculation (fetch_spec /
-// publish_spec / scan_occupancy), the plan of the pass (plan: buffers, lanes, the bin table), the launches of one part
-// (launch_part, launch_rows) and the verdict on a finished part (judge_part); run() queues the parts.
+// publish_spec / scan_occupancy), the plan of the pass (plan: buffers), the launches of one part (launch_part,
+// launch_rows) and the verdict on a finished part (judge_part); run() runs the parts one after another.
 struct QueryPass {
   struct Range { int64_t f0, f1; bool unfused; };     // unfused: the repeat of a range that overflowed k_query_fused
-  struct Run { int lane; int64_t f0, f1; fa_mapper::Spec sp; bool with_rows; bool fused = false, forced_unfused = false, ordered = false; };
+  struct Run { int64_t f0, f1; fa_mapper::Spec sp; bool with_rows; bool fused = false, forced_unfused = false, ordered = false; };
   // ---- what the caller gave ----
   fa_mapper &m;
   Workspace &w;
@@ -995,27 +958,20 @@ struct QueryPass {
   const int64_t npairs;
   uint64_t items_max = 0;
   size_t qs_lds = 0;
-  int64_t F_total = 0, auto_part = 0;
-  Workspace *lanes[3];
-  int n_lanes = 1;
+  int64_t F_total = 0;
   // ---- state of the run ----
   // the speculated bounds are shared by all workspaces: every attempt works on a copy taken under the lock and
   // publishes what it learnt (bounds only ever grow, except the LDS seed slots, which follow the latest pass)
   fa_mapper::Spec sp;
   bool bins_cleared = false;
   std::deque<Range> todo;
-  std::deque<Run> flight;
-  bool busy[3] = {false, false, false}, ran[3] = {false, false, false};
   bool rows_valid = false;
-  int rows_lane = -1;
   unsigned long long t_begin = ~0ULL, t_end = 0;
   int attempts = 0;
 
   QueryPass(fa_mapper &m_, Workspace &w_, const fa_genomes &g_, int32_t g0_, int32_t g1_, fa_cgi_row *rows_dev_, int64_t cap_, int64_t row_base_, fa_cgi_row *host_rows_)
       : m(m_), w(w_), g(g_), g0(g0_), g1(g1_), rows_dev(rows_dev_), cap(cap_), row_base(row_base_), host_rows(host_rows_), st(w_.stream),
-        range_f0(g_.genome_frag_lo[g0_]), range_f1(g_.genome_frag_lo[g1_]), NQ(g1_ - g0_), qcap(m_.qcap), ix(m_.view()), npairs((int64_t)(g1_ - g0_) * m_.G) {
-    lanes[0] = &w; lanes[1] = lanes[2] = nullptr;
-  }
+        range_f0(g_.genome_frag_lo[g0_]), range_f1(g_.genome_frag_lo[g1_]), NQ(g1_ - g0_), qcap(m_.qcap), ix(m_.view()), npairs((int64_t)(g1_ - g0_) * m_.G) {}
 
   // ================================================ speculation ================================================
   void fetch_spec() {
@@ -1064,7 +1020,8 @@ struct QueryPass {
     if (lds_ev > 64 * 1024) return 0;
     int n_scan = 0, n_ev = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n_scan, (const void *)k_l2_scan<uint16_t, uint8_t, 64>, L2_THREADS, lds_scan) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&n_ev, (const void *)k_l2_events<uint16_t, true, 1>, EV_THREADS, lds_ev) != hipSuccess) {
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&n_ev, m.events_packed() ? (const void *)k_l2_events<uint16_t, true> : (const void *)k_l2_events<uint16_t, false>,
+                                                     EV_THREADS, lds_ev) != hipSuccess) {
       (void)hipGetLastError();
       return 0;
     }
@@ -1081,55 +1038,21 @@ struct QueryPass {
     qs_lds = (size_t)next_pow2((uint32_t)std::max(qcap, 2)) * 4;
     FA_REQUIRE(qs_lds <= 150 * 1024, FA_ERR_UNSUPPORTED, "fragment_length too large for the LDS fragment sort");
 
-    // ---- the parts of the pass; optionally (FA_QUERY_LANES = 2 or 3) pipelined over *lanes*: sub-workspaces with their own
-    // stream and buffers, so that part n + 1 is sketched and looked up while part n slides.  The parts share the CGI bin
-    // table (atomicMax); the rows are formed on the lane of the last part, behind the bins of all lanes.  Every part keeps
-    // its own speculation verdict: a void part is queued again (and the rows, if they were formed already, are formed
-    // again after it).  Measured: no gain (bench step 0.623 / 0.622 / 0.641 ms with 1 / 2 / 3 lanes, 16 queries per
-    // launch 237 k / 240 k pairs/s, config 3 2.59 M / 2.55 M) -- every kernel of the path runs its workgroups in one or a
-    // few resident rounds, so a third of the fragments takes nearly as long as all of them, and what the lanes add in
-    // overlap they lose in occupancy.  Hence one lane by default; profiles/EXPERIMENTS.md.
-    static const int lanes_wanted = (int)std::min<uint64_t>(3, std::max<uint64_t>(1, env_u64("FA_QUERY_LANES", 1)));
-    static const int64_t lane_min_frags = (int64_t)env_u64("FA_LANE_MIN_FRAGMENTS", 256);
+    // ---- the parts of the pass run one after another on the workspace's stream.  They share the CGI bin table (atomicMax);
+    // the rows are formed behind the last part.  Every part keeps its own speculation verdict: a void part is queued again
+    // (and the rows, if they were formed already, are formed again after it).
     F_total = range_f1 - range_f0;
-    auto_part = F_total;
-    if (lanes_wanted > 1 && F_total >= 2 * lane_min_frags) {
-      const int64_t parts = std::min<int64_t>(lanes_wanted, F_total / lane_min_frags);
-      auto_part = (F_total + parts - 1) / parts;
-    }
-    if (lanes_wanted > 1 && std::min<int64_t>(auto_part, sp.part_frags) < F_total) {
-      for (int i = 0; i + 1 < lanes_wanted; i++) {
-        if (!w.sub[i]) w.sub[i].reset(new Workspace());
-        Workspace &x = *w.sub[i];
-        if (!x.stream) FA_HIP(hipStreamCreate(&x.stream));
-        lanes[n_lanes++] = &x;
-      }
-    }
-    w.serial++;
-    w.pass_f0 = range_f0; w.pass_F = range_f1 - range_f0;
-    for (int i = 0; i < n_lanes; i++) for (int e = 0; e < 6; e++) if (!lanes[i]->ev[e]) FA_HIP(hipEventCreate(&lanes[i]->ev[e]));
-    if (!w.ev_bins) FA_HIP(hipEventCreate(&w.ev_bins));
-    // the CGI bin table is cleared once per pass: with one lane by the k_clear of the first part launched (a void first
-    // part cleared it all the same), with several lanes up front on the first lane's stream, which the others wait for
+    w.pass_F = F_total;
+    // the CGI bin table is cleared once per pass, by the k_clear of the first part launched (a void first part cleared it
+    // all the same)
     bins_cleared = npairs == 0;
-    if (n_lanes > 1) {
-      if (npairs > 0) FA_HIP(hipMemsetAsync(w.bins.p, 0, (size_t)NQ * std::max(m.total_bins, 1) * sizeof(unsigned long long), st));
-      bins_cleared = true;
-      FA_HIP(hipEventRecord(w.ev_bins, st));
-    }
-
   }
 
   // ================================================ launches ===================================================
-  // the lane that forms the rows waits for the bins of the parts launched on the other lanes
-  void join_lanes(int me) {
-    for (int i = 0; i < n_lanes; i++) if (i != me && ran[i]) FA_HIP(hipStreamWaitEvent(lanes[me]->stream, lanes[i]->ev[4], 0));
-  }
   // forms the rows; returns true if the kernel also hands the pass over to the host (small passes: its last workgroup does)
-  bool launch_rows(Workspace &ln, const PublishArgs &pub) {
-    hipStream_t st = ln.stream;
-    uint32_t *const d_counters = ln.status.p->counters;
-    int32_t *const d_total_rows = &ln.status.p->total_rows;
+  bool launch_rows(const PublishArgs &pub) {
+    uint32_t *const d_counters = w.status.p->counters;
+    int32_t *const d_total_rows = &w.status.p->total_rows;
     RowsArgs ra;
     ra.bins = w.bins.p; ra.genome_bin = m.genome_bin.p; ra.total_bins = m.total_bins; ra.G = m.G; ra.NQ = NQ;
     ra.row_count = w.row_count.p; ra.row_ident = w.row_ident.p;
@@ -1148,7 +1071,7 @@ struct QueryPass {
     } else {
       hipLaunchKernelGGL(k_flag_nonzero, dim3(ceil_div(npairs, 256)), dim3(256), 0, st, w.row_count.p, npairs, w.row_flag.p);
       FA_HIP(hipMemsetAsync(w.row_flag.p + npairs, 0, sizeof(int32_t), st));
-      exclusive_sum_i32(ln.sk.cub_temp, w.row_flag.p, w.row_off.p, (int)npairs + 1, st);
+      exclusive_sum_i32(w.sk.cub_temp, w.row_flag.p, w.row_off.p, (int)npairs + 1, st);
       FA_HIP(hipMemcpyAsync(d_total_rows, w.row_off.p + npairs, sizeof(int32_t), hipMemcpyDeviceToDevice, st));
       hipLaunchKernelGGL(k_emit_rows, dim3(ceil_div(npairs, 256)), dim3(256), 0, st, w.row_count.p, w.row_ident.p, w.row_off.p, m.G,
                          npairs, g.d_total_frag + g0, g0, rows_dev + row_base, cap - row_base);
@@ -1157,8 +1080,6 @@ struct QueryPass {
   }
   // what the stage launches of one part share (sized by size_part)
   struct Part {
-    Workspace &ln;
-    hipStream_t st;
     const fa_mapper::Spec &sp;
     const int64_t f0, f1, F;
     const int t0, ntiles;
@@ -1175,69 +1096,57 @@ struct QueryPass {
     const int32_t *frag_order = nullptr;      // workgroup order of the part (prepare_order), null = identity
     uint32_t order_len = 0;
     Part(QueryPass &q, Run &r)
-        : ln(*q.lanes[r.lane]), st(ln.stream), sp(r.sp), f0(r.f0), f1(r.f1), F(r.f1 - r.f0), t0(q.g.frag_tile_lo[r.f0]),
+        : sp(r.sp), f0(r.f0), f1(r.f1), F(r.f1 - r.f0), t0(q.g.frag_tile_lo[r.f0]),
           ntiles(q.g.frag_tile_lo[r.f1] - q.g.frag_tile_lo[r.f0]), smax(r.sp.smax),
           // (every region of the locus numbering holds at least one locus: a capacity below the number of regions -- only the
           //  FA_LOCI_CAP_MIN hook of the tests gets there -- would number loci beyond the arrays sized and cleared for l_cap)
           l_cap(std::max<int64_t>(r.sp.l_cap, (int64_t)std::min<uint32_t>(LOCI_REGIONS, ev_regions_for(r.f1 - r.f0)))) {}
   };
 
-  // one part: its buffers, then the stages in order, then the hand-over -- all asynchronous on the lane's stream
+  // one part: its buffers, then the stages in order, then the hand-over -- all asynchronous on the workspace's stream
   void launch_part(Run &r) {
     Part p(*this, r);
-    Workspace &ln = p.ln;
-    hipStream_t st = p.st;
     const fa_mapper::Spec &sp = p.sp;
     const int64_t f0 = p.f0, F = p.F;
-    ln.serial = w.serial;
-    if (&ln != &w) FA_HIP(hipStreamWaitEvent(st, w.ev_bins, 0));     // (the bin table is cleared on the first lane's stream)
-    ln.last_F = 0; ln.last_f0 = f0; ln.last_loci = 0;                 // (filled in when the part is accepted)
+    w.last_F = 0; w.last_loci = 0;                                  // (filled in when the part is accepted)
     const int ntiles = p.ntiles;
     // buffers whose size depends only on the geometry of the part
-    ln.sk.stage_hash.ensure((size_t)std::max(ntiles, 1) * TILE);
-    ln.sk.stage_wpos.ensure((size_t)std::max(ntiles, 1) * TILE);
-    ln.sk.tile_count.ensure((size_t)ntiles + 1);
-    ln.q_hash.ensure((size_t)F * qcap); ln.q_off.ensure((size_t)F * qcap); ln.q_cnt.ensure((size_t)F * qcap);
-    ln.q_size.ensure((size_t)F); ln.n_seeds.ensure((size_t)F); ln.ovf_off.ensure((size_t)F);
-    ln.f_loci_lo.ensure((size_t)F); ln.f_loci_n.ensure((size_t)F);
-    ln.status.ensure(1);
-    if (!ln.h_status) {
-      FA_HIP(hipHostMalloc((void **)&ln.h_status, sizeof(PassStatus), hipHostMallocMapped | hipHostMallocCoherent));
-      memset(ln.h_status, 0, sizeof(PassStatus));
+    w.sk.stage_hash.ensure((size_t)std::max(ntiles, 1) * TILE);
+    w.sk.stage_wpos.ensure((size_t)std::max(ntiles, 1) * TILE);
+    w.sk.tile_count.ensure((size_t)ntiles + 1);
+    w.q_hash.ensure((size_t)F * qcap); w.q_off.ensure((size_t)F * qcap); w.q_cnt.ensure((size_t)F * qcap);
+    w.q_size.ensure((size_t)F); w.n_seeds.ensure((size_t)F); w.ovf_off.ensure((size_t)F);
+    w.f_loci_lo.ensure((size_t)F); w.f_loci_n.ensure((size_t)F);
+    w.status.ensure(1);
+    if (!w.h_status) {
+      FA_HIP(hipHostMalloc((void **)&w.h_status, sizeof(PassStatus), hipHostMallocMapped | hipHostMallocCoherent));
+      memset(w.h_status, 0, sizeof(PassStatus));
     }
     // ---- buffers and tables sized by the speculated bounds ----
     const int smax = p.smax;
     const int64_t l_cap = p.l_cap;
     // LDS also holds smax list offsets; the in-place merge keeps at most 32 seeds per thread in registers
-    static const int l1_forced = (int)exp_u64("FA_L1_THREADS", 0);
     // k_l1 runs once per size class of fragments (L1Args::n_lo / n_hi): up to 4 096 hits the 256-thread form with 16 hits per
     // thread (4-wave workgroups, eight per CU: a 5 Mb query is one round of workgroups), up to 7 936 the 512-thread form with 16,
     // beyond the 512-thread form with 32 (above 4 096 hits 512 threads measured best: fewer hits per thread shorten every thread's
     // chain of dependent LDS round trips; 1 024 threads pay more for barriers than they gain).  A class the speculated bound
     // (sp.seed_slots: the largest fragment seen, plus a quarter) does not reach is not launched; the last class takes everything
-    // above its lower bound, overflow into HBM scratch included.  FA_L1_THREADS = 256 / 512 / 1024 forces ONE launch of that form.
+    // above its lower bound, overflow into HBM scratch included.
     {
       const uint32_t cap_max = lds_seed_cap_max(smax), need = std::min(sp.seed_slots, cap_max);
       p.n_l1 = 0;
-      if (l1_forced) {
-        const int nt = l1_forced >= 1024 ? 1024 : (l1_forced >= 512 ? 512 : 256);
-        uint32_t slots = std::min(need, (uint32_t)(L1_INPLACE_MAX * nt));
-        if (nt == 512 && slots <= 16u * 512u) slots = std::min<uint32_t>(16u * 512u - 256u, cap_max);
-        p.l1[p.n_l1++] = Part::L1Class{nt, slots, 0u, 0xFFFFFFFFu};
-      } else {
-        const uint32_t s_slots = std::min<uint32_t>(need, L1_SMALL_HITS);
-        p.l1[p.n_l1++] = Part::L1Class{256, s_slots, 0u, need <= L1_SMALL_HITS ? 0xFFFFFFFFu : s_slots};
-        if (need > L1_SMALL_HITS) {
-          // (a 512-thread workgroup is eight waves: four of them fill a CU whatever their LDS up to 39 KB, so the block table of
-          // l1_block_sort -- a third as many entries as seed slots -- gets all the slots the 16-per-thread form can address)
-          // (7 936, not 8 192: the kilobyte goes to the key buffer behind the slots, which then holds the (key, place) pairs of 1 024
-          // blocks -- the 4 x 10^8-record index of config 3 adds ~500 chance hits, each a block of its own, to the ~250 blocks of a
-          // fragment's relatives -- and four workgroups still fill a CU)
-          const uint32_t m_slots = std::min<uint32_t>(L1_MID_HITS, cap_max);
-          p.l1[p.n_l1++] = Part::L1Class{512, m_slots, s_slots + 1u, need <= m_slots ? 0xFFFFFFFFu : m_slots};
-          if (need > m_slots)
-            p.l1[p.n_l1++] = Part::L1Class{512, std::min<uint32_t>(need, (uint32_t)(L1_INPLACE_MAX * 512)), m_slots + 1u, 0xFFFFFFFFu};
-        }
+      const uint32_t s_slots = std::min<uint32_t>(need, L1_SMALL_HITS);
+      p.l1[p.n_l1++] = Part::L1Class{256, s_slots, 0u, need <= L1_SMALL_HITS ? 0xFFFFFFFFu : s_slots};
+      if (need > L1_SMALL_HITS) {
+        // (a 512-thread workgroup is eight waves: four of them fill a CU whatever their LDS up to 39 KB, so the block table of
+        // l1_block_sort -- a third as many entries as seed slots -- gets all the slots the 16-per-thread form can address)
+        // (7 936, not 8 192: the kilobyte goes to the key buffer behind the slots, which then holds the (key, place) pairs of 1 024
+        // blocks -- the 4 x 10^8-record index of config 3 adds ~500 chance hits, each a block of its own, to the ~250 blocks of a
+        // fragment's relatives -- and four workgroups still fill a CU)
+        const uint32_t m_slots = std::min<uint32_t>(L1_MID_HITS, cap_max);
+        p.l1[p.n_l1++] = Part::L1Class{512, m_slots, s_slots + 1u, need <= m_slots ? 0xFFFFFFFFu : m_slots};
+        if (need > m_slots)
+          p.l1[p.n_l1++] = Part::L1Class{512, std::min<uint32_t>(need, (uint32_t)(L1_INPLACE_MAX * 512)), m_slots + 1u, 0xFFFFFFFFu};
       }
       // The pre-filter of the block sort (l1_block_sort: hits that cannot belong to a candidate are dropped before the sort, one more
       // sweep over the position lists) pays where chance hits push the blocks of a fragment beyond what the register sort holds, and
@@ -1281,12 +1190,12 @@ struct QueryPass {
       if (dbg_l1) fprintf(stderr, "k_l1 classes: need=%u tiny=%.3f small=%.3f mid=%.3f prefilter=%d -> %d launch(es)\n", need, sp.l1_tiny_share, sp.l1_small_share, sp.l1_mid_share, (int)p.l1_prefilter, p.n_l1);
       p.seed_slots = p.l1[p.n_l1 - 1].slots;                       // "fits LDS" for seed_totals and k_l1_big: the last class's slots
     }
-    ln.l_frag.ensure((size_t)l_cap); ln.l_seq.ensure((size_t)l_cap); ln.l_start.ensure((size_t)l_cap); ln.l_end.ensure((size_t)l_cap + 4);
-    ln.l_rfirst.ensure((size_t)l_cap); ln.l_rlast.ensure((size_t)l_cap + 4); ln.l_rpart.ensure((size_t)l_cap);
-    ln.l_group.ensure((size_t)l_cap); ln.l_shared.ensure((size_t)l_cap); ln.l_pos.ensure((size_t)l_cap);
-    ln.group_best.ensure((size_t)l_cap + 2);
-    ln.l_beg.ensure((size_t)l_cap); ln.l_end0.ensure((size_t)l_cap); ln.l_last.ensure((size_t)l_cap); ln.l_ndrop.ensure((size_t)l_cap);
-    ln.l_nev.ensure((size_t)l_cap); ln.l_ioff.ensure((size_t)l_cap); ln.l_redo.ensure((size_t)l_cap + 4);
+    w.l_frag.ensure((size_t)l_cap); w.l_seq.ensure((size_t)l_cap); w.l_start.ensure((size_t)l_cap); w.l_end.ensure((size_t)l_cap + 4);
+    w.l_rfirst.ensure((size_t)l_cap); w.l_rlast.ensure((size_t)l_cap + 4); w.l_rpart.ensure((size_t)l_cap);
+    w.l_group.ensure((size_t)l_cap); w.l_shared.ensure((size_t)l_cap); w.l_pos.ensure((size_t)l_cap);
+    w.group_best.ensure((size_t)l_cap + 2);
+    w.l_beg.ensure((size_t)l_cap); w.l_end0.ensure((size_t)l_cap); w.l_last.ensure((size_t)l_cap); w.l_ndrop.ensure((size_t)l_cap);
+    w.l_nev.ensure((size_t)l_cap); w.l_ioff.ensure((size_t)l_cap); w.l_redo.ensure((size_t)l_cap + 4);
     // A wave of k_l2_scan lasts as long as the longest of its 64 slides, and in k_l1's numbering it holds the loci of one fragment --
     // streams of every length the divergences of the index produce (lane utilisation 85 %).  When the last accepted part had loci
     // for a wave per SIMD and more, the scan takes the loci of every region sorted by stream length (profiles/r06_scan_order.txt:
@@ -1294,75 +1203,71 @@ struct QueryPass {
     // launch, -1 % on one 5 Mb query).  FA_L2_SCAN_ORDER = 0 / 1: never / always.
     static const int scan_order_env = getenv("FA_L2_SCAN_ORDER") ? atoi(getenv("FA_L2_SCAN_ORDER")) : -1;
     p.scan_sorted = scan_order_env < 0 ? sp.l2_loci_last >= 1024 * 64 : scan_order_env != 0;
-    ln.scan_hist.ensure((size_t)2 * LOCI_REGIONS * SCAN_CLASSES);
-    if (p.scan_sorted) ln.scan_order.ensure((size_t)l_cap + 64);
-    ln.ovf_buf.ensure((size_t)sp.scratch_words + 4);
+    w.scan_hist.ensure((size_t)2 * LOCI_REGIONS * SCAN_CLASSES);
+    if (p.scan_sorted) w.scan_order.ensure((size_t)l_cap + 64);
+    w.ovf_buf.ensure((size_t)sp.scratch_words + 4);
     // the locus numbering: one region per sixteen fragments (64 at most), each the largest power of two that fits its share
-    p.loci.count = ln.status.p->loci_region;
+    p.loci.count = w.status.p->loci_region;
     p.loci.n = std::min<uint32_t>(LOCI_REGIONS, ev_regions_for(F));
     p.loci.shift = (uint32_t)floor_log2((int)std::max<int64_t>(1, l_cap / p.loci.n));
-    ln.loci_n = p.loci.n; ln.loci_shift = p.loci.shift;
-    ln.l1_pf = p.l1_prefilter; ln.l1_small_class = p.n_l1 > 1 && p.l1[0].nt == 256;
+    w.loci_n = p.loci.n; w.loci_shift = p.loci.shift;
+    w.l1_pf = p.l1_prefilter; w.l1_small_class = p.n_l1 > 1 && p.l1[0].nt == 256;
     p.wide = smax + 1 >= (1 << EvBits<uint16_t>::RANK);        // slot = rank + 1 must fit the slot field of the 16-bit event
-    ln.items.ensure(((size_t)sp.items_cap + 8) * (p.wide ? 4 : 2));
+    w.items.ensure(((size_t)sp.items_cap + 8) * (p.wide ? 4 : 2));
 
     launch_sketch_stage(r, p);
     prepare_order(p);
     launch_l1_stage(p);
     launch_l2_stage(r, p);
     launch_cgi_stage_and_hand_over(r, p);
-    ran[r.lane] = true;
   }
 
   // Passes of several genomes run the workgroups of k_l2_events in offset-major, XCD-aware
   // order (build_frag_order); the order is built on the host, cached per (batch, fragment range) and uploaded behind K1.
   void prepare_order(Part &p) {
-    Workspace &ln = p.ln;
     static const bool order_on = !(getenv("FA_FRAG_ORDER") && atoi(getenv("FA_FRAG_ORDER")) == 0);
     static const bool order_one = !(getenv("FA_FRAG_ORDER_ONE") && atoi(getenv("FA_FRAG_ORDER_ONE")) == 0);   // (A/B of the one-genome order)
     if (!(order_on && (NQ >= 2 || order_one) && p.F >= 64)) return;
-    if (ln.order_batch != g.serial || ln.order_f0 != p.f0 || ln.order_f1 != p.f1) {
+    if (w.order_batch != g.serial || w.order_f0 != p.f0 || w.order_f1 != p.f1) {
       std::vector<int32_t> ord;
-      ln.order_len = build_frag_order(g, g0, p.f0, p.f1, ord);       // 0: the lists cannot be balanced, identity order
-      if (ln.order_len) {
-        ln.pin_order.ensure(ord.size() * sizeof(int32_t));
-        memcpy(ln.pin_order.p, ord.data(), ord.size() * sizeof(int32_t));
-        ln.frag_order.ensure(ord.size());
-        FA_HIP(hipMemcpyAsync(ln.frag_order.p, ln.pin_order.p, ord.size() * sizeof(int32_t), hipMemcpyHostToDevice, p.st));
+      w.order_len = build_frag_order(g, g0, p.f0, p.f1, ord);       // 0: the lists cannot be balanced, identity order
+      if (w.order_len) {
+        w.pin_order.ensure(ord.size() * sizeof(int32_t));
+        memcpy(w.pin_order.p, ord.data(), ord.size() * sizeof(int32_t));
+        w.frag_order.ensure(ord.size());
+        FA_HIP(hipMemcpyAsync(w.frag_order.p, w.pin_order.p, ord.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
       }
-      ln.order_batch = g.serial; ln.order_f0 = p.f0; ln.order_f1 = p.f1;
+      w.order_batch = g.serial; w.order_f0 = p.f0; w.order_f1 = p.f1;
     }
-    if (ln.order_len) { p.frag_order = ln.frag_order.p; p.order_len = ln.order_len; }
+    if (w.order_len) { p.frag_order = w.frag_order.p; p.order_len = w.order_len; }
   }
 
   // K1 (its extra workgroups zero the tables of the part) + per-fragment sort / unique / index lookup
   void launch_sketch_stage(Run &r, Part &p) {
-    Workspace &ln = p.ln;
-    hipStream_t st = p.st;
     const fa_mapper::Spec &sp = p.sp;
     const int64_t f0 = p.f0, F = p.F;
     const int64_t l_cap = p.l_cap;
     const int t0 = p.t0, ntiles = p.ntiles;
     {
       ClearList cl;
-      cl.add(ln.status.p, offsetof(PassStatus, stamp));
-      cl.a.stamp = &ln.status.p->stamp[0];
-      cl.add(ln.l_end.p, (size_t)l_cap * sizeof(int32_t)); cl.add(ln.l_rlast.p, (size_t)l_cap * sizeof(int32_t));
-      cl.add(ln.group_best.p, (size_t)l_cap * sizeof(unsigned long long));
-      if (p.scan_sorted) cl.add(ln.scan_hist.p, (size_t)2 * LOCI_REGIONS * SCAN_CLASSES * sizeof(uint32_t));
+      cl.add(w.status.p, offsetof(PassStatus, stamp));
+      cl.a.stamp = &w.status.p->stamp[0];
+      cl.add(w.l_end.p, (size_t)l_cap * sizeof(int32_t)); cl.add(w.l_rlast.p, (size_t)l_cap * sizeof(int32_t));
+      cl.add(w.group_best.p, (size_t)l_cap * sizeof(unsigned long long));
+      if (p.scan_sorted) cl.add(w.scan_hist.p, (size_t)2 * LOCI_REGIONS * SCAN_CLASSES * sizeof(uint32_t));
       if (!bins_cleared) { cl.add(w.bins.p, (size_t)NQ * std::max(m.total_bins, 1) * sizeof(unsigned long long)); bins_cleared = true; }
       QuerySketchArgs a;
       a.frag_tile_lo = g.d_frag_tile_lo + f0;
-      a.tile_count = ln.sk.tile_count.p; a.stage_hash = ln.sk.stage_hash.p; a.stage_wpos = ln.sk.stage_wpos.p;
+      a.tile_count = w.sk.tile_count.p; a.stage_hash = w.sk.stage_hash.p; a.stage_wpos = w.sk.stage_wpos.p;
       a.tile_base = t0;                              // frag_tile_lo holds batch-wide tile numbers
-      a.q_hash = ln.q_hash.p; a.q_size = ln.q_size.p; a.qcap = qcap;
-      a.ix = ix; a.q_off = ln.q_off.p; a.q_cnt = ln.q_cnt.p; a.n_seeds = ln.n_seeds.p;
+      a.q_hash = w.q_hash.p; a.q_size = w.q_size.p; a.qcap = qcap;
+      a.ix = ix; a.q_off = w.q_off.p; a.q_cnt = w.q_cnt.p; a.n_seeds = w.n_seeds.p;
       a.sort_cap = (int32_t)(qs_lds / 4);
       a.rec_cap = getenv("FA_QF_CAP") ? std::max(0, std::min(QF_CAP, atoi(getenv("FA_QF_CAP")))) : QF_CAP;
       a.exc_tiles = 0;                                 // (set by launch_sketch_tiles for the fused kernel)
       // ---- K1 (its extra workgroups zero the ranges above beside the hashing) + per-fragment sort / unique / index lookup:
       //      one launch where the pass qualifies (k_query_fused), else k_sketch_fast / k_sketch_tiles, then k_query_sketch ----
-      const bool fused = launch_sketch_tiles(m.P, g.store, g.tiles + t0, ntiles, ln.sk.stage_hash.p, ln.sk.stage_wpos.p, ln.sk.tile_count.p, st, &cl.a,
+      const bool fused = launch_sketch_tiles(m.P, g.store, g.tiles + t0, ntiles, w.sk.stage_hash.p, w.sk.stage_wpos.p, w.sk.tile_count.p, st, &cl.a,
                                              (sp.fuse_off || r.forced_unfused) ? nullptr : &a, F);
       r.fused = fused;
       if (!fused) {
@@ -1375,36 +1280,34 @@ struct QueryPass {
 
   // seed totals, then the candidate regions
   void launch_l1_stage(Part &p) {
-    Workspace &ln = p.ln;
-    hipStream_t st = p.st;
     const fa_mapper::Spec &sp = p.sp;
     const int64_t F = p.F;
     const int smax = p.smax;
     const int64_t l_cap = p.l_cap;
-    int32_t *const d_stats = ln.status.p->stats;
-    uint64_t *const d_totals = ln.status.p->totals;
-    uint32_t *const d_counters = ln.status.p->counters;
-    unsigned long long *const d_pinfo = ln.status.p->pinfo;
+    int32_t *const d_stats = w.status.p->stats;
+    uint64_t *const d_totals = w.status.p->totals;
+    uint32_t *const d_counters = w.status.p->counters;
+    unsigned long long *const d_pinfo = w.status.p->pinfo;
     const uint32_t seed_slots = p.seed_slots;
     // ---- seed totals and speculation checks (the lookup itself is the tail of k_query_sketch).  A kernel of its own
     //      only where k_l1 / k_l1_big need the scratch offsets it produces; else workgroup F of k_l1's launch ----
     const bool fold_totals = sp.scratch_words == 0;
     if (!fold_totals)
-      hipLaunchKernelGGL(k_seed_totals, dim3(1), dim3(1024), 0, st, ln.n_seeds.p, F, seed_slots, d_totals, ln.ovf_off.p,
-                         d_stats, smax, sp.scratch_words, d_pinfo, &ln.status.p->stamp[1], ln.q_size.p);
+      hipLaunchKernelGGL(k_seed_totals, dim3(1), dim3(1024), 0, st, w.n_seeds.p, F, seed_slots, d_totals, w.ovf_off.p,
+                         d_stats, smax, sp.scratch_words, d_pinfo, &w.status.p->stamp[1], w.q_size.p);
     debug_sync(st, "lookup");
     // ---- L1 ----
     {
       L1Args a;
       a.fold_totals = fold_totals ? 1 : 0; a.spec_smax = smax; a.F = F; a.totals = d_totals; a.stats = d_stats;
-      a.spec_scratch_words = sp.scratch_words; a.stamp = &ln.status.p->stamp[1];
-      a.ix = ix; a.q_size = ln.q_size.p; a.q_off = ln.q_off.p; a.q_cnt = ln.q_cnt.p; a.n_seeds = ln.n_seeds.p;
-      a.ovf_off = ln.ovf_off.p; a.ovf_buf = ln.ovf_buf.p; a.min_hits_lut = w.lut_min_hits;
-      a.l_frag = ln.l_frag.p; a.l_seq = ln.l_seq.p; a.l_start = ln.l_start.p; a.l_end = ln.l_end.p; a.l_group = ln.l_group.p;
-      a.l_rfirst = ln.l_rfirst.p; a.l_rlast = ln.l_rlast.p; a.l_rpart = ln.l_rpart.p;
+      a.spec_scratch_words = sp.scratch_words; a.stamp = &w.status.p->stamp[1];
+      a.ix = ix; a.q_size = w.q_size.p; a.q_off = w.q_off.p; a.q_cnt = w.q_cnt.p; a.n_seeds = w.n_seeds.p;
+      a.ovf_off = w.ovf_off.p; a.ovf_buf = w.ovf_buf.p; a.min_hits_lut = w.lut_min_hits;
+      a.l_frag = w.l_frag.p; a.l_seq = w.l_seq.p; a.l_start = w.l_start.p; a.l_end = w.l_end.p; a.l_group = w.l_group.p;
+      a.l_rfirst = w.l_rfirst.p; a.l_rlast = w.l_rlast.p; a.l_rpart = w.l_rpart.p;
       a.counters = d_counters; a.loci = p.loci; a.qcap = qcap; a.frag_len = m.P.fragment_length; a.l_cap = (int32_t)l_cap;
       a.lds_seed_cap = seed_slots; a.totals_seed_cap = seed_slots; a.n_lo = 0; a.n_hi = 0xFFFFFFFFu; a.pinfo = d_pinfo; a.lut_smax = smax; a.scratch_words = sp.scratch_words;
-      a.f_loci_lo = ln.f_loci_lo.p; a.f_loci_n = ln.f_loci_n.p;
+      a.f_loci_lo = w.f_loci_lo.p; a.f_loci_n = w.f_loci_n.p;
       static const bool l1_block_sort_on = !(getenv("FA_L1_BLOCK_SORT") && atoi(getenv("FA_L1_BLOCK_SORT")) == 0);
       static const bool l1_stats = getenv("FA_L1_STATS") && atoi(getenv("FA_L1_STATS")) != 0;
       // Hits that cannot be an end of a candidate skip the fetch of their padded global coordinate (k_l1, scan_run<., NEAR>).  The
@@ -1417,16 +1320,16 @@ struct QueryPass {
       const bool l1_pf_on = p.l1_prefilter;             // (decided with the size classes, when the part was planned)
       a.block_sort = (l1_block_sort_on ? 1 : 0) | (l1_stats ? 2 : 0) | (l1_near_on ? 4 : 0) | (l1_pf_on ? 8 : 0);
       const uint32_t l1_grid = (uint32_t)F;             // (the offset-major order of k_l2_events applied here measured nothing: 75.9 / 75.5 ms on config 3)
-      a.dbg = ln.status.p->dbg;
+      a.dbg = w.status.p->dbg;
       // fragments with more hits than LDS holds (seen before on this mapper: scratch is reserved for them) are cut
       // into LDS-sized chunks at contig boundaries by k_l1_big first; what it cannot cut stays with k_l1's HBM path
       static const bool l1_big = !(getenv("FA_L1_BIG") && atoi(getenv("FA_L1_BIG")) == 0);
       a.big_state = nullptr; a.big_enabled = 0; a.big_cap = 0;
       const int64_t big_room = (int64_t)160 * 1024 - 2048 - ((int64_t)smax + 2) * 16;   // LDS left for a chunk's seeds
       if (l1_big && sp.scratch_words > 0 && big_room >= 4 * 2048) {
-        ln.big_state.ensure((size_t)F);
+        w.big_state.ensure((size_t)F);
         a.big_cap = (uint32_t)std::min<int64_t>((int64_t)L1_BIG_E * L1_BIG_THREADS, big_room / 4 / 256 * 256);
-        a.big_state = ln.big_state.p; a.big_enabled = 1;
+        a.big_state = w.big_state.p; a.big_enabled = 1;
         const size_t lds = l1_big_lds_bytes(a.big_cap, smax);
         if (lds > 64 * 1024) FA_HIP(hipFuncSetAttribute((const void *)k_l1_big, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(k_l1_big, dim3((unsigned)F), dim3(L1_BIG_THREADS), lds, st, a);
@@ -1450,8 +1353,7 @@ struct QueryPass {
       };
       for (int c = 0; c < p.n_l1; c++) {
         const bool fold = fold_totals && c == 0;
-        if (p.l1[c].nt >= 1024) go(std::integral_constant<int, 1024>(), p.l1[c], fold);
-        else if (p.l1[c].nt >= 512) go(std::integral_constant<int, 512>(), p.l1[c], fold);
+        if (p.l1[c].nt >= 512) go(std::integral_constant<int, 512>(), p.l1[c], fold);
         else go(std::integral_constant<int, 256>(), p.l1[c], fold);
       }
     }
@@ -1460,58 +1362,51 @@ struct QueryPass {
 
   // event streams, then the sequential slide
   void launch_l2_stage(Run &r, Part &p) {
-    Workspace &ln = p.ln;
-    hipStream_t st = p.st;
     const fa_mapper::Spec &sp = p.sp;
     const int64_t F = p.F;
     const int smax = p.smax;
     const int64_t l_cap = p.l_cap;
-    uint64_t *const d_totals = ln.status.p->totals;
-    uint32_t *const d_counters = ln.status.p->counters;
-    unsigned long long *const d_pinfo = ln.status.p->pinfo;
+    uint64_t *const d_totals = w.status.p->totals;
+    uint32_t *const d_counters = w.status.p->counters;
+    unsigned long long *const d_pinfo = w.status.p->pinfo;
     const bool wide = p.wide;
     // ---- L2: event streams, then the sequential slide (uint8 state, uint16 redo) ----
     {
-      if (m.stage_events) FA_HIP(hipEventRecord(ln.ev[2], st));
+      if (m.stage_events) FA_HIP(hipEventRecord(w.ev[2], st));
       L2Args a;
-      a.stamp = &ln.status.p->stamp[2];
-      a.ix = ix; a.q_hash = ln.q_hash.p; a.q_size = ln.q_size.p;
-      a.l_frag = ln.l_frag.p; a.l_seq = ln.l_seq.p; a.l_start = ln.l_start.p; a.l_end = ln.l_end.p; a.l_group = ln.l_group.p;
-      a.l_rfirst = ln.l_rfirst.p; a.l_rlast = ln.l_rlast.p; a.l_rpart = ln.l_rpart.p; a.frag_len = m.P.fragment_length;
-      a.l_beg = ln.l_beg.p; a.l_end0 = ln.l_end0.p; a.l_last = ln.l_last.p; a.l_nev = ln.l_nev.p; a.l_ioff = ln.l_ioff.p; a.l_ndrop = ln.l_ndrop.p;
-      a.items = ln.items.p; a.items_cap = sp.items_cap; a.pinfo = d_pinfo; a.l_cap = (int32_t)l_cap;
-      a.l_shared = ln.l_shared.p; a.l_pos = ln.l_pos.p; a.pass_lut = w.lut_pass; a.group_best = ln.group_best.p;
+      a.stamp = &w.status.p->stamp[2];
+      a.ix = ix; a.q_hash = w.q_hash.p; a.q_size = w.q_size.p;
+      a.l_frag = w.l_frag.p; a.l_seq = w.l_seq.p; a.l_start = w.l_start.p; a.l_end = w.l_end.p; a.l_group = w.l_group.p;
+      a.l_rfirst = w.l_rfirst.p; a.l_rlast = w.l_rlast.p; a.l_rpart = w.l_rpart.p; a.frag_len = m.P.fragment_length;
+      a.l_beg = w.l_beg.p; a.l_end0 = w.l_end0.p; a.l_last = w.l_last.p; a.l_nev = w.l_nev.p; a.l_ioff = w.l_ioff.p; a.l_ndrop = w.l_ndrop.p;
+      a.items = w.items.p; a.items_cap = sp.items_cap; a.pinfo = d_pinfo; a.l_cap = (int32_t)l_cap;
+      a.l_shared = w.l_shared.p; a.l_pos = w.l_pos.p; a.pass_lut = w.lut_pass; a.group_best = w.group_best.p;
       a.counters = d_counters; a.loci = p.loci; a.qcap = qcap; a.cmw = m.cmw;
       a.cnt_slots = smax + 1;
       a.rec_total = (unsigned long long *)(d_totals + 3);
-      a.ev_region = ln.status.p->ev_region; a.rec_region = ln.status.p->rec_region;
+      a.ev_region = w.status.p->ev_region; a.rec_region = w.status.p->rec_region;
       a.n_regions = ev_regions_for(F);
       a.region_cap = (sp.items_cap / a.n_regions) & ~7ULL;
-      a.l_redo = ln.l_redo.p;
+      a.l_redo = w.l_redo.p;
       a.redo_count = d_counters + 3;
       {
         // classes of the counting sort: the longest streams hold the records of ~2.6 windows twice (see ev_stage below), so six
         // windows' worth of events over the classes
         const int per_window_ev = std::max(1, 2 * m.P.fragment_length / (m.P.window_size + 1));
         a.scan_class_div = p.scan_sorted ? std::max(8, (per_window_ev * 6 / SCAN_CLASSES + 7) & ~7) : 0;
-        a.scan_hist = ln.scan_hist.p; a.scan_cursor = ln.scan_hist.p + LOCI_REGIONS * SCAN_CLASSES;
-        a.scan_order = p.scan_sorted ? ln.scan_order.p : nullptr;
+        a.scan_hist = w.scan_hist.p; a.scan_cursor = w.scan_hist.p + LOCI_REGIONS * SCAN_CLASSES;
+        a.scan_order = p.scan_sorted ? w.scan_order.p : nullptr;
       }
-      a.f_loci_lo = ln.f_loci_lo.p; a.f_loci_n = ln.f_loci_n.p;
+      a.f_loci_lo = w.f_loci_lo.p; a.f_loci_n = w.f_loci_n.p;
       // several genomes in the pass: the workgroups of k_l2_events in offset-major order (prepare_order)
       a.frag_order = p.frag_order;
       const uint32_t ev_grid = p.frag_order ? p.order_len : (uint32_t)F;
       if (p.frag_order) r.ordered = true;
-#ifdef FA_EXPERIMENTS
-      static const int fused_dbg = (int)env_u64("FA_FUSED_DEBUG", 0);
-      a.dbg = fused_dbg;
-#endif
       // events of one locus staged in LDS per wave of k_l2_events (longer streams are stored directly): a stream holds
       // the records of about 2.6 windows twice, minus the first window -- 5.3 windows' worth at the longest in the bench;
       // the LDS this costs decides how many workgroups a CU holds (2048: 6, 1408: 7; 0.41 vs 0.38 ms for the L2 stage)
-      static const int ev_stage_env = (int)exp_u64("FA_EV_STAGE", 0);
       const int per_window = std::max(1, 2 * m.P.fragment_length / (m.P.window_size + 1));
-      a.ev_stage = ev_stage_env ? (ev_stage_env & ~7) : std::min(2048, std::max(512, (per_window * 11 / 2 + 127) & ~127));
+      a.ev_stage = std::min(2048, std::max(512, (per_window * 11 / 2 + 127) & ~127));
       const size_t ev_lds = ev_sketch_bytes(a.cnt_slots) + (size_t)a.ev_stage * (wide ? 4 : 2) * (EV_THREADS / 64) + 16;
       FA_REQUIRE(ev_lds <= 150 * 1024, FA_ERR_UNSUPPORTED, "query sketch too large for the LDS-staged event kernel");
       // fast pass: one state byte per rank; redo pass: two bytes per rank, only for loci whose counts overflowed
@@ -1523,13 +1418,9 @@ struct QueryPass {
         return ln;
       };
       const int lanes8 = pick_lanes(1), lanes16 = pick_lanes(2);
-      static const size_t scan_pad = (size_t)exp_u64("FA_SCAN_LDS_PAD", 0);   // experiment: fewer scan workgroups per CU
-      const size_t lds8 = scan_lds(lanes8, 1) + scan_pad, lds16 = scan_lds(lanes16, 2);
+      const size_t lds8 = scan_lds(lanes8, 1), lds16 = scan_lds(lanes16, 2);
       // (workgroup b of a scan takes chunk b / n of region b mod n: every region needs its chunks, however few loci it can hold)
       auto scan_grid = [&](int lanes) { return (unsigned)(p.loci.n * (uint32_t)ceil_div((int64_t)1 << p.loci.shift, lanes)); };
-      // the rank structure of k_l2_events (its template parameter RK): 1 = occupancy words (round 6), FA_EV_RANK=0 = the bucket
-      // table + four-entry probe of rounds 2-5 (kept for the A/B and for the unpacked record layout)
-      static const bool ev_rank_occ = !(getenv("FA_EV_RANK") && atoi(getenv("FA_EV_RANK")) == 0);
       auto launch = [&](auto ev_kernel, auto scan8, auto scan8_rt, auto scan16, auto scan16_rt) {
         if (ev_lds > 64 * 1024) FA_HIP(hipFuncSetAttribute((const void *)ev_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ev_lds));
         hipLaunchKernelGGL(ev_kernel, dim3(ev_grid), dim3(EV_THREADS), ev_lds, st, a);
@@ -1556,91 +1447,26 @@ struct QueryPass {
           hipLaunchKernelGGL(scan16_rt, dim3(scan_grid(lanes16)), dim3(L2_THREADS), lds16, st, a);
         }
       };
-#ifdef FA_EXPERIMENTS
-      // FA_L2_FUSED=1 selects the fused form (events generated into an LDS ring and consumed in place: no event arena in
-      // HBM, L2-stage traffic 0.45 GB instead of 1.08 GB per bench step).  It is bit-exact but measured SLOWER than the
-      // two-kernel form on the bench step (0.81 ms against 0.42 ms, profiles/EXPERIMENTS.md): one or two producer waves per 64
-      // loci cannot hide their LDS round trips the way the 32 waves per CU of k_l2_events do, and the slide state (16-18 KB
-      // per 64 loci) leaves no LDS for more.  Kept as an experiment; the default is k_l2_events + k_l2_scan.
-      static const bool fused_on = fused_l2_enabled();
-      // ring rows of 16 events per locus unless the 2 KB a row of 8 saves buy one more workgroup per CU AND the
-      // fragments of this pass then fit the chip in one round (the slide is a latency-bound chain: rounds add up)
-      static const int fu_forced = (int)env_u64("FA_FUSED_C", 0);
-      const int evb = wide ? 4 : 2;
-      auto wg_bytes = [&](int c) { return (fused_lds_bytes<uint8_t>(a.cnt_slots, evb, c) + FU_STATIC_LDS + 511) / 512 * 512; };
-      auto per_cu = [&](int c) { return (int64_t)((160 * 1024) / wg_bytes(c)); };
-      int fu_c = 16;
-      if (fu_forced == 8 || fu_forced == 16) fu_c = fu_forced;
-      else if (per_cu(8) > per_cu(16) && F > per_cu(16) * 256 && F <= per_cu(8) * 256) fu_c = 8;
-      static const size_t fused_pad = (size_t)env_u64("FA_FUSED_LDS_PAD", 0);   // development: unused LDS behind the ring
-      const size_t fl8 = fused_lds_bytes<uint8_t>(a.cnt_slots, evb, fu_c) + fused_pad, fl16 = fused_lds_bytes<uint16_t>(a.cnt_slots, evb, fu_c);
-      const bool fused = fused_on && fl16 <= 150 * 1024 && m.cmw < 65535;   // rec_hf keeps same-hash distances in 16 bits
-      static const int fu_nprod = (int)env_u64("FA_FUSED_PRODUCERS", 2) == 1 ? 1 : 2;
-      const int fu_threads = 64 * (1 + fu_nprod);
-      auto launch_fused = [&](auto k8, auto k16) {
-        if (fl8 > 60 * 1024) FA_HIP(hipFuncSetAttribute((const void *)k8, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fl8));
-        const unsigned grid = (unsigned)(((F + 7) / 8) * 8);                // blockIdx -> (XCD, fragment of that XCD)
-        static const bool dbg_launch = getenv("FA_DEBUG_FUSED") != nullptr;
-        if (dbg_launch) {
-          int nb = -1;
-          (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)k8, fu_threads, fl8);
-          hipFuncAttributes fa_;
-          (void)hipFuncGetAttributes(&fa_, (const void *)k8);
-          fprintf(stderr, "k_l2_fused: F=%lld grid=%u lds=%zu (+%zu static) fu_c=%d cnt_slots=%d redo=%d | occupancy API %d blocks/CU, numRegs %d, sharedSizeBytes %zu, maxDynShared %d\n",
-                  (long long)F, grid, fl8, FU_STATIC_LDS, fu_c, a.cnt_slots, (int)sp.redo, nb, fa_.numRegs, fa_.sharedSizeBytes, fa_.maxDynamicSharedSizeBytes);
-        }
-        hipLaunchKernelGGL(k8, dim3(grid), dim3(fu_threads), fl8, st, a, F);
-        if (!sp.redo) return;
-        if (fl16 > 60 * 1024) FA_HIP(hipFuncSetAttribute((const void *)k16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fl16));
-        hipLaunchKernelGGL(k16, dim3(grid), dim3(fu_threads), fl16, st, a, F);
-      };
-#else
-      const bool fused = false;
-#endif
-      const bool pk = m.packed_geo && !getenv("FA_NO_PACKED_GEO");
-      if (fused) {
-#ifdef FA_EXPERIMENTS
-        auto pick = [&](auto ev_tag) {
-          using EV = decltype(ev_tag);
-          if (fu_nprod == 2) {
-            if (fu_c == 8) launch_fused(k_l2_fused<EV, uint8_t, false, 8, 2>, k_l2_fused<EV, uint16_t, true, 8, 2>);
-            else launch_fused(k_l2_fused<EV, uint8_t, false, 16, 2>, k_l2_fused<EV, uint16_t, true, 16, 2>);
-          } else {
-            if (fu_c == 8) launch_fused(k_l2_fused<EV, uint8_t, false, 8, 1>, k_l2_fused<EV, uint16_t, true, 8, 1>);
-            else launch_fused(k_l2_fused<EV, uint8_t, false, 16, 1>, k_l2_fused<EV, uint16_t, true, 16, 1>);
-          }
-        };
-        if (wide) pick(uint32_t()); else pick(uint16_t());
-        w.last_ms[14] = (float)smax; w.last_ms[15] = (float)fu_c;
-#endif
-      } else if (wide) {
-        if (pk && ev_rank_occ) launch(k_l2_events<uint32_t, true, 1>, k_l2_scan<uint32_t, uint8_t, 64>, k_l2_scan<uint32_t, uint8_t, 0>, k_l2_scan<uint32_t, uint16_t, 64>, k_l2_scan<uint32_t, uint16_t, 0>);
-        else if (pk) launch(k_l2_events<uint32_t, true, 0>, k_l2_scan<uint32_t, uint8_t, 64>, k_l2_scan<uint32_t, uint8_t, 0>, k_l2_scan<uint32_t, uint16_t, 64>, k_l2_scan<uint32_t, uint16_t, 0>);
-        else launch(k_l2_events<uint32_t, false, 0>, k_l2_scan<uint32_t, uint8_t, 64>, k_l2_scan<uint32_t, uint8_t, 0>, k_l2_scan<uint32_t, uint16_t, 64>, k_l2_scan<uint32_t, uint16_t, 0>);
-      } else {
-        if (pk && ev_rank_occ) launch(k_l2_events<uint16_t, true, 1>, k_l2_scan<uint16_t, uint8_t, 64>, k_l2_scan<uint16_t, uint8_t, 0>, k_l2_scan<uint16_t, uint16_t, 64>, k_l2_scan<uint16_t, uint16_t, 0>);
-        else if (pk) launch(k_l2_events<uint16_t, true, 0>, k_l2_scan<uint16_t, uint8_t, 64>, k_l2_scan<uint16_t, uint8_t, 0>, k_l2_scan<uint16_t, uint16_t, 64>, k_l2_scan<uint16_t, uint16_t, 0>);
-        else launch(k_l2_events<uint16_t, false, 0>, k_l2_scan<uint16_t, uint8_t, 64>, k_l2_scan<uint16_t, uint8_t, 0>, k_l2_scan<uint16_t, uint16_t, 64>, k_l2_scan<uint16_t, uint16_t, 0>);
-      }
+      const bool pk = m.events_packed();
+      if (wide) launch(pk ? k_l2_events<uint32_t, true> : k_l2_events<uint32_t, false>, k_l2_scan<uint32_t, uint8_t, 64>, k_l2_scan<uint32_t, uint8_t, 0>, k_l2_scan<uint32_t, uint16_t, 64>, k_l2_scan<uint32_t, uint16_t, 0>);
+      else launch(pk ? k_l2_events<uint16_t, true> : k_l2_events<uint16_t, false>, k_l2_scan<uint16_t, uint8_t, 64>, k_l2_scan<uint16_t, uint8_t, 0>, k_l2_scan<uint16_t, uint16_t, 64>, k_l2_scan<uint16_t, uint16_t, 0>);
     }
     debug_sync(st, "l2 scan");
-    if (m.stage_events) FA_HIP(hipEventRecord(ln.ev[3], st));
+    if (m.stage_events) FA_HIP(hipEventRecord(w.ev[3], st));
   }
 
   // core-genome identity and the one hand-over of the part
   void launch_cgi_stage_and_hand_over(Run &r, Part &p) {
-    Workspace &ln = p.ln;
-    hipStream_t st = p.st;
     const fa_mapper::Spec &sp = p.sp;
     const int64_t f0 = p.f0;
     const int64_t l_cap = p.l_cap;
-    uint32_t *const d_counters = ln.status.p->counters;
+    uint32_t *const d_counters = w.status.p->counters;
     // ---- core-genome identity ----
     if (npairs > 0) {
       CgiArgs a;
-      a.stamp = &ln.status.p->stamp[3];
-      a.ix = ix; a.group_best = ln.group_best.p; a.counters = d_counters; a.l_frag = ln.l_frag.p; a.l_seq = ln.l_seq.p;
-      a.l_pos = ln.l_pos.p; a.q_size = ln.q_size.p; a.ident_lut = w.lut_ident;
+      a.stamp = &w.status.p->stamp[3];
+      a.ix = ix; a.group_best = w.group_best.p; a.counters = d_counters; a.l_frag = w.l_frag.p; a.l_seq = w.l_seq.p;
+      a.l_pos = w.l_pos.p; a.q_size = w.q_size.p; a.ident_lut = w.lut_ident;
       a.frag_query = g.d_frag_query + f0; a.frag_qseq = g.d_frag_qseq + f0; a.bins = w.bins.p;
       a.bin_len = m.P.fragment_length - 20;
       a.query_base = g0;                             // frag_query holds batch-wide genome numbers
@@ -1650,41 +1476,39 @@ struct QueryPass {
     }
     // ---- the one hand-over of the part: results, statistics and the speculation verdict (publish_pass) ----
     PassStatus *h_dev = nullptr;
-    FA_HIP(hipHostGetDevicePointer((void **)&h_dev, ln.h_status, 0));
+    FA_HIP(hipHostGetDevicePointer((void **)&h_dev, w.h_status, 0));
     const bool to_host = r.with_rows && host_rows != nullptr;
-    const PublishArgs pub = publish_args(ln.status.p, h_dev, ++ln.seq, rows_dev + row_base, to_host ? host_rows + row_base : nullptr, cap - row_base);
+    const PublishArgs pub = publish_args(w.status.p, h_dev, ++w.seq, rows_dev + row_base, to_host ? host_rows + row_base : nullptr, cap - row_base);
     bool published = false;
-    if (npairs > 0 && r.with_rows) { join_lanes(r.lane); published = launch_rows(ln, pub); rows_lane = r.lane; rows_valid = true; }
+    if (npairs > 0 && r.with_rows) { published = launch_rows(pub); rows_valid = true; }
     FA_HIP(hipGetLastError());
     debug_sync(st, "cgi");
-    if (n_lanes > 1) FA_HIP(hipEventRecord(ln.ev[4], st));         // (join_lanes: the bins of this part)
     if (!published) hipLaunchKernelGGL(k_publish_status, dim3(1), dim3(256), 0, st, pub);
   }
 
   // ================================================ the verdict on a part ======================================
   // waits for a part and reads its verdict: true = accepted, false = void (its range has to run again)
   bool judge_part(Run &r) {
-    Workspace &ln = *lanes[r.lane];
     fa_mapper::Spec &sp = r.sp;
     const int64_t F = r.f1 - r.f0;
-    wait_published(ln.h_status, ln.seq, ln.stream);
-    const int32_t *h_stats = ln.h_status->stats;
-    const uint64_t *h_totals = ln.h_status->totals;
-    const uint32_t *h_counters = ln.h_status->counters;
-    const unsigned long long *h_pinfo = ln.h_status->pinfo;
+    wait_published(w.h_status, w.seq, w.stream);
+    const int32_t *h_stats = w.h_status->stats;
+    const uint64_t *h_totals = w.h_status->totals;
+    const uint32_t *h_counters = w.h_status->counters;
+    const unsigned long long *h_pinfo = w.h_status->pinfo;
     const uint64_t total_seeds = h_totals[0], max_seeds = h_totals[1];
     uint64_t events_total = h_pinfo[0], records_total = h_totals[3], ev_region_max = 0;
     for (int i = 0; i < EV_REGIONS; i++) {
-      events_total += ln.h_status->ev_region[i]; records_total += ln.h_status->rec_region[i];
-      ev_region_max = std::max<uint64_t>(ev_region_max, ln.h_status->ev_region[i]);
+      events_total += w.h_status->ev_region[i]; records_total += w.h_status->rec_region[i];
+      ev_region_max = std::max<uint64_t>(ev_region_max, w.h_status->ev_region[i]);
     }
     const unsigned long long flags = h_pinfo[1];
     // loci: reserved per region (LociRegions); a region asked for more than it holds = SPEC_LOCI
     uint64_t loci_total = 0, loci_region_max = 0;
-    for (uint32_t i = 0; i < ln.loci_n; i++) {
-      const uint64_t c = ln.h_status->loci_region[i];
+    for (uint32_t i = 0; i < w.loci_n; i++) {
+      const uint64_t c = w.h_status->loci_region[i];
       loci_region_max = std::max(loci_region_max, c);
-      loci_total += std::min<uint64_t>(c, 1ULL << ln.loci_shift);
+      loci_total += std::min<uint64_t>(c, 1ULL << w.loci_shift);
     }
     // a part whose seeds / loci / slide events cannot be addressed with 32-bit offsets is cut down and run again
     if (flags || (h_counters[3] > 0 && !sp.redo)) w.last_ms[9] += 1.0f;   // repeated attempts of this call (speculation misses)
@@ -1718,12 +1542,12 @@ struct QueryPass {
     if (flags & SPEC_LOCI) {
       // every region has to hold its share: size the arrays for the fullest one.  A region holds the largest power of two
       // below its share of l_cap, i.e. more than half of it: twice the need is what makes the repeat fit for certain
-      const int64_t need = (int64_t)(loci_region_max * ln.loci_n);
+      const int64_t need = (int64_t)(loci_region_max * w.loci_n);
       const int64_t want = std::max<int64_t>(sp.l_cap * 2, need * 2);
       const int64_t l_max = (1LL << 31) - 64;
       // a region holds the largest power of two below its share: at the cap that is 2^floor_log2(l_max / n), which the fullest
       // region must fit -- otherwise the repeat would overflow again at the same capacity, for ever
-      const int64_t region_at_cap = (int64_t)1 << floor_log2((int)std::max<int64_t>(1, l_max / (int64_t)ln.loci_n));
+      const int64_t region_at_cap = (int64_t)1 << floor_log2((int)std::max<int64_t>(1, l_max / (int64_t)w.loci_n));
       if (need > l_max || (want >= l_max && (int64_t)loci_region_max > region_at_cap)) {
         shrink_part((double)loci_region_max, (double)region_at_cap, "candidate loci"); publish_spec(sp); return false;
       }
@@ -1754,7 +1578,7 @@ struct QueryPass {
     // (with the filter on and the 256-thread class in use they are fragments whose kept chance hits -- the hashed bits keep about a
     // third of them -- still overfill that class's table of 1 365 entries: an index of 1.6 x 10^9 records leaves ~700 of 2 000, and
     // 47 % of the fragments of the 4000 x 4000 run fell back; the class is folded into the 512-thread form from then on)
-    if (F > 0 && (double)h_counters[0] > 0.005 * (double)F) { if (ln.l1_pf && ln.l1_small_class) sp.l1_no_small = true; sp.l1_prefilter = true; }
+    if (F > 0 && (double)h_counters[0] > 0.005 * (double)F) { if (w.l1_pf && w.l1_small_class) sp.l1_no_small = true; sp.l1_prefilter = true; }
     publish_spec(sp);
     // ---- accepted ----
     {
@@ -1766,18 +1590,18 @@ struct QueryPass {
     if (r.ordered) w.last_ms[19] += 1.0f;
     if (m.stage_events) {
       float ev_ms = 0;
-      FA_HIP(hipEventSynchronize(ln.ev[3]));
-      FA_HIP(hipEventElapsedTime(&ev_ms, ln.ev[2], ln.ev[3]));
+      FA_HIP(hipEventSynchronize(w.ev[3]));
+      FA_HIP(hipEventElapsedTime(&ev_ms, w.ev[2], w.ev[3]));
       w.last_ms[16] += ev_ms;
     }
-    const unsigned long long *stamp = ln.h_status->stamp;              // 100 MHz ticks
+    const unsigned long long *stamp = w.h_status->stamp;              // 100 MHz ticks
     for (int i = 0; i < 4; i++) w.last_ms[i] += (float)((double)(stamp[i + 1] - stamp[i]) * 1e-5);
     t_begin = std::min(t_begin, stamp[0]); t_end = std::max(t_end, stamp[4]);
-    ln.last_F = F;
-    ln.last_loci = (uint32_t)loci_total;
+    w.last_F = F;
+    w.last_loci = (uint32_t)loci_total;
     for (uint32_t i = 0; i < LOCI_REGIONS; i++)
-      ln.last_region_count[i] = i < ln.loci_n ? (uint32_t)std::min<uint64_t>(ln.h_status->loci_region[i], 1ULL << ln.loci_shift) : 0u;
-    ln.last_items = events_total;
+      w.last_region_count[i] = i < w.loci_n ? (uint32_t)std::min<uint64_t>(w.h_status->loci_region[i], 1ULL << w.loci_shift) : 0u;
+    w.last_items = events_total;
     w.last_ms[5] += (float)records_total;   // reference records inside the locus ranges of this call (roofline line)
     w.last_ms[6] += (float)loci_total;
     w.last_ms[7] += (float)events_total;  // slide events
@@ -1787,10 +1611,10 @@ struct QueryPass {
     if (h_counters[5] + h_counters[6] > 0) {
       const double nf = (double)(h_counters[5] + h_counters[6]);
       fprintf(stderr, "[fa] k_l1 phases, shader-clock ticks per fragment (thread 0):");
-      for (int i = 0; i < 8; i++) fprintf(stderr, " %.0f", (double)ln.h_status->dbg[i] / nf);
+      for (int i = 0; i < 8; i++) fprintf(stderr, " %.0f", (double)w.h_status->dbg[i] / nf);
       fprintf(stderr, "  (%u block-sorted, %u merged; one workgroup in 64 sampled; gave up on probes / blocks / counts: %llu %llu %llu; expansion: bitmaps+places %.0f, pairs+bitmaps %.0f, bits %.0f)\n",
-              h_counters[5], h_counters[6], ln.h_status->dbg[8], ln.h_status->dbg[9], ln.h_status->dbg[10], (double)ln.h_status->dbg[11] / nf, (double)ln.h_status->dbg[12] / nf,
-              (double)ln.h_status->dbg[13] / nf);
+              h_counters[5], h_counters[6], w.h_status->dbg[8], w.h_status->dbg[9], w.h_status->dbg[10], (double)w.h_status->dbg[11] / nf, (double)w.h_status->dbg[12] / nf,
+              (double)w.h_status->dbg[13] / nf);
     }
     return true;
   }
@@ -1798,56 +1622,43 @@ struct QueryPass {
 
   // ================================================ the pass ===================================================
   int64_t run() {
-    w.last_F = 0; w.last_f0 = range_f0; w.last_loci = 0; w.last_genomes = &g;
+    w.last_F = 0; w.last_loci = 0; w.last_genomes = &g;
     for (int i = 0; i < 6; i++) if (!w.ev[i]) FA_HIP(hipEventCreate(&w.ev[i]));
     if (range_f1 == range_f0) return 0;
     FA_REQUIRE(m.P.fragment_length > 20, FA_ERR_UNSUPPORTED, "fragment_length must exceed 20 (the reference bins by fragment_length - 20)");
     fetch_spec();
     plan();
     todo.push_back(Range{range_f0, range_f1, false});
-    while (!todo.empty() || !flight.empty()) {
-      // launch on every free lane
-      for (int i = 0; i < n_lanes && !todo.empty(); i++) {
-        if (busy[i]) continue;
-        FA_REQUIRE(attempts < 40 + 4 * (int)(F_total / std::max<int64_t>(1, std::min(auto_part, sp.part_frags)) + 1), FA_ERR_INTERNAL,
-                   "query pass did not converge on its buffer sizes");
-        attempts++;
-        fetch_spec();
-        const Range range = todo.front(); todo.pop_front();
-        const int64_t f1 = std::min(range.f1, range.f0 + std::max<int64_t>(1, std::min(auto_part, sp.part_frags)));
-        if (f1 < range.f1) todo.push_front(Range{f1, range.f1, range.unfused});
-        Run r{i, range.f0, f1, sp, todo.empty() && npairs > 0};
-        r.forced_unfused = range.unfused;
-        if (r.with_rows) rows_valid = false;
-        launch_part(r);
-        busy[i] = true;
-        flight.push_back(r);
-      }
-      // the oldest part in flight
-      Run r = flight.front(); flight.pop_front();
-      const bool ok = judge_part(r);
-      busy[r.lane] = false;
-      if (!ok) {
+    while (!todo.empty()) {
+      FA_REQUIRE(attempts < 40 + 4 * (int)(F_total / std::max<int64_t>(1, std::min(F_total, sp.part_frags)) + 1), FA_ERR_INTERNAL,
+                 "query pass did not converge on its buffer sizes");
+      attempts++;
+      fetch_spec();
+      const Range range = todo.front(); todo.pop_front();
+      const int64_t f1 = std::min(range.f1, range.f0 + std::max<int64_t>(1, sp.part_frags));
+      if (f1 < range.f1) todo.push_front(Range{f1, range.f1, range.unfused});
+      Run r{range.f0, f1, sp, todo.empty() && npairs > 0};
+      r.forced_unfused = range.unfused;
+      if (r.with_rows) rows_valid = false;
+      launch_part(r);
+      if (!judge_part(r)) {
         todo.push_front(Range{r.f0, r.f1, r.forced_unfused});
-        rows_valid = false;                     // (rows formed meanwhile lack this part)
+        rows_valid = false;                     // (rows formed before lack this part)
       }
     }
     int64_t nrows = 0;
     if (npairs > 0) {
       if (!rows_valid) {
         // a part was repeated after the rows had been formed: form them again, behind everything
-        Workspace &ln = w;
-        join_lanes(0);
-        FA_HIP(hipMemsetAsync(&ln.status.p->counters[4], 0, sizeof(uint32_t), ln.stream));
-        FA_HIP(hipMemsetAsync(&ln.status.p->total_rows, 0, sizeof(int32_t), ln.stream));
+        FA_HIP(hipMemsetAsync(&w.status.p->counters[4], 0, sizeof(uint32_t), st));
+        FA_HIP(hipMemsetAsync(&w.status.p->total_rows, 0, sizeof(int32_t), st));
         PassStatus *h_dev = nullptr;
-        FA_HIP(hipHostGetDevicePointer((void **)&h_dev, ln.h_status, 0));
-        const PublishArgs pub = publish_args(ln.status.p, h_dev, ++ln.seq, rows_dev + row_base, host_rows ? host_rows + row_base : nullptr, cap - row_base);
-        if (!launch_rows(ln, pub)) hipLaunchKernelGGL(k_publish_status, dim3(1), dim3(256), 0, ln.stream, pub);
-        wait_published(ln.h_status, ln.seq, ln.stream);
-        rows_lane = 0;
+        FA_HIP(hipHostGetDevicePointer((void **)&h_dev, w.h_status, 0));
+        const PublishArgs pub = publish_args(w.status.p, h_dev, ++w.seq, rows_dev + row_base, host_rows ? host_rows + row_base : nullptr, cap - row_base);
+        if (!launch_rows(pub)) hipLaunchKernelGGL(k_publish_status, dim3(1), dim3(256), 0, st, pub);
+        wait_published(w.h_status, w.seq, st);
       }
-      nrows = lanes[rows_lane]->h_status->total_rows;
+      nrows = w.h_status->total_rows;
     }
     if (t_end > t_begin) w.last_ms[4] += (float)((double)(t_end - t_begin) * 1e-5);   // device wall time of the pass
     FA_REQUIRE(nrows <= cap - row_base, FA_ERR_INVALID, "row buffer too small");
@@ -2722,19 +2533,13 @@ int fa_mapper_query(fa_mapper *m, const void *const *contigs, const int64_t *len
   });
 }
 
-// The parts of the last pass, in fragment order: a pass is pipelined over up to three lanes (run_query_pass), every
-// lane still holds the intermediates of the last part it ran.
-static std::vector<Workspace *> lanes_of_last_pass(Workspace &w) {
-  std::vector<Workspace *> v;
-  for (Workspace *x : {&w, w.sub[0].get(), w.sub[1].get()}) if (x && x->serial == w.serial && x->last_F > 0) v.push_back(x);
-  std::sort(v.begin(), v.end(), [](const Workspace *a, const Workspace *b) { return a->last_f0 < b->last_f0; });
-  // a pass that ran in more parts than there are lanes (several passes of one genome, or parts that were repeated) has
-  // left only its last parts behind: say so instead of handing out a fraction of the pass as if it were all of it
-  int64_t covered = 0;
-  for (const Workspace *x : v) covered += x->last_F;
-  FA_REQUIRE(covered == w.pass_F, FA_ERR_UNSUPPORTED,
+// The workspace holds the intermediates of the last part it ran.  A pass that ran in more parts (several passes of one
+// genome, or parts that were repeated) has left only its last part behind: say so instead of handing out a fraction of
+// the pass as if it were all of it.  Returns whether the workspace holds a pass at all.
+static bool holds_last_pass(const Workspace &w) {
+  FA_REQUIRE(w.last_F == w.pass_F, FA_ERR_UNSUPPORTED,
              "the stage getters hold the last part of every lane only, and the last pass ran in more parts than that");
-  return v;
+  return w.last_F > 0;
 }
 int fa_mapper_debug_mappings(fa_mapper *m, fa_mapping *out, int64_t cap, int64_t *n) {
   return guarded([&] {
@@ -2743,25 +2548,25 @@ int fa_mapper_debug_mappings(fa_mapper *m, fa_mapping *out, int64_t cap, int64_t
     Workspace &w = m->ws[m->last_ws];
     ensure_luts(*m, 1);
     int64_t k = 0;
-    for (Workspace *x : lanes_of_last_pass(w)) {
-      const uint32_t L = x->last_loci;
-      std::vector<int32_t> lf(L), ls(L), lp(L), lsh(L), qs((size_t)x->last_F);
+    if (holds_last_pass(w)) {
+      const uint32_t L = w.last_loci;
+      std::vector<int32_t> lf(L), ls(L), lp(L), lsh(L), qs((size_t)w.last_F);
       size_t at = 0;
-      for_each_locus_slice(*x, [&](size_t first, size_t count) {
-        FA_HIP(hipMemcpyAsync(lf.data() + at, x->l_frag.p + first, count * 4, hipMemcpyDeviceToHost, x->stream));
-        FA_HIP(hipMemcpyAsync(ls.data() + at, x->l_seq.p + first, count * 4, hipMemcpyDeviceToHost, x->stream));
-        FA_HIP(hipMemcpyAsync(lp.data() + at, x->l_pos.p + first, count * 4, hipMemcpyDeviceToHost, x->stream));
-        FA_HIP(hipMemcpyAsync(lsh.data() + at, x->l_shared.p + first, count * 4, hipMemcpyDeviceToHost, x->stream));
+      for_each_locus_slice(w, [&](size_t first, size_t count) {
+        FA_HIP(hipMemcpyAsync(lf.data() + at, w.l_frag.p + first, count * 4, hipMemcpyDeviceToHost, w.stream));
+        FA_HIP(hipMemcpyAsync(ls.data() + at, w.l_seq.p + first, count * 4, hipMemcpyDeviceToHost, w.stream));
+        FA_HIP(hipMemcpyAsync(lp.data() + at, w.l_pos.p + first, count * 4, hipMemcpyDeviceToHost, w.stream));
+        FA_HIP(hipMemcpyAsync(lsh.data() + at, w.l_shared.p + first, count * 4, hipMemcpyDeviceToHost, w.stream));
         at += count;
       });
-      x->q_size.download(qs.data(), (size_t)x->last_F, x->stream);
-      FA_HIP(hipStreamSynchronize(x->stream));
+      w.q_size.download(qs.data(), (size_t)w.last_F, w.stream);
+      FA_HIP(hipStreamSynchronize(w.stream));
       for (uint32_t i = 0; i < L; i++) {
         int s = qs[lf[i]];
         if (lsh[i] < m->stats.pass_shared[s]) continue;
         if (k < cap) {
           fa_mapping r;
-          r.query_seq_id = lf[i] + (int32_t)(x->last_f0 - w.pass_f0); r.ref_seq_id = ls[i]; r.ref_start_pos = lp[i]; r.sketch_size = s;
+          r.query_seq_id = lf[i]; r.ref_seq_id = ls[i]; r.ref_start_pos = lp[i]; r.sketch_size = s;
           r.conserved = lsh[i]; r.query_id = 0;
           out[k] = r;
         }
@@ -2777,21 +2582,18 @@ int fa_mapper_debug_l1(fa_mapper *m, int32_t *frag, int32_t *seq_id, int32_t *rs
     bind_device(m->device);
     Workspace &w = m->ws[m->last_ws];
     int64_t k = 0;
-    for (Workspace *x : lanes_of_last_pass(w)) {
-      int64_t kk = k;
-      for_each_locus_slice(*x, [&](size_t first, size_t count) {
-        const size_t c = (size_t)std::max<int64_t>(0, std::min<int64_t>((int64_t)count, cap - kk));
+    if (holds_last_pass(w)) {
+      for_each_locus_slice(w, [&](size_t first, size_t count) {
+        const size_t c = (size_t)std::max<int64_t>(0, std::min<int64_t>((int64_t)count, cap - k));
         if (c) {
-          FA_HIP(hipMemcpyAsync(frag + kk, x->l_frag.p + first, c * 4, hipMemcpyDeviceToHost, x->stream));
-          FA_HIP(hipMemcpyAsync(seq_id + kk, x->l_seq.p + first, c * 4, hipMemcpyDeviceToHost, x->stream));
-          FA_HIP(hipMemcpyAsync(rs + kk, x->l_start.p + first, c * 4, hipMemcpyDeviceToHost, x->stream));
-          FA_HIP(hipMemcpyAsync(re + kk, x->l_end.p + first, c * 4, hipMemcpyDeviceToHost, x->stream));
+          FA_HIP(hipMemcpyAsync(frag + k, w.l_frag.p + first, c * 4, hipMemcpyDeviceToHost, w.stream));
+          FA_HIP(hipMemcpyAsync(seq_id + k, w.l_seq.p + first, c * 4, hipMemcpyDeviceToHost, w.stream));
+          FA_HIP(hipMemcpyAsync(rs + k, w.l_start.p + first, c * 4, hipMemcpyDeviceToHost, w.stream));
+          FA_HIP(hipMemcpyAsync(re + k, w.l_end.p + first, c * 4, hipMemcpyDeviceToHost, w.stream));
         }
-        kk += (int64_t)count;
+        k += (int64_t)count;
       });
-      FA_HIP(hipStreamSynchronize(x->stream));
-      for (int64_t i = k; i < std::min<int64_t>(kk, cap); i++) frag[i] += (int32_t)(x->last_f0 - w.pass_f0);
-      k = kk;
+      FA_HIP(hipStreamSynchronize(w.stream));
     }
     *n = k;
   });
@@ -2801,17 +2603,12 @@ int fa_mapper_debug_query_sketch(fa_mapper *m, int64_t fragment, uint32_t *hashe
     std::lock_guard<std::mutex> lock(m->mtx);
     bind_device(m->device);
     Workspace &w = m->ws[m->last_ws];
-    for (Workspace *x : lanes_of_last_pass(w)) {
-      const int64_t local = fragment - (x->last_f0 - w.pass_f0);
-      if (local < 0 || local >= x->last_F) continue;
-      int32_t s = 0;
-      FA_HIP(hipMemcpy(&s, x->q_size.p + local, 4, hipMemcpyDeviceToHost));
-      *sketch_size = s;
-      int c = std::min(s, cap);
-      if (c > 0) FA_HIP(hipMemcpy(hashes, x->q_hash.p + (size_t)local * m->qcap, (size_t)c * 4, hipMemcpyDeviceToHost));
-      return;
-    }
-    throw Error(FA_ERR_INVALID, "fragment out of range");
+    if (!holds_last_pass(w) || fragment < 0 || fragment >= w.last_F) throw Error(FA_ERR_INVALID, "fragment out of range");
+    int32_t s = 0;
+    FA_HIP(hipMemcpy(&s, w.q_size.p + fragment, 4, hipMemcpyDeviceToHost));
+    *sketch_size = s;
+    int c = std::min(s, cap);
+    if (c > 0) FA_HIP(hipMemcpy(hashes, w.q_hash.p + (size_t)fragment * m->qcap, (size_t)c * 4, hipMemcpyDeviceToHost));
   });
 }
 int fa_debug_sketch_sequence(const fa_params *params, const void *data, int64_t length, int char_width, uint32_t *hash,
@@ -2892,13 +2689,13 @@ int fa_mapper_debug_locus_events(fa_mapper *m, uint32_t *events, int64_t cap, in
     bind_device(m->device);
     Workspace &w = m->ws[m->last_ws];
     int64_t k = 0;
-    for (Workspace *x : lanes_of_last_pass(w)) {
-      for_each_locus_slice(*x, [&](size_t first, size_t count) {
+    if (holds_last_pass(w)) {
+      for_each_locus_slice(w, [&](size_t first, size_t count) {
         const size_t c = (size_t)std::max<int64_t>(0, std::min<int64_t>((int64_t)count, cap - k));
-        if (c) FA_HIP(hipMemcpyAsync(events + k, x->l_nev.p + first, c * 4, hipMemcpyDeviceToHost, x->stream));
+        if (c) FA_HIP(hipMemcpyAsync(events + k, w.l_nev.p + first, c * 4, hipMemcpyDeviceToHost, w.stream));
         k += (int64_t)count;
       });
-      FA_HIP(hipStreamSynchronize(x->stream));
+      FA_HIP(hipStreamSynchronize(w.stream));
     }
     *n = k;
   });

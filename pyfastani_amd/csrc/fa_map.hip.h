@@ -292,10 +292,6 @@ struct IndexView {
   const uint32_t *wrap_rec;     // [n_wraps] first record behind every 2^32 boundary of that coordinate
   int32_t n_wraps;
   int32_t gpos_bits;            // width of the low word (32; FA_GPOS_BITS shrinks it for the tests)
-#ifdef FA_EXPERIMENTS
-  const uint32_t *ev_bits;      // merged admit / drop order of the L2 slide, one bit per event (k_event_bits)
-  const uint2 *rec_hf;          // (hash, flags | distance to the previous record of the hash << 8) for k_l2_fused
-#endif
   const uint32_t *uniq_hash;
   const uint32_t *uniq_off;
   const uint32_t *pos_ridx;
@@ -2011,10 +2007,6 @@ struct L2Args {
   uint32_t *scan_hist, *scan_cursor; // [loci.n][SCAN_CLASSES] loci per class / placed so far
   uint32_t *scan_order;              // [loci capacity] locus numbers, region by region (nullptr: the identity)
   int32_t scan_class_div;            // events per class; 0 = no ordering
-#ifdef FA_EXPERIMENTS
-  int32_t dbg;                       // FA_FUSED_DEBUG (timing experiments only, results are void): 1 = slider idles,
-                                     // 2 = producer composes no events, 4 = producer issues no loads
-#endif
 };
 
 constexpr int L2_THREADS = 64;
@@ -2039,46 +2031,42 @@ template <typename T> constexpr uint32_t ev_noeval() { return 1u << (8 * sizeof(
 template <typename T> constexpr uint32_t ev_slot_mask() { return ((1u << EvBits<T>::RANK) - 1u) << EV_SLOT; }
 static_assert(EV_SLOT + EvBits<uint16_t>::RANK == 15 && EV_SLOT + EvBits<uint32_t>::RANK <= 31, "event fields overlap");
 
-// Bucket table resolution of k_l2_events: 4096 buckets over the hash range of ~250 sketch entries leave at most two
-// entries in all but a few buckets, so a rank lookup is one table read and one two-entry probe.
-#ifndef FA_EV_QT_BITS
-#define FA_EV_QT_BITS 12
-#endif
 #ifndef FA_EV_WAVES
 #define FA_EV_WAVES 8
 #endif
-constexpr int EV_QT_BITS = FA_EV_QT_BITS;
 constexpr int EV_WAVES_PER_SIMD = FA_EV_WAVES;
-constexpr int EV_PROBE = 4;                // sketch entries compared at once per rank lookup
+// sentinel entries (0xFFFFFFFF) behind the staged query sketch of k_l2_events: a rank look-up reads the entries at ranks x
+// and x + 1 for an x up to s, and a walk stops at the first sentinel.  (Four where two would do: the LDS footprint the
+// kernel's occupancy was set with, from the four-entry probe of rounds 2-5.)
+constexpr int EV_SENTINELS = 4;
 #ifndef FA_EV_RPL
 #define FA_EV_RPL 4
 #endif
 constexpr int EV_RPL = FA_EV_RPL;          // records per lane and trip of k_l2_events
 static_assert(EV_RPL >= 1 && EV_RPL <= 4, "the last trip of a phase is dispatched on 1..4 records per lane");
-__host__ __device__ inline size_t ev_sketch_bytes(int cnt_slots) { return ((size_t)(cnt_slots - 1 + EV_PROBE) * 4 + 15) / 16 * 16; }   // + sentinels
+__host__ __device__ inline size_t ev_sketch_bytes(int cnt_slots) { return ((size_t)(cnt_slots - 1 + EV_SENTINELS) * 4 + 15) / 16 * 16; }
 
-// RK = the rank structure (round 6).  0: the bucket table above + EV_PROBE sketch entries per look-up (rounds 2-5: one table read,
-// four sketch reads, four compare-and-adds, a read of the entry at the final rank: seven LDS instructions with the store).
-// 1: an OCCUPANCY word per bucket -- 2^EV_OCC_BITS buckets of 32 sub-buckets over the same hash range, i.e. 8 times the resolution
-// in three quarters of the LDS: OCC[b] bit j = some sketch hash falls into sub-bucket j of bucket b, R0[b] = sketch entries below
+// The rank structure (round 6): an OCCUPANCY word per bucket -- 2^EV_OCC_BITS buckets of 32 sub-buckets over the hash range
+// of the query sketch: OCC[b] bit j = some sketch hash falls into sub-bucket j of bucket b, R0[b] = sketch entries below
 // bucket b.  The rank of a reference hash is R0[b] + popcount(OCC[b] below its sub-bucket) -- a shift and ONE v_bcnt, which adds
 // R0 in the same instruction --, exact unless a sketch hash shares its sub-bucket: the TWO sketch entries from that rank on (one
 // ds_read2) settle that case and the membership test in the same step; only a hash with two sketch entries of its own sub-bucket
-// below it walks on.  Four LDS instructions per record instead of seven.  (64-bit words, 2^16 sub-buckets: the same time, more
-// vector instructions -- a 64-bit shift and two counts; profiles/EXPERIMENTS.md, round 6.)
+// below it walks on.  Four LDS instructions per record, where the bucket table + four-entry probe of rounds 2-5 took seven
+// (profiles/r06_ev_rank_ab.txt).  (64-bit words, 2^16 sub-buckets: the same time, more vector instructions -- a 64-bit shift
+// and two counts; profiles/EXPERIMENTS.md, round 6.)
+// PACKED: the records are read from the packed layout (rec_hg, rec_prev16), else from the plain arrays.
 constexpr int EV_OCC_BITS = 10, EV_SUB_BITS = 5;
-template <typename T, bool PACKED, int RK>
+template <typename T, bool PACKED>
 __global__ __launch_bounds__(EV_THREADS, EV_WAVES_PER_SIMD) void k_l2_events(L2Args a) {
   extern __shared__ __align__(16) unsigned char lds[];
   stage_stamp(a.stamp);
-  uint32_t *Q = (uint32_t *)lds;                                     // [s + EV_PROBE], staged once per fragment, with sentinels
-  constexpr int QT_BITS = RK ? EV_OCC_BITS + EV_SUB_BITS : EV_QT_BITS;   // resolution of the table over the hash range, in bits
+  uint32_t *Q = (uint32_t *)lds;                                     // [s + EV_SENTINELS], staged once per fragment, with sentinels
+  constexpr int QT_BITS = EV_OCC_BITS + EV_SUB_BITS;                 // resolution of the table over the hash range, in bits
   constexpr int OCC_N = (1 << EV_OCC_BITS) + 1;                      // (+ the bucket behind the range: rank s, nothing occupied)
   constexpr uint32_t SUB_MASK = (1u << EV_SUB_BITS) - 1u;
   static_assert(EV_SUB_BITS == 5, "one 32-bit occupancy word per bucket");
-  __shared__ __align__(8) unsigned char rank_table[RK ? OCC_N * 4 + (OCC_N + 1) * 2 : ((1 << EV_QT_BITS) + 2) * 2];
-  uint16_t *const QT = (uint16_t *)rank_table;                       // RK == 0
-  uint32_t *const OCC = (uint32_t *)rank_table;                      // RK == 1
+  __shared__ __align__(8) unsigned char rank_table[OCC_N * 4 + (OCC_N + 1) * 2];
+  uint32_t *const OCC = (uint32_t *)rank_table;
   uint16_t *const R0 = (uint16_t *)(rank_table + OCC_N * 4);
   const int f = a.frag_order ? a.frag_order[blockIdx.x] : (int)blockIdx.x;
   if (f < 0) return;
@@ -2087,9 +2075,8 @@ __global__ __launch_bounds__(EV_THREADS, EV_WAVES_PER_SIMD) void k_l2_events(L2A
   const int s = a.q_size[f];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   if (a.counters[2] || s > a.cnt_slots - 1) return;                  // loci overflowed / sketch larger than speculated: void pass
-  for (int i = threadIdx.x; i < s + EV_PROBE; i += EV_THREADS) Q[i] = i < s ? a.q_hash[(size_t)f * a.qcap + i] : 0xFFFFFFFFu;
-  if constexpr (RK) { for (int b = threadIdx.x; b < OCC_N; b += EV_THREADS) { OCC[b] = 0u; R0[b] = (uint16_t)s; } }
-  else { for (int b = threadIdx.x; b <= (1 << QT_BITS) + 1; b += EV_THREADS) QT[b] = (uint16_t)s; }
+  for (int i = threadIdx.x; i < s + EV_SENTINELS; i += EV_THREADS) Q[i] = i < s ? a.q_hash[(size_t)f * a.qcap + i] : 0xFFFFFFFFu;
+  for (int b = threadIdx.x; b < OCC_N; b += EV_THREADS) { OCC[b] = 0u; R0[b] = (uint16_t)s; }
   // ---- record range of every locus (the three searchIndex calls of computeL2MappedRegions) and its event count ----
   __shared__ uint32_t sh_wave[EV_THREADS / 64];
   __shared__ uint32_t sh_run, sh_base, sh_ok;
@@ -2156,22 +2143,17 @@ __global__ __launch_bounds__(EV_THREADS, EV_WAVES_PER_SIMD) void k_l2_events(L2A
     sh_base = (uint32_t)(region * a.region_cap + base);
     atomicAdd(&a.rec_region[region], sh_records);
   }
-  // Bucket table over the hash range the query sketch actually spans: minimizer hashes are window minima, i.e. heavily
-  // skewed towards 0, so the buckets divide [0, 2^bits) with 2^bits > the largest query hash rather than the full 32-bit
-  // range.  QT[b] = first query rank whose hash is >= b << qshift (rank i opens the buckets after the one of rank i-1,
-  // up to its own); a reference hash beyond the range ranks after all.
+  // Buckets over the hash range the query sketch actually spans: minimizer hashes are window minima, i.e. heavily skewed
+  // towards 0, so the sub-buckets divide [0, 2^bits) with 2^bits > the largest query hash rather than the full 32-bit
+  // range.  R0[b] = first query rank whose hash is >= the start of bucket b (rank i opens the buckets after the one of
+  // rank i-1, up to its own); a reference hash beyond the range ranks after all.
   const uint32_t hmax = s > 0 ? Q[s - 1] : 0u;
   const int qshift = max(0, (32 - __clz((int)(hmax | 1u))) - QT_BITS);   // hmax < 2^(qshift + QT_BITS)
   for (int i = threadIdx.x; i < s; i += EV_THREADS) {
-    if constexpr (RK) {
-      const uint32_t sb = Q[i] >> qshift;                            // sub-bucket of sketch entry i (< 2^QT_BITS: hmax fits)
-      atomicOr(&OCC[sb >> EV_SUB_BITS], 1u << (sb & SUB_MASK));
-      const int bi = (int)(sb >> EV_SUB_BITS), bp = i ? (int)(Q[i - 1] >> qshift >> EV_SUB_BITS) : -1;
-      for (int b = bp + 1; b <= bi; b++) R0[b] = (uint16_t)i;         // first rank at or behind the start of bucket b
-    } else {
-      const int bi = (int)(Q[i] >> qshift), bp = i ? (int)(Q[i - 1] >> qshift) : -1;
-      for (int b = bp + 1; b <= bi; b++) QT[b] = (uint16_t)i;
-    }
+    const uint32_t sb = Q[i] >> qshift;                              // sub-bucket of sketch entry i (< 2^QT_BITS: hmax fits)
+    atomicOr(&OCC[sb >> EV_SUB_BITS], 1u << (sb & SUB_MASK));
+    const int bi = (int)(sb >> EV_SUB_BITS), bp = i ? (int)(Q[i - 1] >> qshift >> EV_SUB_BITS) : -1;
+    for (int b = bp + 1; b <= bi; b++) R0[b] = (uint16_t)i;           // first rank at or behind the start of bucket b
   }
   __syncthreads();
   if (!sh_ok) {                                                      // the event buffer is too small: void pass
@@ -2230,65 +2212,35 @@ __global__ __launch_bounds__(EV_THREADS, EV_WAVES_PER_SIMD) void k_l2_events(L2A
     constexpr int R = decltype(rpl_tag)::value;
     const int beg = p.beg, end0 = p.end0, ndrop = p.ndrop;
     const int n_init_pad = (end0 - beg + 7) & ~7;
-    // rank of a reference hash among the query hashes and whether it is one of them: the bucket's first rank, then
-    // EV_PROBE sketch entries at once; the few hashes that rank behind all of them walk on (the sentinels stop the
-    // walk).  Both the sketch and the reference hashes crowd towards 0, so two entries were not enough: nine trips out
-    // of ten still took the walk.
-    // (membership is read off the entry AT the final rank -- the sketch is sorted and distinct, so that entry is the first
-    // one >= the hash: one more LDS read instead of four equality tests whose results, kept as booleans across the walk,
-    // the compiler packed into bytes at ten instructions per record)
+    // rank of a reference hash among the query hashes and whether it is one of them (the rank structure above; the
+    // sentinels stop the walk)
     int x[R]; bool found[R];
-    if constexpr (RK) {
-      uint32_t occ[R], r0[R], q0[R], q1[R]; bool more = false;
-#pragma unroll
-      for (int u = 0; u < R; u++) {
-        const uint32_t b = min(t.h[u] >> (qshift + EV_SUB_BITS), (uint32_t)(1 << EV_OCC_BITS));   // the bucket behind the range: rank s
-        occ[u] = OCC[b]; r0[u] = R0[b];
-      }
-#pragma unroll
-      for (int u = 0; u < R; u++) {
-        // sketch entries of the bucket in sub-buckets BELOW the hash's own: shift its own bit to the top, count, take it off
-        // (the shift distance 31 - sub is the complement of the sub-bucket number: the shifter reads five bits)
-        const uint32_t top = occ[u] << (~(t.h[u] >> qshift) & SUB_MASK);
-        x[u] = (int)((uint32_t)__builtin_popcount(top) + r0[u] - (top >> 31));
-      }
-#pragma unroll
-      for (int u = 0; u < R; u++) { q0[u] = Q[x[u]]; q1[u] = Q[x[u] + 1]; }   // (one ds_read2_b32)
-#pragma unroll
-      for (int u = 0; u < R; u++) {
-        // the sketch is sorted and distinct: the hash ranks behind q0 if q0 is smaller, and is a sketch hash iff it equals the
-        // entry at its rank -- q0, or q1 when q0 is smaller
-        found[u] = q0[u] == t.h[u] || q1[u] == t.h[u];
-        x[u] += q0[u] < t.h[u] ? 1 : 0;
-        more = more || q1[u] < t.h[u];
-      }
-      if (__builtin_amdgcn_ballot_w64(more)) {                       // two sketch entries of its own sub-bucket below it: walk on
-#pragma unroll
-        for (int u = 0; u < R; u++) if (q1[u] < t.h[u]) { x[u]++; while (Q[x[u]] < t.h[u]) x[u]++; found[u] = Q[x[u]] == t.h[u]; }
-      }
-    } else {
-    uint32_t q[R][EV_PROBE], qx[R]; bool more = false;
-#pragma unroll
-    for (int u = 0; u < R; u++) x[u] = QT[min(t.h[u] >> qshift, (uint32_t)(1 << QT_BITS))];   // the last bucket is [2^bits, inf): rank s
+    uint32_t occ[R], r0[R], q0[R], q1[R]; bool more = false;
 #pragma unroll
     for (int u = 0; u < R; u++) {
-#pragma unroll
-      for (int j = 0; j < EV_PROBE; j++) q[u][j] = Q[x[u] + j];
+      const uint32_t b = min(t.h[u] >> (qshift + EV_SUB_BITS), (uint32_t)(1 << EV_OCC_BITS));   // the bucket behind the range: rank s
+      occ[u] = OCC[b]; r0[u] = R0[b];
     }
 #pragma unroll
     for (int u = 0; u < R; u++) {
-#pragma unroll
-      for (int j = 0; j < EV_PROBE; j++) x[u] += q[u][j] < t.h[u] ? 1 : 0;     // (a compare and an add-with-carry per entry)
-      more = more || q[u][EV_PROBE - 1] < t.h[u];
-    }
-    if (__builtin_amdgcn_ballot_w64(more)) {
-#pragma unroll
-      for (int u = 0; u < R; u++) if (q[u][EV_PROBE - 1] < t.h[u]) { while (Q[x[u]] < t.h[u]) x[u]++; }
+      // sketch entries of the bucket in sub-buckets BELOW the hash's own: shift its own bit to the top, count, take it off
+      // (the shift distance 31 - sub is the complement of the sub-bucket number: the shifter reads five bits)
+      const uint32_t top = occ[u] << (~(t.h[u] >> qshift) & SUB_MASK);
+      x[u] = (int)((uint32_t)__builtin_popcount(top) + r0[u] - (top >> 31));
     }
 #pragma unroll
-    for (int u = 0; u < R; u++) qx[u] = Q[x[u]];
+    for (int u = 0; u < R; u++) { q0[u] = Q[x[u]]; q1[u] = Q[x[u] + 1]; }   // (one ds_read2_b32)
 #pragma unroll
-    for (int u = 0; u < R; u++) found[u] = qx[u] == t.h[u];
+    for (int u = 0; u < R; u++) {
+      // the sketch is sorted and distinct: the hash ranks behind q0 if q0 is smaller, and is a sketch hash iff it equals the
+      // entry at its rank -- q0, or q1 when q0 is smaller
+      found[u] = q0[u] == t.h[u] || q1[u] == t.h[u];
+      x[u] += q0[u] < t.h[u] ? 1 : 0;
+      more = more || q1[u] < t.h[u];
+    }
+    if (__builtin_amdgcn_ballot_w64(more)) {                         // two sketch entries of its own sub-bucket below it: walk on
+#pragma unroll
+      for (int u = 0; u < R; u++) if (q1[u] < t.h[u]) { x[u]++; while (Q[x[u]] < t.h[u]) x[u]++; found[u] = Q[x[u]] == t.h[u]; }
     }
     if constexpr (PACKED) {
       // Bit arithmetic instead of compare + select: this kernel runs seven waves per SIMD and IS its vector issue slots
@@ -2616,12 +2568,6 @@ __global__ __launch_bounds__(L2_THREADS) void k_l2_scan(L2Args a) {
     atomicMax(&a.group_best[a.l_group[l]], key);
   }
 }
-
-#ifdef FA_EXPERIMENTS
-}  // namespace fa
-#include "../../scripts/experiments/fa_l2_fused.hip.h"   // k_l2_fused, k_event_bits, k_pack_hf (FA_L2_FUSED=1)
-namespace fa {
-#endif
 
 // ----------------------------------------------------------------------------------------------------------
 // computeCGI.  Step 1 (best mapping per reference genome and query fragment) is the group maximum taken by

@@ -151,7 +151,7 @@ for case in range(cases):
     omm = sorted(zip(om["qseq"].tolist(), om["rseq"].tolist(), om["rstart"].tolist(), om["sketch"].tolist(), om["shared"].tolist()))
     try:
         gm = mappings(mapper)
-    except (RuntimeError, NotImplementedError) as e:   # FA_QUERY_LANES / FA_PASS_FRAGMENTS: more parts than the stage getters retain
+    except (RuntimeError, NotImplementedError) as e:   # FA_PASS_FRAGMENTS: more parts than the stage getters retain
         if "stage getters" not in str(e):
             raise
         gm = omm

@@ -1225,10 +1225,10 @@ def test_concurrent_queries_on_one_mapper():
     assert out[0] + out[1] == want
 
 
-@pytest.mark.parametrize("lanes,part", [(3, 40), (2, 0)])
-def test_parts_pipelined_over_lanes_match(lanes, part):
-    # FA_QUERY_LANES > 1 runs the parts of a pass on sub-workspaces with their own streams (run_query_pass); with tiny
-    # buffers the parts are also declared void and repeated while other parts are in flight: same rows, same mappings
+@pytest.mark.parametrize("part", [40, 0])
+def test_parts_of_a_pass_match(part):
+    # FA_PASS_FRAGMENTS cuts a pass into parts (run_query_pass); with tiny buffers parts are also declared void and
+    # repeated: same rows, same mappings
     import subprocess
     import textwrap
     code = textwrap.dedent("""
@@ -1244,13 +1244,13 @@ def test_parts_pipelined_over_lanes_match(lanes, part):
         refs = [[syn.to_ascii(syn.mutate_codes(g, anc, d))] for d in (0.01, 0.05, 0.1, 0.15)]
         q = [syn.to_ascii(syn.mutate_codes(g, anc, 0.03))]
         mapper, hits, ohits, det = T.run_both({}, refs, q, threads=8)
-        if not os.environ.get("FA_PASS_FRAGMENTS"):      # (the stage getters keep the last part of every lane only)
+        if not os.environ.get("FA_PASS_FRAGMENTS"):      # (the stage getters keep the last part of a pass only)
             assert T.gpu_mappings(mapper) == T.oracle_mappings(det), "mappings"
         assert T.hit_tuples(hits) == ohits and len(ohits) == 4, "hits"
         ms = (T.C.c_float * 16)(); T.lib.fa_mapper_last_timings(mapper._h, ms, 16)
         print(json.dumps({"retries": ms[9], "loci": ms[6]}))
     """) % (ROOT, ROOT)
-    env = dict(os.environ, FA_QUERY_LANES=str(lanes), FA_LANE_MIN_FRAGMENTS="64")
+    env = dict(os.environ)
     if part:
         env.update(FA_PASS_FRAGMENTS=str(part), FA_LOCI_CAP_MIN="64", FA_EVENTS_CAP_MIN="4096")
     res = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, env=env)
@@ -1350,8 +1350,9 @@ def test_device_memory_is_stable():
     ({"fragment_length": 20_000, "k": 14}, {}),
 ])
 def test_unpacked_record_geometry(params, env, monkeypatch):
-    # k_l2_events<T, false>: the form every index takes whose fragment length leaves no room for the 13-bit distances of
-    # rec_hg (fa_engine.hip, packed_geo), and FA_NO_PACKED_GEO forces on any index
+    # k_l2_events<T, false> (records from the plain arrays, occupancy-word ranks like the packed form): the form every index
+    # takes whose fragment length leaves no room for the 13-bit distances of rec_hg (fa_engine.hip, packed_geo), and
+    # FA_NO_PACKED_GEO forces on any index
     for key, val in env.items():
         monkeypatch.setenv(key, val)
     g = syn.rng(133)
@@ -1748,14 +1749,14 @@ def test_handles_released_from_a_thread_that_never_entered_the_library():
 
 
 @pytest.mark.parametrize("env", [{"FA_L1_PREFILTER": "1"}, {"FA_L1_PREFILTER": "1", "FA_L1_THIN_SMALL": "0", "FA_L1_THIN_MID": "0"},
-                                 {"FA_L1_THIN_SMALL": "2"}, {"FA_EV_RANK": "0"}, {"FA_L2_SCAN_ORDER": "1"}, {"FA_L2_SCAN_ORDER": "0"}],
-                         ids=["prefilter", "prefilter+every-class", "small-in-middle-form", "probe-ranks", "scan-sorted", "scan-identity"])
+                                 {"FA_L1_THIN_SMALL": "2"}, {"FA_NO_PACKED_GEO": "1"}, {"FA_L2_SCAN_ORDER": "1"}, {"FA_L2_SCAN_ORDER": "0"}],
+                         ids=["prefilter", "prefilter+every-class", "small-in-middle-form", "unpacked-geometry", "scan-sorted", "scan-identity"])
 def test_round6_kernel_forms_forced(env):
     """The forms of round 6 that the defaults only pick on large or unusual indices, forced onto the tests whose inputs reach them:
     the pre-filter of k_l1's block sort on every index (chance hits, planted repeats, the frequency threshold, seed counts across
     the merge tiers, the random-seed regime); every size class of k_l1 with a launch of its own / the small class folded into the
-    512-thread form (the genome-like genomes hold fragments of all three classes); k_l2_events with the rank structure of rounds
-    2-5; k_l2_scan over loci sorted by stream length on passes of any size, and never.  Same oracle, same bit-exact bar."""
+    512-thread form (the genome-like genomes hold fragments of all three classes); k_l2_events reading the records from the plain
+    arrays instead of the packed layout; k_l2_scan over loci sorted by stream length on passes of any size, and never.  Same oracle, same bit-exact bar."""
     import subprocess
     pick = ("test_genome_like or test_frequency_threshold_active or test_seed_counts_across_the_merge_tiers or test_random_seed_regime "
             "or test_l1_candidates or test_end_to_end_vs_oracle or test_seed_overflow_to_hbm_scratch or test_small_sketch_against_crowded_window "
