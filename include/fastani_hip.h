@@ -263,6 +263,18 @@ int fa_mapper_debug_locus_events(fa_mapper *m, uint32_t *events, int64_t cap, in
  * stage ran as ONE launch (k_query_fused), [18] parts that ran K1 and the fragment sketch as two kernels, [19] parts whose
  * k_l2_events workgroups ran in the offset-major order; [23] positions per tile of the last fa_bench_sketch_kernel.  n <= 24. */
 int fa_mapper_last_timings(fa_mapper *m, float *ms, int n);
+/* The speculation record a mapper keeps across its calls, and the kernel forms of the last accepted part of the most
+ * recently finished call: out[0 .. n) (entries beyond the 29 below are 0).  Reads only; takes the mapper lock.
+ * Mapper-wide: [0] initialised, [1] smax (sketch bound of the LUTs and L2 tables), [2] seed_slots (LDS seed slots of k_l1,
+ * follow the latest pass), [3] [4] [5] shares of the last accepted part's fragments in the small / middle / tiny size classes
+ * of k_l1, in parts per million (-1 000 000: none seen yet), [6] l1_prefilter (sticky), [7] l1_no_small (sticky), [8] loci of
+ * the last accepted part (l2_loci_last), [9] redo: the wide-state scan is launched (sticky), [10] fragments per part
+ * (shrinks only), [11] fuse_skip, [12] fuse_penalty (back-off of k_query_fused), [13] smax_misses, [14] scratch words,
+ * [15] slide-event capacity, [16] loci capacity.
+ * Last part: [17] k_l1 launches (size classes), [18] [19] [20] their thread counts (0: none), [21] pre-filter on, [22] k_l2_scan
+ * over sorted loci, [23] 32-bit slide events, [24] k_query_fused, [25] offset-major k_l2_events order, [26] wide-state scan
+ * launched, [27] the sketch bound it ran with, [28] seed slots of its last k_l1 class.  A call that ran no part leaves 17-28 at 0. */
+int fa_mapper_debug_spec(fa_mapper *m, int64_t *out, int n);
 /* on != 0: also bracket the L2 stage of every pass with two HIP events (slot [16] above).  Off by default: an event
  * record costs the stream about as much as a small kernel. */
 int fa_mapper_set_stage_events(fa_mapper *m, int on);

@@ -118,6 +118,7 @@ SIGNATURES = {
     "fa_mapper_debug_locus_events": (_i32, [_vp, _vp, _i64, _vp]),
     "fa_mapper_debug_links": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "fa_mapper_last_timings": (_i32, [_vp, _P(_f32), _i32]),
+    "fa_mapper_debug_spec": (_i32, [_vp, _P(_i64), _i32]),
     "fa_mapper_set_stage_events": (_i32, [_vp, _i32]),
     "fa_mapper_stream": (_i32, [_vp, _P(_vp)]),
     "fa_bench_sketch_kernel": (_i32, [_vp, _vp, _i32, _P(_f32), _P(_u64), _P(_u64)]),

@@ -502,6 +502,14 @@ struct Workspace {
   float last_ms[24] = {0};
   hipEvent_t ev[6] = {nullptr};
   int64_t pass_F = 0;                 // fragments of the last pass
+  // the kernel forms of a part (fa_mapper_debug_spec): those of the part in flight, and those of the last part accepted in the
+  // last call (cleared when a call starts)
+  struct Forms {
+    int n_l1 = 0, l1_threads[3] = {0, 0, 0};
+    bool prefilter = false, scan_sorted = false, wide = false, fused = false, ordered = false, redo = false;
+    int smax = 0;
+    uint32_t seed_slots = 0;
+  } forms, last_forms;
   // the one-query-at-a-time call (fa_mapper_query) recycles its batch object -- no device allocation per call -- and
   // builds the upload image in pinned memory; its rows come back through a pinned block too
   std::unique_ptr<fa_genomes> query_batch;
@@ -1214,6 +1222,11 @@ struct QueryPass {
     w.l1_pf = p.l1_prefilter; w.l1_small_class = p.n_l1 > 1 && p.l1[0].nt == 256;
     p.wide = smax + 1 >= (1 << EvBits<uint16_t>::RANK);        // slot = rank + 1 must fit the slot field of the 16-bit event
     w.items.ensure(((size_t)sp.items_cap + 8) * (p.wide ? 4 : 2));
+    w.forms = Workspace::Forms();
+    w.forms.n_l1 = p.n_l1;
+    for (int c = 0; c < p.n_l1; c++) w.forms.l1_threads[c] = p.l1[c].nt;
+    w.forms.prefilter = p.l1_prefilter; w.forms.scan_sorted = p.scan_sorted; w.forms.wide = p.wide; w.forms.redo = sp.redo;
+    w.forms.smax = smax; w.forms.seed_slots = p.seed_slots;
 
     launch_sketch_stage(r, p);
     prepare_order(p);
@@ -1588,6 +1601,8 @@ struct QueryPass {
     }
     w.last_ms[r.fused ? 17 : 18] += 1.0f;
     if (r.ordered) w.last_ms[19] += 1.0f;
+    w.last_forms = w.forms;
+    w.last_forms.fused = r.fused; w.last_forms.ordered = r.ordered;
     if (m.stage_events) {
       float ev_ms = 0;
       FA_HIP(hipEventSynchronize(w.ev[3]));
@@ -1675,6 +1690,7 @@ static int64_t run_query(fa_mapper &m, Workspace &w, const fa_genomes &g, int32_
   require_device();
   FA_REQUIRE(first >= 0 && count >= 0 && first + count <= g.n_genomes, FA_ERR_INVALID, "genome range out of bounds");
   for (float &x : w.last_ms) x = 0;
+  w.last_forms = Workspace::Forms();
   fa_cgi_row *dst = rows;
   if (!rows_device) { w.rows_dev.ensure((size_t)std::max<int64_t>(cap, 1)); dst = w.rows_dev.p; }
   // a call that is ONE pass and returns a modest number of rows to the host gets them written into pinned memory by the
@@ -2708,6 +2724,19 @@ int fa_mapper_set_stage_events(fa_mapper *m, int on) {
 int fa_mapper_last_timings(fa_mapper *m, float *ms, int n) {
   std::lock_guard<std::mutex> lock(m->mtx);
   for (int i = 0; i < n && i < 24; i++) ms[i] = m->ws[m->last_ws].last_ms[i];
+  return FA_OK;
+}
+int fa_mapper_debug_spec(fa_mapper *m, int64_t *out, int n) {
+  std::lock_guard<std::mutex> lock(m->mtx);
+  const fa_mapper::Spec &s = m->spec;
+  const Workspace::Forms &f = m->ws[m->last_ws].last_forms;
+  auto ppm = [](float share) { return (int64_t)std::lround((double)share * 1e6); };
+  const int64_t v[] = {s.init, s.smax, s.seed_slots, ppm(s.l1_small_share), ppm(s.l1_mid_share), ppm(s.l1_tiny_share),
+                       s.l1_prefilter, s.l1_no_small, s.l2_loci_last, s.redo, s.part_frags, s.fuse_skip, s.fuse_penalty,
+                       s.smax_misses, (int64_t)s.scratch_words, (int64_t)s.items_cap, s.l_cap,
+                       f.n_l1, f.l1_threads[0], f.l1_threads[1], f.l1_threads[2], f.prefilter, f.scan_sorted, f.wide, f.fused,
+                       f.ordered, f.redo, f.smax, f.seed_slots};
+  for (int i = 0; i < n; i++) out[i] = i < (int)(sizeof(v) / sizeof(v[0])) ? v[i] : 0;
   return FA_OK;
 }
 int fa_mapper_stream(fa_mapper *m, void **stream) { *stream = (void *)m->stream; return FA_OK; }

@@ -1,9 +1,12 @@
 """Differential fuzzing of the HIP path against the CPU oracle: random genomes with planted repeats, tandem
 duplications, inversions, N runs and low-complexity stretches; random parameters.  Every L2 mapping and every hit must
-match.  Usage: python scripts/fuzz_parity.py [cases] [seed] [seconds] [default-cell]   (stops after `seconds` if given: a time
-box; a fourth argument keeps every nucleotide case in the default cell k = 16 / fragment 3000 / 80 % with queries of plain
-ACGT -- the cell whose query passes run K1 and the fragment sketch as ONE launch, k_query_fused)"""
-import sys, os, ctypes as C, warnings, time
+match.  Usage: python scripts/fuzz_parity.py [--history] [cases] [seed] [seconds] [default-cell]   (stops after `seconds` if given: a
+time box; a fourth argument keeps every nucleotide case in the default cell k = 16 / fragment 3000 / 80 % with queries of plain
+ACGT -- the cell whose query passes run K1 and the fragment sketch as ONE launch, k_query_fused).  --history: one index per
+case, then 4-8 queries drawn from the generators (plain, tandem, drafts, N / IUPAC, batches) on the SAME mapper, each through
+a random entry point (query_draft, query_genome, GenomeBatch.query(first, count), query_fasta_stream), each compared with the
+oracle: a mapper's speculation record carries the sizes and kernel forms of one query into the next."""
+import sys, os, ctypes as C, warnings, time, tempfile
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import pyfastani_amd as pf
@@ -52,6 +55,9 @@ def to_bytes(g, codes):
         p = int(g.integers(0, len(b) - 2000)); b[p:p + 1000] = bytes(b[p:p + 1000]).lower()
     return bytes(b)
 
+history = "--history" in sys.argv
+if history:
+    sys.argv.remove("--history")
 cases = int(sys.argv[1]) if len(sys.argv) > 1 else 50
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 time_box = float(sys.argv[3]) if len(sys.argv) > 3 else 0.0
@@ -92,10 +98,81 @@ def protein_case(g, case):
         print(f"MISMATCH protein case {case} seed {seed} params {params}: {hits} vs {ohits}")
     return ok
 
+def hit_list(hits):
+    return [(h.name, h.identity, h.matches, h.fragments) for h in hits]
+
+def history_case(g, case, tmp):
+    """One index, then 4-8 queries of every kind through random entry points on the same mapper, each against the oracle."""
+    k = int(g.choice([11, 14, 16, 16, 16, 21])); frag = int(g.choice([500, 1000, 3000, 3000, 5000]))
+    params = dict(k=k, fragment_length=frag, percentage_identity=float(g.choice([75, 80, 80, 90])), minimum_fraction=float(g.choice([0.0, 0.2])))
+    osk = OracleSketch(**params)
+    if osk.window_size >= frag:
+        return True
+    sk = pf.Sketch(**params)
+    length = int(g.integers(max(3 * frag, 8000), 60_000))
+    anc = scramble(g, syn.random_codes(g, length))
+    copies = int(g.choice([1, 1, 2, 8, 30]))                   # many copies of one genome: fragments with thousands of seed hits
+    n_ref = int(g.integers(1, 5))
+    for i in range(n_ref + copies - 1):
+        d = float(g.choice([0.0, 0.01, 0.03, 0.06, 0.1])) if i < n_ref else 0.0
+        r = scramble(g, syn.mutate_codes(g, anc, d)) if g.random() < 0.5 and i < n_ref else syn.mutate_codes(g, anc, d)
+        contigs = [to_bytes(g, x) for x in syn.split_contigs(g, r, int(g.integers(1, 4)))]
+        sk.add_draft(i, contigs); osk.add_draft(i, contigs)
+    other = syn.random_codes(g, length)
+    r = to_bytes(g, other); sk.add_draft("u", [r]); osk.add_draft("u", [r])
+    mapper = sk.index(); osk.index()
+
+    def make_query():
+        kind = str(g.choice(["plain", "tandem", "draft", "dirty", "other"]))
+        src = other if kind == "other" else anc
+        c = syn.mutate_codes(g, src, float(g.choice([0.0, 0.02, 0.05, 0.1])))
+        if kind == "tandem":
+            unit = c[: int(g.integers(200, 2 * frag))]
+            c = np.concatenate([syn.mutate_codes(g, unit, 0.01) for _ in range(max(2, length // (3 * len(unit))))])
+        elif kind != "plain":
+            c = scramble(g, c)
+        pieces = syn.split_contigs(g, c, int(g.integers(2, 6))) if kind == "draft" else [c]
+        return [to_bytes(g, x) if kind == "dirty" else bytes(syn.to_ascii(x)) for x in pieces]
+
+    ok = True
+    for step in range(int(g.integers(4, 9))):
+        entry = str(g.choice(["draft", "genome", "batch", "stream"]))
+        queries = [make_query() for _ in range(int(g.integers(2, 5)) if entry in ("batch", "stream") else 1)]
+        if entry == "genome" and len(queries[0]) > 1:
+            entry = "draft"
+        if entry == "draft":
+            got = [hit_list(mapper.query_draft(queries[0]))]
+        elif entry == "genome":
+            got = [hit_list(mapper.query_genome(queries[0][0]))]
+        elif entry == "batch":
+            first = int(g.integers(0, len(queries))); count = int(g.integers(1, len(queries) - first + 1))
+            got = [hit_list(h) for h in mapper.upload_genomes(queries).query(first, count)]
+            queries = queries[first: first + count]
+        else:
+            paths = []
+            for j, q in enumerate(queries):
+                paths.append(os.path.join(tmp, f"q{step}_{j}.fa"))
+                with open(paths[-1], "wb") as f:
+                    f.write(b"".join(b">c%d\n" % i + x + b"\n" for i, x in enumerate(q)))
+            got = [None] * len(queries)
+            for first, res in mapper.query_fasta_stream(paths):
+                for j, h in enumerate(res):
+                    got[first + j] = hit_list(h)
+        want = [osk.query_draft(q, threads=8) for q in queries]
+        if got != want:
+            ok = False
+            print(f"MISMATCH history case {case} step {step} ({entry}) seed {seed} params {params} copies {copies}: {got} vs {want}")
+    return ok
+
 for case in range(cases):
     if time_box and time.time() - t0 > time_box:
         break
     done = case + 1
+    if history:
+        with warnings.catch_warnings(), tempfile.TemporaryDirectory() as tmp:
+            warnings.simplefilter("ignore")
+            bad += 0 if history_case(g, case, tmp) else 1
+        continue
     if case % 10 == 9:
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")
@@ -161,5 +238,5 @@ for case in range(cases):
         print(f"MISMATCH case {case} seed {seed} params {params} window {osk.window_size}: hits {hits} vs {ohits}; mappings gpu {len(gm)} oracle {len(omm)}")
         sg, so = set(gm), set(omm)
         print("   only gpu", sorted(sg - so)[:4], "only oracle", sorted(so - sg)[:4])
-print(f"{done} cases (seed {seed}), {bad} mismatches, {time.time() - t0:.1f} s")
+print(f"{done} {'history ' if history else ''}cases (seed {seed}), {bad} mismatches, {time.time() - t0:.1f} s")
 sys.exit(1 if bad else 0)

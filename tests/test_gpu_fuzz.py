@@ -48,3 +48,15 @@ def test_fuzz_with_the_coordinate_filter_of_large_indices_forced_on():
                          env=dict(os.environ, FA_L1_NEAR="1"), capture_output=True, text=True, timeout=2400)
     assert res.returncode == 0, f"seed {seed}\n" + res.stdout[-3000:] + res.stderr[-3000:]
     assert "0 mismatches" in res.stdout and int(res.stdout.strip().splitlines()[-1].split()[0]) == cases, res.stdout[-500:]
+
+
+def test_fuzz_histories_against_oracle():
+    """One index per case, then 4-8 queries on the same mapper -- plain, tandem, drafts, N / IUPAC, batches -- each through a random
+    entry point (query_draft, query_genome, GenomeBatch.query(first, count), query_fasta_stream): the sizes and kernel forms one
+    query leaves in the mapper's speculation record are what the next one runs with.  Every answer against the oracle."""
+    seed = (source_seed() ^ 0x3C3C3C) & 0x7FFFFFFF
+    cases = 400
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "fuzz_parity.py"), "--history", str(cases), str(seed)],
+                         capture_output=True, text=True, timeout=2400)
+    assert res.returncode == 0, f"seed {seed}\n" + res.stdout[-3000:] + res.stderr[-3000:]
+    assert "0 mismatches" in res.stdout and int(res.stdout.strip().splitlines()[-1].split()[0]) == cases, res.stdout[-500:]
