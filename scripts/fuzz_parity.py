@@ -1,11 +1,13 @@
 """Differential fuzzing of the HIP path against the CPU oracle: random genomes with planted repeats, tandem
 duplications, inversions, N runs and low-complexity stretches; random parameters.  Every L2 mapping and every hit must
-match.  Usage: python scripts/fuzz_parity.py [--history] [cases] [seed] [seconds] [default-cell]   (stops after `seconds` if given: a
+match.  Usage: python scripts/fuzz_parity.py [--history | --domain] [cases] [seed] [seconds] [default-cell]   (stops after `seconds` if given: a
 time box; a fourth argument keeps every nucleotide case in the default cell k = 16 / fragment 3000 / 80 % with queries of plain
 ACGT -- the cell whose query passes run K1 and the fragment sketch as ONE launch, k_query_fused).  --history: one index per
 case, then 4-8 queries drawn from the generators (plain, tandem, drafts, N / IUPAC, batches) on the SAME mapper, each through
 a random entry point (query_draft, query_genome, GenomeBatch.query(first, count), query_fasta_stream), each compared with the
-oracle: a mapper's speculation record carries the sizes and kernel forms of one query into the next."""
+oracle: a mapper's speculation record carries the sizes and kernel forms of one query into the next.  --domain: the ends of
+the window range -- percentage_identity from 64.5-70 (w = 2-4) and 96-100 (sketches of a handful of records), p_value from
+1e-1 to 1e-12, k from 5 to 33."""
 import sys, os, ctypes as C, warnings, time, tempfile
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -58,6 +60,9 @@ def to_bytes(g, codes):
 history = "--history" in sys.argv
 if history:
     sys.argv.remove("--history")
+domain = "--domain" in sys.argv
+if domain:
+    sys.argv.remove("--domain")
 cases = int(sys.argv[1]) if len(sys.argv) > 1 else 50
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 time_box = float(sys.argv[3]) if len(sys.argv) > 3 else 0.0
@@ -65,6 +70,7 @@ default_cell = len(sys.argv) > 4
 done = 0
 g = syn.rng(seed)
 bad = 0
+degenerate = 0
 t0 = time.time()
 AMINO = np.frombuffer(b"ACDEFGHIKLMNPQRSTVWY", dtype=np.uint8)
 
@@ -185,10 +191,15 @@ for case in range(cases):
     if default_cell:
         k, frag, pid = 16, 3000, 80.0
     params = dict(k=k, fragment_length=frag, percentage_identity=pid, minimum_fraction=minfrac)
+    if domain:
+        params["k"] = int(g.integers(5, 34))
+        params["percentage_identity"] = float(g.choice([64.5, 65, 66, 67, 68, 69, 70, 96, 97, 98, 99, 99.5, 100]))
+        params["p_value"] = float(10.0 ** -g.uniform(1, 12))
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
         osk = OracleSketch(**params)
         if osk.window_size >= frag:      # degenerate cell: nothing maps; covered by the unit tests
+            degenerate += 1
             continue
         sk = pf.Sketch(**params)
         # a third of the cases index with a narrow low word of the global coordinate (FA_GPOS_BITS, read when the index is built):
@@ -238,5 +249,5 @@ for case in range(cases):
         print(f"MISMATCH case {case} seed {seed} params {params} window {osk.window_size}: hits {hits} vs {ohits}; mappings gpu {len(gm)} oracle {len(omm)}")
         sg, so = set(gm), set(omm)
         print("   only gpu", sorted(sg - so)[:4], "only oracle", sorted(so - sg)[:4])
-print(f"{done} {'history ' if history else ''}cases (seed {seed}), {bad} mismatches, {time.time() - t0:.1f} s")
+print(f"{done} {'history ' if history else ''}cases (seed {seed}), {bad} mismatches, {degenerate} degenerate, {time.time() - t0:.1f} s")
 sys.exit(1 if bad else 0)

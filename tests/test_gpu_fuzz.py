@@ -60,3 +60,17 @@ def test_fuzz_histories_against_oracle():
                          capture_output=True, text=True, timeout=2400)
     assert res.returncode == 0, f"seed {seed}\n" + res.stdout[-3000:] + res.stderr[-3000:]
     assert "0 mismatches" in res.stdout and int(res.stdout.strip().splitlines()[-1].split()[0]) == cases, res.stdout[-500:]
+
+
+def test_fuzz_window_domain_against_oracle():
+    """The ends of the window range (scripts/fuzz_parity.py --domain): identities of 64.5-70 % (w = 2-4, thousands of
+    minimizers per fragment) and 96-100 % (sketches of a handful), p-values from 1e-1 to 1e-12, k from 5 to 33."""
+    seed = (source_seed() ^ 0x0F0F0F) & 0x7FFFFFFF
+    cases = 800
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "fuzz_parity.py"), "--domain", str(cases), str(seed)],
+                         capture_output=True, text=True, timeout=2400)
+    assert res.returncode == 0, f"seed {seed}\n" + res.stdout[-3000:] + res.stderr[-3000:]
+    last = res.stdout.strip().splitlines()[-1].split()
+    assert "0 mismatches" in res.stdout and int(last[0]) == cases, res.stdout[-500:]
+    # (k above ~20 and the lowest identities at small k recommend w = fragment: nothing maps, the case is skipped)
+    assert int(last[last.index("degenerate,") - 1]) <= cases * 2 // 3, res.stdout[-500:]
