@@ -18,6 +18,12 @@ is to be compared with `boundary_call`, not with `value`.
 The rows the timed steps wrote are compared with the CPU oracle's rows for the same query and index, outside the timed
 region (`parity_checked`, `rows_compared`); a wrong kernel fails the run instead of printing a number.
 
+A plain run does only what the headline needs: it sets up, warms up, times the steps, writes --dump-outputs and prints the
+line, with the stage times and the L2 roofline the timed steps recorded on the device.  Every other leg runs after the timed
+steps with --full only: `boundary_call`, the CPU oracle legs (parity and `cpu_baseline`), the concurrent clients, the
+saturated legs, configs 4 and 5, the genome-like leg, the sketch-kernel roofline and the HIP-event cross-check of the L2
+stage; at N > 1 the strong leg and the digest check of the strong table; with --strong at N = 1 the files-to-table leg.
+
 With --gpus N > 1 (launched by torch.distributed.run, one rank per GPU): weak scaling by default -- every rank holds
 a replica of the index (built cooperatively: sketch shards all-gathered over RCCL) and maps its own query genome, the
 hit tables of all steps are exchanged by ONE all-gather at the end of the timed region.  --strong maps BASELINE config
@@ -69,6 +75,8 @@ def parse_args():
     ap.add_argument("--refs", type=int, default=100, help="reference genomes in the index (60%% related)")
     ap.add_argument("--length", type=int, default=5_000_000)
     ap.add_argument("--batch", type=int, default=1, help="query genomes mapped per step and per GPU (1 = BASELINE configs[1])")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, run every other leg too (module docstring); the --no-* options and --clients 0 leave some out")
     ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU oracle legs (no parity check, no cpu_baseline)")
     ap.add_argument("--clients", type=int, default=4, help="N=1 only: host threads of the informational concurrent-clients leg (0 = skip)")
     ap.add_argument("--replicated-index", action="store_true", help="N>1: every rank sketches all references itself")
@@ -454,7 +462,7 @@ def weak_scaling(ctx):
     # the device-resident hit table per step, digest compared with the table rank 0 computes alone (never `value`: the N = 1
     # point of `value` must be the BENCH line).  Every rank takes part.
     strong = None
-    if ctx["dist_on"] and not args.no_saturated and args.saturated_steps > 0:
+    if args.full and ctx["dist_on"] and not args.no_saturated and args.saturated_steps > 0:
         strong = strong_core(ctx, args.saturated_steps, 1)
     if rank != 0:
         return None
@@ -469,42 +477,41 @@ def weak_scaling(ctx):
 
     value = world * n_pairs_step * args.steps / elapsed
     # ---- roofline of the dominant kernel, from the stage times taken inside the timed region (device stamps of the
-    #      100 MHz counter at the stage boundaries; cross-checked below with HIP events on the library's stream) ----
+    #      100 MHz counter at the stage boundaries; with --full cross-checked below with HIP events on the library's stream) ----
     phase = dict(zip(["sketch_ms", "lookup_l1_ms", "l2_ms", "cgi_ms", "total_ms"], [float(x) for x in phase_ms]))
-    # K1 alone, repeated, for the minimizer-extraction roofline the north star asks for
-    k1_ms, bases, mins = C.c_float(0), C.c_uint64(0), C.c_uint64(0)
-    one_genome = mapper.upload_genomes(queries[:1])           # (one 5 Mb genome: the launch a one-query pass issues)
-    check(lib.fa_bench_sketch_kernel(mapper._h, one_genome._h, 50, C.byref(k1_ms), C.byref(bases), C.byref(mins)))
-    k1_bytes = bases.value * 0.25 + mins.value * 12.0   # 2-bit input + 12 B per emitted MinimizerInfo
-    k1_gbs = k1_bytes / (k1_ms.value * 1e-3) / 1e9
-    ms = (C.c_float * 8)()
-    lib.fa_mapper_last_timings(mapper._h, ms, 8)
-    l2_records, n_loci = float(ms[5]), float(ms[6])
-    # the same stage bracketed by two HIP events on the library's stream, in extra (untimed) steps: an event record
-    # costs the stream about as much as a small kernel, so the timed steps run without them
-    check(lib.fa_mapper_set_stage_events(mapper._h, 1))
-    ev_ms, ev_steps = 0.0, min(max(args.steps, 1), 20)
-    for i in range(ev_steps):
-        step(i % table.shape[0])
-        ms24 = (C.c_float * 24)()
-        lib.fa_mapper_last_timings(mapper._h, ms24, 24)
-        ev_ms += float(ms24[16])
-    check(lib.fa_mapper_set_stage_events(mapper._h, 0))
-    ev_ms /= ev_steps
+    l2_records, n_loci = (float(x) for x in stage_log[args.steps - 1, 5:7])      # (those of the last timed step)
     # every reference record inside a locus range is one 12-byte MinimizerInfo of the reference's layout
     l2_bytes = l2_records * 12.0
     l2_gbs = l2_bytes / max(phase["l2_ms"] * 1e-3, 1e-9) / 1e9
     l2_name = "k_l2_events+k_l2_scan"
     dominant = l2_name if phase["l2_ms"] >= phase["sketch_ms"] else "k_sketch_fast"
-    roof = {l2_name: (l2_gbs, phase["l2_ms"]), "k_sketch_fast": (k1_gbs, k1_ms.value)}[dominant]
-    traffic, traffic_source = (profiled_traffic("l2" if dominant == l2_name else "k1")
-                               if args.batch == 1 and args.refs == 100 and args.length == 5_000_000 else (None, None))
     standard = args.batch == 1 and args.refs == 100 and args.length == 5_000_000
-    roof_extra = issue_floor("step", phase["l2_ms"]) if standard and dominant == l2_name else {}
-    k1_model = valu_model().get("k_sketch_fast", {})
-    sketch_extra = ({"issue_floor_gbases_per_s": k1_model["issue_floor_gbases_per_s"],
-                     "valu_frac": bases.value / (k1_ms.value * 1e-3) / 1e9 / k1_model["issue_floor_gbases_per_s"],
-                     "issue_floor_source": valu_model().get("_source")} if k1_model else {})
+    sketch, ev_ms = None, None
+    if args.full:
+        # K1 alone, repeated, for the minimizer-extraction roofline the north star asks for
+        sketch = sketch_roofline(mapper, queries[:1])
+        # the L2 stage bracketed by two HIP events on the library's stream, in extra (untimed) steps: an event record
+        # costs the stream about as much as a small kernel, so the timed steps run without them
+        check(lib.fa_mapper_set_stage_events(mapper._h, 1))
+        ev_ms, ev_steps = 0.0, min(max(args.steps, 1), 20)
+        for i in range(ev_steps):
+            step(i % table.shape[0])
+            ms24 = (C.c_float * 24)()
+            lib.fa_mapper_last_timings(mapper._h, ms24, 24)
+            ev_ms += float(ms24[16])
+        check(lib.fa_mapper_set_stage_events(mapper._h, 0))
+        ev_ms /= ev_steps
+    # (a dominant sketch stage has its roofline from the sketch kernel's own run only: --full)
+    roof = {l2_name: (l2_gbs, phase["l2_ms"], l2_bytes, "l2"),
+            "k_sketch_fast": sketch and (sketch["achieved"], sketch["kernel_ms"], sketch["algorithmic_bytes"], "k1")}[dominant]
+    roofline = None
+    if roof:
+        traffic, traffic_source = profiled_traffic(roof[3]) if standard else (None, None)
+        roofline = {"bound": "hbm", "kernel": dominant, "achieved": roof[0], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": roof[0] / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source, "kernel_ms": roof[1],
+                    "kernel_ms_source": "device stamps (100 MHz counter) at the stage boundaries of every timed step, on the library's stream",
+                    "kernel_ms_hip_events": ev_ms if dominant == l2_name else None, "algorithmic_bytes": roof[2],
+                    **(issue_floor("step", phase["l2_ms"]) if standard and dominant == l2_name else {})}
     result = {
         "metric": "genome-pair ANI/sec (5 Mb bacterial, 3 kb frags)",
         "value": value,
@@ -522,19 +529,11 @@ def weak_scaling(ctx):
         "dtype": "u32",
         "data": "synthetic",
         "config": {"workload": f"{args.batch} query x {args.refs} synthetic {args.length / 1e6:g} Mb refs per GPU, k=16 frag=3000 w={mapper.window_size}",
-                   "timed_region": "device-resident pass (packed query in HBM -> hit rows in HBM); the host-bytes -> Hit-list call is `boundary_call`",
+                   "timed_region": "device-resident pass (packed query in HBM -> hit rows in HBM); the host-bytes -> Hit-list call is `boundary_call` (--full)",
                    "queries_rotated": ROTATE, "pairs_per_step_per_gpu": n_pairs_step, "pairs_per_step": world * n_pairs_step, "hits_per_step": n_hits, "l2_loci": int(n_loci), "l2_records": int(l2_records), "parallelism": f"query-sharded x{world}",
                    "index_minimizers": n_min, "index_build": index_mode, "index_build_s": t_index, "host_pack_s": t_pack, "head": git_head()},
-        "roofline": {"bound": "hbm", "kernel": dominant, "achieved": roof[0], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": roof[0] / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source, "kernel_ms": roof[1],
-                     "kernel_ms_source": "device stamps (100 MHz counter) at the stage boundaries of every timed step, on the library's stream",
-                     "kernel_ms_hip_events": ev_ms if dominant == l2_name else None,
-                     "algorithmic_bytes": l2_bytes if dominant == l2_name else k1_bytes, **roof_extra},
-        "roofline_sketch": {"bound": "hbm", "kernel": "k_sketch_fast", "achieved": k1_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                            "frac": k1_gbs / HBM_PEAK_GBS, "kernel_ms": k1_ms.value, "gbases_per_s": bases.value / (k1_ms.value * 1e-3) / 1e9,
-                            "algorithmic_bytes": k1_bytes,
-                            "note": "the sketch kernel alone over the query's tiles (50 launches, fa_bench_sketch_kernel); in the timed step the same tile body runs inside k_query_fused, in one launch with the per-fragment sort and index lookup",
-                            **sketch_extra},
+        **({"roofline": roofline} if roofline else {}),
+        **({"roofline_sketch": sketch} if sketch else {}),
         "phases_ms": phase,
         **({"stage_bounds": stage_bounds("step", phase)} if standard else {}),
         "rccl_ranks": dist.get_world_size() if ctx["dist_on"] else 1,
@@ -545,7 +544,7 @@ def weak_scaling(ctx):
             raise SystemExit(f"STRONG LEG FAILURE: the all-gathered hit table of {world} ranks ({strong['table_sha256']}) differs from the "
                              f"table one rank computes ({strong['table_sha256_n1']})")
         result["strong"] = strong
-    if world == 1:
+    if world == 1 and args.full:
         timed_rows = [table[i, 1: counts[i] + 1].cpu().numpy().reshape(-1).view(ROW_DTYPE) for i in range(args.steps)]
         if not args.no_boundary:
             result["boundary_call"] = boundary_call(args, mapper, queries[0], timed_rows[::ROTATE])
@@ -565,6 +564,25 @@ def weak_scaling(ctx):
         if not args.no_cpu_baseline:              # the CPU oracle legs are an N=1 measurement (rank 0 only)
             result.update(oracle_legs(args, anc, names, refs, mapper, [qs[0] for qs in rot_queries], timed_rows))
     return result
+
+
+def sketch_roofline(mapper, query):
+    """`roofline_sketch`: the sketch kernel alone over one query genome's tiles, 50 launches timed by HIP events."""
+    from pyfastani_amd._lib import lib, check
+    k1_ms, bases, mins = C.c_float(0), C.c_uint64(0), C.c_uint64(0)
+    one_genome = mapper.upload_genomes(query)           # (one 5 Mb genome: the launch a one-query pass issues)
+    check(lib.fa_bench_sketch_kernel(mapper._h, one_genome._h, 50, C.byref(k1_ms), C.byref(bases), C.byref(mins)))
+    k1_bytes = bases.value * 0.25 + mins.value * 12.0   # SURVEY.md 8d: 2-bit input + 12 B per emitted MinimizerInfo
+    k1_gbs = k1_bytes / (k1_ms.value * 1e-3) / 1e9
+    k1_model = valu_model().get("k_sketch_fast", {})
+    sketch_extra = ({"issue_floor_gbases_per_s": k1_model["issue_floor_gbases_per_s"],
+                     "valu_frac": bases.value / (k1_ms.value * 1e-3) / 1e9 / k1_model["issue_floor_gbases_per_s"],
+                     "issue_floor_source": valu_model().get("_source")} if k1_model else {})
+    return {"bound": "hbm", "kernel": "k_sketch_fast", "achieved": k1_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": k1_gbs / HBM_PEAK_GBS, "kernel_ms": k1_ms.value, "gbases_per_s": bases.value / (k1_ms.value * 1e-3) / 1e9,
+            "algorithmic_bytes": k1_bytes,
+            "note": "the sketch kernel alone over the query's tiles (50 launches, fa_bench_sketch_kernel); in the timed step the same tile body runs inside k_query_fused, in one launch with the per-fragment sort and index lookup",
+            **sketch_extra}
 
 
 def boundary_call(args, mapper, query, timed_rows):
@@ -1021,10 +1039,10 @@ def strong_core(ctx, steps, warmup, dump=None):
     fence(ctx)
     elapsed = max_over_ranks(ctx, time.perf_counter() - t0)
     exchange_ms = max_over_ranks(ctx, exchange.exchange_ms(steps))
-    # ---- N > 1: the table every rank holds now must be the table ONE rank computes.  Rank 0 maps all genomes against its
+    # ---- --full, N > 1: the table every rank holds now must be the table ONE rank computes.  Rank 0 maps all genomes against its
     #      replica (outside the timed region, no collective) and the digests are compared; the other ranks wait at the fence. ----
     n1_digest = None
-    if ctx["dist_on"] and rank == 0:
+    if args.full and ctx["dist_on"] and rank == 0:
         everything = mapper.upload_genomes(genomes)
         alone = sharding.ResidentHitTable(list(range(n)), n * n, 1, collective=False)
         n1_digest = _sha256_rows(sharding.ResidentHitTable.rows_of(alone.step(everything)))
@@ -1036,7 +1054,7 @@ def strong_core(ctx, steps, warmup, dump=None):
     if dump:
         dump_outputs(dump, rows)
     from_files = None
-    if world == 1 and not ctx["dist_on"] and not args.no_fasta_leg:
+    if args.full and world == 1 and not ctx["dist_on"] and not args.no_fasta_leg:
         del batch, exchange, tables
         from_files = fasta_to_table_leg(ctx, genomes)
         if from_files["table_sha256"] != _sha256_rows(rows):

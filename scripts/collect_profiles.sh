@@ -14,7 +14,7 @@ set -u
 TAG=${1:-r03}
 MODE=${2:-default}
 export TMPDIR=/tmp
-COMMON="--no-cpu-baseline --clients 0 --no-saturated"
+COMMON="--full --no-cpu-baseline --clients 0 --no-saturated"
 case "$MODE" in
   default) NAME=$TAG;           ARGS="$COMMON";            STATS="--steps 20 --warmup 3"; PMC="--steps 3 --warmup 1"; export FA_PROFILE_SUM_STEPS=0 ;;
   batch16) NAME=${TAG}_batch16; ARGS="$COMMON --no-boundary --batch 16"; STATS="--steps 10 --warmup 2"; PMC="--steps 2 --warmup 1"; export FA_PROFILE_SUM_STEPS=0 ;;

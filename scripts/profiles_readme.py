@@ -8,7 +8,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # (regex on the name without its round prefix, command, what it holds); first match wins
 PATTERNS = [
-    (r"bench_(default|first)(_detail)?\.json$", "python bench.py --gpus 1 --steps 20 --warmup 5", "the bench contract line of the round (`_detail`: the full result behind it)"),
+    (r"bench_(default|first)(_detail)?\.json$", "python bench.py --gpus 1 --steps 20 --warmup 5 --full", "the bench contract line of the round (`_detail`: the full result behind it)"),
     (r"(batch16_|config3_|config4_|config5_k\d+_f\d+_)?bench_kernel_stats\.csv$", "bash scripts/collect_profiles.sh <round> [leg]", "`rocprofv3 --kernel-trace --stats` of the leg: per-kernel calls and durations"),
     (r"(batch16_|config3_|config4_|config5_k\d+_f\d+_)?bench_under_rocprof\.json$", "bash scripts/collect_profiles.sh <round> [leg]", "the bench line printed under the profiler"),
     (r"(batch16_|config3_|config4_|config5_k\d+_f\d+_)?traffic\.json$", "bash scripts/collect_profiles.sh <round> [leg]", "HBM bytes per kernel from separate `--pmc FETCH_SIZE` / `--pmc WRITE_SIZE` passes (bench.py doubles FETCH_SIZE as the guide prescribes)"),
@@ -25,7 +25,7 @@ PATTERNS = [
     (r"l1_classes_ab\.txt$", "bash scripts/r06/ab_rank_and_classes.sh", "k_l1 launched per size class of fragments"),
     (r"l1_prefilter\.txt$", "bash scripts/r06/prefilter.sh", "the pre-filter of k_l1's block sort: parity, config 3, 2000 x 2000, 4000 x 4000"),
     (r"scan_order\.txt$", "bash scripts/r06/scan_order.sh", "k_l2_scan over loci sorted by stream length: parity forced on, A/B on every saturated leg"),
-    (r"fasta_read_once\.txt$", "python bench.py --strong --steps 1 --warmup 1", "the files-to-table leg of config 3 repeated: the spread of the read-once variant"),
+    (r"fasta_read_once\.txt$", "python bench.py --strong --steps 1 --warmup 1 --full", "the files-to-table leg of config 3 repeated: the spread of the read-once variant"),
     (r"genome_like.*\.json$", "python bench.py --leg genome_like", "the genome-like leg (repeats, indels, inversion) alone"),
     (r"scale_\d+x\d+\.json$|scale_probe.*\.txt$", "python bench.py --strong --families F --members 50", "all-vs-all beyond config 3 (index of 8 x 10^8 / 1.6 x 10^9 records)"),
     (r"ingest.*\.(json|txt)$|fasta_read_once\.txt$", "python scripts/time_ingest.py", "FASTA files to packed words / to the hit table"),

@@ -1,7 +1,7 @@
 #!/bin/bash
 # round 6: the bench line at the head, the scale runs beyond config 3, and the fuzz campaign on the final library
 O=gpurun_out; mkdir -p $O
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --detail $O/r06_bench_detail.json > $O/r06_bench_default.json 2> $O/r06_bench_default.err; echo "bench rc=$?"; tail -c 2900 $O/r06_bench_default.json; echo
+timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full --detail $O/r06_bench_detail.json > $O/r06_bench_default.json 2> $O/r06_bench_default.err; echo "bench rc=$?"; tail -c 2900 $O/r06_bench_default.json; echo
 timeout 900 python3 bench.py --strong --families 40 --members 50 --steps 1 --warmup 1 --no-fasta-leg --detail $O/r06_scale_2000x2000.json > /dev/null 2> $O/s2000.err
 timeout 900 python3 bench.py --strong --families 80 --members 50 --steps 1 --warmup 1 --no-fasta-leg --detail $O/r06_scale_4000x4000.json > /dev/null 2> $O/s4000.err
 for n in 2000 4000; do python3 -c "

@@ -52,6 +52,19 @@ def test_default_arguments_are_one_gpu():
     assert args.gpus == 1 and args.steps > 0
 
 
+def test_full_is_an_option_and_off_by_default():
+    """A plain run times the headline only; every other leg runs with --full."""
+    bench = _load_bench()
+    old = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"]
+        assert bench.parse_args().full is False
+        sys.argv += ["--full"]
+        assert bench.parse_args().full is True
+    finally:
+        sys.argv = old
+
+
 def test_the_strong_workload_is_generated_once_and_mapped_by_the_other_ranks(monkeypatch):
     """`shared_workload`: rank 0 writes the contigs into one file, the other ranks map it; same genomes, same shape, the files
     gone afterwards.  Two 'ranks' are two threads here, the barrier a threading.Barrier (no GPU, no process group)."""

@@ -27,7 +27,8 @@ def _run_ranks(script_or_args, n, env=None, timeout=1200):
     return subprocess.run(cmd, env=e, capture_output=True, text=True, timeout=timeout, cwd=ROOT)
 
 
-STRONG_SMALL = ["--strong", "--families", "2", "--members", "5", "--length", "300000", "--steps", "2", "--warmup", "1"]
+# --full: the files-to-table leg at N = 1 and the digest check of the all-gathered table at N > 1
+STRONG_SMALL = ["--strong", "--families", "2", "--members", "5", "--length", "300000", "--steps", "2", "--warmup", "1", "--full"]
 
 
 def _line_and_detail(out):
@@ -137,12 +138,39 @@ def test_bench_dump_outputs_is_the_last_timed_step(tmp_path):
         assert np.array_equal(dumps[1][n], dumps[0][n]), n
 
 
+def test_bench_plain_run_is_the_headline_and_full_adds_the_legs(tmp_path):
+    """A plain run sets up, warms up, times its steps and prints the line: no leg beyond the headline runs.  The same command
+    with --full adds them after the timed steps -- here the reference-shaped boundary call, the concurrent clients, the
+    sketch-kernel roofline and the CPU oracle legs, whose parity check covers the rows of every timed step."""
+    base = ["--refs", "6", "--length", "400000", "--steps", "3", "--warmup", "1"]
+    legs = ("boundary_call", "concurrent_clients", "saturated", "config5_cells", "genome_like", "strong", "roofline_sketch",
+            "parity_checked", "parity", "cpu_baseline")
+    lines = {}
+    for name, extra in (("plain", []), ("full", ["--full", "--no-saturated", "--clients", "2"])):
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + base + extra + ["--detail", str(tmp_path / f"{name}.json")],
+                             capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
+        short, lines[name] = _line_and_detail(res.stdout)
+        assert short["steps"] == 3 and short["warmup"] == 1 and short["value"] > 0 and short["ms_per_step"] > 0
+    plain, full = lines["plain"], lines["full"]
+    assert not [k for k in legs if k in plain], plain.keys()
+    assert plain["phases_ms"]["l2_ms"] > 0 and plain["config"]["hits_per_step"] == full["config"]["hits_per_step"] >= 4
+    assert plain["config"]["l2_records"] == full["config"]["l2_records"] > 0
+    assert "roofline" not in plain or plain["roofline"]["kernel_ms_hip_events"] is None
+    assert [k for k in legs if k in full] == ["boundary_call", "concurrent_clients", "roofline_sketch", "parity_checked", "parity",
+                                              "cpu_baseline"]
+    assert full["boundary_call"]["hits_match_timed_rows"] is True and full["concurrent_clients"]["threads"] == 2
+    assert full["parity_checked"] is True and full["parity"]["timed_steps_checked"] == 3
+    assert full["rows_compared"] >= full["config"]["hits_per_step"]
+    assert full["cpu_baseline"]["kind"] == "port" and full["roofline_sketch"]["kernel_ms"] > 0 and full["roofline"]["frac"] > 0
+
+
 def test_bench_launches_its_own_ranks_and_carries_the_strong_leg():
     """`python bench.py --gpus 2` with NO launcher around it (the command a scaling run issues): the process starts its two
     ranks as a child `torch.distributed.run` before it imports torch, relays rank 0's line and exits with the child's status.
-    The line is the weak-scaled step (`value`) AND the strong leg -- config 3 in miniature dealt over both ranks, the
+    The line is the weak-scaled step (`value`) AND, with --full, the strong leg -- config 3 in miniature dealt over both ranks, the
     all-gathered table's digest equal to the digest of the table rank 0 computes alone."""
-    args = ["--gpus", "2", "--refs", "6", "--length", "300000", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+    args = ["--gpus", "2", "--refs", "6", "--length", "300000", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
             "--families", "2", "--members", "5", "--saturated-steps", "2"]
     env = dict(os.environ, FA_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
@@ -163,7 +191,7 @@ def test_bench_line_carries_configs_4_and_5():
     """The N = 1 run at reduced size: the contract line holds one number + roofline fraction per saturated leg and per config-5
     cell; the detail file holds `saturated.config4` (draft assemblies all-vs-all) and `config5_cells` (the nine (k,
     fragment_length) cells) with pairs/s, per-stage ms, the sketch-stage form and the oracle-free properties."""
-    args = ["--refs", "6", "--length", "1500000", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--clients", "0", "--no-boundary",
+    args = ["--refs", "6", "--length", "1500000", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--clients", "0", "--no-boundary",
             "--families", "2", "--members", "4", "--saturated-steps", "1", "--config4", "2x4", "--config5", "2x3", "--genome-like", "2x3"]
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True, timeout=1800, cwd=ROOT)
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
@@ -242,7 +270,7 @@ def test_bench_exchanges_through_rccl_at_world_size_one():
     """bench.py as ONE rank with FA_BENCH_FORCE_DIST=1: the weak-scaled line's `exchange()` and the strong leg's
     `ResidentHitTable.step` all-gather go through RCCL (backend nccl, one rank), the index is built through the cooperative
     path, and the strong leg's table has the digest of the table computed without any collective."""
-    args = ["--gpus", "1", "--refs", "6", "--length", "300000", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-boundary",
+    args = ["--gpus", "1", "--refs", "6", "--length", "300000", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-boundary",
             "--clients", "0", "--families", "2", "--members", "5", "--saturated-steps", "2"]
     res = _run_ranks([os.path.join(ROOT, "bench.py")] + args, 1, env={"FA_BENCH_FORCE_DIST": "1"})
     assert res.returncode == 0, res.stdout + res.stderr
@@ -261,7 +289,7 @@ def test_bench_refuses_a_world_size_that_is_not_gpus():
 @pytest.mark.skipif(_gpus() < 2, reason="needs two GPUs (RCCL: one rank per device)")
 def test_bench_self_launch_rccl_two_gpus():
     """The same command on two real GPUs: RCCL (`nccl` backend) carries the all-gathers."""
-    args = ["--gpus", "2", "--refs", "6", "--length", "300000", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+    args = ["--gpus", "2", "--refs", "6", "--length", "300000", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
             "--families", "2", "--members", "5", "--saturated-steps", "2"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "FA_BENCH_SHARE_GPU")}
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, env=env, capture_output=True, text=True, timeout=1200, cwd=ROOT)
