@@ -25,6 +25,7 @@
 #include "fa_fasta.h"
 #include "fa_lease.h"
 #include "fa_map.hip.h"
+#include "fa_policy.h"
 #include "fa_sketch.hip.h"
 #include "fa_sketch_fast.hip.h"
 #include "fa_stats.h"
@@ -80,10 +81,24 @@ static void validate_params(const fa_params &p) {
              "window_size/kmer_size too large for the LDS-staged sketch kernel (tile + 2w + k must fit 160 KiB)");
 }
 
-static int floor_log2(int v) {
-  int l = 0;
-  while ((2 << l) <= v) l++;
-  return l;
+// FA_* knobs: env_set = the knob is set (to anything); env_num = its value (atof), `unset` when it is not set; env_u64 = a
+// positive count, else `dflt`
+static bool env_set(const char *name) { return getenv(name) != nullptr; }
+static double env_num(const char *name, double unset) {
+  const char *e = getenv(name);
+  return e ? atof(e) : unset;
+}
+static uint64_t env_u64(const char *name, uint64_t dflt) {
+  const char *e = getenv(name);
+  long long x = e ? atoll(e) : 0;
+  return x > 0 ? (uint64_t)x : dflt;
+}
+
+// launches `kernel` with `lds` bytes of dynamic LDS; above 64 KB the kernel has to be allowed them first
+template <typename Kernel, typename... Args>
+static void launch_lds(Kernel kernel, dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args &...args) {
+  if (lds > 64 * 1024) FA_HIP(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -104,8 +119,8 @@ struct StageTrace {
   const char *what;
   std::chrono::steady_clock::time_point t0, t;
   std::vector<std::pair<std::string, double>> acc;
-  explicit StageTrace(const char *w) : on(getenv("FA_TRACE") != nullptr), what(w) {
-    live = on && atoi(getenv("FA_TRACE")) >= 2;
+  explicit StageTrace(const char *w) : on(env_set("FA_TRACE")), what(w) {
+    live = on && env_num("FA_TRACE", 0) >= 2;
     t0 = t = std::chrono::steady_clock::now();
   }
   void mark(const char *stage, hipStream_t st) {
@@ -153,14 +168,13 @@ static bool launch_sketch_tiles(const fa_params &P, const StoreView &store, cons
   a.protein = P.alphabet_size != 4;
   a.npos_cap = TILE + 2 * P.window_size - 2;
   // FA_K1_GENERAL=1: every tile through the 64-bit form of the window minimum (tests compare the two)
-  static const bool k1_general = getenv("FA_K1_GENERAL") && atoi(getenv("FA_K1_GENERAL")) != 0;
+  static const bool k1_general = env_num("FA_K1_GENERAL", 0) != 0;
   a.fast = (!k1_general && P.window_size >= 3 && P.window_size <= 1000) ? 1 : 0;   // (three padded arrays in the LDS of two key arrays)
   size_t lds = sketch_lds_bytes(P.kmer_size, P.window_size);
   size_t image = lds - ((size_t)a.npos_cap * 16 + ((size_t)a.npos_cap / 64 + 1) * 8 + (TILE / 64) * 8 + (TILE / 64 + 1) * 4 + 16 + 4 * 256 * 8);
   a.code_words = (int32_t)(image / 4);
   auto launch = [&](auto kernel) {
-    if (lds > 64 * 1024) FA_HIP(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kernel, dim3(ntiles + extra), dim3(SK_THREADS), lds, st, a);
+    launch_lds(kernel, dim3(ntiles + extra), dim3(SK_THREADS), lds, st, a);
     extra = 0; a.clear.count = 0; a.clear.stamp = nullptr;          // (only the first launch zeroes)
   };
   // plain-ACGT tiles from the 2-bit image; protein tiles and tiles with other bytes through the byte image
@@ -177,7 +191,7 @@ static bool launch_sketch_tiles(const fa_params &P, const StoreView &store, cons
     // staging arrays FIRST (a launch whose other workgroups exit at once, and which carries the zeroing workgroups of the pass);
     // the fused kernel takes their records from there.  The run-time-w forms of the fused kernel do not fit the registers of seven waves per
     // SIMD -- a few words would go to scratch memory, which the runtime then keeps per stream for good -- and are not built.
-    static const bool fuse_on = !(getenv("FA_QUERY_FUSED") && atoi(getenv("FA_QUERY_FUSED")) == 0);
+    static const bool fuse_on = env_num("FA_QUERY_FUSED", 1) != 0;
     const bool may_fuse = fuse && fuse_on && (int64_t)5 * P.fragment_length / (P.window_size + 1) <= QF_CAP;
     auto launch_fast = [&](auto kernel) {
       hipLaunchKernelGGL(kernel, dim3(ntiles + extra), dim3(SK_THREADS), flds, st, a);
@@ -416,28 +430,6 @@ struct fa_genomes {
 };
 static std::atomic<uint64_t> g_batch_serial{0};
 
-// Every small counter / statistic of a pass in ONE device block, mirrored into pinned host memory by one copy.
-static uint64_t env_u64(const char *name, uint64_t dflt) {
-  const char *e = getenv(name);
-  long long x = e ? atoll(e) : 0;
-  return x > 0 ? (uint64_t)x : dflt;
-}
-
-struct PassStatus {
-  int32_t stats[4];                 // [0] largest query sketch
-  int32_t total_rows, pad0[3];
-  uint64_t totals[4];               // seeds, largest fragment, scratch words, reference records in L2 ranges
-  uint32_t counters[8];             // [0] fragments k_l1 merged instead of block-sorting, [1] fragments on the HBM road / cut by k_l1_big; [2] loci overflow, wide-state loci, finished row workgroups, k_l1 roads (2: FA_L1_STATS samples)
-  unsigned long long pinfo[4];      // slide events reserved (fused L2 form), speculation flags
-  unsigned long long ev_region[EV_REGIONS], rec_region[EV_REGIONS];   // k_l2_events: events reserved / records read per arena region
-  uint32_t loci_region[LOCI_REGIONS];                                  // k_l1: loci reserved per region (LociRegions)
-  unsigned long long dbg[16];       // FA_L1_STATS=1: shader-clock ticks of k_l1's phases, summed over the sampled workgroups (thread 0's view); [8..10] why block sorts gave up
-  unsigned long long stamp[6];      // stage_stamp: pass start, lookup, L2, CGI, end (100 MHz ticks); not cleared with the rest
-  uint32_t seq, pad1;               // host copy only: number of the pass whose status this is (k_publish_status)
-};
-
-static_assert(offsetof(PassStatus, stamp) % 16 == 0, "k_clear zeroes whole 16-byte words: the cleared prefix of the status block must end on one");
-
 // The hand-over of a pass (publish_pass, fa_map.hip.h): copies the status block -- and, for a one-query call whose rows go to the host, the rows --
 // into pinned host memory and then releases the pass number.  The host polls that word instead of waiting for a
 // device-to-host copy and a stream synchronisation, which together return tens of microseconds after the GPU is done
@@ -450,12 +442,6 @@ static PublishArgs publish_args(PassStatus *dev, PassStatus *host_mapped, uint32
   p.rows_dev = rows_dev; p.rows_host = rows_host; p.cap = cap;
   return p;
 }
-// regions of the event arena used by a part of F fragments (L2Args::n_regions): a power of two, one per sixteen fragments
-static uint32_t ev_regions_for(int64_t F) {
-  uint32_t n = 1;
-  while (n < (uint32_t)EV_REGIONS && (int64_t)n * 16 <= F) n <<= 1;
-  return n;
-}
 // host side of k_publish_status: polls for FA_SPIN_US microseconds (default 20 000), then sleeps on the stream
 static void wait_published(const PassStatus *h, uint32_t seq, hipStream_t st) {
   static const uint64_t spin_us = env_u64("FA_SPIN_US", 20000);
@@ -463,6 +449,13 @@ static void wait_published(const PassStatus *h, uint32_t seq, hipStream_t st) {
   FA_HIP(hipStreamSynchronize(st));
   FA_REQUIRE(__atomic_load_n(&h->seq, __ATOMIC_ACQUIRE) == seq, FA_ERR_INTERNAL, "the status of the pass was not published");
 }
+
+// The slots of Workspace::last_ms (fa_mapper_last_timings), laid out as include/fastani_hip.h documents: [MS_STAGE + 0..3] sketch,
+// lookup + L1, L2, CGI ms; [MS_HOST + 0..2] the host-side split of fa_mapper_query; also [MS_L1_SORTED] [MS_L1_MERGED] (FA_L1_STATS
+// samples) and [MS_L1_OFF_FAST] (fragments that left k_l1's fast form)
+enum TimingSlot : int { MS_STAGE = 0, MS_TOTAL = 4, MS_RECORDS, MS_LOCI, MS_EVENTS, MS_WIDE, MS_REPEATS, MS_HOST = 10, MS_CALL = 13,
+                        MS_L2_EVENTS = 16, MS_FUSED, MS_UNFUSED, MS_ORDERED, MS_L1_SORTED, MS_L1_MERGED, MS_L1_OFF_FAST, MS_TILE_LEN, MS_SLOTS };
+static_assert(MS_REPEATS == 9 && MS_ORDERED == 19 && MS_TILE_LEN == 23 && MS_SLOTS == 24, "the layout of fa_mapper_last_timings is ABI");
 
 // Everything one query call owns: its stream, every intermediate of the pipeline, its status block and timing events.
 struct Workspace {
@@ -495,21 +488,15 @@ struct Workspace {
   int64_t last_F = 0;
   uint32_t last_loci = 0;             // loci of the last accepted part (all regions)
   uint32_t loci_n = 1, loci_shift = 0;                    // regions of the locus numbering of the part in flight / last accepted
-  bool l1_pf = false, l1_small_class = false;             // the part in flight ran k_l1 with the pre-filter / with the 256-thread class next to others
   uint32_t last_region_count[LOCI_REGIONS] = {0};         // live loci per region of the last accepted part
   uint64_t last_items = 0;
   const fa_genomes *last_genomes = nullptr;
-  float last_ms[24] = {0};
+  float last_ms[MS_SLOTS] = {0};
   hipEvent_t ev[6] = {nullptr};
   int64_t pass_F = 0;                 // fragments of the last pass
   // the kernel forms of a part (fa_mapper_debug_spec): those of the part in flight, and those of the last part accepted in the
   // last call (cleared when a call starts)
-  struct Forms {
-    int n_l1 = 0, l1_threads[3] = {0, 0, 0};
-    bool prefilter = false, scan_sorted = false, wide = false, fused = false, ordered = false, redo = false;
-    int smax = 0;
-    uint32_t seed_slots = 0;
-  } forms, last_forms;
+  Forms forms, last_forms;
   // the one-query-at-a-time call (fa_mapper_query) recycles its batch object -- no device allocation per call -- and
   // builds the upload image in pinned memory; its rows come back through a pinned block too
   std::unique_ptr<fa_genomes> query_batch;
@@ -541,7 +528,7 @@ struct fa_mapper {
   bool packed_geo = false;
   // k_l2_events reads the packed record layout (rec_hg, rec_prev16) when the index has one; FA_NO_PACKED_GEO=1 takes the
   // plain arrays on any index (the tests reach the unpacked form on small indices that way)
-  bool events_packed() const { return packed_geo && !getenv("FA_NO_PACKED_GEO"); }
+  bool events_packed() const { return packed_geo && !env_set("FA_NO_PACKED_GEO"); }
   int64_t N = 0, U = 0;
   int32_t C = 0, G = 0, table_bits = 4, freq_threshold = INT_MAX, total_bins = 0;
   std::vector<uint64_t> lengths;
@@ -552,27 +539,7 @@ struct fa_mapper {
   DevBuf<int32_t> d_min_hits, d_pass;
   DevBuf<float> d_ident;
   // data-dependent sizes speculated from earlier passes (see run_query_pass); shared by all workspaces, guarded by mtx
-  struct Spec {
-    bool init = false;
-    int smax = 0;
-    uint32_t seed_slots = 0;
-    uint64_t scratch_words = 0, items_cap = 0;
-    int64_t l_cap = 0;
-    int64_t part_frags = 0;   // fragments per part of a pass (shrinks when a part overflows the 32-bit workspace)
-    bool redo = false;        // launch the wide-state scan as well (set once a locus overflowed the one-byte state)
-    // k_query_fused met a fragment with more records than its LDS holds: the void range runs again through the two kernels
-    // (`fuse_off`, a property of that attempt only).  The mapper keeps a back-off, not a verdict: the first overflow costs
-    // nothing afterwards, consecutive ones skip 1, 3, 7 ... 63 passes before the fused form is tried again, and a fused pass
-    // that is accepted clears the record -- one dense fragment no longer decides every later query of the mapper.
-    bool fuse_off = false;
-    int fuse_skip = 0, fuse_penalty = 0;
-    int smax_misses = 0;      // times the largest sketch outgrew the bound (the first growth is tight, later ones are not)
-    // share of the fragments of the last accepted part in the two lower size classes of k_l1 (-1: not seen yet)
-    float l1_small_share = -1.0f, l1_mid_share = -1.0f, l1_tiny_share = -1.0f;   // (tiny: up to half the small class's bound)
-    bool l1_prefilter = false;  // an accepted part saw fragments fall off k_l1's block sort: later passes drop dead hits before the sort (sticky)
-    int64_t l2_loci_last = 0;   // loci of the last accepted part: k_l2_scan sorts its loci by stream length when there are waves to balance
-    bool l1_no_small = false;   // ... and they still did with the pre-filter on and the 256-thread class in use: its table is too small for this index (sticky)
-  } spec;
+  Spec spec;
   // Queries are re-entrant (_fastani.pyx:1158-1161): every call takes one of NWS workspaces -- its own stream and every
   // intermediate of the pipeline -- so calls from different host threads overlap on the device (their phases interleave,
   // which is worth ~27 % of throughput over strictly serial calls).  `mtx` guards the pool, the speculation record and
@@ -830,13 +797,6 @@ static void ensure_luts(fa_mapper &m, int smax) {
   }
 }
 
-// seed hits of one fragment sorted in LDS by k_l1 (4 bytes each); more go through HBM scratch
-static uint32_t lds_seed_cap_max(int smax) {
-  // (the dynamic request of k_l1 -- l1_lds_bytes: seeds, list offsets and sources, six staged locus arrays -- plus its static
-  // LDS, a few hundred bytes, must stay within the 160 KB of a CU)
-  const int64_t room = 160 * 1024 - 2048 - (int64_t)L1_STAGE * 6 * 4 - std::max<int64_t>(((int64_t)smax + 2) * 8, 1024 * 10) - 64;
-  return (uint32_t)std::max<int64_t>(256, room / 4 / 256 * 256);
-}
 
 
 // zero several device ranges with one launch (every DevBuf is at least 16-byte aligned; sizes are rounded up to 16 bytes:
@@ -861,7 +821,7 @@ struct ClearList {
 
 // FA_DEBUG_SYNC=1: synchronise after every stage of a query pass and name the stage that failed
 static void debug_sync(hipStream_t st, const char *stage) {
-  static const bool on = getenv("FA_DEBUG_SYNC") != nullptr;
+  static const bool on = env_set("FA_DEBUG_SYNC");
   if (!on) return;
   fprintf(stderr, "[fa] %s ...\n", stage);
   hipError_t e = hipStreamSynchronize(st);
@@ -870,69 +830,29 @@ static void debug_sync(hipStream_t st, const char *stage) {
 
 // fragments mapped per pass (bounds the workspace); FA_PASS_FRAGMENTS overrides it (tests force several passes)
 static int64_t pass_fragments() {
-  static const int64_t v = [] {
-    const char *e = getenv("FA_PASS_FRAGMENTS");
-    long long x = e ? atoll(e) : 0;
-    return (int64_t)(x > 0 ? x : 48 * 1024);
-  }();
+  static const int64_t v = (int64_t)env_u64("FA_PASS_FRAGMENTS", 48 * 1024);
   return v;
 }
 
-// Workgroup order of k_l2_events over the fragments [f0, f1) of a pass that holds several genomes: fragments sorted by their
-// offset inside their genome (then by genome), every group of equal offset dealt to the XCD whose list is the shortest so far
-// (equal-sized genomes: group p lands on XCD p mod 8), and the eight lists interleaved the way workgroups are dispatched
-// (workgroup b runs on XCD b mod 8); -1 pads the shorter lists.  Returns 0 -- the caller keeps the identity order -- when
-// the lists cannot be balanced: fewer groups than XCDs (a batch of plasmids or viral contigs of one or two fragments each
-// would put every real workgroup on one XCD) or more than 15 % of padding.
-static uint32_t build_frag_order(const fa_genomes &g, int32_t g0, int64_t f0, int64_t f1, std::vector<int32_t> &out) {
-  const int64_t F = f1 - f0;
-  out.clear();
-  int32_t q = g0;
-  while (g.genome_frag_lo[q + 1] <= f0) q++;
-  if (g.genome_frag_lo[q + 1] >= f1) {
-    // ONE genome (round 5): its fragments in eight contiguous runs, one per XCD.  The loci of neighbouring fragments overlap by
-    // two thirds on every reference (a locus spans ~2.6 fragment lengths), so the workgroups of a run read the same index
-    // stretches -- from their XCD's L2 instead of the memory side, where the identity order (fragment b on XCD b mod 8)
-    // had put every neighbour on another XCD.
-    if (F < 64) return 0;
-    const int64_t run = (F + 7) / 8;
-    out.assign((size_t)run * 8, -1);
-    for (int64_t i = 0; i < F; i++) out[(size_t)((i % run) * 8 + i / run)] = (int32_t)i;
-    return (uint32_t)out.size();
+// Dynamic LDS of k_l2_events and k_l2_scan at a sketch bound (their tables hold cnt_slots = smax + 1 ranks) for the fragments
+// of an index: what scan_occupancy asks the runtime about is what launch_l2_stage launches with.
+struct L2Lds {
+  int slots, ev_stage, scan_class_div;
+  size_t events;
+  L2Lds(const fa_params &P, int smax, bool wide) : slots(smax + 1) {
+    const int per_window = std::max(1, 2 * P.fragment_length / (P.window_size + 1));
+    // events of one locus staged in LDS per wave of k_l2_events (longer streams are stored directly): a stream holds
+    // the records of about 2.6 windows twice, minus the first window -- 5.3 windows' worth at the longest in the bench;
+    // the LDS this costs decides how many workgroups a CU holds (2048: 6, 1408: 7; 0.41 vs 0.38 ms for the L2 stage)
+    ev_stage = std::min(2048, std::max(512, (per_window * 11 / 2 + 127) & ~127));
+    events = ev_sketch_bytes(slots) + (size_t)ev_stage * (wide ? 4 : 2) * (EV_THREADS / 64) + 16;
+    // classes of k_l2_order's counting sort: the longest streams hold the records of ~2.6 windows twice (see ev_stage), so six
+    // windows' worth of events over the classes
+    scan_class_div = std::max(8, (per_window * 6 / SCAN_CLASSES + 7) & ~7);
   }
-  // offset of every fragment inside its genome, counting sort by it (stable: genomes stay in order inside a group)
-  std::vector<int32_t> off((size_t)F);
-  int32_t max_off = 0;
-  for (int64_t i = 0, qq = q; i < F; i++) {
-    while (g.genome_frag_lo[qq + 1] <= f0 + i) qq++;
-    off[(size_t)i] = (int32_t)(f0 + i - g.genome_frag_lo[qq]);
-    max_off = std::max(max_off, off[(size_t)i]);
-  }
-  if (max_off + 1 < 8) return 0;
-  std::vector<int32_t> start((size_t)max_off + 2, 0);
-  for (int64_t i = 0; i < F; i++) start[(size_t)off[(size_t)i] + 1]++;
-  for (int32_t p = 0; p <= max_off; p++) start[(size_t)p + 1] += start[(size_t)p];
-  std::vector<int32_t> sorted((size_t)F), fill(start.begin(), start.end() - 1);
-  for (int64_t i = 0; i < F; i++) sorted[(size_t)fill[(size_t)off[(size_t)i]]++] = (int32_t)i;
-  // groups -> XCD lists (the shortest list takes the next group; ties to the lowest XCD), then interleave
-  size_t len[8] = {0};
-  std::vector<uint8_t> xcd_of((size_t)max_off + 1);
-  for (int32_t p = 0; p <= max_off; p++) {
-    int x = 0;
-    for (int i = 1; i < 8; i++) if (len[i] < len[x]) x = i;
-    xcd_of[(size_t)p] = (uint8_t)x;
-    len[x] += (size_t)(start[(size_t)p + 1] - start[(size_t)p]);
-  }
-  const size_t longest = *std::max_element(len, len + 8);
-  if ((double)longest * 8.0 > 1.15 * (double)F) return 0;
-  out.assign(longest * 8, -1);
-  size_t at[8] = {0};
-  for (int32_t p = 0; p <= max_off; p++) {
-    const size_t x = xcd_of[(size_t)p];
-    for (int32_t i = start[(size_t)p]; i < start[(size_t)p + 1]; i++) out[(at[x]++) * 8 + x] = sorted[(size_t)i];
-  }
-  return (uint32_t)out.size();
-}
+  // k_l2_scan with `lanes` loci per workgroup and `bytes` of state per rank (1: the fast pass, 2: the wide-state redo pass)
+  size_t scan(int lanes, int bytes) const { return ((size_t)(slots + 1) * lanes * bytes + 15) / 16 * 16; }
+};
 
 // One pass of the hot path over genomes [g0, g1) of a resident batch.  Everything between the first kernel and the
 // final read-back is asynchronous on one stream: sizes that depend on the data (largest sketch, seed hits per
@@ -949,7 +869,7 @@ static uint32_t build_frag_order(const fa_genomes &g, int32_t g0, int64_t f0, in
 // launch_rows) and the verdict on a finished part (judge_part); run() runs the parts one after another.
 struct QueryPass {
   struct Range { int64_t f0, f1; bool unfused; };     // unfused: the repeat of a range that overflowed k_query_fused
-  struct Run { int64_t f0, f1; fa_mapper::Spec sp; bool with_rows; bool fused = false, forced_unfused = false, ordered = false; };
+  struct Run { int64_t f0, f1; Spec sp; bool with_rows; bool fused = false, forced_unfused = false, ordered = false; };
   // ---- what the caller gave ----
   fa_mapper &m;
   Workspace &w;
@@ -970,7 +890,7 @@ struct QueryPass {
   // ---- state of the run ----
   // the speculated bounds are shared by all workspaces: every attempt works on a copy taken under the lock and
   // publishes what it learnt (bounds only ever grow, except the LDS seed slots, which follow the latest pass)
-  fa_mapper::Spec sp;
+  Spec sp;
   bool bins_cleared = false;
   std::deque<Range> todo;
   bool rows_valid = false;
@@ -984,48 +904,29 @@ struct QueryPass {
   // ================================================ speculation ================================================
   void fetch_spec() {
     std::lock_guard<std::mutex> lock(m.mtx);
-    fa_mapper::Spec &ms = m.spec;
-    if (!ms.init) {
-      ms.init = true;
-      ms.smax = (int)env_u64("FA_SMAX_INIT", 256);                  // (development: a smaller first guess for small fragments)
-      ms.seed_slots = 4096;
-      ms.scratch_words = 0;
-      ms.l_cap = (int64_t)env_u64("FA_LOCI_CAP_MIN", 1u << 18);   // the tests force the retry path with a tiny value
-      ms.items_cap = env_u64("FA_EVENTS_CAP_MIN", 1u << 26);
-      ms.part_frags = pass_fragments();
-    }
+    Spec &ms = m.spec;
+    // (FA_SMAX_INIT: development, a smaller first guess for small fragments; FA_LOCI_CAP_MIN: the tests force the retry path
+    // with a tiny value)
+    if (!ms.init)
+      ms = spec_first_use((int)env_u64("FA_SMAX_INIT", 256), (int64_t)env_u64("FA_LOCI_CAP_MIN", 1u << 18), env_u64("FA_EVENTS_CAP_MIN", 1u << 26),
+                          pass_fragments());
     sp = ms;
     sp.fuse_off = ms.fuse_skip > 0;
     FA_REQUIRE(sp.smax < 32768, FA_ERR_UNSUPPORTED, "query sketch larger than 32767 minimizers");
     ensure_luts(m, sp.smax);
     w.lut_min_hits = m.d_min_hits.p; w.lut_pass = m.d_pass.p; w.lut_ident = m.d_ident.p;
   }
-  void publish_spec(const fa_mapper::Spec &sp) {
+  void publish_spec(const Spec &sp) {
     std::lock_guard<std::mutex> lock(m.mtx);
-    fa_mapper::Spec &ms = m.spec;
-    ms.smax = std::max(ms.smax, sp.smax);
-    ms.seed_slots = sp.seed_slots;
-    ms.scratch_words = std::max(ms.scratch_words, sp.scratch_words);
-    ms.items_cap = std::max(ms.items_cap, sp.items_cap);
-    ms.l_cap = std::max(ms.l_cap, sp.l_cap);
-    ms.part_frags = std::min(ms.part_frags, sp.part_frags);
-    ms.redo = ms.redo || sp.redo;
-    ms.l1_small_share = sp.l1_small_share; ms.l1_mid_share = sp.l1_mid_share; ms.l1_tiny_share = sp.l1_tiny_share;
-    ms.l1_prefilter = ms.l1_prefilter || sp.l1_prefilter; ms.l1_no_small = ms.l1_no_small || sp.l1_no_small;
-    ms.l2_loci_last = sp.l2_loci_last;
-    ms.smax_misses = std::max(ms.smax_misses, sp.smax_misses);
+    spec_merge(m.spec, sp);
   }
   // workgroups per CU of the two L2 kernels at a sketch bound (their LDS grows with it), as one number; 0 = not the usual
   // instantiation (wide events, fewer than 64 loci per scan workgroup) or the runtime does not say
   int scan_occupancy(int smax) {
-    const int slots = smax + 1;
-    if (slots + 1 >= (1 << EvBits<uint16_t>::RANK) || !m.packed_geo) return 0;
-    const size_t lds_scan = ((size_t)(slots + 1) * L2_THREADS + 15) / 16 * 16;
-    if (lds_scan > 64 * 1024) return 0;
-    const int per_window = std::max(1, 2 * m.P.fragment_length / (m.P.window_size + 1));
-    const int ev_stage = std::min(2048, std::max(512, (per_window * 11 / 2 + 127) & ~127));
-    const size_t lds_ev = ev_sketch_bytes(slots) + (size_t)ev_stage * 2 * (EV_THREADS / 64) + 16;
-    if (lds_ev > 64 * 1024) return 0;
+    if (smax + 2 >= (1 << EV_RANK16) || !m.packed_geo) return 0;
+    const L2Lds lds(m.P, smax, false);
+    const size_t lds_scan = lds.scan(L2_THREADS, 1), lds_ev = lds.events;
+    if (lds_scan > 64 * 1024 || lds_ev > 64 * 1024) return 0;
     int n_scan = 0, n_ev = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n_scan, (const void *)k_l2_scan<uint16_t, uint8_t, 64>, L2_THREADS, lds_scan) != hipSuccess ||
         hipOccupancyMaxActiveBlocksPerMultiprocessor(&n_ev, m.events_packed() ? (const void *)k_l2_events<uint16_t, true> : (const void *)k_l2_events<uint16_t, false>,
@@ -1072,7 +973,7 @@ struct QueryPass {
     ra.emit = npairs <= std::min<int64_t>(emit_max, 16384);
     ra.pub = pub;
     if (!ra.emit) ra.pub.seq = 0;
-    ra.done = d_counters + 4; ra.query_total_frag = g.d_total_frag + g0; ra.query_id_base = g0;
+    ra.done = &d_counters[CNT_ROWS_DONE]; ra.query_total_frag = g.d_total_frag + g0; ra.query_id_base = g0;
     ra.rows = rows_dev + row_base; ra.cap = cap - row_base; ra.total_rows = d_total_rows;
     hipLaunchKernelGGL(k_cgi_rows, dim3(ceil_div(npairs, 4)), dim3(256), 0, st, ra);
     if (ra.emit) {
@@ -1088,18 +989,14 @@ struct QueryPass {
   }
   // what the stage launches of one part share (sized by size_part)
   struct Part {
-    const fa_mapper::Spec &sp;
+    const Spec &sp;
     const int64_t f0, f1, F;
     const int t0, ntiles;
     const int smax;
     const int64_t l_cap;
-    struct L1Class { int nt; uint32_t slots, n_lo, n_hi; };   // one launch of k_l1: the fragments with n_lo <= hits <= n_hi
-    L1Class l1[3];
-    int n_l1 = 0;
-    bool l1_prefilter = false;                                // this part drops dead hits before k_l1's block sort
+    L1Plan l1;                                                // the launches of k_l1 (plan_l1)
     bool scan_sorted = false;                                 // k_l2_scan takes its loci sorted by stream length (k_l2_order)
-    uint32_t seed_slots = 0;                                  // slots of the last class
-    bool wide = false;
+    bool wide = false;                                        // 32-bit slide events (wide_events)
     LociRegions loci{nullptr, 1, 0};          // regions of the locus numbering of this part
     const int32_t *frag_order = nullptr;      // workgroup order of the part (prepare_order), null = identity
     uint32_t order_len = 0;
@@ -1114,7 +1011,7 @@ struct QueryPass {
   // one part: its buffers, then the stages in order, then the hand-over -- all asynchronous on the workspace's stream
   void launch_part(Run &r) {
     Part p(*this, r);
-    const fa_mapper::Spec &sp = p.sp;
+    const Spec &sp = p.sp;
     const int64_t f0 = p.f0, F = p.F;
     w.last_F = 0; w.last_loci = 0;                                  // (filled in when the part is accepted)
     const int ntiles = p.ntiles;
@@ -1133,70 +1030,11 @@ struct QueryPass {
     // ---- buffers and tables sized by the speculated bounds ----
     const int smax = p.smax;
     const int64_t l_cap = p.l_cap;
-    // LDS also holds smax list offsets; the in-place merge keeps at most 32 seeds per thread in registers
-    // k_l1 runs once per size class of fragments (L1Args::n_lo / n_hi): up to 4 096 hits the 256-thread form with 16 hits per
-    // thread (4-wave workgroups, eight per CU: a 5 Mb query is one round of workgroups), up to 7 936 the 512-thread form with 16,
-    // beyond the 512-thread form with 32 (above 4 096 hits 512 threads measured best: fewer hits per thread shorten every thread's
-    // chain of dependent LDS round trips; 1 024 threads pay more for barriers than they gain).  A class the speculated bound
-    // (sp.seed_slots: the largest fragment seen, plus a quarter) does not reach is not launched; the last class takes everything
-    // above its lower bound, overflow into HBM scratch included.
     {
-      const uint32_t cap_max = lds_seed_cap_max(smax), need = std::min(sp.seed_slots, cap_max);
-      p.n_l1 = 0;
-      const uint32_t s_slots = std::min<uint32_t>(need, L1_SMALL_HITS);
-      p.l1[p.n_l1++] = Part::L1Class{256, s_slots, 0u, need <= L1_SMALL_HITS ? 0xFFFFFFFFu : s_slots};
-      if (need > L1_SMALL_HITS) {
-        // (a 512-thread workgroup is eight waves: four of them fill a CU whatever their LDS up to 39 KB, so the block table of
-        // l1_block_sort -- a third as many entries as seed slots -- gets all the slots the 16-per-thread form can address)
-        // (7 936, not 8 192: the kilobyte goes to the key buffer behind the slots, which then holds the (key, place) pairs of 1 024
-        // blocks -- the 4 x 10^8-record index of config 3 adds ~500 chance hits, each a block of its own, to the ~250 blocks of a
-        // fragment's relatives -- and four workgroups still fill a CU)
-        const uint32_t m_slots = std::min<uint32_t>(L1_MID_HITS, cap_max);
-        p.l1[p.n_l1++] = Part::L1Class{512, m_slots, s_slots + 1u, need <= m_slots ? 0xFFFFFFFFu : m_slots};
-        if (need > m_slots)
-          p.l1[p.n_l1++] = Part::L1Class{512, std::min<uint32_t>(need, (uint32_t)(L1_INPLACE_MAX * 512)), m_slots + 1u, 0xFFFFFFFFu};
-      }
-      // The pre-filter of the block sort (l1_block_sort: hits that cannot belong to a candidate are dropped before the sort, one more
-      // sweep over the position lists) pays where chance hits push the blocks of a fragment beyond what the register sort holds, and
-      // costs where they do not (profiles/r06_l1_prefilter.txt: lookup + L1 70.4 -> 60.9 ms on config 3, 211 -> 156 on 2000 x 2000
-      // genomes, 38.9 -> 20.1 in the (k = 14, fragment 1000) cell, whose 28-bit hashes collide everywhere; 52.8 -> 66.3 us on the
-      // one-query step, 5.4 -> 6.2 ms in the (16, 3000) cell).  So it follows the evidence: on from 3 x 10^8 index records (~400
-      // chance hits per fragment), and on any index once an accepted part of this mapper had one fragment in two hundred fall back
-      // to the merge (Spec::l1_prefilter, sticky).  FA_L1_PREFILTER = 0 / 1: never / always.
-      static const int l1_pf_env = getenv("FA_L1_PREFILTER") ? atoi(getenv("FA_L1_PREFILTER")) : -1;
-      p.l1_prefilter = l1_pf_env < 0 ? (m.N >= 300000000LL || sp.l1_prefilter) : l1_pf_env != 0;
-      // Which classes get a launch of their own is decided from the shares `seed_totals` counted in the last accepted part (a launch
-      // walks every fragment: 1.7 million workgroups that return at once cost config 3 two milliseconds of 67).  Measured (round 6,
-      // profiles/r06_l1_classes_ab.txt, r06_l1_prefilter.txt): fragments of ~1 500 hits -- a genome-like index of 200 genomes --
-      // take 7.5 ms per step in the 256-thread form and 10.3 in the 512-thread one; config 3's fragments of 3 000-4 000 hits, nine in
-      // ten below the 4 096 bound, take 69.2 in the 512-thread form against 70.4 WITHOUT the pre-filter (their ~500 chance hits are
-      // blocks of their own, and the 256-thread form sorts 1 024 blocks at most: what overflows takes the merge) and 60.9 against
-      // 70.2 WITH it.  So: with the pre-filter the small class is kept when it holds a third of the fragments; without, when half
-      // the fragments hold at most HALF its bound.  The middle class is kept from a twentieth of the fragments on (the
-      // 32-hits-per-thread form behind it runs two workgroups per CU and is three times slower per fragment), or to carry the
-      // small ones.  Ranges stay contiguous from 0: a wrong guess costs time, not results.
-      static const float thin_small = getenv("FA_L1_THIN_SMALL") ? (float)atof(getenv("FA_L1_THIN_SMALL")) : -1.0f;
-      static const float thin_mid = getenv("FA_L1_THIN_MID") ? (float)atof(getenv("FA_L1_THIN_MID")) : 0.05f;
-      if (p.n_l1 >= 2) {
-        // S form for the small fragments, or do they ride in the middle form; the middle class stays if it has fragments of its
-        // own worth a launch, or small ones to carry
-        const bool keep_s = thin_small >= 0.0f ? (sp.l1_small_share < 0.0f || sp.l1_small_share >= thin_small)        // (forced: tests, A/B)
-                            : sp.l1_no_small ? false
-                            : p.l1_prefilter ? (sp.l1_small_share < 0.0f || sp.l1_small_share >= 0.35f)
-                                             : (sp.l1_tiny_share < 0.0f || sp.l1_tiny_share >= 0.5f);
-        const bool keep_m = !keep_s || p.n_l1 == 2 || sp.l1_mid_share < 0.0f || sp.l1_mid_share >= thin_mid;
-        Part::L1Class c[3];
-        int n = 0;
-        uint32_t lo = 0u;                                            // lower bound of the next class kept
-        if (keep_s) { c[n++] = p.l1[0]; lo = p.l1[0].n_hi + 1u; }
-        if (keep_m) { c[n] = p.l1[1]; c[n].n_lo = lo; lo = p.l1[1].n_hi == 0xFFFFFFFFu ? lo : p.l1[1].n_hi + 1u; n++; }
-        if (p.n_l1 == 3) { c[n] = p.l1[2]; c[n].n_lo = lo; n++; }
-        for (int i = 0; i < n; i++) p.l1[i] = c[i];
-        p.n_l1 = n;
-      }
-      static const bool dbg_l1 = getenv("FA_DEBUG_L1") != nullptr;
-      if (dbg_l1) fprintf(stderr, "k_l1 classes: need=%u tiny=%.3f small=%.3f mid=%.3f prefilter=%d -> %d launch(es)\n", need, sp.l1_tiny_share, sp.l1_small_share, sp.l1_mid_share, (int)p.l1_prefilter, p.n_l1);
-      p.seed_slots = p.l1[p.n_l1 - 1].slots;                       // "fits LDS" for seed_totals and k_l1_big: the last class's slots
+      static const L1Knobs knobs{(int)env_num("FA_L1_PREFILTER", -1), (float)env_num("FA_L1_THIN_SMALL", -1.0), (float)env_num("FA_L1_THIN_MID", 0.05)};
+      p.l1 = plan_l1(sp, m.N, knobs);
+      static const bool dbg_l1 = env_set("FA_DEBUG_L1");
+      if (dbg_l1) fprintf(stderr, "k_l1 classes: need=%u tiny=%.3f small=%.3f mid=%.3f prefilter=%d -> %d launch(es)\n", p.l1.need, sp.l1_tiny_share, sp.l1_small_share, sp.l1_mid_share, (int)p.l1.prefilter, p.l1.n);
     }
     w.l_frag.ensure((size_t)l_cap); w.l_seq.ensure((size_t)l_cap); w.l_start.ensure((size_t)l_cap); w.l_end.ensure((size_t)l_cap + 4);
     w.l_rfirst.ensure((size_t)l_cap); w.l_rlast.ensure((size_t)l_cap + 4); w.l_rpart.ensure((size_t)l_cap);
@@ -1204,13 +1042,8 @@ struct QueryPass {
     w.group_best.ensure((size_t)l_cap + 2);
     w.l_beg.ensure((size_t)l_cap); w.l_end0.ensure((size_t)l_cap); w.l_last.ensure((size_t)l_cap); w.l_ndrop.ensure((size_t)l_cap);
     w.l_nev.ensure((size_t)l_cap); w.l_ioff.ensure((size_t)l_cap); w.l_redo.ensure((size_t)l_cap + 4);
-    // A wave of k_l2_scan lasts as long as the longest of its 64 slides, and in k_l1's numbering it holds the loci of one fragment --
-    // streams of every length the divergences of the index produce (lane utilisation 85 %).  When the last accepted part had loci
-    // for a wave per SIMD and more, the scan takes the loci of every region sorted by stream length (profiles/r06_scan_order.txt:
-    // L2 stage -8 % on config 3, -9 % on config 4, -10 % on genome-like inputs and in the (16, 1000) cell, -6 % at 16 queries per
-    // launch, -1 % on one 5 Mb query).  FA_L2_SCAN_ORDER = 0 / 1: never / always.
-    static const int scan_order_env = getenv("FA_L2_SCAN_ORDER") ? atoi(getenv("FA_L2_SCAN_ORDER")) : -1;
-    p.scan_sorted = scan_order_env < 0 ? sp.l2_loci_last >= 1024 * 64 : scan_order_env != 0;
+    static const int scan_order_knob = (int)env_num("FA_L2_SCAN_ORDER", -1);
+    p.scan_sorted = scan_sorted(sp, scan_order_knob);
     w.scan_hist.ensure((size_t)2 * LOCI_REGIONS * SCAN_CLASSES);
     if (p.scan_sorted) w.scan_order.ensure((size_t)l_cap + 64);
     w.ovf_buf.ensure((size_t)sp.scratch_words + 4);
@@ -1219,14 +1052,13 @@ struct QueryPass {
     p.loci.n = std::min<uint32_t>(LOCI_REGIONS, ev_regions_for(F));
     p.loci.shift = (uint32_t)floor_log2((int)std::max<int64_t>(1, l_cap / p.loci.n));
     w.loci_n = p.loci.n; w.loci_shift = p.loci.shift;
-    w.l1_pf = p.l1_prefilter; w.l1_small_class = p.n_l1 > 1 && p.l1[0].nt == 256;
-    p.wide = smax + 1 >= (1 << EvBits<uint16_t>::RANK);        // slot = rank + 1 must fit the slot field of the 16-bit event
+    p.wide = wide_events(smax);
     w.items.ensure(((size_t)sp.items_cap + 8) * (p.wide ? 4 : 2));
-    w.forms = Workspace::Forms();
-    w.forms.n_l1 = p.n_l1;
-    for (int c = 0; c < p.n_l1; c++) w.forms.l1_threads[c] = p.l1[c].nt;
-    w.forms.prefilter = p.l1_prefilter; w.forms.scan_sorted = p.scan_sorted; w.forms.wide = p.wide; w.forms.redo = sp.redo;
-    w.forms.smax = smax; w.forms.seed_slots = p.seed_slots;
+    w.forms = Forms();
+    w.forms.n_l1 = p.l1.n;
+    for (int c = 0; c < p.l1.n; c++) w.forms.l1_threads[c] = p.l1.c[c].nt;
+    w.forms.prefilter = p.l1.prefilter; w.forms.scan_sorted = p.scan_sorted; w.forms.wide = p.wide; w.forms.redo = sp.redo;
+    w.forms.smax = smax; w.forms.seed_slots = p.l1.seed_slots();
 
     launch_sketch_stage(r, p);
     prepare_order(p);
@@ -1235,15 +1067,15 @@ struct QueryPass {
     launch_cgi_stage_and_hand_over(r, p);
   }
 
-  // Passes of several genomes run the workgroups of k_l2_events in offset-major, XCD-aware
-  // order (build_frag_order); the order is built on the host, cached per (batch, fragment range) and uploaded behind K1.
+  // The workgroup order of k_l2_events (frag_order_gate, build_frag_order), built on the host, cached per (batch, fragment
+  // range) and uploaded behind K1.
   void prepare_order(Part &p) {
-    static const bool order_on = !(getenv("FA_FRAG_ORDER") && atoi(getenv("FA_FRAG_ORDER")) == 0);
-    static const bool order_one = !(getenv("FA_FRAG_ORDER_ONE") && atoi(getenv("FA_FRAG_ORDER_ONE")) == 0);   // (A/B of the one-genome order)
-    if (!(order_on && (NQ >= 2 || order_one) && p.F >= 64)) return;
+    static const bool order_on = env_num("FA_FRAG_ORDER", 1) != 0;
+    static const bool order_one = env_num("FA_FRAG_ORDER_ONE", 1) != 0;   // (A/B of the one-genome order)
+    if (!frag_order_gate(order_on, order_one, NQ, p.F)) return;
     if (w.order_batch != g.serial || w.order_f0 != p.f0 || w.order_f1 != p.f1) {
       std::vector<int32_t> ord;
-      w.order_len = build_frag_order(g, g0, p.f0, p.f1, ord);       // 0: the lists cannot be balanced, identity order
+      w.order_len = build_frag_order(g.genome_frag_lo.data(), g0, p.f0, p.f1, ord);       // 0: the lists cannot be balanced, identity order
       if (w.order_len) {
         w.pin_order.ensure(ord.size() * sizeof(int32_t));
         memcpy(w.pin_order.p, ord.data(), ord.size() * sizeof(int32_t));
@@ -1257,7 +1089,7 @@ struct QueryPass {
 
   // K1 (its extra workgroups zero the tables of the part) + per-fragment sort / unique / index lookup
   void launch_sketch_stage(Run &r, Part &p) {
-    const fa_mapper::Spec &sp = p.sp;
+    const Spec &sp = p.sp;
     const int64_t f0 = p.f0, F = p.F;
     const int64_t l_cap = p.l_cap;
     const int t0 = p.t0, ntiles = p.ntiles;
@@ -1276,24 +1108,21 @@ struct QueryPass {
       a.q_hash = w.q_hash.p; a.q_size = w.q_size.p; a.qcap = qcap;
       a.ix = ix; a.q_off = w.q_off.p; a.q_cnt = w.q_cnt.p; a.n_seeds = w.n_seeds.p;
       a.sort_cap = (int32_t)(qs_lds / 4);
-      a.rec_cap = getenv("FA_QF_CAP") ? std::max(0, std::min(QF_CAP, atoi(getenv("FA_QF_CAP")))) : QF_CAP;
+      a.rec_cap = (int)std::max(0.0, std::min((double)QF_CAP, env_num("FA_QF_CAP", QF_CAP)));
       a.exc_tiles = 0;                                 // (set by launch_sketch_tiles for the fused kernel)
       // ---- K1 (its extra workgroups zero the ranges above beside the hashing) + per-fragment sort / unique / index lookup:
       //      one launch where the pass qualifies (k_query_fused), else k_sketch_fast / k_sketch_tiles, then k_query_sketch ----
       const bool fused = launch_sketch_tiles(m.P, g.store, g.tiles + t0, ntiles, w.sk.stage_hash.p, w.sk.stage_wpos.p, w.sk.tile_count.p, st, &cl.a,
                                              (sp.fuse_off || r.forced_unfused) ? nullptr : &a, F);
       r.fused = fused;
-      if (!fused) {
-        if (qs_lds > 64 * 1024) FA_HIP(hipFuncSetAttribute((const void *)k_query_sketch, hipFuncAttributeMaxDynamicSharedMemorySize, (int)qs_lds));
-        hipLaunchKernelGGL(k_query_sketch, dim3((unsigned)F), dim3(MAP_THREADS), qs_lds, st, a);
-      }
+      if (!fused) launch_lds(k_query_sketch, dim3((unsigned)F), dim3(MAP_THREADS), qs_lds, st, a);
     }
     debug_sync(st, "sketch");
   }
 
   // seed totals, then the candidate regions
   void launch_l1_stage(Part &p) {
-    const fa_mapper::Spec &sp = p.sp;
+    const Spec &sp = p.sp;
     const int64_t F = p.F;
     const int smax = p.smax;
     const int64_t l_cap = p.l_cap;
@@ -1301,7 +1130,7 @@ struct QueryPass {
     uint64_t *const d_totals = w.status.p->totals;
     uint32_t *const d_counters = w.status.p->counters;
     unsigned long long *const d_pinfo = w.status.p->pinfo;
-    const uint32_t seed_slots = p.seed_slots;
+    const uint32_t seed_slots = p.l1.seed_slots();
     // ---- seed totals and speculation checks (the lookup itself is the tail of k_query_sketch).  A kernel of its own
     //      only where k_l1 / k_l1_big need the scratch offsets it produces; else workgroup F of k_l1's launch ----
     const bool fold_totals = sp.scratch_words == 0;
@@ -1321,53 +1150,40 @@ struct QueryPass {
       a.counters = d_counters; a.loci = p.loci; a.qcap = qcap; a.frag_len = m.P.fragment_length; a.l_cap = (int32_t)l_cap;
       a.lds_seed_cap = seed_slots; a.totals_seed_cap = seed_slots; a.n_lo = 0; a.n_hi = 0xFFFFFFFFu; a.pinfo = d_pinfo; a.lut_smax = smax; a.scratch_words = sp.scratch_words;
       a.f_loci_lo = w.f_loci_lo.p; a.f_loci_n = w.f_loci_n.p;
-      static const bool l1_block_sort_on = !(getenv("FA_L1_BLOCK_SORT") && atoi(getenv("FA_L1_BLOCK_SORT")) == 0);
-      static const bool l1_stats = getenv("FA_L1_STATS") && atoi(getenv("FA_L1_STATS")) != 0;
-      // Hits that cannot be an end of a candidate skip the fetch of their padded global coordinate (k_l1, scan_run<., NEAR>).  The
-      // hits it saves are the chance hits, whose number grows with the index (~500 per fragment at 4 x 10^8 records, ~50 at
-      // 4 x 10^7), and it costs a second LDS read per hit: lookup + L1 70.8 -> 67.0 ms per step on 1000 x 1000 genomes, 28.6 ->
-      // 28.6 on 500 x 500, 10.1 -> 10.6 on 200 x 200 (profiles/r05_l1_near_time.txt) -- so it is on from 3 x 10^8 records.
-      // FA_L1_NEAR = 0 / 1: never / always (the A/B of the HBM fetch: profiles/r05_l1_near_fetch.txt).
-      static const int l1_near_env = getenv("FA_L1_NEAR") ? atoi(getenv("FA_L1_NEAR")) : -1;
-      const bool l1_near_on = l1_near_env < 0 ? m.N >= 300000000LL : l1_near_env != 0;
-      const bool l1_pf_on = p.l1_prefilter;             // (decided with the size classes, when the part was planned)
+      static const bool l1_block_sort_on = env_num("FA_L1_BLOCK_SORT", 1) != 0;
+      static const bool l1_stats = env_num("FA_L1_STATS", 0) != 0;
+      static const int l1_near_knob = (int)env_num("FA_L1_NEAR", -1);
+      const bool l1_near_on = l1_near(m.N, l1_near_knob);
+      const bool l1_pf_on = p.l1.prefilter;             // (decided with the size classes, when the part was planned)
       a.block_sort = (l1_block_sort_on ? 1 : 0) | (l1_stats ? 2 : 0) | (l1_near_on ? 4 : 0) | (l1_pf_on ? 8 : 0);
       const uint32_t l1_grid = (uint32_t)F;             // (the offset-major order of k_l2_events applied here measured nothing: 75.9 / 75.5 ms on config 3)
       a.dbg = w.status.p->dbg;
       // fragments with more hits than LDS holds (seen before on this mapper: scratch is reserved for them) are cut
       // into LDS-sized chunks at contig boundaries by k_l1_big first; what it cannot cut stays with k_l1's HBM path
-      static const bool l1_big = !(getenv("FA_L1_BIG") && atoi(getenv("FA_L1_BIG")) == 0);
+      static const bool l1_big = env_num("FA_L1_BIG", 1) != 0;
       a.big_state = nullptr; a.big_enabled = 0; a.big_cap = 0;
       const int64_t big_room = (int64_t)160 * 1024 - 2048 - ((int64_t)smax + 2) * 16;   // LDS left for a chunk's seeds
       if (l1_big && sp.scratch_words > 0 && big_room >= 4 * 2048) {
         w.big_state.ensure((size_t)F);
         a.big_cap = (uint32_t)std::min<int64_t>((int64_t)L1_BIG_E * L1_BIG_THREADS, big_room / 4 / 256 * 256);
         a.big_state = w.big_state.p; a.big_enabled = 1;
-        const size_t lds = l1_big_lds_bytes(a.big_cap, smax);
-        if (lds > 64 * 1024) FA_HIP(hipFuncSetAttribute((const void *)k_l1_big, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(k_l1_big, dim3((unsigned)F), dim3(L1_BIG_THREADS), lds, st, a);
+        launch_lds(k_l1_big, dim3((unsigned)F), dim3(L1_BIG_THREADS), l1_big_lds_bytes(a.big_cap, smax), st, a);
       }
-      // one launch per size class (Part::L1Class); the seed totals ride in the first one
-      auto go = [&](auto nt_tag, const Part::L1Class &c, bool fold) {
+      // one launch per size class (L1Class); the seed totals ride in the first one
+      auto go = [&](auto nt_tag, const L1Class &c, bool fold) {
         constexpr int NTT = decltype(nt_tag)::value;
         const size_t lds = l1_lds_bytes(c.slots, smax, NTT);
         FA_REQUIRE(lds + 1024 <= 160 * 1024, FA_ERR_UNSUPPORTED, "query sketch too large for the LDS tables of the L1 kernel");
-        static const bool dbg = getenv("FA_DEBUG_L1") != nullptr;
+        static const bool dbg = env_set("FA_DEBUG_L1");
         if (dbg) fprintf(stderr, "k_l1<%d>: F=%lld hits %u..%u seed_slots=%u smax=%d lds=%zu\n", NTT, (long long)F, c.n_lo, c.n_hi, c.slots, smax, lds);
         L1Args b = a;
         b.lds_seed_cap = c.slots; b.n_lo = c.n_lo; b.n_hi = c.n_hi; b.fold_totals = fold ? 1 : 0;
-        if (c.slots <= 16 * (uint32_t)NTT) {
-          if (lds > 64 * 1024) FA_HIP(hipFuncSetAttribute((const void *)k_l1<NTT, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-          hipLaunchKernelGGL((k_l1<NTT, 16>), dim3(l1_grid + (fold ? 1u : 0u)), dim3(NTT), lds, st, b);
-        } else {
-          if (lds > 64 * 1024) FA_HIP(hipFuncSetAttribute((const void *)k_l1<NTT, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-          hipLaunchKernelGGL((k_l1<NTT, 32>), dim3(l1_grid + (fold ? 1u : 0u)), dim3(NTT), lds, st, b);
-        }
+        launch_lds(c.slots <= 16 * (uint32_t)NTT ? k_l1<NTT, 16> : k_l1<NTT, 32>, dim3(l1_grid + (fold ? 1u : 0u)), dim3(NTT), lds, st, b);
       };
-      for (int c = 0; c < p.n_l1; c++) {
+      for (int c = 0; c < p.l1.n; c++) {
         const bool fold = fold_totals && c == 0;
-        if (p.l1[c].nt >= 512) go(std::integral_constant<int, 512>(), p.l1[c], fold);
-        else go(std::integral_constant<int, 256>(), p.l1[c], fold);
+        if (p.l1.c[c].nt >= 512) go(std::integral_constant<int, 512>(), p.l1.c[c], fold);
+        else go(std::integral_constant<int, 256>(), p.l1.c[c], fold);
       }
     }
     debug_sync(st, "l1");
@@ -1375,7 +1191,7 @@ struct QueryPass {
 
   // event streams, then the sequential slide
   void launch_l2_stage(Run &r, Part &p) {
-    const fa_mapper::Spec &sp = p.sp;
+    const Spec &sp = p.sp;
     const int64_t F = p.F;
     const int smax = p.smax;
     const int64_t l_cap = p.l_cap;
@@ -1396,69 +1212,47 @@ struct QueryPass {
       a.l_shared = w.l_shared.p; a.l_pos = w.l_pos.p; a.pass_lut = w.lut_pass; a.group_best = w.group_best.p;
       a.counters = d_counters; a.loci = p.loci; a.qcap = qcap; a.cmw = m.cmw;
       a.cnt_slots = smax + 1;
-      a.rec_total = (unsigned long long *)(d_totals + 3);
+      a.rec_total = (unsigned long long *)&d_totals[TOT_RECORDS];
       a.ev_region = w.status.p->ev_region; a.rec_region = w.status.p->rec_region;
       a.n_regions = ev_regions_for(F);
       a.region_cap = (sp.items_cap / a.n_regions) & ~7ULL;
       a.l_redo = w.l_redo.p;
-      a.redo_count = d_counters + 3;
-      {
-        // classes of the counting sort: the longest streams hold the records of ~2.6 windows twice (see ev_stage below), so six
-        // windows' worth of events over the classes
-        const int per_window_ev = std::max(1, 2 * m.P.fragment_length / (m.P.window_size + 1));
-        a.scan_class_div = p.scan_sorted ? std::max(8, (per_window_ev * 6 / SCAN_CLASSES + 7) & ~7) : 0;
-        a.scan_hist = w.scan_hist.p; a.scan_cursor = w.scan_hist.p + LOCI_REGIONS * SCAN_CLASSES;
-        a.scan_order = p.scan_sorted ? w.scan_order.p : nullptr;
-      }
+      a.redo_count = &d_counters[CNT_WIDE];
+      const L2Lds lds(m.P, smax, wide);
+      a.scan_class_div = p.scan_sorted ? lds.scan_class_div : 0;
+      a.scan_hist = w.scan_hist.p; a.scan_cursor = w.scan_hist.p + LOCI_REGIONS * SCAN_CLASSES;
+      a.scan_order = p.scan_sorted ? w.scan_order.p : nullptr;
       a.f_loci_lo = w.f_loci_lo.p; a.f_loci_n = w.f_loci_n.p;
       // several genomes in the pass: the workgroups of k_l2_events in offset-major order (prepare_order)
       a.frag_order = p.frag_order;
       const uint32_t ev_grid = p.frag_order ? p.order_len : (uint32_t)F;
       if (p.frag_order) r.ordered = true;
-      // events of one locus staged in LDS per wave of k_l2_events (longer streams are stored directly): a stream holds
-      // the records of about 2.6 windows twice, minus the first window -- 5.3 windows' worth at the longest in the bench;
-      // the LDS this costs decides how many workgroups a CU holds (2048: 6, 1408: 7; 0.41 vs 0.38 ms for the L2 stage)
-      const int per_window = std::max(1, 2 * m.P.fragment_length / (m.P.window_size + 1));
-      a.ev_stage = std::min(2048, std::max(512, (per_window * 11 / 2 + 127) & ~127));
-      const size_t ev_lds = ev_sketch_bytes(a.cnt_slots) + (size_t)a.ev_stage * (wide ? 4 : 2) * (EV_THREADS / 64) + 16;
+      a.ev_stage = lds.ev_stage;
+      const size_t ev_lds = lds.events;
       FA_REQUIRE(ev_lds <= 150 * 1024, FA_ERR_UNSUPPORTED, "query sketch too large for the LDS-staged event kernel");
       // fast pass: one state byte per rank; redo pass: two bytes per rank, only for loci whose counts overflowed
-      auto scan_lds = [&](int ln, int bytes) { return ((size_t)(a.cnt_slots + 1) * ln * bytes + 15) / 16 * 16; };
       auto pick_lanes = [&](int bytes) {
         int ln = L2_THREADS;
-        while (ln > 1 && scan_lds(ln, bytes) > 144 * 1024) ln >>= 1;   // large sketches (tiny windows): fewer loci per workgroup
-        FA_REQUIRE(scan_lds(ln, bytes) <= 160 * 1024, FA_ERR_UNSUPPORTED, "query sketch too large for the LDS-resident L2 state");
+        while (ln > 1 && lds.scan(ln, bytes) > 144 * 1024) ln >>= 1;   // large sketches (tiny windows): fewer loci per workgroup
+        FA_REQUIRE(lds.scan(ln, bytes) <= 160 * 1024, FA_ERR_UNSUPPORTED, "query sketch too large for the LDS-resident L2 state");
         return ln;
       };
       const int lanes8 = pick_lanes(1), lanes16 = pick_lanes(2);
-      const size_t lds8 = scan_lds(lanes8, 1), lds16 = scan_lds(lanes16, 2);
+      const size_t lds8 = lds.scan(lanes8, 1), lds16 = lds.scan(lanes16, 2);
       // (workgroup b of a scan takes chunk b / n of region b mod n: every region needs its chunks, however few loci it can hold)
       auto scan_grid = [&](int lanes) { return (unsigned)(p.loci.n * (uint32_t)ceil_div((int64_t)1 << p.loci.shift, lanes)); };
       auto launch = [&](auto ev_kernel, auto scan8, auto scan8_rt, auto scan16, auto scan16_rt) {
-        if (ev_lds > 64 * 1024) FA_HIP(hipFuncSetAttribute((const void *)ev_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ev_lds));
-        hipLaunchKernelGGL(ev_kernel, dim3(ev_grid), dim3(EV_THREADS), ev_lds, st, a);
+        launch_lds(ev_kernel, dim3(ev_grid), dim3(EV_THREADS), ev_lds, st, a);
         debug_sync(st, "l2 events");
         if (p.scan_sorted)
           hipLaunchKernelGGL(k_l2_order, dim3((unsigned)(p.loci.n * (uint32_t)ceil_div((int64_t)1 << p.loci.shift, 256))), dim3(256), 0, st, a);
         // the number of loci is only known on the device: launch for the capacity, surplus workgroups exit at once
         a.lanes = lanes8;
-        if (lanes8 == L2_THREADS) {
-          if (lds8 > 64 * 1024) FA_HIP(hipFuncSetAttribute((const void *)scan8, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds8));
-          hipLaunchKernelGGL(scan8, dim3(scan_grid(lanes8)), dim3(L2_THREADS), lds8, st, a);
-        } else {
-          if (lds8 > 64 * 1024) FA_HIP(hipFuncSetAttribute((const void *)scan8_rt, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds8));
-          hipLaunchKernelGGL(scan8_rt, dim3(scan_grid(lanes8)), dim3(L2_THREADS), lds8, st, a);
-        }
+        launch_lds(lanes8 == L2_THREADS ? scan8 : scan8_rt, dim3(scan_grid(lanes8)), dim3(L2_THREADS), lds8, st, a);
         // the wide-state pass is only launched once some locus has needed it (a part that finds out too late is repeated)
         if (!sp.redo) return;
         a.lanes = lanes16;
-        if (lanes16 == L2_THREADS) {
-          if (lds16 > 64 * 1024) FA_HIP(hipFuncSetAttribute((const void *)scan16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16));
-          hipLaunchKernelGGL(scan16, dim3(scan_grid(lanes16)), dim3(L2_THREADS), lds16, st, a);
-        } else {
-          if (lds16 > 64 * 1024) FA_HIP(hipFuncSetAttribute((const void *)scan16_rt, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16));
-          hipLaunchKernelGGL(scan16_rt, dim3(scan_grid(lanes16)), dim3(L2_THREADS), lds16, st, a);
-        }
+        launch_lds(lanes16 == L2_THREADS ? scan16 : scan16_rt, dim3(scan_grid(lanes16)), dim3(L2_THREADS), lds16, st, a);
       };
       const bool pk = m.events_packed();
       if (wide) launch(pk ? k_l2_events<uint32_t, true> : k_l2_events<uint32_t, false>, k_l2_scan<uint32_t, uint8_t, 64>, k_l2_scan<uint32_t, uint8_t, 0>, k_l2_scan<uint32_t, uint16_t, 64>, k_l2_scan<uint32_t, uint16_t, 0>);
@@ -1470,7 +1264,7 @@ struct QueryPass {
 
   // core-genome identity and the one hand-over of the part
   void launch_cgi_stage_and_hand_over(Run &r, Part &p) {
-    const fa_mapper::Spec &sp = p.sp;
+    const Spec &sp = p.sp;
     const int64_t f0 = p.f0;
     const int64_t l_cap = p.l_cap;
     uint32_t *const d_counters = w.status.p->counters;
@@ -1488,12 +1282,16 @@ struct QueryPass {
       hipLaunchKernelGGL(k_cgi_bins, dim3(ceil_div(l_cap, 256)), dim3(256), 0, st, a);
     }
     // ---- the one hand-over of the part: results, statistics and the speculation verdict (publish_pass) ----
+    if (r.with_rows) rows_valid = true;
+    hand_over(r.with_rows);
+  }
+  // hands the pass over to the host (publish_args): with `rows` the rows are formed first (launch_rows, whose last workgroup
+  // hands over for small passes); otherwise k_publish_status does
+  void hand_over(bool rows) {
     PassStatus *h_dev = nullptr;
     FA_HIP(hipHostGetDevicePointer((void **)&h_dev, w.h_status, 0));
-    const bool to_host = r.with_rows && host_rows != nullptr;
-    const PublishArgs pub = publish_args(w.status.p, h_dev, ++w.seq, rows_dev + row_base, to_host ? host_rows + row_base : nullptr, cap - row_base);
-    bool published = false;
-    if (npairs > 0 && r.with_rows) { published = launch_rows(pub); rows_valid = true; }
+    const PublishArgs pub = publish_args(w.status.p, h_dev, ++w.seq, rows_dev + row_base, rows && host_rows ? host_rows + row_base : nullptr, cap - row_base);
+    const bool published = rows && launch_rows(pub);
     FA_HIP(hipGetLastError());
     debug_sync(st, "cgi");
     if (!published) hipLaunchKernelGGL(k_publish_status, dim3(1), dim3(256), 0, st, pub);
@@ -1502,134 +1300,56 @@ struct QueryPass {
   // ================================================ the verdict on a part ======================================
   // waits for a part and reads its verdict: true = accepted, false = void (its range has to run again)
   bool judge_part(Run &r) {
-    fa_mapper::Spec &sp = r.sp;
+    Spec &sp = r.sp;
     const int64_t F = r.f1 - r.f0;
     wait_published(w.h_status, w.seq, w.stream);
-    const int32_t *h_stats = w.h_status->stats;
-    const uint64_t *h_totals = w.h_status->totals;
-    const uint32_t *h_counters = w.h_status->counters;
-    const unsigned long long *h_pinfo = w.h_status->pinfo;
-    const uint64_t total_seeds = h_totals[0], max_seeds = h_totals[1];
-    uint64_t events_total = h_pinfo[0], records_total = h_totals[3], ev_region_max = 0;
-    for (int i = 0; i < EV_REGIONS; i++) {
-      events_total += w.h_status->ev_region[i]; records_total += w.h_status->rec_region[i];
-      ev_region_max = std::max<uint64_t>(ev_region_max, w.h_status->ev_region[i]);
-    }
-    const unsigned long long flags = h_pinfo[1];
-    // loci: reserved per region (LociRegions); a region asked for more than it holds = SPEC_LOCI
-    uint64_t loci_total = 0, loci_region_max = 0;
-    for (uint32_t i = 0; i < w.loci_n; i++) {
-      const uint64_t c = w.h_status->loci_region[i];
-      loci_region_max = std::max(loci_region_max, c);
-      loci_total += std::min<uint64_t>(c, 1ULL << w.loci_shift);
-    }
-    // a part whose seeds / loci / slide events cannot be addressed with 32-bit offsets is cut down and run again
-    if (flags || (h_counters[3] > 0 && !sp.redo)) w.last_ms[9] += 1.0f;   // repeated attempts of this call (speculation misses)
-    auto shrink_part = [&](double have, double limit, const char *what) {
-      FA_REQUIRE(F > 1, FA_ERR_UNSUPPORTED, std::string("a single query fragment produces too many ") + what);
-      sp.part_frags = std::max<int64_t>(1, std::min<int64_t>(F / 2, (int64_t)((double)F * limit / have * 0.8)));
-    };
-    if (total_seeds >= (1ULL << 31)) { shrink_part((double)total_seeds, 2147483648.0, "seed hits"); publish_spec(sp); return false; }
-    // bounds for the next pass (or the repeat of this one)
-    // (a multiple of 8 just above the largest sketch seen: every slot of the bound costs k_l2_scan 64 bytes of LDS per wave,
-    // and on the bench workload -- largest sketch 263 -- 272 slots let nine of its workgroups share a CU where 288 let eight)
-    // The first growth is that tight bound; if the workload keeps producing larger sketches (every raise voids a pass and
-    // rebuilds the O(s^2) LUTs) later ones take an eighth of headroom, cut back to the largest bound that leaves k_l2_scan and
-    // k_l2_events the workgroups per CU the tight bound would (scan_occupancy).
-    if (h_stats[0] > sp.smax) {
-      const int tight = (h_stats[0] + 4 + 7) / 8 * 8;
-      int bound = tight;
-      if (sp.smax_misses > 0) {
-        const int roomy = (h_stats[0] + h_stats[0] / 8 + 7) / 8 * 8;
-        const int want = scan_occupancy(tight);
-        bound = want > 0 ? tight : roomy;
-        for (int s2 = tight + 8; want > 0 && s2 <= roomy && scan_occupancy(s2) == want; s2 += 8) bound = s2;
-      }
-      sp.smax = bound;
-      sp.smax_misses++;
-    }
-    // LDS slots for the seed sort: a quarter of headroom over the largest fragment seen, (LDS per workgroup sets how many fragments a CU works on at once)
-    uint32_t want_slots = std::min<uint32_t>(lds_seed_cap_max(sp.smax), std::max<uint32_t>(1024, (uint32_t)((std::min<uint64_t>(max_seeds + max_seeds / 4, 1u << 30) + 255) / 256 * 256)));
-    const bool slots_changed = want_slots != sp.seed_slots;
-    if (flags & SPEC_SCRATCH) sp.scratch_words = std::max<uint64_t>(sp.scratch_words, h_totals[2] + h_totals[2] / 4);
-    if (flags & SPEC_LOCI) {
-      // every region has to hold its share: size the arrays for the fullest one.  A region holds the largest power of two
-      // below its share of l_cap, i.e. more than half of it: twice the need is what makes the repeat fit for certain
-      const int64_t need = (int64_t)(loci_region_max * w.loci_n);
-      const int64_t want = std::max<int64_t>(sp.l_cap * 2, need * 2);
-      const int64_t l_max = (1LL << 31) - 64;
-      // a region holds the largest power of two below its share: at the cap that is 2^floor_log2(l_max / n), which the fullest
-      // region must fit -- otherwise the repeat would overflow again at the same capacity, for ever
-      const int64_t region_at_cap = (int64_t)1 << floor_log2((int)std::max<int64_t>(1, l_max / (int64_t)w.loci_n));
-      if (need > l_max || (want >= l_max && (int64_t)loci_region_max > region_at_cap)) {
-        shrink_part((double)loci_region_max, (double)region_at_cap, "candidate loci"); publish_spec(sp); return false;
-      }
-      sp.l_cap = std::min(want, l_max);
-    }
-    if (flags & SPEC_QFUSE) {
+    const PassStatus &h = *w.h_status;
+    const Verdict v = judge(sp, h, w.forms, F, w.loci_n, w.loci_shift, items_max, [&](int s) { return scan_occupancy(s); });
+    if (v.miss) w.last_ms[MS_REPEATS] += 1.0f;   // repeated attempts of this call (speculation misses)
+    if (v.fuse_overflow) {
       r.forced_unfused = true;                           // this range again, through the two kernels
       std::lock_guard<std::mutex> lock(m.mtx);
-      m.spec.fuse_penalty = m.spec.fuse_penalty ? std::min(64, m.spec.fuse_penalty * 2) : 1;
-      m.spec.fuse_skip = m.spec.fuse_penalty - 1;
+      fuse_overflowed(m.spec);
     }
-    if (flags & SPEC_EVENTS) {
-      // every region has to hold its share: size the arena for the fullest one (the fused form reserves from one counter)
-      const uint64_t need = std::max<uint64_t>(h_pinfo[0], ev_region_max * ev_regions_for(F));
-      if (need > items_max) { shrink_part((double)need, (double)items_max, "slide events"); publish_spec(sp); return false; }
-      sp.items_cap = std::min<uint64_t>(items_max, std::max<uint64_t>(sp.items_cap * 2, need + need / 4));
-    }
-    if (flags) { if (slots_changed && (flags & SPEC_SCRATCH)) sp.seed_slots = want_slots; publish_spec(sp); return false; }   // void part: run it again
-    if (h_counters[3] > 0 && !sp.redo) { sp.redo = true; publish_spec(sp); return false; }   // loci overflowed the byte state and the wide pass was not launched
-    if (slots_changed) {
-      // fragments that do not fit the LDS slots use HBM scratch, which must exist: size it for the new slot count lazily
-      sp.seed_slots = want_slots;
-    }
-    sp.l2_loci_last = (int64_t)loci_total;
-    if (F > 0) { sp.l1_small_share = (float)h_stats[1] / (float)F; sp.l1_mid_share = (float)h_stats[2] / (float)F; sp.l1_tiny_share = (float)h_stats[3] / (float)F; }
-    // fragments whose hits were too scattered for the block sort (they took the merge, at twice the time): from one in two hundred
-    // on, the passes that follow drop the hits that cannot belong to a candidate before the sort (launch_l1_stage)
-    // (with the filter on and the 256-thread class in use they are fragments whose kept chance hits -- the hashed bits keep about a
-    // third of them -- still overfill that class's table of 1 365 entries: an index of 1.6 x 10^9 records leaves ~700 of 2 000, and
-    // 47 % of the fragments of the 4000 x 4000 run fell back; the class is folded into the 512-thread form from then on)
-    if (F > 0 && (double)h_counters[0] > 0.005 * (double)F) { if (w.l1_pf && w.l1_small_class) sp.l1_no_small = true; sp.l1_prefilter = true; }
+    FA_REQUIRE(v.kind != Verdict::FAILED, FA_ERR_UNSUPPORTED, std::string("a single query fragment produces too many ") + v.what);
     publish_spec(sp);
+    if (v.kind != Verdict::ACCEPTED) return false;      // void part: run it again
     // ---- accepted ----
     {
       std::lock_guard<std::mutex> lock(m.mtx);
-      if (r.fused) m.spec.fuse_penalty = 0;                                             // the fused form holds again
-      else if (sp.fuse_off && !r.forced_unfused && m.spec.fuse_skip > 0) m.spec.fuse_skip--;   // one pass of the back-off served
+      fuse_accepted(m.spec, r.fused, sp.fuse_off && !r.forced_unfused);
     }
-    w.last_ms[r.fused ? 17 : 18] += 1.0f;
-    if (r.ordered) w.last_ms[19] += 1.0f;
+    w.last_ms[r.fused ? MS_FUSED : MS_UNFUSED] += 1.0f;
+    if (r.ordered) w.last_ms[MS_ORDERED] += 1.0f;
     w.last_forms = w.forms;
     w.last_forms.fused = r.fused; w.last_forms.ordered = r.ordered;
     if (m.stage_events) {
       float ev_ms = 0;
       FA_HIP(hipEventSynchronize(w.ev[3]));
       FA_HIP(hipEventElapsedTime(&ev_ms, w.ev[2], w.ev[3]));
-      w.last_ms[16] += ev_ms;
+      w.last_ms[MS_L2_EVENTS] += ev_ms;
     }
-    const unsigned long long *stamp = w.h_status->stamp;              // 100 MHz ticks
-    for (int i = 0; i < 4; i++) w.last_ms[i] += (float)((double)(stamp[i + 1] - stamp[i]) * 1e-5);
+    const unsigned long long *stamp = h.stamp;                         // 100 MHz ticks
+    for (int i = 0; i < 4; i++) w.last_ms[MS_STAGE + i] += (float)((double)(stamp[i + 1] - stamp[i]) * 1e-5);
     t_begin = std::min(t_begin, stamp[0]); t_end = std::max(t_end, stamp[4]);
     w.last_F = F;
-    w.last_loci = (uint32_t)loci_total;
+    w.last_loci = (uint32_t)v.loci;
     for (uint32_t i = 0; i < LOCI_REGIONS; i++)
-      w.last_region_count[i] = i < w.loci_n ? (uint32_t)std::min<uint64_t>(w.h_status->loci_region[i], 1ULL << w.loci_shift) : 0u;
-    w.last_items = events_total;
-    w.last_ms[5] += (float)records_total;   // reference records inside the locus ranges of this call (roofline line)
-    w.last_ms[6] += (float)loci_total;
-    w.last_ms[7] += (float)events_total;  // slide events
-    w.last_ms[8] += (float)h_counters[3]; // loci that needed the wide L2 state
-    w.last_ms[20] += (float)h_counters[5]; w.last_ms[21] += (float)h_counters[6];   // FA_L1_STATS=1: fragments block-sorted / merged by k_l1
-    w.last_ms[22] += (float)(h_counters[0] + h_counters[1]);   // fragments that left k_l1's fast form (exact): merged in LDS, HBM road, k_l1_big
-    if (h_counters[5] + h_counters[6] > 0) {
-      const double nf = (double)(h_counters[5] + h_counters[6]);
+      w.last_region_count[i] = i < w.loci_n ? (uint32_t)std::min<uint64_t>(h.loci_region[i], 1ULL << w.loci_shift) : 0u;
+    w.last_items = v.events;
+    const uint32_t *c = h.counters;
+    w.last_ms[MS_RECORDS] += (float)v.records;   // reference records inside the locus ranges of this call (roofline line)
+    w.last_ms[MS_LOCI] += (float)v.loci;
+    w.last_ms[MS_EVENTS] += (float)v.events;     // slide events
+    w.last_ms[MS_WIDE] += (float)c[CNT_WIDE];   // loci that needed the wide L2 state
+    w.last_ms[MS_L1_SORTED] += (float)c[CNT_L1_SORTED]; w.last_ms[MS_L1_MERGED] += (float)c[CNT_L1_MERGED];   // FA_L1_STATS=1: fragments block-sorted / merged by k_l1
+    w.last_ms[MS_L1_OFF_FAST] += (float)(c[CNT_MERGED] + c[CNT_OFF_FAST]);   // fragments that left k_l1's fast form (exact): merged in LDS, HBM road, k_l1_big
+    if (c[CNT_L1_SORTED] + c[CNT_L1_MERGED] > 0) {
+      const double nf = (double)(c[CNT_L1_SORTED] + c[CNT_L1_MERGED]);
       fprintf(stderr, "[fa] k_l1 phases, shader-clock ticks per fragment (thread 0):");
-      for (int i = 0; i < 8; i++) fprintf(stderr, " %.0f", (double)w.h_status->dbg[i] / nf);
+      for (int i = 0; i < 8; i++) fprintf(stderr, " %.0f", (double)h.dbg[i] / nf);
       fprintf(stderr, "  (%u block-sorted, %u merged; one workgroup in 64 sampled; gave up on probes / blocks / counts: %llu %llu %llu; expansion: bitmaps+places %.0f, pairs+bitmaps %.0f, bits %.0f)\n",
-              h_counters[5], h_counters[6], w.h_status->dbg[8], w.h_status->dbg[9], w.h_status->dbg[10], (double)w.h_status->dbg[11] / nf, (double)w.h_status->dbg[12] / nf,
-              (double)w.h_status->dbg[13] / nf);
+              c[CNT_L1_SORTED], c[CNT_L1_MERGED], h.dbg[8], h.dbg[9], h.dbg[10], (double)h.dbg[11] / nf, (double)h.dbg[12] / nf, (double)h.dbg[13] / nf);
     }
     return true;
   }
@@ -1665,17 +1385,14 @@ struct QueryPass {
     if (npairs > 0) {
       if (!rows_valid) {
         // a part was repeated after the rows had been formed: form them again, behind everything
-        FA_HIP(hipMemsetAsync(&w.status.p->counters[4], 0, sizeof(uint32_t), st));
+        FA_HIP(hipMemsetAsync(&w.status.p->counters[CNT_ROWS_DONE], 0, sizeof(uint32_t), st));
         FA_HIP(hipMemsetAsync(&w.status.p->total_rows, 0, sizeof(int32_t), st));
-        PassStatus *h_dev = nullptr;
-        FA_HIP(hipHostGetDevicePointer((void **)&h_dev, w.h_status, 0));
-        const PublishArgs pub = publish_args(w.status.p, h_dev, ++w.seq, rows_dev + row_base, host_rows ? host_rows + row_base : nullptr, cap - row_base);
-        if (!launch_rows(pub)) hipLaunchKernelGGL(k_publish_status, dim3(1), dim3(256), 0, st, pub);
+        hand_over(true);
         wait_published(w.h_status, w.seq, st);
       }
       nrows = w.h_status->total_rows;
     }
-    if (t_end > t_begin) w.last_ms[4] += (float)((double)(t_end - t_begin) * 1e-5);   // device wall time of the pass
+    if (t_end > t_begin) w.last_ms[MS_TOTAL] += (float)((double)(t_end - t_begin) * 1e-5);   // device wall time of the pass
     FA_REQUIRE(nrows <= cap - row_base, FA_ERR_INVALID, "row buffer too small");
     return nrows;
   }
@@ -1690,7 +1407,7 @@ static int64_t run_query(fa_mapper &m, Workspace &w, const fa_genomes &g, int32_
   require_device();
   FA_REQUIRE(first >= 0 && count >= 0 && first + count <= g.n_genomes, FA_ERR_INVALID, "genome range out of bounds");
   for (float &x : w.last_ms) x = 0;
-  w.last_forms = Workspace::Forms();
+  w.last_forms = Forms();
   fa_cgi_row *dst = rows;
   if (!rows_device) { w.rows_dev.ensure((size_t)std::max<int64_t>(cap, 1)); dst = w.rows_dev.p; }
   // a call that is ONE pass and returns a modest number of rows to the host gets them written into pinned memory by the
@@ -1856,7 +1573,7 @@ static void fill_genomes(fa_genomes *g, const fa_params &P, hipStream_t st, cons
   // packed words STRAIGHT from the pinned image over PCIe -- every word is read once, by the workgroup that hashes it, and the
   // kernel is bound by its hashing, so the 1.25 MB travel inside its 67 us instead of in a 28 us copy in front of it; only the
   // tile and fragment tables (read by every stage) are copied.  FA_QUERY_ZERO_COPY=0: the whole image is copied.
-  static const bool zero_copy_on = !(getenv("FA_QUERY_ZERO_COPY") && atoi(getenv("FA_QUERY_ZERO_COPY")) == 0);
+  static const bool zero_copy_on = env_num("FA_QUERY_ZERO_COPY", 1) != 0;
   const bool zero_copy = zero_copy_on && pin && !sync_pinned && !hs.protein;
   if (zero_copy) FA_HIP(hipMemcpyAsync(g->blob.p + o_tiles, img + o_tiles, image_bytes - o_tiles, hipMemcpyHostToDevice, st));
   else FA_HIP(hipMemcpyAsync(g->blob.p, img, image_bytes, hipMemcpyHostToDevice, st));
@@ -2542,8 +2259,8 @@ int fa_mapper_query(fa_mapper *m, const void *const *contigs, const int64_t *len
     const auto t0 = std::chrono::steady_clock::now();
     *n_rows = run_query(*m, *lease.w, *g, 0, 1, rows, cap, false);
     // host-side split of the boundary call (wall clock): packing, fragment/tile tables, H2D, pass + rows D2H
-    for (int i = 0; i < 3; i++) lease.w->last_ms[10 + i] = host_ms[i];
-    lease.w->last_ms[13] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    for (int i = 0; i < 3; i++) lease.w->last_ms[MS_HOST + i] = host_ms[i];
+    lease.w->last_ms[MS_CALL] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     lease.w->last_genomes = nullptr;
     lease.w->query_batch = std::move(g);                 // keep the device buffers for the next call
   });
@@ -2723,13 +2440,13 @@ int fa_mapper_set_stage_events(fa_mapper *m, int on) {
 }
 int fa_mapper_last_timings(fa_mapper *m, float *ms, int n) {
   std::lock_guard<std::mutex> lock(m->mtx);
-  for (int i = 0; i < n && i < 24; i++) ms[i] = m->ws[m->last_ws].last_ms[i];
+  for (int i = 0; i < n && i < MS_SLOTS; i++) ms[i] = m->ws[m->last_ws].last_ms[i];
   return FA_OK;
 }
 int fa_mapper_debug_spec(fa_mapper *m, int64_t *out, int n) {
   std::lock_guard<std::mutex> lock(m->mtx);
-  const fa_mapper::Spec &s = m->spec;
-  const Workspace::Forms &f = m->ws[m->last_ws].last_forms;
+  const Spec &s = m->spec;
+  const Forms &f = m->ws[m->last_ws].last_forms;
   auto ppm = [](float share) { return (int64_t)std::lround((double)share * 1e6); };
   const int64_t v[] = {s.init, s.smax, s.seed_slots, ppm(s.l1_small_share), ppm(s.l1_mid_share), ppm(s.l1_tiny_share),
                        s.l1_prefilter, s.l1_no_small, s.l2_loci_last, s.redo, s.part_frags, s.fuse_skip, s.fuse_penalty,
@@ -2782,7 +2499,7 @@ int fa_bench_sketch_kernel(fa_mapper *m, fa_genomes *g, int repeat, float *ms_pe
       retiled.upload(cut, w.stream);
       tiles = retiled.p; ntiles = (int)cut.size();
     }
-    w.last_ms[23] = (float)tile_len;
+    w.last_ms[MS_TILE_LEN] = (float)tile_len;
     w.sk.stage_hash.ensure((size_t)ntiles * TILE);
     w.sk.stage_wpos.ensure((size_t)ntiles * TILE);
     w.sk.tile_count.ensure((size_t)ntiles + 1);

@@ -21,6 +21,7 @@
 #pragma once
 
 #include "fa_common.h"
+#include "fa_policy.h"
 #include "fa_sketch.hip.h"
 #include "fa_sketch_fast.hip.h"
 
@@ -29,13 +30,7 @@ namespace fa {
 
 
 constexpr int MAP_THREADS = 256;
-// loci of one fragment merged in LDS by k_l1 (more fall back to a second pass that writes them to HBM).  128, not 256: with
-// 3 KB of stage instead of 6 the kernel's 21.7 KB let seven workgroups share a CU, i.e. the 1666 fragments of a 5 Mb query run
-// in ONE resident round (85 -> 81 us; 928 -> 872 us at 16 queries per launch); a fragment has one locus per related contig
-constexpr int L1_STAGE = 128;
-// the size classes of k_l1 (hits of a fragment): up to 16 per thread of the 256-thread form; up to the slots the 512-thread,
-// 16-per-thread form is given (a kilobyte short of 16 x 512: see Part::L1Class); everything beyond
-constexpr uint32_t L1_SMALL_HITS = 16u * 256u, L1_MID_HITS = 16u * 512u - 256u;
+// (L1_STAGE, the k_l1 size classes, the SPEC_* flags, the region counts and the status block's slots: fa_policy.h)
 constexpr uint32_t SEED_PAD = 0xFFFFFFFFu;
 
 // ----------------------------------------------------------------------------------------------------------
@@ -493,12 +488,6 @@ __device__ __forceinline__ void query_sketch_tail(const QuerySketchArgs &a, int 
   }
 }
 
-// Pass-level speculation.  A query pass is launched without intermediate host synchronisation, sized by what earlier
-// passes needed (largest sketch, LDS seed slots, HBM seed scratch, loci and event capacities).  Kernels check those
-// bounds on the device, skip the work that does not fit and raise a flag; the host reads the flags once at the end of
-// the pass and, if any is set, grows the bounds and runs the pass again.
-constexpr uint32_t SPEC_SMAX = 1, SPEC_SCRATCH = 2, SPEC_LOCI = 4, SPEC_EVENTS = 8, SPEC_QFUSE = 16;
-
 // ----------------------------------------------------------------------------------------------------------
 // K1 and the per-fragment sketch in ONE launch (query passes over plain-ACGT genomes, 4 <= w <= 64): workgroup f hashes
 // the tiles of fragment f one after the other (skf_tile, fa_sketch_fast.hip.h), collects their records in LDS instead
@@ -577,11 +566,11 @@ __global__ __launch_bounds__(SK_THREADS, QF_WAVES(KT, WT)) void k_query_fused(Sk
   query_sketch_tail(q, f, qbuf, n, n > 0 ? qbuf[0] : 0u, sh_wpos0);
 }
 
-// totals[0] = sum of seeds, [1] = largest fragment, [2] = HBM scratch words for fragments whose seeds do not fit the
+// totals[TOT_SEEDS] = sum of seeds, [TOT_MAX_FRAG] = largest fragment, [TOT_SCRATCH] = HBM scratch words for fragments whose seeds do not fit the
 // LDS slots of k_l1 (their offsets go to ovf_off).  One workgroup: thousands of same-address atomics from k_lookup cost
 // more than this.  Also checks the speculated sketch-size and scratch bounds.
 // (one workgroup of any size: a kernel of its own when k_l1 needs the scratch offsets, else an extra workgroup of k_l1)
-// stats[0] = the largest query sketch of the pass, taken here from q_size (one writer, in a launch behind the one that
+// stats[STAT_SMAX] = the largest query sketch of the pass, taken here from q_size (one writer, in a launch behind the one that
 // zeroes the status block: the sketch kernels themselves must not write into that block -- k_query_fused shares its launch
 // with the zeroing workgroups).  q_size[f] < 0 is k_query_fused's "more records than my LDS holds": SPEC_QFUSE.
 __device__ __forceinline__ void seed_totals(const uint32_t *n_seeds, int64_t F, uint32_t lds_seed_cap, uint64_t *totals,
@@ -638,16 +627,16 @@ __device__ __forceinline__ void seed_totals(const uint32_t *n_seeds, int64_t F, 
     }
   }
   if (threadIdx.x == 0) {
-    totals[0] = sh_sum; totals[1] = sh_max;
+    totals[TOT_SEEDS] = sh_sum; totals[TOT_MAX_FRAG] = sh_max;
     const unsigned long long words = sh_words;
-    totals[2] = words;
+    totals[TOT_SCRATCH] = words;
     unsigned long long flags = 0;
-    stats[0] = sh_smax;
-    stats[1] = (int32_t)sh_small; stats[2] = (int32_t)sh_mid; stats[3] = (int32_t)sh_tiny;   // (what the host picks the size classes of k_l1 by)
+    stats[STAT_SMAX] = sh_smax;
+    stats[STAT_SMALL] = (int32_t)sh_small; stats[STAT_MID] = (int32_t)sh_mid; stats[STAT_TINY] = (int32_t)sh_tiny;   // (what the host picks the size classes of k_l1 by)
     if (sh_smax > spec_smax) flags |= SPEC_SMAX;
     if (sh_qf) flags |= SPEC_QFUSE;
     if (words > spec_scratch_words || words >= (1ULL << 32)) flags |= SPEC_SCRATCH;
-    if (flags) atomicOr(&pinfo[1], flags);
+    if (flags) atomicOr(&pinfo[PI_FLAGS], flags);
   }
 }
 __global__ __launch_bounds__(1024) void k_seed_totals(const uint32_t *n_seeds, int64_t F, uint32_t lds_seed_cap, uint64_t *totals,
@@ -667,9 +656,8 @@ __global__ __launch_bounds__(1024) void k_seed_totals(const uint32_t *n_seeds, i
 // at most), region r holds the loci [r << shift, (r << shift) + count[r]).  One counter for everything made thousands of
 // workgroups queue on one address for ~12 ns each -- 20 us at the end of k_l1 on a single query, whose 1 666 workgroups all
 // arrive there within one resident round.  A locus number is live iff it lies inside the filled part of its region.
-constexpr int LOCI_REGIONS = 64;
 struct LociRegions {
-  uint32_t *count;              // [n] loci reserved per region (may exceed the capacity: the pass is void then, counters[2])
+  uint32_t *count;              // [n] loci reserved per region (may exceed the capacity: the pass is void then, counters[CNT_LOCI_OVF])
   uint32_t n, shift;
 };
 __device__ __forceinline__ bool locus_live(const LociRegions &g, uint32_t l) {
@@ -730,7 +718,6 @@ struct L1Args {
 
 // dynamic LDS of k_l1: the seed hits [cap], the list offsets and sources [lut_smax + 2 each], the staged loci (6 arrays
 // of L1_STAGE)
-constexpr int L1_INPLACE_MAX = 32;  // most seeds per thread the in-place merge keeps in registers (template parameter E: 16 or 32)
 __host__ __device__ inline size_t l1_off_offset(uint32_t seed_cap) { return ((size_t)seed_cap * 4 + 15) / 16 * 16; }
 // (nt = threads of the workgroup: once the lists are merged the same bytes hold (contig, window) of a trip's seeds by thread)
 __host__ __device__ inline size_t l1_stage_offset(uint32_t seed_cap, int lut_smax, int nt) {
@@ -1188,9 +1175,9 @@ __global__ __launch_bounds__(NT, (E == 16 ? 8 : 4)) void k_l1(L1Args a) {
       if (block_sorted) n = n_live;
       if (!block_sorted) list_offsets();                                // (the key buffer may have overwritten them)
     }
-    if (l1_dbg) atomicAdd(&a.counters[block_sorted ? 5 : 6], 1u);   // FA_L1_STATS=1: which road the fragments took
+    if (l1_dbg) atomicAdd(&a.counters[block_sorted ? CNT_L1_SORTED : CNT_L1_MERGED], 1u);   // FA_L1_STATS=1: which road the fragments took
     // fragments that left the fast form (block sort -> gather + merge), counted exactly and always: one atomic on the rare road
-    if (!block_sorted && tid == 0) atomicAdd(&a.counters[0], 1u);
+    if (!block_sorted && tid == 0) atomicAdd(&a.counters[CNT_MERGED], 1u);
     phase(1);
     if (!block_sorted) {
     // flat gather, two elements per thread and trip so that two index reads are in flight
@@ -1271,7 +1258,7 @@ __global__ __launch_bounds__(NT, (E == 16 ? 8 : 4)) void k_l1(L1Args a) {
   } else {
     // ---- more seed hits than LDS holds: lists gathered into HBM scratch and sorted there ----
     seeds = a.ovf_buf + a.ovf_off[f];
-    if (tid == 0) { sh_run = 0; atomicAdd(&a.counters[1], 1u); }         // (off the fast form: the HBM road)
+    if (tid == 0) { sh_run = 0; atomicAdd(&a.counters[CNT_OFF_FAST], 1u); }         // (off the fast form: the HBM road)
     __syncthreads();
     for (int j0 = 0; j0 < s; j0 += blockDim.x) {
       int j = j0 + tid;
@@ -1344,7 +1331,7 @@ __global__ __launch_bounds__(NT, (E == 16 ? 8 : 4)) void k_l1(L1Args a) {
       if (lane == 0) {
         bool fits;
         uint32_t base = reserve_loci(a.loci, f, cnt0, fits), cnt = cnt0;
-        if (!fits) { atomicExch(&a.counters[2], 1u); atomicOr(&a.pinfo[1], (unsigned long long)SPEC_LOCI); cnt = 0; }
+        if (!fits) { atomicExch(&a.counters[CNT_LOCI_OVF], 1u); atomicOr(&a.pinfo[PI_FLAGS], (unsigned long long)SPEC_LOCI); cnt = 0; }
         sh_base = base;
         sh_gbase = cnt;
         a.f_loci_lo[f] = base; a.f_loci_n[f] = cnt;
@@ -1507,7 +1494,7 @@ __global__ __launch_bounds__(NT, (E == 16 ? 8 : 4)) void k_l1(L1Args a) {
         uint32_t cnt = total;
         bool fits;
         uint32_t base = reserve_loci(a.loci, f, cnt, fits);
-        if (!fits) { atomicExch(&a.counters[2], 1u); atomicOr(&a.pinfo[1], (unsigned long long)SPEC_LOCI); cnt = 0; }
+        if (!fits) { atomicExch(&a.counters[CNT_LOCI_OVF], 1u); atomicOr(&a.pinfo[PI_FLAGS], (unsigned long long)SPEC_LOCI); cnt = 0; }
         sh_base = base;
         sh_gbase = cnt;
         a.f_loci_lo[f] = base; a.f_loci_n[f] = cnt;
@@ -1635,7 +1622,7 @@ __global__ __launch_bounds__(NT, (E == 16 ? 8 : 4)) void k_l1(L1Args a) {
         uint32_t cnt = cnt0;
         bool fits = true;
         uint32_t base = cnt ? reserve_loci(a.loci, f, cnt, fits) : 0;
-        if (!fits) { atomicExch(&a.counters[2], 1u); atomicOr(&a.pinfo[1], (unsigned long long)SPEC_LOCI); cnt = 0; }
+        if (!fits) { atomicExch(&a.counters[CNT_LOCI_OVF], 1u); atomicOr(&a.pinfo[PI_FLAGS], (unsigned long long)SPEC_LOCI); cnt = 0; }
         sh_base = base;
         sh_gbase = cnt;   // reuse: number of loci (0 => skip)
         a.f_loci_lo[f] = base; a.f_loci_n[f] = cnt;
@@ -1904,11 +1891,11 @@ __global__ __launch_bounds__(L1_BIG_THREADS) void k_l1_big(L1Args a) {
     uint32_t cnt = sh_loci;
     bool fits = true;
     uint32_t base = cnt ? reserve_loci(a.loci, f, cnt, fits) : 0;
-    if (!fits) { atomicExch(&a.counters[2], 1u); atomicOr(&a.pinfo[1], (unsigned long long)SPEC_LOCI); cnt = 0; }
+    if (!fits) { atomicExch(&a.counters[CNT_LOCI_OVF], 1u); atomicOr(&a.pinfo[PI_FLAGS], (unsigned long long)SPEC_LOCI); cnt = 0; }
     sh_base = base; sh_cnt = cnt;
     a.f_loci_lo[f] = base; a.f_loci_n[f] = cnt;
     a.big_state[f] = 1;
-    atomicAdd(&a.counters[1], 1u);                                       // (off the fast form: cut into LDS-sized chunks here)
+    atomicAdd(&a.counters[CNT_OFF_FAST], 1u);                                       // (off the fast form: cut into LDS-sized chunks here)
   }
   __threadfence_block();
   __syncthreads();
@@ -2015,7 +2002,6 @@ constexpr int SCAN_CLASSES = 32;
 __device__ __forceinline__ uint32_t scan_class(uint32_t nev, int32_t div) {   // 0 = the longest streams
   return (uint32_t)(SCAN_CLASSES - 1) - min((uint32_t)(SCAN_CLASSES - 1), nev / (uint32_t)div);
 }
-constexpr int EV_REGIONS = 64;
 
 // Event word, from the low end: dM:2 | dW:2 | spare | drop | slot (= query rank + 1; 0 is the padding no-op) | no-eval
 // (the top bit), where dM / dW are two's complement -1 / 0 / +1: the change of the matched bit of that rank, resp. of
@@ -2024,7 +2010,7 @@ constexpr int EV_REGIONS = 64;
 // so with 64 one-byte lanes per slot row the masked event IS the row's LDS offset, and a set top bit turns the shared
 // count of an event that carries no comparison into a negative number instead of costing a select.
 template <typename T> struct EvBits;
-template <> struct EvBits<uint16_t> { static constexpr int RANK = 9; };    // sketches up to 510 minimizers
+template <> struct EvBits<uint16_t> { static constexpr int RANK = EV_RANK16; };    // sketches up to 510 minimizers
 template <> struct EvBits<uint32_t> { static constexpr int RANK = 24; };
 constexpr int EV_DM = 0, EV_DW = 2, EV_DROP = 5, EV_SLOT = 6;
 template <typename T> constexpr uint32_t ev_noeval() { return 1u << (8 * sizeof(T) - 1); }
@@ -2074,7 +2060,7 @@ __global__ __launch_bounds__(EV_THREADS, EV_WAVES_PER_SIMD) void k_l2_events(L2A
   if (l_n == 0) return;
   const int s = a.q_size[f];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (a.counters[2] || s > a.cnt_slots - 1) return;                  // loci overflowed / sketch larger than speculated: void pass
+  if (a.counters[CNT_LOCI_OVF] || s > a.cnt_slots - 1) return;                  // loci overflowed / sketch larger than speculated: void pass
   for (int i = threadIdx.x; i < s + EV_SENTINELS; i += EV_THREADS) Q[i] = i < s ? a.q_hash[(size_t)f * a.qcap + i] : 0xFFFFFFFFu;
   for (int b = threadIdx.x; b < OCC_N; b += EV_THREADS) { OCC[b] = 0u; R0[b] = (uint16_t)s; }
   // ---- record range of every locus (the three searchIndex calls of computeL2MappedRegions) and its event count ----
@@ -2139,7 +2125,7 @@ __global__ __launch_bounds__(EV_THREADS, EV_WAVES_PER_SIMD) void k_l2_events(L2A
     const uint32_t region = (uint32_t)f & (a.n_regions - 1);
     const unsigned long long base = atomicAdd(&a.ev_region[region], (unsigned long long)sh_run);   // order of fragments is irrelevant
     sh_ok = base + sh_run <= a.region_cap;
-    if (!sh_ok) atomicOr(&a.pinfo[1], (unsigned long long)SPEC_EVENTS);
+    if (!sh_ok) atomicOr(&a.pinfo[PI_FLAGS], (unsigned long long)SPEC_EVENTS);
     sh_base = (uint32_t)(region * a.region_cap + base);
     atomicAdd(&a.rec_region[region], sh_records);
   }
@@ -2483,7 +2469,7 @@ __global__ __launch_bounds__(256) void k_l2_order(L2Args a) {
   const uint32_t r = blockIdx.x & (a.loci.n - 1u), off = (blockIdx.x / a.loci.n) * 256u + threadIdx.x;
   // (a pass that raised a speculation flag is void and will be repeated: its class counts may not match its stream lengths --
   // k_l2_events zeroes the lengths of a fragment whose events found no room -- so nothing is ordered, and k_l2_scan does nothing)
-  if (a.counters[2] || a.pinfo[1]) return;
+  if (a.counters[CNT_LOCI_OVF] || a.pinfo[PI_FLAGS]) return;   // (any flag: SPEC_VOID)
   const uint32_t live = min(a.loci.count[r], 1u << a.loci.shift);
   if ((blockIdx.x / a.loci.n) * 256u >= live) return;                  // (uniform: nothing of this chunk is live)
   if (threadIdx.x < SCAN_CLASSES) sh_cnt[threadIdx.x] = 0;
@@ -2514,8 +2500,8 @@ __global__ __launch_bounds__(L2_THREADS) void k_l2_scan(L2Args a) {
   // workgroup b takes chunk b / n of region b mod n (regions are filled from their start: the workgroups that have loci come
   // first in dispatch order, as they did with one dense numbering, and the empty ones behind them exit at once)
   const uint32_t region = blockIdx.x & (a.loci.n - 1u), off = (blockIdx.x / a.loci.n) * (uint32_t)LN + (uint32_t)lane;
-  if (a.counters[2] || off >= (1u << a.loci.shift) || off >= a.loci.count[region]) return;    // (locus_live of the identity order)
-  if (a.scan_order && a.pinfo[1]) return;                             // void pass: no order was made (k_l2_order)
+  if (a.counters[CNT_LOCI_OVF] || off >= (1u << a.loci.shift) || off >= a.loci.count[region]) return;    // (locus_live of the identity order)
+  if (a.scan_order && a.pinfo[PI_FLAGS]) return;                      // void pass: no order was made (k_l2_order; SPEC_VOID)
   // place `off` of the region: the locus of that number, or -- sorted by stream length -- the one k_l2_order put there
   const uint32_t l = a.scan_order ? a.scan_order[(region << a.loci.shift) + off] : (region << a.loci.shift) + off;
   if (REDO) { if (!a.l_redo[l]) return; }
@@ -2596,12 +2582,12 @@ struct CgiArgs {
 __global__ void k_cgi_bins(CgiArgs a) {
   stage_stamp(a.stamp);
   uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (a.counters[2] || g >= a.group_bound) return;                    // (a group carries the number of its first locus; the table of
+  if (a.counters[CNT_LOCI_OVF] || g >= a.group_bound) return;                    // (a group carries the number of its first locus; the table of
                                                                       //  group maxima is cleared per pass: no maximum, no group)
   // A void part must leave no trace in the bin table, which later parts and the repeat of this one accumulate into: when a
   // locus overflowed the one-byte slide state and the wide pass was not launched, the group maxima lack that locus, and a
   // lesser locus of its group could land in a bin the true best never touches (the host repeats the part, fa_engine.hip)
-  if (a.counters[3] && !a.wide_launched) return;
+  if (a.counters[CNT_WIDE] && !a.wide_launched) return;
   unsigned long long best = a.group_best[g];
   if (best == 0) return;
   uint32_t l = 0xFFFFFFFFu - (uint32_t)(best & 0xFFFFFFFFu);

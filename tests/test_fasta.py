@@ -62,7 +62,7 @@ def test_add_fasta_many_counts_like_add_fasta(tmp_path):
 def test_host_pieces_against_their_definition():
     """The host-only pieces of the library -- the 2-bit packer, the FASTA readers (the one-sweep reader of round 5 against
     the byte-by-byte definition of the store on 40 random files, prefixes of records, protein), the statistics tables, the
-    workspace lease -- built from the same headers with AddressSanitizer + UBSan and run (scripts/host_sanitize/driver.cpp)."""
+    workspace lease, the policy of a query pass (fa_policy.h) -- built from the same headers with AddressSanitizer + UBSan and run (scripts/host_sanitize/driver.cpp)."""
     import shutil
     import subprocess
     if not shutil.which("g++"):
