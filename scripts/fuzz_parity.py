@@ -1,13 +1,15 @@
 """Differential fuzzing of the HIP path against the CPU oracle: random genomes with planted repeats, tandem
 duplications, inversions, N runs and low-complexity stretches; random parameters.  Every L2 mapping and every hit must
-match.  Usage: python scripts/fuzz_parity.py [--history | --domain] [cases] [seed] [seconds] [default-cell]   (stops after `seconds` if given: a
+match.  Usage: python scripts/fuzz_parity.py [--history | --domain | --contigs] [cases] [seed] [seconds] [default-cell]   (stops after `seconds` if given: a
 time box; a fourth argument keeps every nucleotide case in the default cell k = 16 / fragment 3000 / 80 % with queries of plain
 ACGT -- the cell whose query passes run K1 and the fragment sketch as ONE launch, k_query_fused).  --history: one index per
 case, then 4-8 queries drawn from the generators (plain, tandem, drafts, N / IUPAC, batches) on the SAME mapper, each through
 a random entry point (query_draft, query_genome, GenomeBatch.query(first, count), query_fasta_stream), each compared with the
 oracle: a mapper's speculation record carries the sizes and kernel forms of one query into the next.  --domain: the ends of
 the window range -- percentage_identity from 64.5-70 (w = 2-4) and 96-100 (sketches of a handful of records), p_value from
-1e-1 to 1e-12, k from 5 to 33."""
+1e-1 to 1e-12, k from 5 to 33.  --contigs: references and queries cut into 1-400 contigs by tests/contig_domain.py's cut_at at the
+case's own critical lengths (0, 1, k - 1 ... k + w + 1, cmw, fragment - 1 / + 0 / + 1, two fragments, the tile seams), half of the genomes with repeats inside
+their contigs (plant_repeats), with a 30 % chance each of a genome without a contig and of a genome of contigs too short for a record; batches as in the default mode."""
 import sys, os, ctypes as C, warnings, time, tempfile
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -63,6 +65,12 @@ if history:
 domain = "--domain" in sys.argv
 if domain:
     sys.argv.remove("--domain")
+contig_mode = "--contigs" in sys.argv
+if contig_mode:
+    sys.argv.remove("--contigs")
+    # the generator lives beside the tests that share it; the other modes do not need it
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import contig_domain as cd
 cases = int(sys.argv[1]) if len(sys.argv) > 1 else 50
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 time_box = float(sys.argv[3]) if len(sys.argv) > 3 else 0.0
@@ -170,6 +178,75 @@ def history_case(g, case, tmp):
             print(f"MISMATCH history case {case} step {step} ({entry}) seed {seed} params {params} copies {copies}: {got} vs {want}")
     return ok
 
+def contigs_case(g, case):
+    """Fragmented references and queries at the case's own critical lengths; one query through query_draft (hits, every L2
+    mapping, index size, threshold) or, every fourth case, 1-3 queries as a resident batch."""
+    k = int(g.choice([11, 14, 16, 16, 16, 21])); frag = int(g.choice([200, 500, 1000, 3000, 3000]))
+    params = dict(k=k, fragment_length=frag, percentage_identity=float(g.choice([75, 80, 80, 85])), minimum_fraction=float(g.choice([0.0, 0.2, 0.5])))
+    osk = OracleSketch(**params)
+    w = osk.window_size
+    if w >= frag:
+        return None
+    sk = pf.Sketch(**params)
+    lengths = cd.critical_lengths(k, w, frag, (cd.k1_tile_len(w),) + cd.FORCED_TILES)
+
+    def cut(codes, filler):
+        seq = to_bytes(g, codes) if g.random() < 0.3 else bytes(syn.to_ascii(codes))
+        if g.random() < 0.15:
+            return [seq]
+        at = int(g.integers(0, len(lengths)))
+        contigs = cd.cut_at(g, seq, lengths[at:] + lengths[:at], filler)
+        if g.random() < 0.5:
+            contigs = cd.plant_repeats(contigs, k, w, frag)      # the same hash twice inside a contig: rec_prev and the linked flags
+        return contigs[:399] + [b"".join(contigs[399:])] if len(contigs) > 400 else contigs
+
+    def odd_genomes():
+        out = []
+        if g.random() < 0.3:
+            out.append([])
+        if g.random() < 0.3:
+            out.append([bytes(syn.to_ascii(syn.random_codes(g, int(g.integers(0, min(k, w)))))) for _ in range(int(g.integers(1, 6)))])
+        return out
+
+    length = int(g.integers(max(12 * frag, 15_000), 120_000))
+    anc = scramble(g, syn.random_codes(g, length)) if g.random() < 0.5 else syn.random_codes(g, length)
+    refs = [cut(syn.mutate_codes(g, anc, float(g.choice([0.0, 0.01, 0.03, 0.06, 0.1]))), cd.ref_filler(k, w, frag)) for _ in range(int(g.integers(1, 5)))]
+    if g.random() < 0.5:
+        refs.append([bytes(syn.to_ascii(syn.random_codes(g, length // 2)))])
+    for odd in odd_genomes():
+        refs.insert(int(g.integers(0, len(refs) + 1)), odd)
+    for i, contigs in enumerate(refs):
+        sk.add_draft(i, contigs); osk.add_draft(i, contigs)
+    mapper = sk.index(); osk.index()
+    queries = [cut(syn.mutate_codes(g, anc, float(g.choice([0.0, 0.02, 0.05, 0.1]))), cd.query_filler(k, w, frag))
+               for _ in range(int(g.integers(1, 4)) if case % 4 == 0 else 1)]
+    ok = len(mapper.lookup_index) == osk.index_size and mapper.occurences_threshold == osk.freq_threshold
+    if len(queries) > 1:
+        for odd in odd_genomes():
+            queries.insert(int(g.integers(0, len(queries) + 1)), odd)
+        got = [hit_list(hs) for hs in mapper.upload_genomes(queries).query()]
+        want = [osk.query_draft(q, threads=8) for q in queries]
+        ok = ok and got == want
+        if not ok:
+            print(f"MISMATCH contigs batch case {case} seed {seed} params {params}: {got} vs {want}")
+        return ok
+    hits = hit_list(mapper.query_draft(queries[0]))
+    ohits, det = osk.query_draft(queries[0], threads=8, details=True)
+    omm = cd.mapping_tuples(det)
+    try:
+        gm = mappings(mapper)
+    except (RuntimeError, NotImplementedError) as e:   # only a pass forced into parts may leave the stage getters without its mappings
+        if "stage getters" not in str(e) or not os.environ.get("FA_PASS_FRAGMENTS"):
+            raise
+        gm = omm
+    ok = ok and hits == ohits and gm == omm
+    if not ok:
+        print(f"MISMATCH contigs case {case} seed {seed} params {params} window {w} contigs {[len(r) for r in refs]} / {len(queries[0])}: "
+              f"hits {hits} vs {ohits}; mappings gpu {len(gm)} oracle {len(omm)}")
+        sg, so = set(gm), set(omm)
+        print("   only gpu", sorted(sg - so)[:4], "only oracle", sorted(so - sg)[:4])
+    return ok
+
 for case in range(cases):
     if time_box and time.time() - t0 > time_box:
         break
@@ -178,6 +255,13 @@ for case in range(cases):
         with warnings.catch_warnings(), tempfile.TemporaryDirectory() as tmp:
             warnings.simplefilter("ignore")
             bad += 0 if history_case(g, case, tmp) else 1
+        continue
+    if contig_mode:
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            res = contigs_case(g, case)
+        degenerate += res is None
+        bad += res is False
         continue
     if case % 10 == 9:
         with warnings.catch_warnings():

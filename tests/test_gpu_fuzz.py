@@ -74,3 +74,19 @@ def test_fuzz_window_domain_against_oracle():
     assert "0 mismatches" in res.stdout and int(last[0]) == cases, res.stdout[-500:]
     # (k above ~20 and the lowest identities at small k recommend w = fragment: nothing maps, the case is skipped)
     assert int(last[last.index("degenerate,") - 1]) <= cases * 2 // 3, res.stdout[-500:]
+
+
+def test_fuzz_contig_domain_against_oracle():
+    """Fragmented references and queries (scripts/fuzz_parity.py --contigs): every genome cut into 1-400 contigs at the case's
+    own critical lengths (tests/contig_domain.py), half of them with repeats inside their contigs, genomes without a contig
+    and genomes of contigs too short for a record.
+    A fixed 350 cases: 20.5 s on an MI355X, next to 21.0 s for the --domain leg (800 cases, most of them cheap or degenerate)
+    in the same run."""
+    seed = (source_seed() ^ 0x717171) & 0x7FFFFFFF
+    cases = 350
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "fuzz_parity.py"), "--contigs", str(cases), str(seed)],
+                         capture_output=True, text=True, timeout=2400)
+    assert res.returncode == 0, f"seed {seed}\n" + res.stdout[-3000:] + res.stderr[-3000:]
+    last = res.stdout.strip().splitlines()[-1].split()
+    assert "0 mismatches" in res.stdout and int(last[0]) == cases, res.stdout[-500:]
+    assert int(last[last.index("degenerate,") - 1]) <= cases // 4, res.stdout[-500:]

@@ -1560,6 +1560,24 @@ def _links_by_definition(h, s, w, cmw):
     return prev, fwd, bwd, flags
 
 
+def links_match_their_definitions(mapper):
+    """fa_mapper_debug_links of an index against _links_by_definition over its own records (shared with
+    tests/test_gpu_contig_domain.py); returns cmw and the defined rec_prev and flags for the caller's own counts."""
+    h, s, w = mapper.minimizers._arrays()
+    n = len(h)
+    prev, fwd, bwd = (np.empty(n, np.int32) for _ in range(3))
+    flags = np.empty(n, np.uint8)
+    got = C.c_int64(0)
+    check(lib.fa_mapper_debug_links(mapper._h, prev.ctypes.data, fwd.ctypes.data, bwd.ctypes.data, flags.ctypes.data, n, C.byref(got)))
+    assert got.value == n
+    cmw = max(1, mapper.fragment_length - (mapper.window_size - 1) - (mapper.k - 1))
+    wprev, wfwd, wbwd, wflags = _links_by_definition(h, s, w, cmw)
+    assert np.array_equal(fwd, wfwd) and np.array_equal(bwd, wbwd)
+    assert np.array_equal(prev, wprev)
+    assert np.array_equal(flags, wflags)
+    return cmw, wprev, wflags
+
+
 def _check_links(params, seed):
     g = syn.rng(seed)
     sk = pf.Sketch(**params)
@@ -1570,20 +1588,8 @@ def _check_links(params, seed):
         base[90_000:90_400] = 0                                   # a low-complexity run: same hash in consecutive windows
         seq = syn.to_ascii(base)
         sk.add_draft(f"g{i}", [seq[:70_000], seq[70_000:110_000], seq[110_000:], seq[:frag + 50]])
-    mapper = sk.index()
-    h, s, w = mapper.minimizers._arrays()
-    n = len(h)
-    prev, fwd, bwd = (np.empty(n, np.int32) for _ in range(3))
-    flags = np.empty(n, np.uint8)
-    got = C.c_int64(0)
-    check(lib.fa_mapper_debug_links(mapper._h, prev.ctypes.data, fwd.ctypes.data, bwd.ctypes.data, flags.ctypes.data, n, C.byref(got)))
-    assert got.value == n
-    cmw = max(1, frag - (mapper.window_size - 1) - (k - 1))
-    wprev, wfwd, wbwd, wflags = _links_by_definition(h, s, w, cmw)
+    cmw, wprev, wflags = links_match_their_definitions(sk.index())
     assert (wprev >= 0).sum() > 100 and (wflags & 1).any() and (wflags & 2).any() and (wflags & 4).any()
-    assert np.array_equal(fwd, wfwd) and np.array_equal(bwd, wbwd)
-    assert np.array_equal(prev, wprev)
-    assert np.array_equal(flags, wflags)
     return cmw
 
 
