@@ -72,6 +72,21 @@ typedef struct fa_mapping {
   int32_t query_id;
 } fa_mapping;
 
+/* one mapping that computeCGI kept: best of its query fragment for this reference genome (step 1) and best of its
+ * reference bin (step 2); the rows' count_seq of a pair = its number of records, the rows' identity = the float32
+ * mean of their identities in the order given.  What FastANI's --visualize dumps per fragment (Parameters.visualize,
+ * include/fastani/map/map_parameters.pxd:22-24). */
+typedef struct fa_hit_mapping {
+  int32_t query_id;         /* position of the query genome in the batch, as in fa_cgi_row */
+  int32_t query_seq_id;     /* querySeqId: fragment number inside its query genome */
+  int32_t ref_genome_id;    /* refGenomeId */
+  int32_t ref_seq_id;       /* refSeqId: contig of the reference */
+  int32_t ref_start_pos;    /* refStartPos (= meanOptimalPos) on that contig */
+  int32_t sketch_size;      /* sketchSize of the query fragment */
+  int32_t conserved;        /* conservedSketches */
+  float identity;           /* nucIdentity, the value the row averages */
+} fa_hit_mapping;           /* 32 bytes */
+
 /* ---- library ---------------------------------------------------------- */
 const char *fa_last_error(void);
 int fa_version(void);
@@ -170,6 +185,14 @@ int fa_mapper_query(fa_mapper *m, const void *const *contigs, const int64_t *len
                     fa_cgi_row *rows, int64_t cap, int64_t *n_rows, int *n_short, uint64_t *total_fragments,
                     uint64_t *total_length);
 
+/* fa_mapper_query that also returns the mappings behind its rows: one fa_hit_mapping per (reference genome, reference
+ * bin) that computeCGI kept, in (ref_genome_id, bin) order -- the order in which the row's identities are summed.  A pair
+ * holds at most one record per query fragment, so total_fragments x reference genomes is a safe map_cap.  A smaller
+ * buffer is an error (FA_ERR_INVALID, nothing is written beyond map_cap; *n_maps still receives the full count). */
+int fa_mapper_query_mappings(fa_mapper *m, const void *const *contigs, const int64_t *lengths, int n_contigs, int char_width,
+                             fa_cgi_row *rows, int64_t cap, int64_t *n_rows, int *n_short, uint64_t *total_fragments,
+                             uint64_t *total_length, fa_hit_mapping *maps, int64_t map_cap, int64_t *n_maps);
+
 /* ---- host ingest: FASTA files ------------------------------------------ */
 /* Record reader with the semantics of pyfastani._fasta.Parser (src/pyfastani/_fasta.pyx:41-103): records exist only
  * if the first line starts with '>'; id = header line without '>' and newline; sequence lines joined, ASCII letters
@@ -232,6 +255,19 @@ int fa_genomes_info(fa_genomes *g, int32_t *n_genomes, uint64_t *total_fragments
  * all-gather) with room for `cap` rows. */
 int fa_mapper_query_genomes(fa_mapper *m, fa_genomes *g, int32_t first, int32_t count, fa_cgi_row *rows, int64_t cap,
                             int64_t *n_rows, int rows_device);
+
+/* fa_mapper_query_genomes that also returns the mappings behind its rows, in (query_id, ref_genome_id, bin) order; the
+ * records of consecutive passes follow one another.  A safe map_cap is the number of query fragments of the range
+ * (fa_genomes_info) times the number of reference genomes; a smaller buffer is an error (FA_ERR_INVALID, nothing is
+ * written beyond map_cap; *n_maps still receives the full count, so a caller that cannot afford the bound may size a
+ * second call from a first).  With a host destination the library keeps a device buffer of map_cap records in the
+ * workspace, and a winner table of 16 bytes per (query of a pass, reference bin); both stay allocated with the workspace's
+ * other buffers: map a large table in sub-ranges.  If maps_device is non-zero, `maps` is a DEVICE pointer
+ * with room for map_cap records, as `rows` is under rows_device.  The winner table and the compaction behind these records
+ * exist only in calls through these two entry points: fa_mapper_query_genomes launches and allocates what it always did. */
+int fa_mapper_query_genomes_mappings(fa_mapper *m, fa_genomes *g, int32_t first, int32_t count, fa_cgi_row *rows, int64_t cap,
+                                     int64_t *n_rows, int rows_device, fa_hit_mapping *maps, int64_t map_cap,
+                                     int64_t *n_maps, int maps_device);
 
 /* stage-level introspection used by the parity tests */
 int fa_mapper_debug_mappings(fa_mapper *m, fa_mapping *out, int64_t cap, int64_t *n); /* L2 results of the last query call */

@@ -6,6 +6,11 @@ Drop-in for the path ``Sketch`` -> ``add_draft``/``add_genome`` -> ``index`` -> 
 ``_fastani.pyx`` re-based on ``fastani_hip.pxd``); all compute runs in hand-written HIP kernels for
 gfx950 behind the C ABI of ``include/fastani_hip.h``.  There is no CPU fallback, and importing the package needs neither
 PyTorch nor numpy (``pyfastani_amd.sharding``, the multi-GPU layer, imports torch when it is used).
+
+Beyond the reference's surface: resident query batches (``Mapper.upload_genomes`` -> `GenomeBatch`), FASTA ingest, and the
+fragment mappings behind the hits -- ``Mapper.query_draft_mappings`` / ``query_genome_mappings`` and
+``GenomeBatch.query_mappings`` return them as ``pyfastani_amd._batch.MAPPING_DTYPE`` records (numpy), and
+``pyfastani_amd.outputs`` places them on the query's contigs and writes them as a table.
 """
 try:
     from ._fastani import (

@@ -9,3 +9,11 @@ ROW_DTYPE = np.dtype(
      ("identity", "<f4")]
 )
 assert ROW_DTYPE.itemsize == 20
+
+# one mapping that computeCGI kept (``fa_hit_mapping``): what `GenomeBatch.query_mappings` and
+# `Mapper.query_draft_mappings` return beside the rows
+MAPPING_DTYPE = np.dtype(
+    [("query_id", "<i4"), ("query_seq_id", "<i4"), ("ref_genome_id", "<i4"), ("ref_seq_id", "<i4"), ("ref_start_pos", "<i4"),
+     ("sketch_size", "<i4"), ("conserved", "<i4"), ("identity", "<f4")]
+)
+assert MAPPING_DTYPE.itemsize == 32

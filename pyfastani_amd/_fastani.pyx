@@ -1129,17 +1129,22 @@ cdef class Mapper(_Parameterized):
     # -- queries -------------------------------------------------------------------------------------------------------
     cdef list _hits_of_rows(self, const hip.fa_cgi_row* rows, int64_t n_rows, uint64_t total_length):
         # _fastani.pyx:1121-1136; `uint64 >= uint64 * float` is evaluated in float exactly like the C expression
+        return [Hit(self._names[rows[i].ref_genome_id], rows[i].identity, rows[i].count_seq, rows[i].total_query_fragments)
+                for i in self._hit_order(rows, n_rows, total_length)]
+
+    cdef list _hit_order(self, const hip.fa_cgi_row* rows, int64_t n_rows, uint64_t total_length):
+        # the rows that pass the minimum_fraction filter, in the order of the hit list
         cdef int64_t i
         cdef uint64_t min_length, shared_length
-        cdef list hits = []
+        cdef list kept = []
         self._load_lengths()
         for i in range(n_rows):
             min_length = min(total_length, self._lengths[rows[i].ref_genome_id])
             shared_length = <uint64_t> rows[i].count_seq * <uint64_t> self._p.fragment_length
             if <float> shared_length >= <float> min_length * self._p.min_fraction:
-                hits.append(Hit(self._names[rows[i].ref_genome_id], rows[i].identity, rows[i].count_seq, rows[i].total_query_fragments))
-        hits.sort(key=_hit_identity, reverse=True)                            # stable, :1135
-        return hits
+                kept.append((rows[i].identity, i))
+        kept.sort(key=_first, reverse=True)                                   # stable, :1135
+        return [k[1] for k in kept]
 
     def _rows_to_hits(self, rows, total_length):
         """`Hit` list of raw rows given as objects with the ``fa_cgi_row`` attributes (the batch path and the tests)."""
@@ -1153,6 +1158,61 @@ cdef class Mapper(_Parameterized):
             r.identity = x.identity
             buf.push_back(r)
         return self._hits_of_rows(buf.data(), <int64_t> buf.size(), total_length)
+
+    cdef tuple _query_draft_mappings(self, object contigs, int threads=0):
+        # _query_draft through fa_mapper_query_mappings: the hits, and the mappings behind them
+        import numpy as np
+        cdef vector[const void*] ptrs
+        cdef vector[int64_t] lens
+        cdef vector[hip.fa_cgi_row] rows
+        cdef list keep = []
+        cdef int64_t n_rows = 0, n_maps = 0, map_cap = 0, n = 0
+        cdef int n_short = 0, width, code
+        cdef uint64_t total_fragments = 0, total_length = 0
+        cdef uintptr_t pm
+        cdef size_t j
+        if threads < 0:
+            raise ValueError(f"`threads` must be positive or null, got {threads!r}")   # :1050
+        width = _borrow_all(contigs, ptrs, lens, keep)
+        rows.resize(max(len(self._names), 1))
+        n = <int64_t> ptrs.size()
+        for j in range(ptrs.size()):
+            map_cap += lens[j] // self._p.fragment_length                     # a pair keeps one mapping per query fragment at most
+        map_cap = max(1, map_cap * max(1, len(self._names)))
+        maps = np.empty(map_cap, dtype=_mapping_dtype())
+        pm = maps.ctypes.data
+        if ptrs.empty():
+            ptrs.push_back(NULL)
+            lens.push_back(0)
+        with nogil:
+            code = hip.fa_mapper_query_mappings(self._hm, ptrs.data(), lens.data(), <int> n, width, rows.data(), <int64_t> rows.size(),
+                                                &n_rows, &n_short, &total_fragments, &total_length,
+                                                <hip.fa_hit_mapping*> pm, map_cap, &n_maps)
+        _check(code)
+        for _ in range(n_short):
+            warnings.warn("Mapper received a short sequence relative to parameters, mapping will not be computed.",
+                          UserWarning)                                        # :1063-1069
+        order = self._hit_order(rows.data(), n_rows, total_length)
+        hits = [Hit(self._names[rows[i].ref_genome_id], rows[i].identity, rows[i].count_seq, rows[i].total_query_fragments)
+                for i in order]
+        maps = maps[:n_maps]
+        # the records of a pair are consecutive (device order: reference genome, then bin): those of the hits, in the hits' order
+        genome = maps["ref_genome_id"]
+        parts = [maps[np.searchsorted(genome, rows[i].ref_genome_id, "left"):np.searchsorted(genome, rows[i].ref_genome_id, "right")]
+                 for i in order]
+        return hits, (np.concatenate(parts) if parts else maps[:0].copy())
+
+    def query_draft_mappings(self, object contigs, int threads=0):
+        """`query_draft`, and the fragment mappings behind its hits (what FastANI's ``--visualize`` dumps): ``(hits,
+        mappings)``.  ``mappings`` is a structured array (`pyfastani_amd._batch.MAPPING_DTYPE`) with one record per query
+        fragment that counts towards a hit -- ``len`` of a hit's records is its ``matches``, their float32 mean its
+        ``identity`` --, hit by hit in the order of ``hits``, and inside a hit along the reference.  ``query_seq_id`` is the
+        fragment number inside the query (`pyfastani_amd.outputs.fragment_coordinates` turns it into contig and offset)."""
+        return self._query_draft_mappings(contigs, threads)
+
+    def query_genome_mappings(self, object sequence, int threads=0):
+        """`query_genome`, and the fragment mappings behind its hits (see `query_draft_mappings`)."""
+        return self._query_draft_mappings((sequence,), threads)
 
     cdef list _query_draft(self, object contigs, int threads=0):
         # _fastani.pyx:1006-1136.  `threads` is validated for signature compatibility; fragment-level parallelism is the
@@ -1308,8 +1368,8 @@ cdef class Mapper(_Parameterized):
         return batch.query(first, count)
 
 
-def _hit_identity(Hit hit):
-    return hit.identity
+def _first(tuple pair):
+    return pair[0]
 
 
 def _unpickle_mapper(state):
@@ -1330,6 +1390,19 @@ def _row_dtype():
                                ("total_query_fragments", "<i4"), ("identity", "<f4")])
         assert _ROW_DTYPE.itemsize == sizeof(hip.fa_cgi_row)
     return _ROW_DTYPE
+
+
+cdef object _MAPPING_DTYPE = None
+
+
+def _mapping_dtype():
+    global _MAPPING_DTYPE
+    if _MAPPING_DTYPE is None:
+        import numpy as np
+        _MAPPING_DTYPE = np.dtype([("query_id", "<i4"), ("query_seq_id", "<i4"), ("ref_genome_id", "<i4"), ("ref_seq_id", "<i4"),
+                                   ("ref_start_pos", "<i4"), ("sketch_size", "<i4"), ("conserved", "<i4"), ("identity", "<f4")])
+        assert _MAPPING_DTYPE.itemsize == sizeof(hip.fa_hit_mapping)
+    return _MAPPING_DTYPE
 
 
 cdef class GenomeBatch:
@@ -1481,6 +1554,31 @@ cdef class GenomeBatch:
             code = hip.fa_mapper_query_genomes(self._mapper._hm, self._hg, first, c, <hip.fa_cgi_row*> p, cap, &n_rows, 0)
         _check(code)
         return rows[:n_rows]
+
+    def query_mappings(self, int first=0, count=None):
+        """``(rows, mappings)`` for genomes [first, first+count): the rows of `query_rows` (unfiltered) and the fragment
+        mappings behind them (`pyfastani_amd._batch.MAPPING_DTYPE`), in (query, reference genome, position on the reference)
+        order: a row's ``count_seq`` is the number of its records, its ``identity`` their float32 mean in that order.
+        The buffers are sized by the safe bound (query fragments of the range x reference genomes x 32 bytes, on the host and in
+        HBM): take the mappings of a large table range by range."""
+        import numpy as np
+        cdef int c = self.n_genomes - first if count is None else count
+        cdef int64_t n_ref = max(1, len(self._mapper._names))
+        cdef int64_t cap = max(1, <int64_t> c * n_ref)
+        cdef int64_t n_rows = 0, n_maps = 0
+        cdef int code
+        if first < 0 or c < 0 or first + c > self.n_genomes:
+            raise ValueError("genome range out of bounds")
+        # a pair keeps one mapping per query fragment at most
+        cdef int64_t map_cap = max(1, <int64_t> int(self.total_fragments[first:first + c].sum()) * n_ref)
+        rows = np.zeros(cap, dtype=_row_dtype())
+        maps = np.empty(map_cap, dtype=_mapping_dtype())
+        cdef uintptr_t p = rows.ctypes.data, pm = maps.ctypes.data
+        with nogil:
+            code = hip.fa_mapper_query_genomes_mappings(self._mapper._hm, self._hg, first, c, <hip.fa_cgi_row*> p, cap, &n_rows, 0,
+                                                        <hip.fa_hit_mapping*> pm, map_cap, &n_maps, 0)
+        _check(code)
+        return rows[:n_rows], maps[:n_maps].copy()
 
     def query_rows_device(self, int first, int count, uintptr_t device_ptr, int64_t cap):
         """Same, but the rows are written to a caller-owned DEVICE buffer (e.g. a torch tensor feeding an RCCL all-gather).

@@ -50,6 +50,20 @@ class Mapping(C.Structure):
     ]
 
 
+class HitMapping(C.Structure):
+    # one mapping computeCGI kept (fa_hit_mapping)
+    _fields_ = [
+        ("query_id", C.c_int32),
+        ("query_seq_id", C.c_int32),
+        ("ref_genome_id", C.c_int32),
+        ("ref_seq_id", C.c_int32),
+        ("ref_start_pos", C.c_int32),
+        ("sketch_size", C.c_int32),
+        ("conserved", C.c_int32),
+        ("identity", C.c_float),
+    ]
+
+
 # every symbol of include/fastani_hip.h: (restype, argtypes)
 _vp, _i32, _i64, _u64, _u32, _f32, _f64 = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_uint32, C.c_float, C.c_double
 _P = C.POINTER
@@ -91,10 +105,13 @@ SIGNATURES = {
     "fa_mapper_num_genomes": (_i32, [_vp, _P(_i64)]),
     "fa_mapper_get_state": (_i32, [_vp, _vp, _vp]),
     "fa_mapper_query": (_i32, [_vp, _P(_vp), _P(_i64), _i32, _i32, _vp, _i64, _P(_i64), _P(_i32), _P(_u64), _P(_u64)]),
+    "fa_mapper_query_mappings": (_i32, [_vp, _P(_vp), _P(_i64), _i32, _i32, _vp, _i64, _P(_i64), _P(_i32), _P(_u64), _P(_u64),
+                                        _vp, _i64, _P(_i64)]),
     "fa_genomes_upload": (_i32, [_vp, _P(_vp), _P(_i64), _vp, _i64, _i32, _i32, _P(_vp)]),
     "fa_genomes_free": (None, [_vp]),
     "fa_genomes_info": (_i32, [_vp, _P(_i32), _vp, _vp, _vp]),
     "fa_mapper_query_genomes": (_i32, [_vp, _vp, _i32, _i32, _vp, _i64, _P(_i64), _i32]),
+    "fa_mapper_query_genomes_mappings": (_i32, [_vp, _vp, _i32, _i32, _vp, _i64, _P(_i64), _i32, _vp, _i64, _P(_i64), _i32]),
     "fa_mapper_debug_mappings": (_i32, [_vp, _vp, _i64, _P(_i64)]),
     "fa_mapper_debug_l1": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _P(_i64)]),
     "fa_mapper_debug_query_sketch": (_i32, [_vp, _i64, _vp, _i32, _P(_i32)]),

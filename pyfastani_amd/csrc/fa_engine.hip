@@ -481,6 +481,12 @@ struct Workspace {
   DevBuf<unsigned long long> group_best, bins;
   DevBuf<float> row_ident;
   DevBuf<fa_cgi_row> rows_dev;
+  // only on workspaces that served a call for the mappings behind the rows (MapSink): the winner table parallel to `bins`,
+  // the chunk counts / offsets of the compaction, and the records of a call that wants them on the host
+  DevBuf<MapWinner> winners;
+  DevBuf<int32_t> map_chunk_count;
+  DevBuf<int64_t> map_chunk_off;
+  DevBuf<fa_hit_mapping> maps_dev;
   // LUT pointers captured for the call (the mapper may publish larger tables while this call is in flight)
   const int32_t *lut_min_hits = nullptr, *lut_pass = nullptr;
   const float *lut_ident = nullptr;
@@ -807,6 +813,7 @@ struct ClearList {
   ClearList() { a.count = 0; a.stamp = nullptr; }
   void add(void *p, size_t bytes) {
     if (!bytes) return;
+    FA_REQUIRE(a.count < (int)(sizeof(a.ptr) / sizeof(a.ptr[0])), FA_ERR_INTERNAL, "more ranges to clear than ClearArgs holds");
     a.ptr[a.count] = (uint4 *)p; a.n16[a.count] = (bytes + 15) / 16; a.count++;
   }
   void launch(hipStream_t st) {
@@ -854,6 +861,16 @@ struct L2Lds {
   size_t scan(int lanes, int bytes) const { return ((size_t)(slots + 1) * lanes * bytes + 15) / 16 * 16; }
 };
 
+// Where a call wants the mappings behind its rows (fa_mapper_query_mappings); `on` = false: it does not, and the pass
+// launches and allocates nothing for them.  Passes append: `base` records are in place.  `count` learns the number of
+// records, also when they do not fit.
+struct MapSink {
+  bool on = false;
+  fa_hit_mapping *dev = nullptr;
+  int64_t cap = 0, base = 0;
+  int64_t *count = nullptr;
+};
+
 // One pass of the hot path over genomes [g0, g1) of a resident batch.  Everything between the first kernel and the
 // final read-back is asynchronous on one stream: sizes that depend on the data (largest sketch, seed hits per
 // fragment, loci, slide events) are *speculated* from earlier passes (fa_mapper::spec), checked on the device, and the
@@ -878,12 +895,15 @@ struct QueryPass {
   fa_cgi_row *const rows_dev;
   const int64_t cap, row_base;
   fa_cgi_row *const host_rows;
+  const MapSink maps;
   // ---- constants of the pass ----
   hipStream_t st;
   const int64_t range_f0, range_f1;
   const int NQ, qcap;
   const IndexView ix;
   const int64_t npairs;
+  int32_t map_chunks = 0;             // workgroups of the mapping compaction (maps.on)
+  int64_t nmaps = 0;                  // result: records of the pass, whatever the room
   uint64_t items_max = 0;
   size_t qs_lds = 0;
   int64_t F_total = 0;
@@ -897,8 +917,9 @@ struct QueryPass {
   unsigned long long t_begin = ~0ULL, t_end = 0;
   int attempts = 0;
 
-  QueryPass(fa_mapper &m_, Workspace &w_, const fa_genomes &g_, int32_t g0_, int32_t g1_, fa_cgi_row *rows_dev_, int64_t cap_, int64_t row_base_, fa_cgi_row *host_rows_)
-      : m(m_), w(w_), g(g_), g0(g0_), g1(g1_), rows_dev(rows_dev_), cap(cap_), row_base(row_base_), host_rows(host_rows_), st(w_.stream),
+  QueryPass(fa_mapper &m_, Workspace &w_, const fa_genomes &g_, int32_t g0_, int32_t g1_, fa_cgi_row *rows_dev_, int64_t cap_, int64_t row_base_, fa_cgi_row *host_rows_,
+            const MapSink &maps_)
+      : m(m_), w(w_), g(g_), g0(g0_), g1(g1_), rows_dev(rows_dev_), cap(cap_), row_base(row_base_), host_rows(host_rows_), maps(maps_), st(w_.stream),
         range_f0(g_.genome_frag_lo[g0_]), range_f1(g_.genome_frag_lo[g1_]), NQ(g1_ - g0_), qcap(m_.qcap), ix(m_.view()), npairs((int64_t)(g1_ - g0_) * m_.G) {}
 
   // ================================================ speculation ================================================
@@ -944,6 +965,14 @@ struct QueryPass {
     w.bins.ensure((size_t)NQ * std::max(m.total_bins, 1) + 2);
     w.row_count.ensure((size_t)npairs + 1); w.row_ident.ensure((size_t)npairs + 1);
     w.row_flag.ensure((size_t)npairs + 1); w.row_off.ensure((size_t)npairs + 1);
+    if (maps.on) {
+      // the winner table is sized and cleared with the bins; the compaction takes the bins of the pass in chunks
+      const int64_t chunks = ceil_div((int64_t)NQ * m.total_bins, (int64_t)MAP_CHUNK);
+      FA_REQUIRE(chunks < (1LL << 31) - 1, FA_ERR_UNSUPPORTED, "too many reference bins in one pass for the mapping output");
+      map_chunks = (int32_t)chunks;
+      w.winners.ensure((size_t)NQ * std::max(m.total_bins, 1) + 2);
+      w.map_chunk_count.ensure((size_t)map_chunks + 1); w.map_chunk_off.ensure((size_t)map_chunks + 1);
+    }
     qs_lds = (size_t)next_pow2((uint32_t)std::max(qcap, 2)) * 4;
     FA_REQUIRE(qs_lds <= 150 * 1024, FA_ERR_UNSUPPORTED, "fragment_length too large for the LDS fragment sort");
 
@@ -986,6 +1015,18 @@ struct QueryPass {
                          npairs, g.d_total_frag + g0, g0, rows_dev + row_base, cap - row_base);
     }
     return ra.emit != 0;
+  }
+  // the mappings of the whole pass, behind its last part and in front of launch_rows (whose last workgroup may hand the
+  // pass over): count per chunk, scan, write; the total goes into the status block and travels with the hand-over
+  void launch_maps() {
+    MapEmitArgs ea;
+    ea.bins = w.bins.p; ea.winners = w.winners.p; ea.contig_genome = m.contig_genome.p;
+    ea.n_bins = (int64_t)NQ * m.total_bins; ea.total_bins = std::max(m.total_bins, 1); ea.query_id_base = g0; ea.n_chunks = map_chunks;
+    ea.chunk_count = w.map_chunk_count.p; ea.chunk_off = w.map_chunk_off.p;
+    ea.maps = maps.dev + maps.base; ea.cap = maps.cap - maps.base; ea.total_maps = &w.status.p->total_maps;
+    if (map_chunks) hipLaunchKernelGGL(k_map_count, dim3(map_chunks), dim3(256), 0, st, ea);
+    hipLaunchKernelGGL(k_map_scan, dim3(1), dim3(1024), 0, st, ea);
+    if (map_chunks) hipLaunchKernelGGL(k_map_write, dim3(map_chunks), dim3(256), 0, st, ea);
   }
   // what the stage launches of one part share (sized by size_part)
   struct Part {
@@ -1100,7 +1141,11 @@ struct QueryPass {
       cl.add(w.l_end.p, (size_t)l_cap * sizeof(int32_t)); cl.add(w.l_rlast.p, (size_t)l_cap * sizeof(int32_t));
       cl.add(w.group_best.p, (size_t)l_cap * sizeof(unsigned long long));
       if (p.scan_sorted) cl.add(w.scan_hist.p, (size_t)2 * LOCI_REGIONS * SCAN_CLASSES * sizeof(uint32_t));
-      if (!bins_cleared) { cl.add(w.bins.p, (size_t)NQ * std::max(m.total_bins, 1) * sizeof(unsigned long long)); bins_cleared = true; }
+      if (!bins_cleared) {
+        cl.add(w.bins.p, (size_t)NQ * std::max(m.total_bins, 1) * sizeof(unsigned long long));
+        if (maps.on) cl.add(w.winners.p, (size_t)NQ * std::max(m.total_bins, 1) * sizeof(MapWinner));
+        bins_cleared = true;
+      }
       QuerySketchArgs a;
       a.frag_tile_lo = g.d_frag_tile_lo + f0;
       a.tile_count = w.sk.tile_count.p; a.stage_hash = w.sk.stage_hash.p; a.stage_wpos = w.sk.stage_wpos.p;
@@ -1280,6 +1325,7 @@ struct QueryPass {
       a.wide_launched = sp.redo ? 1 : 0;
       a.group_bound = p.loci.n << p.loci.shift;
       hipLaunchKernelGGL(k_cgi_bins, dim3(ceil_div(l_cap, 256)), dim3(256), 0, st, a);
+      if (maps.on) hipLaunchKernelGGL(k_cgi_winners, dim3(ceil_div(l_cap, 256)), dim3(256), 0, st, a, w.winners.p);
     }
     // ---- the one hand-over of the part: results, statistics and the speculation verdict (publish_pass) ----
     if (r.with_rows) rows_valid = true;
@@ -1291,6 +1337,7 @@ struct QueryPass {
     PassStatus *h_dev = nullptr;
     FA_HIP(hipHostGetDevicePointer((void **)&h_dev, w.h_status, 0));
     const PublishArgs pub = publish_args(w.status.p, h_dev, ++w.seq, rows_dev + row_base, rows && host_rows ? host_rows + row_base : nullptr, cap - row_base);
+    if (rows && maps.on) launch_maps();
     const bool published = rows && launch_rows(pub);
     FA_HIP(hipGetLastError());
     debug_sync(st, "cgi");
@@ -1391,6 +1438,7 @@ struct QueryPass {
         wait_published(w.h_status, w.seq, st);
       }
       nrows = w.h_status->total_rows;
+      if (maps.on) nmaps = w.h_status->total_maps;
     }
     if (t_end > t_begin) w.last_ms[MS_TOTAL] += (float)((double)(t_end - t_begin) * 1e-5);   // device wall time of the pass
     FA_REQUIRE(nrows <= cap - row_base, FA_ERR_INVALID, "row buffer too small");
@@ -1398,12 +1446,25 @@ struct QueryPass {
   }
 };
 
+// (the records of the pass are appended to `maps`, whose base moves on; the caller learns the count before a destination
+// that is too small is refused)
 static int64_t run_query_pass(fa_mapper &m, Workspace &w, const fa_genomes &g, int32_t g0, int32_t g1, fa_cgi_row *rows_dev, int64_t cap,
-                              int64_t row_base, fa_cgi_row *host_rows = nullptr) {
-  return QueryPass(m, w, g, g0, g1, rows_dev, cap, row_base, host_rows).run();
+                              int64_t row_base, fa_cgi_row *host_rows, MapSink &maps) {
+  QueryPass pass(m, w, g, g0, g1, rows_dev, cap, row_base, host_rows, maps);
+  const int64_t nrows = pass.run();
+  if (maps.on) {
+    *maps.count = maps.base + pass.nmaps;
+    FA_REQUIRE(pass.nmaps <= maps.cap - maps.base, FA_ERR_INVALID, "mapping buffer too small");
+    maps.base += pass.nmaps;
+  }
+  return nrows;
 }
 
-static int64_t run_query(fa_mapper &m, Workspace &w, const fa_genomes &g, int32_t first, int32_t count, fa_cgi_row *rows, int64_t cap, bool rows_device) {
+// The mappings a call asked for (fa_mapper_query_mappings): the destination as the caller gave it.
+struct MapRequest { fa_hit_mapping *maps; int64_t cap; int64_t *n_maps; bool device; };
+
+static int64_t run_query(fa_mapper &m, Workspace &w, const fa_genomes &g, int32_t first, int32_t count, fa_cgi_row *rows, int64_t cap, bool rows_device,
+                         const MapRequest *want = nullptr) {
   require_device();
   FA_REQUIRE(first >= 0 && count >= 0 && first + count <= g.n_genomes, FA_ERR_INVALID, "genome range out of bounds");
   for (float &x : w.last_ms) x = 0;
@@ -1418,13 +1479,20 @@ static int64_t run_query(fa_mapper &m, Workspace &w, const fa_genomes &g, int32_
     w.pin_rows.ensure(std::max<size_t>((size_t)cap * sizeof(fa_cgi_row), 4096));
     FA_HIP(hipHostGetDevicePointer((void **)&host_rows, w.pin_rows.p, 0));
   }
+  MapSink sink;
+  if (want) {
+    FA_REQUIRE(want->cap >= 0 && (want->maps || want->cap == 0) && want->n_maps, FA_ERR_INVALID, "mapping buffer missing");
+    sink.on = true; sink.cap = want->cap; sink.dev = want->maps; sink.count = want->n_maps;
+    if (!want->device) { w.maps_dev.ensure((size_t)std::max<int64_t>(want->cap, 1)); sink.dev = w.maps_dev.p; }
+    *want->n_maps = 0;
+  }
   int64_t nrows = 0;
   int32_t g0 = first;
   while (g0 < first + count) {
     int32_t g1 = g0 + 1;
     while (g1 < first + count && g.genome_frag_lo[g1 + 1] - g.genome_frag_lo[g0] <= pass_fragments()) g1++;
     // frag_query is batch-wide: the bins of a pass are indexed by (genome - g0), handled through the pointer offset below
-    nrows += run_query_pass(m, w, g, g0, g1, dst, cap, nrows, host_rows);
+    nrows += run_query_pass(m, w, g, g0, g1, dst, cap, nrows, host_rows, sink);
     g0 = g1;
   }
   if (!rows_device && nrows) {
@@ -1437,6 +1505,10 @@ static int64_t run_query(fa_mapper &m, Workspace &w, const fa_genomes &g, int32_
       FA_HIP(hipStreamSynchronize(w.stream));
     }
     memcpy(rows, w.pin_rows.p, bytes);
+  }
+  if (want && !want->device && sink.base) {
+    FA_HIP(hipMemcpyAsync(want->maps, w.maps_dev.p, (size_t)sink.base * sizeof(fa_hit_mapping), hipMemcpyDeviceToHost, w.stream));
+    FA_HIP(hipStreamSynchronize(w.stream));
   }
   return nrows;
 }
@@ -2244,9 +2316,18 @@ int fa_mapper_query_genomes(fa_mapper *m, fa_genomes *g, int32_t first, int32_t 
     *n_rows = run_query(*m, *lease.w, *g, first, count, rows, cap, rows_device != 0);
   });
 }
-int fa_mapper_query(fa_mapper *m, const void *const *contigs, const int64_t *lengths, int n_contigs, int char_width,
-                    fa_cgi_row *rows, int64_t cap, int64_t *n_rows, int *n_short, uint64_t *total_fragments,
-                    uint64_t *total_length) {
+int fa_mapper_query_genomes_mappings(fa_mapper *m, fa_genomes *g, int32_t first, int32_t count, fa_cgi_row *rows, int64_t cap,
+                                     int64_t *n_rows, int rows_device, fa_hit_mapping *maps, int64_t map_cap, int64_t *n_maps,
+                                     int maps_device) {
+  return guarded([&] {
+    WorkspaceLease lease(*m);
+    const MapRequest want{maps, map_cap, n_maps, maps_device != 0};
+    *n_rows = run_query(*m, *lease.w, *g, first, count, rows, cap, rows_device != 0, &want);
+  });
+}
+static int query_one(fa_mapper *m, const void *const *contigs, const int64_t *lengths, int n_contigs, int char_width,
+                     fa_cgi_row *rows, int64_t cap, int64_t *n_rows, int *n_short, uint64_t *total_fragments,
+                     uint64_t *total_length, const MapRequest *want) {
   return guarded([&] {
     WorkspaceLease lease(*m);
     std::vector<int32_t> cg((size_t)std::max(n_contigs, 1), 0);
@@ -2257,13 +2338,24 @@ int fa_mapper_query(fa_mapper *m, const void *const *contigs, const int64_t *len
     if (total_fragments) *total_fragments = g->total_fragments[0];
     if (total_length) *total_length = g->total_length[0];
     const auto t0 = std::chrono::steady_clock::now();
-    *n_rows = run_query(*m, *lease.w, *g, 0, 1, rows, cap, false);
+    *n_rows = run_query(*m, *lease.w, *g, 0, 1, rows, cap, false, want);
     // host-side split of the boundary call (wall clock): packing, fragment/tile tables, H2D, pass + rows D2H
     for (int i = 0; i < 3; i++) lease.w->last_ms[MS_HOST + i] = host_ms[i];
     lease.w->last_ms[MS_CALL] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     lease.w->last_genomes = nullptr;
     lease.w->query_batch = std::move(g);                 // keep the device buffers for the next call
   });
+}
+int fa_mapper_query(fa_mapper *m, const void *const *contigs, const int64_t *lengths, int n_contigs, int char_width,
+                    fa_cgi_row *rows, int64_t cap, int64_t *n_rows, int *n_short, uint64_t *total_fragments,
+                    uint64_t *total_length) {
+  return query_one(m, contigs, lengths, n_contigs, char_width, rows, cap, n_rows, n_short, total_fragments, total_length, nullptr);
+}
+int fa_mapper_query_mappings(fa_mapper *m, const void *const *contigs, const int64_t *lengths, int n_contigs, int char_width,
+                             fa_cgi_row *rows, int64_t cap, int64_t *n_rows, int *n_short, uint64_t *total_fragments,
+                             uint64_t *total_length, fa_hit_mapping *maps, int64_t map_cap, int64_t *n_maps) {
+  const MapRequest want{maps, map_cap, n_maps, false};
+  return query_one(m, contigs, lengths, n_contigs, char_width, rows, cap, n_rows, n_short, total_fragments, total_length, &want);
 }
 
 // The workspace holds the intermediates of the last part it ran.  A pass that ran in more parts (several passes of one

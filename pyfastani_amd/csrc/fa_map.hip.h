@@ -2579,27 +2579,55 @@ struct CgiArgs {
   unsigned long long *stamp;    // stage_stamp: start of the CGI stage
 };
 
-__global__ void k_cgi_bins(CgiArgs a) {
-  stage_stamp(a.stamp);
-  uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (a.counters[CNT_LOCI_OVF] || g >= a.group_bound) return;                    // (a group carries the number of its first locus; the table of
+// What the bin key cannot carry of a bin's winner (fa_hit_mapping): a table parallel to the bins, kept only by calls that
+// asked for the mappings behind their rows.  One 16-byte store per entry.
+struct MapWinner { int32_t ref_seq_id, ref_start_pos, conserved, sketch_size; };
+static_assert(sizeof(MapWinner) == 16, "a winner entry is written with one 16-byte store");
+
+// The step-1 survivor of group g as step 2 sees it: its bin, its key and what the key does not hold.  False where the group
+// has none or the part is void -- k_cgi_bins and k_cgi_winners must take the same exits.
+__device__ __forceinline__ bool cgi_survivor(const CgiArgs &a, uint32_t g, size_t &idx, unsigned long long &key, MapWinner &win) {
+  if (a.counters[CNT_LOCI_OVF] || g >= a.group_bound) return false;              // (a group carries the number of its first locus; the table of
                                                                       //  group maxima is cleared per pass: no maximum, no group)
   // A void part must leave no trace in the bin table, which later parts and the repeat of this one accumulate into: when a
   // locus overflowed the one-byte slide state and the wide pass was not launched, the group maxima lack that locus, and a
   // lesser locus of its group could land in a bin the true best never touches (the host repeats the part, fa_engine.hip)
-  if (a.counters[CNT_WIDE] && !a.wide_launched) return;
+  if (a.counters[CNT_WIDE] && !a.wide_launched) return false;
   unsigned long long best = a.group_best[g];
-  if (best == 0) return;
+  if (best == 0) return false;
   uint32_t l = 0xFFFFFFFFu - (uint32_t)(best & 0xFFFFFFFFu);
   int shared = (int)(best >> 32);
   int f = a.l_frag[l];
   int s = a.q_size[f];
   float ident = a.ident_lut[(size_t)s * (size_t)(s + 1) / 2 + shared];
   int seq = a.l_seq[l];
-  int bin = a.ix.contig_bin[seq] + a.l_pos[l] / a.bin_len;
-  unsigned long long key = ((unsigned long long)__float_as_uint(ident) << 32) |
-                           (unsigned long long)(0xFFFFFFFFu - (uint32_t)a.frag_qseq[f]);
-  atomicMax(&a.bins[(size_t)(a.frag_query[f] - a.query_base) * a.ix.total_bins + bin], key);
+  int pos = a.l_pos[l];
+  int bin = a.ix.contig_bin[seq] + pos / a.bin_len;
+  key = ((unsigned long long)__float_as_uint(ident) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)a.frag_qseq[f]);
+  idx = (size_t)(a.frag_query[f] - a.query_base) * a.ix.total_bins + bin;
+  win.ref_seq_id = seq; win.ref_start_pos = pos; win.conserved = shared; win.sketch_size = s;
+  return true;
+}
+
+__global__ void k_cgi_bins(CgiArgs a) {
+  stage_stamp(a.stamp);
+  uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  size_t idx;
+  unsigned long long key;
+  MapWinner win;
+  if (cgi_survivor(a, g, idx, key, win)) atomicMax(&a.bins[idx], key);
+}
+
+// Behind k_cgi_bins in every part of a pass that keeps mappings: the survivor whose key holds its bin now leaves its entry.
+// Keys are unique inside a bin (querySeqId is unique per query genome), so one thread at most matches per bin: plain stores.
+// A void part leaves nothing (the exits of cgi_survivor), its repeat rewrites the same entries, and a later part that takes
+// a bin over overwrites its entry.
+__global__ void k_cgi_winners(CgiArgs a, MapWinner *winners) {
+  uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  size_t idx;
+  unsigned long long key;
+  MapWinner win;
+  if (cgi_survivor(a, g, idx, key, win) && a.bins[idx] == key) winners[idx] = win;
 }
 
 // One wave per (query genome, reference genome) pair: coalesced 64-bin reads, then the non-empty bins are added one
@@ -2789,6 +2817,97 @@ __global__ void k_emit_rows(const int32_t *row_count, const float *row_ident, co
 __global__ void k_flag_nonzero(const int32_t *row_count, int64_t n, int32_t *flag) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) flag[i] = row_count[i] != 0;
+}
+
+// ----------------------------------------------------------------------------------------------------------
+// The mappings behind the rows (fa_mapper_query_mappings): an ordered compaction of the non-empty bins of a pass into
+// fa_hit_mapping records.  The bins of a query lie in (reference genome, bin) order, so the linear order of the table IS
+// the (query, reference genome, bin) order in which k_cgi_rows adds the identities.  Count per chunk, scan the chunk
+// counts, write: a workgroup takes MAP_CHUNK consecutive bins, each of its waves 64 * MAP_ITERS of them in coalesced
+// 64-bin reads (issued together), and a bin's place among its wave's is the population count of the ballot below its lane.
+// A bin is mapped where the upper word of its key -- the identity -- is not zero, as in k_cgi_rows.
+// ----------------------------------------------------------------------------------------------------------
+constexpr int MAP_ITERS = 8, MAP_CHUNK = 256 * MAP_ITERS;
+struct MapEmitArgs {
+  const unsigned long long *bins;   // [n_bins] = [NQ * total_bins]
+  const MapWinner *winners;         // [n_bins]
+  const int32_t *contig_genome;
+  int64_t n_bins;
+  int32_t total_bins, query_id_base, n_chunks;
+  int32_t *chunk_count;             // [n_chunks]
+  int64_t *chunk_off;               // [n_chunks] records of the pass in front of the chunk
+  fa_hit_mapping *maps;             // the records of the pass start here
+  int64_t cap;                      // room from there on: nothing is written beyond it
+  int64_t *total_maps;              // in the status block: the full count, whatever the room
+};
+
+// keys of the wave's MAP_ITERS reads of 64 bins (0 beyond the table); returns how many are mapped
+__device__ __forceinline__ int map_load_keys(const MapEmitArgs &a, int64_t base, unsigned long long (&key)[MAP_ITERS]) {
+#pragma unroll
+  for (int u = 0; u < MAP_ITERS; u++) key[u] = base + 64 * u < a.n_bins ? a.bins[base + 64 * u] : 0ULL;
+  int n = 0;
+#pragma unroll
+  for (int u = 0; u < MAP_ITERS; u++) n += __popcll(__ballot((uint32_t)(key[u] >> 32) != 0u));
+  return n;
+}
+
+__global__ __launch_bounds__(256) void k_map_count(MapEmitArgs a) {
+  __shared__ int sh_wave[4];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  unsigned long long key[MAP_ITERS];
+  const int n = map_load_keys(a, (int64_t)blockIdx.x * MAP_CHUNK + wv * (64 * MAP_ITERS) + lane, key);
+  if (lane == 0) sh_wave[wv] = n;
+  __syncthreads();
+  if (threadIdx.x == 0) a.chunk_count[blockIdx.x] = sh_wave[0] + sh_wave[1] + sh_wave[2] + sh_wave[3];
+}
+
+// exclusive 64-bit sum of the chunk counts by one workgroup (thread t owns a run of consecutive chunks) + the pass's total
+__global__ __launch_bounds__(1024) void k_map_scan(MapEmitArgs a) {
+  __shared__ long long sh_wave[16];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int per = (a.n_chunks + 1023) / 1024;
+  const int c0 = min(a.n_chunks, (int)threadIdx.x * per), c1 = min(a.n_chunks, c0 + per);
+  long long mine = 0;
+  for (int c = c0; c < c1; c++) mine += a.chunk_count[c];
+  long long incl = mine;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) { const long long v = __shfl_up(incl, d); if (lane >= d) incl += v; }
+  if (lane == 63) sh_wave[wv] = incl;
+  __syncthreads();
+  long long off = incl - mine;
+  for (int w = 0; w < wv; w++) off += sh_wave[w];
+  for (int c = c0; c < c1; c++) { a.chunk_off[c] = off; off += a.chunk_count[c]; }
+  if (threadIdx.x == 1023) *a.total_maps = off;
+}
+
+__global__ __launch_bounds__(256) void k_map_write(MapEmitArgs a) {
+  __shared__ int sh_wave[4];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int64_t base = (int64_t)blockIdx.x * MAP_CHUNK + wv * (64 * MAP_ITERS) + lane;
+  unsigned long long key[MAP_ITERS];
+  const int n = map_load_keys(a, base, key);
+  if (lane == 0) sh_wave[wv] = n;
+  __syncthreads();
+  int64_t off = a.chunk_off[blockIdx.x];
+  for (int w = 0; w < wv; w++) off += sh_wave[w];
+  const unsigned long long below = (1ULL << lane) - 1ULL;
+#pragma unroll
+  for (int u = 0; u < MAP_ITERS; u++) {
+    const bool mapped = (uint32_t)(key[u] >> 32) != 0u;
+    const unsigned long long mask = __ballot(mapped);
+    const int64_t o = off + __popcll(mask & below);
+    off += __popcll(mask);
+    if (!mapped || o >= a.cap) continue;
+    const int64_t i = base + 64 * u;
+    const MapWinner w = a.winners[i];
+    fa_hit_mapping r;
+    r.query_id = a.query_id_base + (int32_t)(i / a.total_bins);
+    r.query_seq_id = (int32_t)(0xFFFFFFFFu - (uint32_t)(key[u] & 0xFFFFFFFFu));
+    r.ref_genome_id = a.contig_genome[w.ref_seq_id];
+    r.ref_seq_id = w.ref_seq_id; r.ref_start_pos = w.ref_start_pos; r.sketch_size = w.sketch_size; r.conserved = w.conserved;
+    r.identity = __uint_as_float((uint32_t)(key[u] >> 32));
+    a.maps[o] = r;
+  }
 }
 
 

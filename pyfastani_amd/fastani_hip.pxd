@@ -37,6 +37,16 @@ cdef extern from "fastani_hip.h" nogil:
         int32_t conserved
         int32_t query_id
 
+    ctypedef struct fa_hit_mapping:     # one mapping computeCGI kept (what FastANI's --visualize dumps per fragment)
+        int32_t query_id
+        int32_t query_seq_id
+        int32_t ref_genome_id
+        int32_t ref_seq_id
+        int32_t ref_start_pos
+        int32_t sketch_size
+        int32_t conserved
+        float identity
+
     const char* fa_last_error()
     int fa_version()
     int fa_device_trim(uint64_t* held_bytes)
@@ -89,6 +99,9 @@ cdef extern from "fastani_hip.h" nogil:
     int fa_mapper_query(fa_mapper* m, const void* const* contigs, const int64_t* lengths, int n_contigs, int char_width,
                         fa_cgi_row* rows, int64_t cap, int64_t* n_rows, int* n_short, uint64_t* total_fragments,
                         uint64_t* total_length)                                               # body of _query_draft, :1052-1118
+    int fa_mapper_query_mappings(fa_mapper* m, const void* const* contigs, const int64_t* lengths, int n_contigs, int char_width,
+                                 fa_cgi_row* rows, int64_t cap, int64_t* n_rows, int* n_short, uint64_t* total_fragments,
+                                 uint64_t* total_length, fa_hit_mapping* maps, int64_t map_cap, int64_t* n_maps)
 
     # resident batches (many-to-many extension)
     int fa_genomes_upload(fa_mapper* m, const void* const* contigs, const int64_t* lengths, const int32_t* contig_genome,
@@ -107,3 +120,6 @@ cdef extern from "fastani_hip.h" nogil:
     int fa_genomes_info(fa_genomes* g, int32_t* n_genomes, uint64_t* total_fragments, uint64_t* total_length, int32_t* n_short)
     int fa_mapper_query_genomes(fa_mapper* m, fa_genomes* g, int32_t first, int32_t count, fa_cgi_row* rows, int64_t cap,
                                 int64_t* n_rows, int rows_device)
+    int fa_mapper_query_genomes_mappings(fa_mapper* m, fa_genomes* g, int32_t first, int32_t count, fa_cgi_row* rows, int64_t cap,
+                                         int64_t* n_rows, int rows_device, fa_hit_mapping* maps, int64_t map_cap,
+                                         int64_t* n_maps, int maps_device)

@@ -2,7 +2,8 @@
 include/fastani/cgi/compute_core_identity.pxd:39-51 -- not exposed by pyfastani, provided here for all-vs-all runs).
 
 The rows are ``cgi::CGI_Results`` records (``pyfastani_amd._batch.ROW_DTYPE``): query_id, ref_genome_id, count_seq,
-total_query_fragments, identity.
+total_query_fragments, identity.  The fragment mappings behind them (``pyfastani_amd._batch.MAPPING_DTYPE``, from
+`GenomeBatch.query_mappings` / `Mapper.query_draft_mappings`) are what FastANI's ``--visualize`` dumps per fragment.
 """
 import numpy as np
 
@@ -50,3 +51,45 @@ def write_hits(path, query_names, reference_names, rows):
         for r in rows[order]:
             f.write(f"{query_names[r['query_id']]}\t{reference_names[r['ref_genome_id']]}\t{r['identity']:.6g}\t"
                     f"{r['count_seq']}\t{r['total_query_fragments']}\n")
+
+
+def fragment_coordinates(contig_lengths, fragment_length):
+    """Where every query fragment lies in its genome: ``(contig, offset)``, two int64 arrays indexed by ``querySeqId``
+    (``query_seq_id`` of a mapping).  A contig of length ``n`` holds ``n // fragment_length`` fragments, numbered on from
+    the contigs before it (_fastani.pyx:1097,1104); ``contig`` is the index into ``contig_lengths`` as given, short contigs
+    included."""
+    if fragment_length <= 0:
+        raise ValueError("fragment_length must be positive")
+    counts = np.asarray(contig_lengths, dtype=np.int64) // int(fragment_length)
+    contig = np.repeat(np.arange(len(counts), dtype=np.int64), counts)
+    first = np.cumsum(counts) - counts                           # querySeqId of every contig's first fragment
+    offset = (np.arange(int(counts.sum()), dtype=np.int64) - first[contig]) * int(fragment_length)
+    return contig, offset
+
+
+MAPPING_COLUMNS = ("query", "query_fragment", "query_contig", "query_start", "query_end", "reference", "reference_contig",
+                   "reference_start", "identity", "conserved", "sketch_size")
+
+
+def write_mappings(path, query_names, reference_names, mappings, query_contig_lengths=None, fragment_length=None):
+    """The fragment mappings as a tab-separated table, one line per record in the order given, under a header line naming
+    the columns (`MAPPING_COLUMNS`).  ``query_contig_lengths`` (one sequence of contig lengths per query genome, indexed by
+    ``query_id``) and ``fragment_length`` place every fragment on its contig; without them the three query coordinate
+    columns hold ``NA``.  ``reference_contig`` is the contig's number in the whole reference (``refSeqId``) and
+    ``reference_start`` the position on that contig.  This is the project's own layout: upstream's visualisation file is
+    written by code outside the reference checkout, and no byte parity with it is claimed."""
+    if (query_contig_lengths is None) != (fragment_length is None):
+        raise ValueError("query_contig_lengths and fragment_length go together")
+    coords = {}
+    with open(path, "w") as f:
+        f.write("\t".join(MAPPING_COLUMNS) + "\n")
+        for r in mappings:
+            q, frag = int(r["query_id"]), int(r["query_seq_id"])
+            where = ("NA", "NA", "NA")
+            if fragment_length is not None:
+                if q not in coords:
+                    coords[q] = fragment_coordinates(query_contig_lengths[q], fragment_length)
+                contig, offset = coords[q]
+                where = (int(contig[frag]), int(offset[frag]), int(offset[frag]) + int(fragment_length))
+            f.write(f"{query_names[q]}\t{frag}\t{where[0]}\t{where[1]}\t{where[2]}\t{reference_names[r['ref_genome_id']]}\t"
+                    f"{r['ref_seq_id']}\t{r['ref_start_pos']}\t{r['identity']:.6g}\t{r['conserved']}\t{r['sketch_size']}\n")
