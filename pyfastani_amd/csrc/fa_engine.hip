@@ -1207,7 +1207,7 @@ struct QueryPass {
       // into LDS-sized chunks at contig boundaries by k_l1_big first; what it cannot cut stays with k_l1's HBM path
       static const bool l1_big = env_num("FA_L1_BIG", 1) != 0;
       a.big_state = nullptr; a.big_enabled = 0; a.big_cap = 0;
-      const int64_t big_room = (int64_t)160 * 1024 - 2048 - ((int64_t)smax + 2) * 16;   // LDS left for a chunk's seeds
+      const int64_t big_room = (int64_t)160 * 1024 - 2048 - ((int64_t)smax + 2) * 16 - (int64_t)L1_BIG_THREADS * 8;   // LDS left for a chunk's seeds
       if (l1_big && sp.scratch_words > 0 && big_room >= 4 * 2048) {
         w.big_state.ensure((size_t)F);
         a.big_cap = (uint32_t)std::min<int64_t>((int64_t)L1_BIG_E * L1_BIG_THREADS, big_room / 4 / 256 * 256);
@@ -1223,7 +1223,11 @@ struct QueryPass {
         if (dbg) fprintf(stderr, "k_l1<%d>: F=%lld hits %u..%u seed_slots=%u smax=%d lds=%zu\n", NTT, (long long)F, c.n_lo, c.n_hi, c.slots, smax, lds);
         L1Args b = a;
         b.lds_seed_cap = c.slots; b.n_lo = c.n_lo; b.n_hi = c.n_hi; b.fold_totals = fold ? 1 : 0;
-        launch_lds(c.slots <= 16 * (uint32_t)NTT ? k_l1<NTT, 16> : k_l1<NTT, 32>, dim3(l1_grid + (fold ? 1u : 0u)), dim3(NTT), lds, st, b);
+        // (plan_l1 gives a 256-thread class L1_SMALL_HITS = 16 x 256 slots at most: it has no 32-hits-per-thread form)
+        constexpr uint32_t E_MAX = NTT == 256 ? 16u : (uint32_t)L1_INPLACE_MAX;
+        FA_REQUIRE(c.slots <= E_MAX * (uint32_t)NTT, FA_ERR_INTERNAL, "more seed slots than a workgroup of the L1 kernel merges");
+        const auto kernel = c.slots <= 16u * (uint32_t)NTT ? k_l1<NTT, 16> : k_l1<NTT, (int)E_MAX>;
+        launch_lds(kernel, dim3(l1_grid + (fold ? 1u : 0u)), dim3(NTT), lds, st, b);
       };
       for (int c = 0; c < p.l1.n; c++) {
         const bool fold = fold_totals && c == 0;

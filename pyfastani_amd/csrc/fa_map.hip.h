@@ -1097,6 +1097,249 @@ __device__ __forceinline__ bool l1_block_sort(const L1Args &a, int s, uint32_t n
   return true;
 }
 
+// ---- the pieces k_l1 and k_l1_big share: the rare roads of L1 (hits that l1_block_sort gives up on, more hits than LDS
+//      holds, more loci than the LDS stage holds) and the way out.  Called by the whole workgroup (NT threads) unless said. ----
+
+// Exclusive prefix sum of the lengths of the s position lists of a fragment: off[j] = first hit of list j, off[s] = all hits
+// (returned), qo[j] = where list j starts in the index.  list(j, src) returns the length of list j and sets its start.
+template <int NT, class List>
+__device__ __forceinline__ uint32_t l1_list_offsets(int s, uint32_t *off, uint32_t *qo, List list) {
+  __shared__ uint32_t sh_scan[NT / 64];
+  __shared__ uint32_t sh_run;       // running offset
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  if (tid == 0) sh_run = 0;
+  __syncthreads();
+  for (int j0 = 0; j0 < s; j0 += NT) {
+    const int j = j0 + tid;
+    uint32_t src = 0;
+    const uint32_t cnt = j < s ? list(j, src) : 0;
+    const uint32_t incl = wave_incl_scan(cnt);
+    if (lane == 63) sh_scan[wv] = incl;
+    __syncthreads();
+    uint32_t o = sh_run + incl - cnt;
+    for (int q = 0; q < wv; q++) o += sh_scan[q];
+    if (j < s) { off[j] = o; qo[j] = src; }
+    __syncthreads();
+    if (tid == 0) { uint32_t tot = 0; for (int q = 0; q < NT / 64; q++) tot += sh_scan[q]; sh_run += tot; }
+    __syncthreads();
+  }
+  if (tid == 0) off[s] = sh_run;
+  __syncthreads();
+  return off[s];
+}
+
+// The position lists of the query minimizers are each sorted already (CSR order = record order): gather them back to back
+// into A[0, n) (flat, two elements per thread and trip so that two index reads are in flight) ...
+template <int NT>
+__device__ __forceinline__ void l1_gather_lists(const uint32_t *pos_ridx, uint32_t *A, const uint32_t *off, const uint32_t *qo, int s, uint32_t n) {
+  const int tid = threadIdx.x;
+  auto locate = [&](uint32_t i) __attribute__((always_inline)) {
+    int lo = 0, hi = s - 1;                                              // the list j with off[j] <= i < off[j + 1]
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (off[mid + 1] <= i) lo = mid + 1; else hi = mid; }
+    return lo;
+  };
+  for (uint32_t i0 = tid; i0 < n; i0 += 2 * NT) {
+    const uint32_t i1 = i0 + NT;
+    const int j0 = locate(i0), j1 = i1 < n ? locate(i1) : 0;
+    const uint32_t v0 = pos_ridx[qo[j0] + (i0 - off[j0])];
+    const uint32_t v1 = i1 < n ? pos_ridx[qo[j1] + (i1 - off[j1])] : 0u;
+    A[i0] = v0;
+    if (i1 < n) A[i1] = v1;
+  }
+  __syncthreads();
+}
+// ... and merge them pairwise, bottom-up (record indices are unique: no ties).  A run is a group of 2^k consecutive lists, so
+// its bounds come from the prefix sums of the list lengths.  n <= E x NT.
+// Merge path, in place.  Thread t produces the outputs [t x per, (t + 1) x per) of every level: it finds where that
+// range starts on the merge path of its pair of runs (ONE binary search along the diagonal), then merges `per`
+// elements sequentially -- one LDS read and a compare per output, the same number of steps in every lane -- keeps
+// them in registers across the barrier that separates the reads of a level from its writes, and writes them back.
+// 4 bytes of LDS per seed; the chain of dependent LDS round trips per level is (two searches) + per.
+template <int NT, int E>
+__device__ __forceinline__ void l1_merge_lists(uint32_t *A, const uint32_t *off, int s, uint32_t n) {
+  const int tid = threadIdx.x;
+  // outputs per thread (<= E + 1), made ODD: thread t reads and writes around A[t x per], and with an even stride the
+  // 64 lanes of a wave share 32 / gcd(per, 64) ... banks (per = 12: four-way, per = 16: sixteen-way conflicts)
+  const uint32_t per = ((n + NT - 1) / NT) | 1u;
+  const uint32_t o_lo = (uint32_t)tid * per;
+  for (int k = 0; (1 << k) < s; k++) {
+    uint32_t out[E + 1];
+    const int w2 = 2 << k;                                             // lists per pair of runs
+    const int npairs = (s + w2 - 1) / w2;
+    uint32_t A0 = 0, A1 = 0, A2 = 0, ia = 0, ib = 0;
+    int p = 0;
+    if (o_lo < n) {
+      // the pair that holds output o_lo: the last one starting at or before it
+      int lo = 0, hi = npairs - 1;
+      while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (off[min(mid * w2, s)] <= o_lo) lo = mid; else hi = mid - 1; }
+      p = lo;
+      A0 = off[min(p * w2, s)]; A1 = off[min(p * w2 + (w2 >> 1), s)]; A2 = off[min((p + 1) * w2, s)];
+      // merge path: how many of the first (o_lo - A0) outputs of the pair come from its left run
+      const uint32_t diag = o_lo - A0, lenA = A1 - A0, lenB = A2 - A1;
+      uint32_t l = diag > lenB ? diag - lenB : 0u, h = min(diag, lenA);
+      while (l < h) { const uint32_t mid = (l + h) >> 1; if (A[A0 + mid] < A[A1 + diag - 1 - mid]) l = mid + 1; else h = mid; }
+      ia = l; ib = diag - l;
+    }
+    uint32_t ka = (o_lo < n && A0 + ia < A1) ? A[A0 + ia] : 0xFFFFFFFFu;
+    uint32_t kb = (o_lo < n && A1 + ib < A2) ? A[A1 + ib] : 0xFFFFFFFFu;
+#pragma unroll
+    for (int e = 0; e < E + 1; e++) {
+      const uint32_t o = o_lo + e;
+      out[e] = 0;
+      if ((uint32_t)e < per && o < n) {
+        while (o >= A2) {                                              // next pair (empty ones are skipped)
+          p++;
+          A0 = off[min(p * w2, s)]; A1 = off[min(p * w2 + (w2 >> 1), s)]; A2 = off[min((p + 1) * w2, s)];
+          ia = 0; ib = 0;
+          ka = A0 < A1 ? A[A0] : 0xFFFFFFFFu;
+          kb = A1 < A2 ? A[A1] : 0xFFFFFFFFu;
+        }
+        const bool take_a = ka < kb;                                   // an exhausted run reads as +inf
+        out[e] = take_a ? ka : kb;
+        ia += take_a ? 1u : 0u; ib += take_a ? 0u : 1u;
+        const uint32_t nxt = take_a ? A0 + ia : A1 + ib, end = take_a ? A1 : A2;
+        const uint32_t v = nxt < end ? A[nxt] : 0xFFFFFFFFu;
+        ka = take_a ? v : ka; kb = take_a ? kb : v;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < E + 1; e++) {
+      const uint32_t o = o_lo + e;
+      if ((uint32_t)e < per && o < n) A[o] = out[e];
+    }
+    __syncthreads();
+  }
+}
+
+// The candidate scan (computeL1CandidateRegions) over the sorted hits seeds[0, n), n >= m, NT candidates per trip.  Candidate i
+// -- hit i and its partner i + m - 1 -- is flagged when the two lie within `len` padded bases; a flagged candidate that the
+// previous flagged one does not reach is the HEAD of a locus.  Every flagged candidate is handed to
+//   sink(slot, head, last_here, ra, rb)   slot: number of its locus, counted from slot0 + 1; ra, rb: records of the hit and of
+//                                         its partner (the partner of a head fixes the start of the locus); last_here: no
+//                                         later candidate of this wave and trip belongs to the locus,
+// and the end of a locus is its last flagged seed: only `last_here` lanes should touch it (same-address atomics from every
+// lane would serialise).  Returns slot0 + the loci found.  g_trip: [NT] in LDS.
+template <int NT, class Sink>
+__device__ __forceinline__ uint32_t l1_scan_trips(const IndexView &ix, const uint32_t *seeds, uint32_t n, int m, int len, uint32_t slot0,
+                                                  uint64_t *g_trip, Sink sink) {
+  // running head count and the last flagged candidate so far, double-buffered by trip parity so that
+  // thread 0 can publish the next trip's values while slower waves still read this trip's
+  __shared__ uint32_t sh_heads[2];
+  __shared__ int sh_has_prev[2];
+  __shared__ uint64_t sh_prev_g[2];
+  __shared__ uint64_t w_last_g[2][NT / 64];
+  __shared__ int w_any[2][NT / 64];
+  __shared__ uint32_t w_heads[NT / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const uint32_t ncand = n - (uint32_t)m + 1;
+  const uint64_t len64 = (uint64_t)len;
+  __syncthreads();                                                       // (a call before this one has returned sh_heads[] everywhere)
+  if (tid == 0) { sh_heads[0] = slot0; sh_has_prev[0] = 0; sh_prev_g[0] = 0; }
+  __syncthreads();
+  int par = 0;
+  // coordinate of the seed this thread owns in the first trip; later trips are fetched one trip ahead
+  uint32_t ra_n = (uint32_t)tid < n ? seeds[tid] : 0u;
+  uint32_t lo_n = (uint32_t)tid < n ? ix.rec_gpos[ra_n] : 0u;
+  for (uint32_t i0 = 0; i0 < ncand; i0 += NT) {
+    const uint32_t i = i0 + tid;
+    // every lane fetches the coordinate of its own seed once and leaves it in LDS for its wave: the partner seed
+    // i+m-1 and the previous flagged candidate are other lanes' seeds (an 8-byte LDS read each where a `__shfl` -- a
+    // ds_bpermute, ~18 cycles of the CU's LDS pipe -- per word cost a fifth of k_l1 on this road)
+    const uint32_t ra = ra_n;
+    const uint64_t ga = gpos_make(ix, ra, lo_n);
+    g_trip[tid] = ga;
+    // (the slots written above are read below by OTHER lanes of the same wave only: order the store before those reads
+    // explicitly -- no instruction on gfx950, where a wave's LDS operations complete in order -- instead of relying on it)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    if (i0 + NT < ncand) {
+      const uint32_t in = i + NT;
+      ra_n = in < n ? seeds[in] : 0u;
+      lo_n = in < n ? ix.rec_gpos[ra_n] : 0u;
+    }
+    const uint32_t rb = i < ncand ? seeds[i + m - 1] : 0u;
+    uint64_t gb = g_trip[min(tid + m - 1, NT - 1)];                      // (read by its own wave only: LDS keeps a wave's order)
+    if (lane + m - 1 >= 64 && i < ncand) gb = gpos_of(ix, rb);
+    const bool flag = i < ncand && gb - ga < len64;
+    // previous flagged candidate (in order): inside the wave, else earlier waves, else the carry
+    const uint64_t bal = __ballot(flag);
+    const uint64_t below = bal & ((1ULL << lane) - 1ULL);
+    const int src_lane = below ? 63 - __clzll(below) : -1;
+    uint64_t gp = g_trip[(tid & ~63) + max(src_lane, 0)];
+    if (lane == 0) w_any[par][wv] = bal != 0;
+    if (bal && lane == 63 - __clzll(bal)) w_last_g[par][wv] = ga;
+    __syncthreads();
+    bool has_prev = src_lane >= 0;
+    if (!has_prev) {
+      for (int q = wv - 1; q >= 0 && !has_prev; q--) if (w_any[par][q]) { has_prev = true; gp = w_last_g[par][q]; }
+      if (!has_prev && sh_has_prev[par]) { has_prev = true; gp = sh_prev_g[par]; }
+    }
+    const bool head = flag && !(has_prev && gb - gp < len64);
+    // inclusive scan of heads -> slot of the locus every flagged candidate belongs to
+    const uint64_t hb = __ballot(head);
+    if (lane == 0) w_heads[wv] = __popcll(hb);
+    __syncthreads();
+    uint32_t slot = sh_heads[par] + __popcll(hb & ((2ULL << lane) - 1ULL));
+    for (int q = 0; q < wv; q++) slot += w_heads[q];
+    if (flag) {
+      const uint64_t above = (lane == 63) ? 0ULL : (bal & ~((2ULL << lane) - 1ULL));
+      const bool last_here = above == 0 || ((hb >> (__ffsll((long long)above) - 1)) & 1ULL);
+      sink(slot, head, last_here, ra, rb);
+    }
+    if (tid == 0) {
+      // next trip's carry goes to the other parity: nobody reads it before the next trip's first barrier
+      uint32_t tot = sh_heads[par];
+      for (int q = 0; q < NT / 64; q++) tot += w_heads[q];
+      sh_heads[par ^ 1] = tot;
+      int hp = sh_has_prev[par];
+      uint64_t pg = sh_prev_g[par];
+      for (int q = NT / 64 - 1; q >= 0; q--) if (w_any[par][q]) { hp = 1; pg = w_last_g[par][q]; break; }
+      sh_has_prev[par ^ 1] = hp; sh_prev_g[par ^ 1] = pg;
+    }
+    par ^= 1;
+  }
+  __syncthreads();
+  return sh_heads[par];
+}
+
+// `cnt` loci for fragment f, by ONE thread: reserves them (reserve_loci), raises the overflow flags if they do not fit their
+// region -- the pass is void then and nothing may be written -- and publishes the fragment's range.  Returns the loci to
+// write (0: none), `base` = the number of the first.
+__device__ __forceinline__ uint32_t l1_reserve(const L1Args &a, int f, uint32_t cnt, uint32_t &base) {
+  bool fits = true;
+  base = cnt ? reserve_loci(a.loci, f, cnt, fits) : 0;
+  if (!fits) { atomicExch(&a.counters[CNT_LOCI_OVF], 1u); atomicOr(&a.pinfo[PI_FLAGS], (unsigned long long)SPEC_LOCI); cnt = 0; }
+  a.f_loci_lo[f] = base; a.f_loci_n[f] = cnt;
+  return cnt;
+}
+// (contig, start, end) of `cnt` loci from their three records (first seed, its partner, last flagged seed); the arrays are
+// the LDS stage or the loci's final place
+template <int NT>
+__device__ __forceinline__ void l1_locus_fields(const IndexView &ix, int len, uint32_t cnt, const int32_t *rfirst, const int32_t *rpart,
+                                                const int32_t *rlast, int32_t *seq, int32_t *start, int32_t *end) {
+  for (uint32_t q = threadIdx.x; q < cnt; q += NT) {
+    seq[q] = ix.rec_seq[rfirst[q]];
+    start[q] = max(0, ix.rec_wpos[rpart[q]] - len + 1);
+    end[q] = ix.rec_wpos[rlast[q]];
+  }
+}
+// groups, by ONE wave: consecutive loci of a fragment on the same reference genome.  A group is numbered by the first locus
+// it holds -- group[i] = base + (first locus of the group of locus i) -- so it needs no counter of its own.
+__device__ __forceinline__ void l1_number_groups(const IndexView &ix, uint32_t cnt, const int32_t *seq, int32_t *group, uint32_t base) {
+  const int lane = threadIdx.x & 63;
+  uint32_t last_head = 0;
+  for (uint32_t i0 = 0; i0 < cnt; i0 += 64) {
+    const uint32_t i = i0 + lane;
+    bool gh = false;
+    if (i < cnt) gh = (i == 0) || ix.contig_genome[seq[i]] != ix.contig_genome[seq[i - 1]];
+    const uint64_t gb = __ballot(gh);
+    const uint64_t upto = gb & ((2ULL << lane) - 1ULL);
+    if (i < cnt) group[i] = (int32_t)(base + (upto ? i0 + (uint32_t)(63 - __clzll(upto)) : last_head));
+    if (gb) last_head = i0 + (uint32_t)(63 - __clzll(gb));
+  }
+}
+
 // NT threads per workgroup (256 measured best: wider workgroups pay more for the cross-wave scans and barriers).
 // E = elements per thread the in-place merge can hold (16 for small fragments: fewer registers, more workgroups per CU).
 template <int NT, int E>
@@ -1109,14 +1352,7 @@ __global__ __launch_bounds__(NT, (E == 16 ? 8 : 4)) void k_l1(L1Args a) {
       return;
     }
   }
-  __shared__ uint32_t sh_scan[NT / 64];
-  __shared__ uint32_t sh_run;       // running offset (gather)
-  // candidate pass: running head count and the last flagged candidate so far, double-buffered by trip parity so that
-  // thread 0 can publish the next trip's values while slower waves still read this trip's
-  __shared__ uint32_t sh_heads[2];
-  __shared__ int sh_has_prev[2];
-  __shared__ uint64_t sh_prev_g[2];
-  __shared__ uint32_t sh_base, sh_gbase;
+  __shared__ uint32_t sh_base, sh_gbase;         // l1_reserve: first locus of the fragment, loci to write (0: none)
   const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int s = a.q_size[f];
   uint32_t n = a.n_seeds[f];                     // (the LIVE hits once the pre-filter of the block sort has dropped the dead ones)
@@ -1135,35 +1371,18 @@ __global__ __launch_bounds__(NT, (E == 16 ? 8 : 4)) void k_l1(L1Args a) {
   auto phase = [&](int k) __attribute__((always_inline)) {
     if (l1_dbg) { const long long now = clock64(); atomicAdd(&a.dbg[k], (unsigned long long)(now - tk)); tk = now; }
   };
+  // list j of the fragment: its length, and where it starts in the index
+  auto list = [&](int j, uint32_t &src) __attribute__((always_inline)) {
+    const uint32_t cnt = a.q_cnt[(size_t)f * a.qcap + j];
+    src = cnt ? a.q_off[(size_t)f * a.qcap + j] : 0u;
+    return cnt;
+  };
+  uint32_t *off = (uint32_t *)(lds + l1_off_offset(a.lds_seed_cap));    // [s + 1] first seed of every list
+  uint32_t *qo = off + a.lut_smax + 2;                                   // [s] where every list starts in the index
   if (in_lds) {
-    // ---- the position lists of the query minimizers are each sorted already (CSR order = record order): gather them
-    //      back to back and merge them pairwise, bottom-up (record indices are unique: no ties).  A run is a group of
-    //      2^k consecutive lists, so its bounds come from the prefix sums of the list lengths. ----
     const uint32_t cap = a.lds_seed_cap;
     uint32_t *A = (uint32_t *)lds;
-    uint32_t *off = (uint32_t *)(lds + l1_off_offset(cap));             // [s + 1] first seed of every list
-    uint32_t *qo = off + a.lut_smax + 2;                                 // [s] where every list starts in the index
-    auto list_offsets = [&]() __attribute__((always_inline)) {
-      if (tid == 0) sh_run = 0;
-      __syncthreads();
-      for (int j0 = 0; j0 < s; j0 += NT) {
-        const int j = j0 + tid;
-        const uint32_t cnt = j < s ? a.q_cnt[(size_t)f * a.qcap + j] : 0;
-        const uint32_t src = (j < s && cnt) ? a.q_off[(size_t)f * a.qcap + j] : 0u;
-        const uint32_t incl = wave_incl_scan(cnt);
-        if (lane == 63) sh_scan[wv] = incl;
-        __syncthreads();
-        uint32_t o = sh_run + incl - cnt;
-        for (int q = 0; q < wv; q++) o += sh_scan[q];
-        if (j < s) { off[j] = o; qo[j] = src; }
-        __syncthreads();
-        if (tid == 0) { uint32_t tot = 0; for (int q = 0; q < NT / 64; q++) tot += sh_scan[q]; sh_run += tot; }
-        __syncthreads();
-      }
-      if (tid == 0) off[s] = n;
-      __syncthreads();
-    };
-    list_offsets();
+    l1_list_offsets<NT>(s, off, qo, list);
     phase(0);
     // hits that cluster in stretches of the index (the usual case) are sorted block-wise: l1_block_sort (its key buffer is
     // everything behind the seed slots -- the list offsets, which it has used by then, and the locus stage)
@@ -1173,109 +1392,23 @@ __global__ __launch_bounds__(NT, (E == 16 ? 8 : 4)) void k_l1(L1Args a) {
       uint32_t n_live = n;
       block_sorted = l1_block_sort<NT, E / 2, 4>(a, s, n, cap, A, off, qo, off, kl, n_live, a.frag_len);
       if (block_sorted) n = n_live;
-      if (!block_sorted) list_offsets();                                // (the key buffer may have overwritten them)
+      if (!block_sorted) l1_list_offsets<NT>(s, off, qo, list);         // (the key buffer may have overwritten them)
     }
     if (l1_dbg) atomicAdd(&a.counters[block_sorted ? CNT_L1_SORTED : CNT_L1_MERGED], 1u);   // FA_L1_STATS=1: which road the fragments took
     // fragments that left the fast form (block sort -> gather + merge), counted exactly and always: one atomic on the rare road
     if (!block_sorted && tid == 0) atomicAdd(&a.counters[CNT_MERGED], 1u);
     phase(1);
-    if (!block_sorted) {
-    // flat gather, two elements per thread and trip so that two index reads are in flight
-    auto locate = [&](uint32_t i) __attribute__((always_inline)) {
-      int lo = 0, hi = s - 1;                                              // the list j with off[j] <= i < off[j + 1]
-      while (lo < hi) { const int mid = (lo + hi) >> 1; if (off[mid + 1] <= i) lo = mid + 1; else hi = mid; }
-      return lo;
-    };
-    for (uint32_t i0 = tid; i0 < n; i0 += 2 * NT) {
-      const uint32_t i1 = i0 + NT;
-      const int j0 = locate(i0), j1 = i1 < n ? locate(i1) : 0;
-      const uint32_t v0 = a.ix.pos_ridx[qo[j0] + (i0 - off[j0])];
-      const uint32_t v1 = i1 < n ? a.ix.pos_ridx[qo[j1] + (i1 - off[j1])] : 0u;
-      A[i0] = v0;
-      if (i1 < n) A[i1] = v1;
-    }
-    __syncthreads();
-    // Merge path, in place.  Thread t produces the outputs [t x per, (t + 1) x per) of every level: it finds where that
-    // range starts on the merge path of its pair of runs (ONE binary search along the diagonal), then merges `per`
-    // elements sequentially -- one LDS read and a compare per output, the same number of steps in every lane -- keeps
-    // them in registers across the barrier that separates the reads of a level from its writes, and writes them back.
-    // 4 bytes of LDS per seed; the chain of dependent LDS round trips per level is (two searches) + per.
-    // outputs per thread (<= E + 1), made ODD: thread t reads and writes around A[t x per], and with an even stride the
-    // 64 lanes of a wave share 32 / gcd(per, 64) ... banks (per = 12: four-way, per = 16: sixteen-way conflicts)
-    const uint32_t per = ((n + NT - 1) / NT) | 1u;
-    const uint32_t o_lo = (uint32_t)tid * per;
-    for (int k = 0; (1 << k) < s; k++) {
-      uint32_t out[E + 1];
-      const int w2 = 2 << k;                                             // lists per pair of runs
-      const int npairs = (s + w2 - 1) / w2;
-      uint32_t A0 = 0, A1 = 0, A2 = 0, ia = 0, ib = 0;
-      int p = 0;
-      if (o_lo < n) {
-        // the pair that holds output o_lo: the last one starting at or before it
-        int lo = 0, hi = npairs - 1;
-        while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (off[min(mid * w2, s)] <= o_lo) lo = mid; else hi = mid - 1; }
-        p = lo;
-        A0 = off[min(p * w2, s)]; A1 = off[min(p * w2 + (w2 >> 1), s)]; A2 = off[min((p + 1) * w2, s)];
-        // merge path: how many of the first (o_lo - A0) outputs of the pair come from its left run
-        const uint32_t diag = o_lo - A0, lenA = A1 - A0, lenB = A2 - A1;
-        uint32_t l = diag > lenB ? diag - lenB : 0u, h = min(diag, lenA);
-        while (l < h) { const uint32_t mid = (l + h) >> 1; if (A[A0 + mid] < A[A1 + diag - 1 - mid]) l = mid + 1; else h = mid; }
-        ia = l; ib = diag - l;
-      }
-      uint32_t ka = (o_lo < n && A0 + ia < A1) ? A[A0 + ia] : 0xFFFFFFFFu;
-      uint32_t kb = (o_lo < n && A1 + ib < A2) ? A[A1 + ib] : 0xFFFFFFFFu;
-#pragma unroll
-      for (int e = 0; e < E + 1; e++) {
-        const uint32_t o = o_lo + e;
-        out[e] = 0;
-        if ((uint32_t)e < per && o < n) {
-          while (o >= A2) {                                              // next pair (empty ones are skipped)
-            p++;
-            A0 = off[min(p * w2, s)]; A1 = off[min(p * w2 + (w2 >> 1), s)]; A2 = off[min((p + 1) * w2, s)];
-            ia = 0; ib = 0;
-            ka = A0 < A1 ? A[A0] : 0xFFFFFFFFu;
-            kb = A1 < A2 ? A[A1] : 0xFFFFFFFFu;
-          }
-          const bool take_a = ka < kb;                                   // an exhausted run reads as +inf
-          out[e] = take_a ? ka : kb;
-          ia += take_a ? 1u : 0u; ib += take_a ? 0u : 1u;
-          const uint32_t nxt = take_a ? A0 + ia : A1 + ib, end = take_a ? A1 : A2;
-          const uint32_t v = nxt < end ? A[nxt] : 0xFFFFFFFFu;
-          ka = take_a ? v : ka; kb = take_a ? kb : v;
-        }
-      }
-      __syncthreads();
-#pragma unroll
-      for (int e = 0; e < E + 1; e++) {
-        const uint32_t o = o_lo + e;
-        if ((uint32_t)e < per && o < n) A[o] = out[e];
-      }
-      __syncthreads();
-    }
-    }
+    if (!block_sorted) { l1_gather_lists<NT>(a.ix.pos_ridx, A, off, qo, s, n); l1_merge_lists<NT, E>(A, off, s, n); }
     phase(2);
     seeds = A;
   } else {
     // ---- more seed hits than LDS holds: lists gathered into HBM scratch and sorted there ----
     seeds = a.ovf_buf + a.ovf_off[f];
-    if (tid == 0) { sh_run = 0; atomicAdd(&a.counters[CNT_OFF_FAST], 1u); }         // (off the fast form: the HBM road)
-    __syncthreads();
-    for (int j0 = 0; j0 < s; j0 += blockDim.x) {
-      int j = j0 + tid;
-      uint32_t cnt = j < s ? a.q_cnt[(size_t)f * a.qcap + j] : 0;
-      uint32_t incl = cnt;
-      for (int d = 1; d < 64; d <<= 1) { uint32_t o = __shfl_up(incl, d); if (lane >= d) incl += o; }
-      if (lane == 63) sh_scan[wv] = incl;
-      __syncthreads();
-      uint32_t off = sh_run + incl - cnt;
-      for (int q = 0; q < wv; q++) off += sh_scan[q];
-      if (cnt) {
-        uint32_t src = a.q_off[(size_t)f * a.qcap + j];
-        for (uint32_t t = 0; t < cnt; t++) seeds[off + t] = a.ix.pos_ridx[src + t];
-      }
-      __syncthreads();
-      if (tid == 0) { uint32_t tot = 0; for (int q = 0; q < NT / 64; q++) tot += sh_scan[q]; sh_run += tot; }
-      __syncthreads();
+    if (tid == 0) atomicAdd(&a.counters[CNT_OFF_FAST], 1u);                          // (off the fast form: the HBM road)
+    l1_list_offsets<NT>(s, off, qo, list);
+    for (int j = tid; j < s; j += NT) {
+      const uint32_t o = off[j], cnt = off[j + 1] - o, src = qo[j];
+      for (uint32_t t = 0; t < cnt; t++) seeds[o + t] = a.ix.pos_ridx[src + t];
     }
     for (uint32_t i = n + tid; i < n32; i += blockDim.x) seeds[i] = SEED_PAD;
     __syncthreads();
@@ -1310,32 +1443,11 @@ __global__ __launch_bounds__(NT, (E == 16 ? 8 : 4)) void k_l1(L1Args a) {
     // as the candidate scan knows the count does not overlap that queue with the rest of the work: the compiler's atomic
     // optimizer waits for the answer on the spot).
     uint32_t *st_grp = (uint32_t *)(lds + l1_off_offset(a.lds_seed_cap));   // (the list offsets are no longer needed)
-    // (contig, start, end) of every locus from its three records
-    for (uint32_t q = tid; q < cnt0; q += NT) {
-      st_seq[q] = a.ix.rec_seq[st_rfirst[q]];
-      st_start[q] = max(0, a.ix.rec_wpos[st_rpart[q]] - len + 1);
-      st_end[q] = a.ix.rec_wpos[st_rlast[q]];
-    }
+    l1_locus_fields<NT>(a.ix, len, cnt0, st_rfirst, st_rpart, st_rlast, st_seq, st_start, st_end);
     __syncthreads();
     if (wv == 0) {
-      uint32_t last_head = 0;
-      for (uint32_t i0 = 0; i0 < cnt0; i0 += 64) {
-        const uint32_t i = i0 + lane;
-        bool gh = false;
-        if (i < cnt0) gh = (i == 0) || a.ix.contig_genome[st_seq[i]] != a.ix.contig_genome[st_seq[i - 1]];
-        const uint64_t gb = __ballot(gh);
-        const uint64_t upto = gb & ((2ULL << lane) - 1ULL);
-        if (i < cnt0) st_grp[i] = upto ? i0 + (uint32_t)(63 - __clzll(upto)) : last_head;   // first locus of the group of locus i
-        if (gb) last_head = i0 + (uint32_t)(63 - __clzll(gb));
-      }
-      if (lane == 0) {
-        bool fits;
-        uint32_t base = reserve_loci(a.loci, f, cnt0, fits), cnt = cnt0;
-        if (!fits) { atomicExch(&a.counters[CNT_LOCI_OVF], 1u); atomicOr(&a.pinfo[PI_FLAGS], (unsigned long long)SPEC_LOCI); cnt = 0; }
-        sh_base = base;
-        sh_gbase = cnt;
-        a.f_loci_lo[f] = base; a.f_loci_n[f] = cnt;
-      }
+      l1_number_groups(a.ix, cnt0, st_seq, (int32_t *)st_grp, 0u);       // first locus of the group of every locus
+      if (lane == 0) { uint32_t base; sh_gbase = l1_reserve(a, f, cnt0, base); sh_base = base; }
     }
     __syncthreads();
     if (sh_gbase == 0) return;
@@ -1490,15 +1602,7 @@ __global__ __launch_bounds__(NT, (E == 16 ? 8 : 4)) void k_l1(L1Args a) {
     const bool staged = total <= (uint32_t)L1_STAGE;
     if (!staged) {
       // more loci than the stage holds: reserve, and write them straight to HBM
-      if (tid == 0) {
-        uint32_t cnt = total;
-        bool fits;
-        uint32_t base = reserve_loci(a.loci, f, cnt, fits);
-        if (!fits) { atomicExch(&a.counters[CNT_LOCI_OVF], 1u); atomicOr(&a.pinfo[PI_FLAGS], (unsigned long long)SPEC_LOCI); cnt = 0; }
-        sh_base = base;
-        sh_gbase = cnt;
-        a.f_loci_lo[f] = base; a.f_loci_n[f] = cnt;
-      }
+      if (tid == 0) { uint32_t base; sh_gbase = l1_reserve(a, f, total, base); sh_base = base; }
       __syncthreads();
       if (sh_gbase == 0) return;
     }
@@ -1531,102 +1635,26 @@ __global__ __launch_bounds__(NT, (E == 16 ? 8 : 4)) void k_l1(L1Args a) {
   } else {
   uint64_t *g_trip = (uint64_t *)(lds + l1_off_offset(a.lds_seed_cap));  // [NT] (the list offsets are no longer needed)
   for (int pass = 0; pass < 2; pass++) {
-    if (tid == 0) { sh_heads[0] = 0; sh_has_prev[0] = 0; sh_prev_g[0] = 0; }
-    __syncthreads();
-    int par = 0;
-    // coordinate of the seed this thread owns in the first trip; later trips are fetched one trip ahead
-    uint32_t ra_n = (uint32_t)tid < n ? seeds[tid] : 0u;
-    uint32_t lo_n = (uint32_t)tid < n ? a.ix.rec_gpos[ra_n] : 0u;
-    for (uint32_t i0 = 0; i0 < ncand; i0 += NT) {
-      uint32_t i = i0 + tid;
-      // every lane fetches the coordinate of its own seed once and leaves it in LDS for its wave: the partner seed
-      // i+m-1 and the previous flagged candidate are other lanes' seeds (an 8-byte LDS read each where a `__shfl` -- a
-      // ds_bpermute, ~18 cycles of the CU's LDS pipe -- per word cost a fifth of this kernel)
-      const uint32_t ra = ra_n;
-      const uint64_t ga = gpos_make(a.ix, ra, lo_n);
-      g_trip[tid] = ga;
-      // (the slots written above are read below by OTHER lanes of the same wave only: order the store before those reads
-      // explicitly -- no instruction on gfx950, where a wave's LDS operations complete in order -- instead of relying on it)
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      if (i0 + NT < ncand) {
-        const uint32_t in = i + NT;
-        ra_n = in < n ? seeds[in] : 0u;
-        lo_n = in < n ? a.ix.rec_gpos[ra_n] : 0u;
-      }
-      const int rb = i < ncand ? (int)seeds[i + m - 1] : 0;               // record of the partner seed: it fixes the locus start
-      uint64_t gb = g_trip[min(tid + m - 1, NT - 1)];                      // (read by its own wave only: LDS keeps a wave's order)
-      if (lane + m - 1 >= 64 && i < ncand) gb = gpos_of(a.ix, (uint32_t)rb);
-      const bool flag = i < ncand && gb - ga < len64;
-      // previous flagged candidate (in order): inside the wave, else earlier waves, else the carry
-      uint64_t bal = __ballot(flag);
-      __shared__ uint64_t w_last_g[2][NT / 64];
-      __shared__ int w_any[2][NT / 64];
-      uint64_t below = bal & ((1ULL << lane) - 1ULL);
-      int src_lane = below ? 63 - __clzll(below) : -1;
-      uint64_t gp = g_trip[(tid & ~63) + max(src_lane, 0)];
-      if (lane == 0) w_any[par][wv] = bal != 0;
-      if (bal && lane == 63 - __clzll(bal)) w_last_g[par][wv] = ga;
-      __syncthreads();
-      bool has_prev = src_lane >= 0;
-      if (!has_prev) {
-        for (int q = wv - 1; q >= 0 && !has_prev; q--) if (w_any[par][q]) { has_prev = true; gp = w_last_g[par][q]; }
-        if (!has_prev && sh_has_prev[par]) { has_prev = true; gp = sh_prev_g[par]; }
-      }
-      bool head = flag && !(has_prev && gb - gp < len64);
-      // inclusive scan of heads -> slot of the locus every flagged candidate belongs to
-      uint64_t hb = __ballot(head);
-      __shared__ uint32_t w_heads[NT / 64];
-      if (lane == 0) w_heads[wv] = __popcll(hb);
-      __syncthreads();
-      uint32_t slot = sh_heads[par] + __popcll(hb & ((2ULL << lane) - 1ULL));
-      for (int q = 0; q < wv; q++) slot += w_heads[q];
-      if (flag) {
-        // the end of a locus is its last flagged seed; only the last flagged lane of a locus inside this wave
-        // touches memory (same-address atomics from every lane would serialise)
-        const uint64_t above = (lane == 63) ? 0ULL : (bal & ~((2ULL << lane) - 1ULL));
-        const bool last_here = above == 0 || ((hb >> (__ffsll((long long)above) - 1)) & 1ULL);
-        if (pass == 0) {
-          if (slot <= (uint32_t)L1_STAGE) {
-            if (head) { st_rfirst[slot - 1] = (int32_t)ra; st_rpart[slot - 1] = rb; }
-            if (last_here) atomicMax(&st_rlast[slot - 1], (int32_t)ra);
-          }
-        } else {
-          uint32_t li = sh_base + slot - 1;
-          if (head) { a.l_frag[li] = f; a.l_rfirst[li] = (int32_t)ra; a.l_rpart[li] = rb; }
-          if (last_here) atomicMax(&a.l_rlast[li], (int32_t)ra);
+    const uint32_t cnt0 = l1_scan_trips<NT>(a.ix, seeds, n, m, len, 0u, g_trip, [&](uint32_t slot, bool head, bool last_here, uint32_t ra, uint32_t rb) __attribute__((always_inline)) {
+      if (pass == 0) {
+        if (slot <= (uint32_t)L1_STAGE) {
+          if (head) { st_rfirst[slot - 1] = (int32_t)ra; st_rpart[slot - 1] = (int32_t)rb; }
+          if (last_here) atomicMax(&st_rlast[slot - 1], (int32_t)ra);
         }
+      } else {
+        const uint32_t li = sh_base + slot - 1;
+        if (head) { a.l_frag[li] = f; a.l_rfirst[li] = (int32_t)ra; a.l_rpart[li] = (int32_t)rb; }
+        if (last_here) atomicMax(&a.l_rlast[li], (int32_t)ra);
       }
-      if (tid == 0) {
-        // next trip's carry goes to the other parity: nobody reads it before the next trip's first barrier
-        uint32_t tot = sh_heads[par];
-        for (int q = 0; q < NT / 64; q++) tot += w_heads[q];
-        sh_heads[par ^ 1] = tot;
-        int hp = sh_has_prev[par];
-        uint64_t pg = sh_prev_g[par];
-        for (int q = NT / 64 - 1; q >= 0; q--) if (w_any[par][q]) { hp = 1; pg = w_last_g[par][q]; break; }
-        sh_has_prev[par ^ 1] = hp; sh_prev_g[par ^ 1] = pg;
-      }
-      par ^= 1;
-    }
-    __syncthreads();
+    });
     phase(3);
     if (pass == 0) {
-      const uint32_t cnt0 = sh_heads[par];
       if (cnt0 > 0 && cnt0 <= (uint32_t)L1_STAGE) {
         staged_epilogue(cnt0);
         return;
       }
       // more loci than the stage holds (or none): reserve, then a second pass writes them straight to HBM
-      if (tid == 0) {
-        uint32_t cnt = cnt0;
-        bool fits = true;
-        uint32_t base = cnt ? reserve_loci(a.loci, f, cnt, fits) : 0;
-        if (!fits) { atomicExch(&a.counters[CNT_LOCI_OVF], 1u); atomicOr(&a.pinfo[PI_FLAGS], (unsigned long long)SPEC_LOCI); cnt = 0; }
-        sh_base = base;
-        sh_gbase = cnt;   // reuse: number of loci (0 => skip)
-        a.f_loci_lo[f] = base; a.f_loci_n[f] = cnt;
-      }
+      if (tid == 0) { uint32_t base; sh_gbase = l1_reserve(a, f, cnt0, base); sh_base = base; }
       __syncthreads();
       if (sh_gbase == 0) return;
     }
@@ -1637,30 +1665,10 @@ __global__ __launch_bounds__(NT, (E == 16 ? 8 : 4)) void k_l1(L1Args a) {
   __threadfence_block();
   __syncthreads();
   const uint32_t nl = sh_gbase, base = sh_base;
-  for (uint32_t q = tid; q < nl; q += NT) {
-    const uint32_t li = base + q;
-    a.l_seq[li] = a.ix.rec_seq[a.l_rfirst[li]];
-    a.l_start[li] = max(0, a.ix.rec_wpos[a.l_rpart[li]] - len + 1);
-    a.l_end[li] = a.ix.rec_wpos[a.l_rlast[li]];
-  }
+  l1_locus_fields<NT>(a.ix, len, nl, a.l_rfirst + base, a.l_rpart + base, a.l_rlast + base, a.l_seq + base, a.l_start + base, a.l_end + base);
   __threadfence_block();
   __syncthreads();
-  if (wv == 0) {
-    // a group is numbered by the first locus it holds (see staged_epilogue): no counter of its own
-    uint32_t last_head = 0;
-    for (uint32_t i0 = 0; i0 < nl; i0 += 64) {
-      uint32_t i = i0 + lane;
-      bool gh = false;
-      if (i < nl) {
-        int g = a.ix.contig_genome[a.l_seq[base + i]];
-        gh = (i == 0) || g != a.ix.contig_genome[a.l_seq[base + i - 1]];
-      }
-      const uint64_t gb = __ballot(gh);
-      const uint64_t upto = gb & ((2ULL << lane) - 1ULL);
-      if (i < nl) a.l_group[base + i] = (int32_t)(base + (upto ? i0 + (uint32_t)(63 - __clzll(upto)) : last_head));
-      if (gb) last_head = i0 + (uint32_t)(63 - __clzll(gb));
-    }
-  }
+  if (wv == 0) l1_number_groups(a.ix, nl, a.l_seq + base, a.l_group + base, base);
 }
 
 // ----------------------------------------------------------------------------------------------------------
@@ -1668,22 +1676,22 @@ __global__ __launch_bounds__(NT, (E == 16 ? 8 : 4)) void k_l1(L1Args a) {
 // The hits are cut at CONTIG boundaries -- no candidate spans two contigs -- into chunks that fit LDS: every list
 // proposes the record `share` entries ahead of its cursor, the smallest proposal, rounded down to the start of its
 // contig, bounds the chunk (no list then contributes more than `share` = cap / s hits).  Every chunk goes through the
-// same gather, merge-path merge and candidate pass as in k_l1; the loci are collected in the fragment's HBM scratch
+// gather, the merge-path merge and the trip-by-trip candidate scan; the loci are collected in the fragment's HBM scratch
 // and moved to their final place at the end.  A fragment that cannot be cut (one contig alone holds more than a fair
 // share of some list) or whose loci outgrow the scratch is left to k_l1's HBM path (big_state = 0).
 // ----------------------------------------------------------------------------------------------------------
 constexpr int L1_BIG_THREADS = 512, L1_BIG_E = 32;
 __host__ __device__ inline size_t l1_big_lds_bytes(uint32_t seed_cap, int lut_smax) {
-  return ((size_t)seed_cap * 4 + 15) / 16 * 16 + ((size_t)lut_smax + 2) * 16;   // seeds, then off / qo / cur / nxt
+  // seeds, then off / qo / cur / nxt, then the coordinates of a trip of the candidate scan
+  return ((size_t)seed_cap * 4 + 15) / 16 * 16 + ((size_t)lut_smax + 2) * 16 + (size_t)L1_BIG_THREADS * 8;
 }
 
 __global__ __launch_bounds__(L1_BIG_THREADS) void k_l1_big(L1Args a) {
   constexpr int NT = L1_BIG_THREADS, E = L1_BIG_E;
   extern __shared__ __align__(16) unsigned char lds[];
-  __shared__ uint32_t sh_scan[NT / 64], sh_min[NT / 64], sh_first[NT / 64];
-  __shared__ uint32_t sh_run, sh_loci, sh_firstrem, sh_bound, sh_base, sh_cnt;
-  __shared__ int sh_has_prev, sh_fail, sh_last;
-  __shared__ uint64_t sh_prev_g;
+  __shared__ uint32_t sh_min[NT / 64], sh_first[NT / 64];
+  __shared__ uint32_t sh_loci, sh_firstrem, sh_bound, sh_base, sh_cnt;
+  __shared__ int sh_fail, sh_last;
   const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int s = a.q_size[f];
   const uint32_t n = a.n_seeds[f];
@@ -1696,6 +1704,7 @@ __global__ __launch_bounds__(L1_BIG_THREADS) void k_l1_big(L1Args a) {
   uint32_t *off = (uint32_t *)(lds + ((size_t)cap * 4 + 15) / 16 * 16);  // [s + 1] first hit of every list inside the chunk
   uint32_t *qo = off + a.lut_smax + 2;                                   // [s] where the chunk's part of every list starts in the index
   uint32_t *cur = qo + a.lut_smax + 2, *nxt = cur + a.lut_smax + 2;      // [s] cursor of every list, and its value after the chunk
+  uint64_t *g_trip = (uint64_t *)(nxt + a.lut_smax + 2);                 // [NT] (l1_scan_trips)
   // loci collected in the fragment's scratch as three record numbers each (first seed, its partner, last flagged seed: see
   // k_l1), arrays of LC entries
   const uint32_t LC = n32 / 5;
@@ -1736,148 +1745,28 @@ __global__ __launch_bounds__(L1_BIG_THREADS) void k_l1_big(L1Args a) {
     if (sh_fail || sh_firstrem == 0xFFFFFFFFu) break;                    // cannot cut / nothing left
     const uint32_t bound = sh_bound;
     // ---- the chunk's part of every list: [cur, nxt) with nxt = first entry >= bound ----
-    if (tid == 0) sh_run = 0;
-    __syncthreads();
-    for (int j0 = 0; j0 < s; j0 += NT) {
-      const int j = j0 + tid;
-      uint32_t cnt = 0;
-      if (j < s) {
-        const uint32_t c = qcnt[j], cj = cur[j];
-        uint32_t lo = cj, hi = bound == 0xFFFFFFFFu ? c : min(c, cj + share + 1);
-        if (bound != 0xFFFFFFFFu) { while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (a.ix.pos_ridx[qoff[j] + mid] < bound) lo = mid + 1; else hi = mid; } }
-        else lo = c;
-        nxt[j] = lo; cnt = lo - cj;
-        qo[j] = qoff[j] + cj;
-      }
-      uint32_t incl = cnt;
-      for (int d = 1; d < 64; d <<= 1) { uint32_t o = __shfl_up(incl, d); if (lane >= d) incl += o; }
-      if (lane == 63) sh_scan[wv] = incl;
-      __syncthreads();
-      uint32_t o = sh_run + incl - cnt;
-      for (int q = 0; q < wv; q++) o += sh_scan[q];
-      if (j < s) off[j] = o;
-      __syncthreads();
-      if (tid == 0) { uint32_t tot = 0; for (int q = 0; q < NT / 64; q++) tot += sh_scan[q]; sh_run += tot; }
-      __syncthreads();
-    }
-    const uint32_t nc = sh_run;                                          // hits of the chunk (<= cap by construction)
-    if (tid == 0) off[s] = nc;
-    __syncthreads();
+    const uint32_t nc = l1_list_offsets<NT>(s, off, qo, [&](int j, uint32_t &src) __attribute__((always_inline)) {
+      const uint32_t c = qcnt[j], cj = cur[j];
+      uint32_t lo = cj, hi = bound == 0xFFFFFFFFu ? c : min(c, cj + share + 1);
+      if (bound != 0xFFFFFFFFu) { while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (a.ix.pos_ridx[qoff[j] + mid] < bound) lo = mid + 1; else hi = mid; } }
+      else lo = c;
+      nxt[j] = lo;
+      src = qoff[j] + cj;
+      return lo - cj;
+    });                                                                  // hits of the chunk (<= cap by construction)
     if (nc > cap) { if (tid == 0) sh_fail = 1; __syncthreads(); break; }
-    // ---- gather + merge-path merge in LDS (as in k_l1) ----
-    auto locate = [&](uint32_t i) __attribute__((always_inline)) {
-      int lo = 0, hi = s - 1;
-      while (lo < hi) { const int mid = (lo + hi) >> 1; if (off[mid + 1] <= i) lo = mid + 1; else hi = mid; }
-      return lo;
-    };
-    for (uint32_t i = tid; i < nc; i += NT) { const int j = locate(i); A[i] = a.ix.pos_ridx[qo[j] + (i - off[j])]; }
-    __syncthreads();
-    {
-      const uint32_t per = ((nc + NT - 1) / NT) | 1u;                  // (odd, as in k_l1: no bank conflicts between the lanes' ranges)
-      const uint32_t o_lo = (uint32_t)tid * per;
-      for (int k = 0; (1 << k) < s; k++) {
-        uint32_t out[E + 1];
-        const int w2 = 2 << k;
-        const int npairs = (s + w2 - 1) / w2;
-        uint32_t A0 = 0, A1 = 0, A2 = 0, ia = 0, ib = 0;
-        int p = 0;
-        if (o_lo < nc) {
-          int lo = 0, hi = npairs - 1;
-          while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (off[min(mid * w2, s)] <= o_lo) lo = mid; else hi = mid - 1; }
-          p = lo;
-          A0 = off[min(p * w2, s)]; A1 = off[min(p * w2 + (w2 >> 1), s)]; A2 = off[min((p + 1) * w2, s)];
-          const uint32_t diag = o_lo - A0, lenA = A1 - A0, lenB = A2 - A1;
-          uint32_t l = diag > lenB ? diag - lenB : 0u, h = min(diag, lenA);
-          while (l < h) { const uint32_t mid = (l + h) >> 1; if (A[A0 + mid] < A[A1 + diag - 1 - mid]) l = mid + 1; else h = mid; }
-          ia = l; ib = diag - l;
-        }
-        uint32_t ka = (o_lo < nc && A0 + ia < A1) ? A[A0 + ia] : 0xFFFFFFFFu;
-        uint32_t kb = (o_lo < nc && A1 + ib < A2) ? A[A1 + ib] : 0xFFFFFFFFu;
-#pragma unroll
-        for (int e = 0; e < E + 1; e++) {
-          const uint32_t o = o_lo + e;
-          out[e] = 0;
-          if ((uint32_t)e < per && o < nc) {
-            while (o >= A2) {
-              p++;
-              A0 = off[min(p * w2, s)]; A1 = off[min(p * w2 + (w2 >> 1), s)]; A2 = off[min((p + 1) * w2, s)];
-              ia = 0; ib = 0;
-              ka = A0 < A1 ? A[A0] : 0xFFFFFFFFu;
-              kb = A1 < A2 ? A[A1] : 0xFFFFFFFFu;
-            }
-            const bool take_a = ka < kb;
-            out[e] = take_a ? ka : kb;
-            ia += take_a ? 1u : 0u; ib += take_a ? 0u : 1u;
-            const uint32_t nx = take_a ? A0 + ia : A1 + ib, end = take_a ? A1 : A2;
-            const uint32_t v = nx < end ? A[nx] : 0xFFFFFFFFu;
-            ka = take_a ? v : ka; kb = take_a ? kb : v;
-          }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int e = 0; e < E + 1; e++) {
-          const uint32_t o = o_lo + e;
-          if ((uint32_t)e < per && o < nc) A[o] = out[e];
-        }
-        __syncthreads();
-      }
-    }
-    // ---- candidates of the chunk (computeL1CandidateRegions on its sorted hits; nothing carries over a contig start) ----
+    l1_gather_lists<NT>(a.ix.pos_ridx, A, off, qo, s, nc);
+    l1_merge_lists<NT, E>(A, off, s, nc);
+    // ---- candidates of the chunk (nothing carries over a contig start); a locus beyond the scratch: the fragment is k_l1's ----
     if ((uint32_t)m <= nc) {
-      const uint32_t ncand = nc - (uint32_t)m + 1;
-      if (tid == 0) { sh_run = 0; sh_has_prev = 0; sh_prev_g = 0; }
-      __syncthreads();
-      const uint32_t loci0 = sh_loci;
-      const uint64_t len64 = (uint64_t)len;
-      for (uint32_t i0 = 0; i0 < ncand; i0 += NT) {
-        const uint32_t i = i0 + tid;
-        uint32_t ra = 0, rb = 0;
-        uint64_t ga = 0;
-        if (i < nc) { ra = A[i]; ga = gpos_of(a.ix, ra); }
-        uint64_t gb = (uint64_t)__shfl((long long)ga, (lane + m - 1) & 63);
-        if (i < ncand) rb = A[i + m - 1];
-        if (lane + m - 1 >= 64 && i < ncand) gb = gpos_of(a.ix, rb);
-        const bool flag = i < ncand && gb - ga < len64;
-        uint64_t bal = __ballot(flag);
-        __shared__ uint64_t w_last_g[NT / 64];
-        __shared__ int w_any[NT / 64];
-        uint64_t below = bal & ((1ULL << lane) - 1ULL);
-        int src_lane = below ? 63 - __clzll(below) : -1;
-        uint64_t gp = (uint64_t)__shfl((long long)ga, src_lane < 0 ? 0 : src_lane);
-        if (lane == 0) w_any[wv] = bal != 0;
-        if (bal && lane == 63 - __clzll(bal)) w_last_g[wv] = ga;
-        __syncthreads();
-        bool has_prev = src_lane >= 0;
-        if (!has_prev) {
-          for (int q = wv - 1; q >= 0 && !has_prev; q--) if (w_any[q]) { has_prev = true; gp = w_last_g[q]; }
-          if (!has_prev && sh_has_prev) { has_prev = true; gp = sh_prev_g; }
-        }
-        bool head = flag && !(has_prev && gb - gp < len64);
-        uint64_t hb = __ballot(head);
-        __shared__ uint32_t w_heads[NT / 64];
-        if (lane == 0) w_heads[wv] = __popcll(hb);
-        __syncthreads();
-        uint32_t slot = sh_run + __popcll(hb & ((2ULL << lane) - 1ULL));
-        for (int q = 0; q < wv; q++) slot += w_heads[q];
-        if (flag) {
-          const uint64_t above = (lane == 63) ? 0ULL : (bal & ~((2ULL << lane) - 1ULL));
-          const bool last_here = above == 0 || ((hb >> (__ffsll((long long)above) - 1)) & 1ULL);
-          const uint32_t li = loci0 + slot - 1;
-          if (li < LC) {
-            if (head) { S_rfirst[li] = (int32_t)ra; S_rpart[li] = (int32_t)rb; }
-            if (last_here) atomicMax(&S_rlast[li], (int32_t)ra);
-          } else sh_fail = 1;                                           // more loci than the scratch holds
-        }
-        __syncthreads();
-        if (tid == 0) {
-          uint32_t tot = 0;
-          for (int q = 0; q < NT / 64; q++) tot += w_heads[q];
-          sh_run += tot;
-          for (int q = NT / 64 - 1; q >= 0; q--) if (w_any[q]) { sh_has_prev = 1; sh_prev_g = w_last_g[q]; break; }
-        }
-        __syncthreads();
-      }
-      if (tid == 0) sh_loci = loci0 + sh_run;
+      const uint32_t loci = l1_scan_trips<NT>(a.ix, A, nc, m, len, sh_loci, g_trip, [&](uint32_t slot, bool head, bool last_here, uint32_t ra, uint32_t rb) __attribute__((always_inline)) {
+        const uint32_t li = slot - 1;
+        if (li < LC) {
+          if (head) { S_rfirst[li] = (int32_t)ra; S_rpart[li] = (int32_t)rb; }
+          if (last_here) atomicMax(&S_rlast[li], (int32_t)ra);
+        } else sh_fail = 1;                                             // more loci than the scratch holds
+      });
+      if (tid == 0) sh_loci = loci;
     }
     // ---- next chunk ----
     for (int j = tid; j < s; j += NT) cur[j] = nxt[j];
@@ -1886,14 +1775,10 @@ __global__ __launch_bounds__(L1_BIG_THREADS) void k_l1_big(L1Args a) {
   }
   __syncthreads();
   if (sh_fail) return;                                                   // big_state stays 0: k_l1 takes the fragment
-  // ---- the loci to their final place, then the groups (as in k_l1) ----
+  // ---- the loci to their final place, then the groups ----
   if (tid == 0) {
-    uint32_t cnt = sh_loci;
-    bool fits = true;
-    uint32_t base = cnt ? reserve_loci(a.loci, f, cnt, fits) : 0;
-    if (!fits) { atomicExch(&a.counters[CNT_LOCI_OVF], 1u); atomicOr(&a.pinfo[PI_FLAGS], (unsigned long long)SPEC_LOCI); cnt = 0; }
-    sh_base = base; sh_cnt = cnt;
-    a.f_loci_lo[f] = base; a.f_loci_n[f] = cnt;
+    uint32_t base;
+    sh_cnt = l1_reserve(a, f, sh_loci, base); sh_base = base;
     a.big_state[f] = 1;
     atomicAdd(&a.counters[CNT_OFF_FAST], 1u);                                       // (off the fast form: cut into LDS-sized chunks here)
   }
@@ -1902,28 +1787,12 @@ __global__ __launch_bounds__(L1_BIG_THREADS) void k_l1_big(L1Args a) {
   const uint32_t nl = sh_cnt, base = sh_base;
   for (uint32_t q = tid; q < nl; q += NT) {
     const uint32_t li = base + q;
-    const int32_t rf = S_rfirst[q], rp = S_rpart[q], rl = S_rlast[q];
-    a.l_frag[li] = f; a.l_seq[li] = a.ix.rec_seq[rf]; a.l_start[li] = max(0, a.ix.rec_wpos[rp] - len + 1); a.l_rfirst[li] = rf; a.l_rpart[li] = rp;
-    a.l_end[li] = a.ix.rec_wpos[rl]; a.l_rlast[li] = rl;
+    a.l_frag[li] = f; a.l_rfirst[li] = S_rfirst[q]; a.l_rpart[li] = S_rpart[q]; a.l_rlast[li] = S_rlast[q];
   }
+  l1_locus_fields<NT>(a.ix, len, nl, S_rfirst, S_rpart, S_rlast, a.l_seq + base, a.l_start + base, a.l_end + base);
   __threadfence_block();
   __syncthreads();
-  if (wv == 0) {
-    // a group is numbered by the first locus it holds (see staged_epilogue): no counter of its own
-    uint32_t last_head = 0;
-    for (uint32_t i0 = 0; i0 < nl; i0 += 64) {
-      uint32_t i = i0 + lane;
-      bool gh = false;
-      if (i < nl) {
-        int g = a.ix.contig_genome[a.l_seq[base + i]];
-        gh = (i == 0) || g != a.ix.contig_genome[a.l_seq[base + i - 1]];
-      }
-      const uint64_t gb = __ballot(gh);
-      const uint64_t upto = gb & ((2ULL << lane) - 1ULL);
-      if (i < nl) a.l_group[base + i] = (int32_t)(base + (upto ? i0 + (uint32_t)(63 - __clzll(upto)) : last_head));
-      if (gb) last_head = i0 + (uint32_t)(63 - __clzll(gb));
-    }
-  }
+  if (wv == 0) l1_number_groups(a.ix, nl, a.l_seq + base, a.l_group + base, base);
 }
 
 // ----------------------------------------------------------------------------------------------------------

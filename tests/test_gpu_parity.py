@@ -516,17 +516,25 @@ def test_chunked_l1_and_its_fallback(layout):
     assert hit_tuples(hits) == ohits
 
 
-def test_chunked_l1_more_loci_than_its_scratch():
-    # 70 % identity needs only two seed hits per candidate, and the references hold 26-base pieces of the query more than
-    # a fragment apart: 31 370 seed hits (values from the oracle) in 7 605 separate loci.  k_l1_big collects loci in a
-    # fifth of the fragment's scratch (32 768 words: 6 553 loci); they do not fit, so it hands the fragment back to k_l1,
-    # whose HBM path writes them straight to their place.
+# (references, pieces per reference) -> (seed hits of the fragment, L1 loci, L2 mappings): the oracle's values
+MANY_LOCI = {(100, 80): (31370, 7605, 5699), (12, 40): (1894, 480, 354), (30, 40): (5149, 1199, 891), (30, 80): (10355, 2389, 1780)}
+
+
+@pytest.mark.parametrize("n_refs,pieces", list(MANY_LOCI))
+def test_chunked_l1_more_loci_than_its_scratch(n_refs, pieces):
+    # 70 % identity needs only two seed hits per candidate (sketch size 1 195), and the references hold 26-base pieces of the
+    # query more than a fragment apart: every piece is a locus of its own, far more than the 128 loci k_l1 stages in LDS.
+    # 100 x 80: 31 370 seed hits in 7 605 loci.  k_l1_big collects loci in a fifth of the fragment's scratch (32 768 words:
+    #   6 553 loci); they do not fit, so it hands the fragment back to k_l1, whose HBM path writes them straight to their place.
+    # the other three: the hits fit the LDS seed slots of one size class each -- 1 894: k_l1<256,16>, 5 149: k_l1<512,16>,
+    #   10 355: k_l1<512,32> -- are sorted there, and the loci go from the saved ballots straight to HBM (the unstaged branch
+    #   and the tail behind it).
     g = syn.rng(972)
     q = syn.random_codes(g, 3000)
     refs = []
-    for _ in range(100):
-        c = syn.random_codes(g, 80 * 3100)
-        for j in range(80):
+    for _ in range(n_refs):
+        c = syn.random_codes(g, pieces * 3100)
+        for j in range(pieces):
             a = int(g.integers(0, 3000 - 26))
             c[j * 3100 + 100: j * 3100 + 126] = q[a: a + 26]
         refs.append([syn.to_ascii(c)])
@@ -535,9 +543,20 @@ def test_chunked_l1_more_loci_than_its_scratch():
     n = C.c_int64(0)
     arr = [np.empty(1 << 14, np.int32) for _ in range(4)]
     check(lib.fa_mapper_debug_l1(mapper._h, *[a.ctypes.data for a in arr], 1 << 14, C.byref(n)))
-    assert n.value == 7605
-    assert gpu_mappings(mapper) == oracle_mappings(det) and len(det["mappings"]["rseq"]) > 5000
+    n_hits, n_loci, n_maps = MANY_LOCI[(n_refs, pieces)]
+    assert n.value == n_loci
+    assert gpu_mappings(mapper) == oracle_mappings(det) and len(det["mappings"]["rseq"]) == n_maps
     assert hit_tuples(hits) == ohits
+    if (n_refs, pieces) != (100, 80):
+        # the fragment never left LDS: the seed slots of the accepted pass hold its hits (k_l1_big and the HBM road of k_l1 take
+        # fragments with MORE hits than slots only), and the mapper reserved no HBM scratch beyond what a fresh mapper's first
+        # attempt asks for -- nothing at 1 894 hits, which fit its 4 096 slots; with more hits that attempt is void, raises
+        # SPEC_SCRATCH for the fragment's padded size plus a quarter, and the repeat runs with slots that hold the fragment.
+        from test_gpu_history import spec
+        sp = spec(mapper)
+        n32 = 1 << (n_hits - 1).bit_length()
+        assert sp["f_seed_slots"] >= n_hits
+        assert sp["scratch_words"] == (0 if n_hits <= 4096 else n32 + n32 // 4)
 
 
 def test_chunked_l1_switched_off_matches():
