@@ -188,10 +188,29 @@ int fa_mapper_query(fa_mapper *m, const void *const *contigs, const int64_t *len
 /* fa_mapper_query that also returns the mappings behind its rows: one fa_hit_mapping per (reference genome, reference
  * bin) that computeCGI kept, in (ref_genome_id, bin) order -- the order in which the row's identities are summed.  A pair
  * holds at most one record per query fragment, so total_fragments x reference genomes is a safe map_cap.  A smaller
- * buffer is an error (FA_ERR_INVALID, nothing is written beyond map_cap; *n_maps still receives the full count). */
+ * buffer is an error (FA_ERR_INVALID, nothing is written beyond map_cap).  *n_maps then holds the records up to and
+ * including the pass that did not fit -- the count of the call only if the call is one pass;
+ * fa_mapper_query_mappings_stream with a null sink gives the count of the whole call. */
 int fa_mapper_query_mappings(fa_mapper *m, const void *const *contigs, const int64_t *lengths, int n_contigs, int char_width,
                              fa_cgi_row *rows, int64_t cap, int64_t *n_rows, int *n_short, uint64_t *total_fragments,
                              uint64_t *total_length, fa_hit_mapping *maps, int64_t map_cap, int64_t *n_maps);
+
+/* The mappings as a stream: the records leave the device in windows of at most S records (the mapping stage,
+ * fa_mapper_set_mapping_stage) through two buffers of S records in HBM and two in pinned host memory that belong to the
+ * workspace and do not grow with the table.  `sink` is called once per window, in order, from the calling thread, with
+ * every window of a pass full except its last; the records of consecutive passes follow one another in the order of the
+ * buffer entry points, and a pass without records calls nothing.  `records` is valid during the call only.  A non-zero
+ * return ends the query with FA_ERR_INVALID; the mapper stays usable.  sink == NULL counts: no record is written anywhere
+ * and *n_maps is the number of records of the whole call, over all its passes. */
+typedef int (*fa_mapping_sink)(void *user, const fa_hit_mapping *records, int64_t n);
+int fa_mapper_query_mappings_stream(fa_mapper *m, const void *const *contigs, const int64_t *lengths, int n_contigs, int char_width,
+                                    fa_cgi_row *rows, int64_t cap, int64_t *n_rows, int *n_short, uint64_t *total_fragments,
+                                    uint64_t *total_length, fa_mapping_sink sink, void *user, int64_t *n_maps);
+/* records per stage buffer (>= 1) of the mapping calls that follow; the default is FA_MAP_STAGE_MB (64) megabytes' worth */
+int fa_mapper_set_mapping_stage(fa_mapper *m, int64_t records);
+/* of the workspace the last mapping call used: records per stage buffer, bytes of its HBM stage, bytes of its pinned stage
+ * (both 0 while no call has sent records to the host), bytes of its winner table */
+int fa_mapper_mapping_memory(fa_mapper *m, int64_t out[4]);
 
 /* ---- host ingest: FASTA files ------------------------------------------ */
 /* Record reader with the semantics of pyfastani._fasta.Parser (src/pyfastani/_fasta.pyx:41-103): records exist only
@@ -259,15 +278,19 @@ int fa_mapper_query_genomes(fa_mapper *m, fa_genomes *g, int32_t first, int32_t 
 /* fa_mapper_query_genomes that also returns the mappings behind its rows, in (query_id, ref_genome_id, bin) order; the
  * records of consecutive passes follow one another.  A safe map_cap is the number of query fragments of the range
  * (fa_genomes_info) times the number of reference genomes; a smaller buffer is an error (FA_ERR_INVALID, nothing is
- * written beyond map_cap; *n_maps still receives the full count, so a caller that cannot afford the bound may size a
- * second call from a first).  With a host destination the library keeps a device buffer of map_cap records in the
- * workspace, and a winner table of 16 bytes per (query of a pass, reference bin); both stay allocated with the workspace's
- * other buffers: map a large table in sub-ranges.  If maps_device is non-zero, `maps` is a DEVICE pointer
- * with room for map_cap records, as `rows` is under rows_device.  The winner table and the compaction behind these records
- * exist only in calls through these two entry points: fa_mapper_query_genomes launches and allocates what it always did. */
+ * written beyond map_cap).  *n_maps then holds the records up to and including the pass that did not fit, which is the
+ * count of the call only if the call is one pass: fa_mapper_query_genomes_mappings_stream with a null sink counts the whole
+ * call, and with a sink needs no bound at all.  A host destination is filled through the workspace's mapping stage (see
+ * fa_mapper_query_mappings_stream): the library holds no device buffer of map_cap records.  The workspace keeps a winner
+ * table of 16 bytes per (query of a pass, reference bin).  If maps_device is non-zero, `maps` is a DEVICE pointer with room
+ * for map_cap records, as `rows` is under rows_device, and every pass writes its records straight into it.  The winner
+ * table, the stage and the compaction behind these records exist only in calls through the mapping entry points:
+ * fa_mapper_query_genomes launches and allocates what it always did. */
 int fa_mapper_query_genomes_mappings(fa_mapper *m, fa_genomes *g, int32_t first, int32_t count, fa_cgi_row *rows, int64_t cap,
                                      int64_t *n_rows, int rows_device, fa_hit_mapping *maps, int64_t map_cap,
                                      int64_t *n_maps, int maps_device);
+int fa_mapper_query_genomes_mappings_stream(fa_mapper *m, fa_genomes *g, int32_t first, int32_t count, fa_cgi_row *rows, int64_t cap,
+                                            int64_t *n_rows, int rows_device, fa_mapping_sink sink, void *user, int64_t *n_maps);
 
 /* stage-level introspection used by the parity tests */
 int fa_mapper_debug_mappings(fa_mapper *m, fa_mapping *out, int64_t cap, int64_t *n); /* L2 results of the last query call */

@@ -9,7 +9,8 @@ PyTorch nor numpy (``pyfastani_amd.sharding``, the multi-GPU layer, imports torc
 
 Beyond the reference's surface: resident query batches (``Mapper.upload_genomes`` -> `GenomeBatch`), FASTA ingest, and the
 fragment mappings behind the hits -- ``Mapper.query_draft_mappings`` / ``query_genome_mappings`` and
-``GenomeBatch.query_mappings`` return them as ``pyfastani_amd._batch.MAPPING_DTYPE`` records (numpy), and
+``GenomeBatch.query_mappings`` return them as ``pyfastani_amd._batch.MAPPING_DTYPE`` records (numpy),
+``GenomeBatch.iter_mappings`` yields them range by range for tables that should not stay in memory, and
 ``pyfastani_amd.outputs`` places them on the query's contigs and writes them as a table.
 """
 try:

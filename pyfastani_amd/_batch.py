@@ -1,5 +1,7 @@
 """Row layout of the hit table (``cgi::CGI_Results``, include/fastani/cgi/cgid_types.pxd:19-27 of the reference, plus the
 query index of a batch) as a numpy structured dtype, and the resident-batch class (implemented in the compiled binding)."""
+import os
+
 import numpy as np
 
 from ._fastani import GenomeBatch  # noqa: F401  (re-export)
@@ -17,3 +19,29 @@ MAPPING_DTYPE = np.dtype(
      ("sketch_size", "<i4"), ("conserved", "<i4"), ("identity", "<f4")]
 )
 assert MAPPING_DTYPE.itemsize == 32
+
+
+def pass_fragments():
+    """Fragments the library maps per pass (``FA_PASS_FRAGMENTS``, read when the library starts; 49152 by default)."""
+    return int(os.environ.get("FA_PASS_FRAGMENTS") or 48 * 1024)
+
+
+def plan_ranges(fragment_counts, pass_fragments, first=0, count=None):
+    """Genomes [first, first + count) cut into consecutive ranges ``[(first_genome, n_genomes), ...]`` the way the library
+    cuts a call into passes: a range takes genomes while their fragments stay within ``pass_fragments``, and always at least
+    one, so a single larger genome is a range of its own.  Every genome of the range is in exactly one of them, in order."""
+    counts = [int(x) for x in fragment_counts]
+    count = len(counts) - first if count is None else count
+    if first < 0 or count < 0 or first + count > len(counts):
+        raise ValueError("genome range out of bounds")
+    if pass_fragments < 1:
+        raise ValueError("pass_fragments must be positive")
+    out, g0, end = [], first, first + count
+    while g0 < end:
+        g1, total = g0 + 1, counts[g0]
+        while g1 < end and total + counts[g1] <= pass_fragments:
+            total += counts[g1]
+            g1 += 1
+        out.append((g0, g1 - g0))
+        g0 = g1
+    return out

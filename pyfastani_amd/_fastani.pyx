@@ -17,6 +17,7 @@ Nothing in this module needs PyTorch; the few methods that hand device tensors t
 cimport cython
 from cpython.unicode cimport PyUnicode_DATA, PyUnicode_KIND, PyUnicode_GET_LENGTH
 from libc.stdint cimport int32_t, int64_t, uint32_t, uint64_t, uintptr_t
+from libc.stdlib cimport free, realloc
 from libc.string cimport memcpy
 from libcpp.vector cimport vector
 
@@ -1166,36 +1167,31 @@ cdef class Mapper(_Parameterized):
         cdef vector[int64_t] lens
         cdef vector[hip.fa_cgi_row] rows
         cdef list keep = []
-        cdef int64_t n_rows = 0, n_maps = 0, map_cap = 0, n = 0
+        cdef int64_t n_rows = 0, n_maps = 0, n = 0
         cdef int n_short = 0, width, code
         cdef uint64_t total_fragments = 0, total_length = 0
-        cdef uintptr_t pm
-        cdef size_t j
+        cdef _MapRecords acc
         if threads < 0:
             raise ValueError(f"`threads` must be positive or null, got {threads!r}")   # :1050
         width = _borrow_all(contigs, ptrs, lens, keep)
         rows.resize(max(len(self._names), 1))
         n = <int64_t> ptrs.size()
-        for j in range(ptrs.size()):
-            map_cap += lens[j] // self._p.fragment_length                     # a pair keeps one mapping per query fragment at most
-        map_cap = max(1, map_cap * max(1, len(self._names)))
-        maps = np.empty(map_cap, dtype=_mapping_dtype())
-        pm = maps.ctypes.data
         if ptrs.empty():
             ptrs.push_back(NULL)
             lens.push_back(0)
+        acc.p = NULL
+        acc.n = acc.cap = 0
+        acc.failed = 0
         with nogil:
-            code = hip.fa_mapper_query_mappings(self._hm, ptrs.data(), lens.data(), <int> n, width, rows.data(), <int64_t> rows.size(),
-                                                &n_rows, &n_short, &total_fragments, &total_length,
-                                                <hip.fa_hit_mapping*> pm, map_cap, &n_maps)
-        _check(code)
+            code = hip.fa_mapper_query_mappings_stream(self._hm, ptrs.data(), lens.data(), <int> n, width, rows.data(), <int64_t> rows.size(),
+                                                       &n_rows, &n_short, &total_fragments, &total_length, _append_records, &acc, &n_maps)
+        maps = _take_records(&acc, code)
         for _ in range(n_short):
             warnings.warn("Mapper received a short sequence relative to parameters, mapping will not be computed.",
                           UserWarning)                                        # :1063-1069
         order = self._hit_order(rows.data(), n_rows, total_length)
         hits = [Hit(self._names[rows[i].ref_genome_id], rows[i].identity, rows[i].count_seq, rows[i].total_query_fragments)
                 for i in order]
-        maps = maps[:n_maps]
         # the records of a pair are consecutive (device order: reference genome, then bin): those of the hits, in the hits' order
         genome = maps["ref_genome_id"]
         parts = [maps[np.searchsorted(genome, rows[i].ref_genome_id, "left"):np.searchsorted(genome, rows[i].ref_genome_id, "right")]
@@ -1213,6 +1209,19 @@ cdef class Mapper(_Parameterized):
     def query_genome_mappings(self, object sequence, int threads=0):
         """`query_genome`, and the fragment mappings behind its hits (see `query_draft_mappings`)."""
         return self._query_draft_mappings((sequence,), threads)
+
+    def set_mapping_stage(self, int64_t records):
+        """Records per window in which the mapping calls that follow bring their records to the host
+        (``fa_mapper_set_mapping_stage``): the library holds two buffers of that many records in HBM and two in pinned host
+        memory per workspace, whatever the size of the table.  The default is ``FA_MAP_STAGE_MB`` (64) megabytes' worth."""
+        _check(hip.fa_mapper_set_mapping_stage(self._hm, records))
+
+    def mapping_memory(self):
+        """``(stage records, HBM stage bytes, pinned stage bytes, winner-table bytes)`` of the workspace that served the last
+        mapping call (``fa_mapper_mapping_memory``)."""
+        cdef int64_t out[4]
+        _check(hip.fa_mapper_mapping_memory(self._hm, out))
+        return (out[0], out[1], out[2], out[3])
 
     cdef list _query_draft(self, object contigs, int threads=0):
         # _fastani.pyx:1006-1136.  `threads` is validated for signature compatibility; fragment-level parallelism is the
@@ -1405,6 +1414,57 @@ def _mapping_dtype():
     return _MAPPING_DTYPE
 
 
+# The sink of the streaming entry points as the binding uses it: the windows are appended to one host array that grows by
+# half its size when a window does not fit, so the array never holds more than 1.5 times the records, and nothing is sized
+# by a bound on the table.
+cdef struct _MapRecords:
+    hip.fa_hit_mapping* p
+    int64_t n
+    int64_t cap
+    int failed
+
+
+cdef int _append_records(void* user, const hip.fa_hit_mapping* records, int64_t n) noexcept nogil:
+    cdef _MapRecords* a = <_MapRecords*> user
+    cdef int64_t cap
+    cdef void* q
+    if a.n + n > a.cap:
+        cap = max(a.n + n, a.cap + a.cap // 2)
+        q = realloc(a.p, <size_t> cap * sizeof(hip.fa_hit_mapping))
+        if q == NULL:
+            a.failed = 1
+            return 1
+        a.p = <hip.fa_hit_mapping*> q
+        a.cap = cap
+    memcpy(a.p + a.n, records, <size_t> n * sizeof(hip.fa_hit_mapping))
+    a.n += n
+    return 0
+
+
+cdef object _take_records(_MapRecords* a, int code):
+    # the records as a numpy array of their own (the C array is cut to its contents first, then copied and freed); raises
+    # what the call raised
+    import numpy as np
+    cdef uintptr_t pm
+    cdef void* q
+    try:
+        if a.failed:
+            raise MemoryError("no memory for the mapping records")
+        _check(code)
+        if a.n and a.n < a.cap:
+            q = realloc(a.p, <size_t> a.n * sizeof(hip.fa_hit_mapping))
+            if q != NULL:
+                a.p = <hip.fa_hit_mapping*> q
+        maps = np.empty(a.n, dtype=_mapping_dtype())
+        if a.n:
+            pm = maps.ctypes.data
+            memcpy(<void*> pm, a.p, <size_t> a.n * sizeof(hip.fa_hit_mapping))
+        return maps
+    finally:
+        free(a.p)
+        a.p = NULL
+
+
 cdef class GenomeBatch:
     """Many query genomes packed 2-bit in HBM, mapped without leaving the device: the many-to-many extension of the
     reference's one-query-at-a-time ``Mapper.query_draft`` (_fastani.pyx:1006-1136) -- the same per-genome semantics,
@@ -1559,26 +1619,41 @@ cdef class GenomeBatch:
         """``(rows, mappings)`` for genomes [first, first+count): the rows of `query_rows` (unfiltered) and the fragment
         mappings behind them (`pyfastani_amd._batch.MAPPING_DTYPE`), in (query, reference genome, position on the reference)
         order: a row's ``count_seq`` is the number of its records, its ``identity`` their float32 mean in that order.
-        The buffers are sized by the safe bound (query fragments of the range x reference genomes x 32 bytes, on the host and in
-        HBM): take the mappings of a large table range by range."""
+        The records arrive in windows of the mapper's mapping stage (`Mapper.set_mapping_stage`) and are collected in an
+        array that grows with their number.  For a table whose records should not stay in memory, see `iter_mappings`."""
         import numpy as np
         cdef int c = self.n_genomes - first if count is None else count
         cdef int64_t n_ref = max(1, len(self._mapper._names))
         cdef int64_t cap = max(1, <int64_t> c * n_ref)
         cdef int64_t n_rows = 0, n_maps = 0
         cdef int code
+        cdef _MapRecords acc
         if first < 0 or c < 0 or first + c > self.n_genomes:
             raise ValueError("genome range out of bounds")
-        # a pair keeps one mapping per query fragment at most
-        cdef int64_t map_cap = max(1, <int64_t> int(self.total_fragments[first:first + c].sum()) * n_ref)
         rows = np.zeros(cap, dtype=_row_dtype())
-        maps = np.empty(map_cap, dtype=_mapping_dtype())
-        cdef uintptr_t p = rows.ctypes.data, pm = maps.ctypes.data
+        cdef uintptr_t p = rows.ctypes.data
+        acc.p = NULL
+        acc.n = acc.cap = 0
+        acc.failed = 0
         with nogil:
-            code = hip.fa_mapper_query_genomes_mappings(self._mapper._hm, self._hg, first, c, <hip.fa_cgi_row*> p, cap, &n_rows, 0,
-                                                        <hip.fa_hit_mapping*> pm, map_cap, &n_maps, 0)
-        _check(code)
-        return rows[:n_rows], maps[:n_maps].copy()
+            code = hip.fa_mapper_query_genomes_mappings_stream(self._mapper._hm, self._hg, first, c, <hip.fa_cgi_row*> p, cap, &n_rows, 0,
+                                                               _append_records, &acc, &n_maps)
+        maps = _take_records(&acc, code)
+        return rows[:n_rows], maps
+
+    def iter_mappings(self, int first=0, count=None):
+        """`query_mappings` range by range: a generator of ``(first_genome, n_genomes, rows, mappings)`` over consecutive
+        genome ranges of [first, first+count), each of at most ``FA_PASS_FRAGMENTS`` fragments -- one pass of the device
+        pipeline -- or one genome that is larger (`pyfastani_amd._batch.plan_ranges`).  What it yields, concatenated, is what
+        `query_mappings` returns; taken range by range (`pyfastani_amd.outputs.write_mappings` with ``append=True``) a table
+        of any size passes through the memory of one range."""
+        from ._batch import plan_ranges, pass_fragments
+        cdef int c = self.n_genomes - first if count is None else count
+        if first < 0 or c < 0 or first + c > self.n_genomes:
+            raise ValueError("genome range out of bounds")
+        for lo, n in plan_ranges(self.total_fragments, pass_fragments(), first, c):
+            rows, maps = self.query_mappings(lo, n)
+            yield lo, n, rows, maps
 
     def query_rows_device(self, int first, int count, uintptr_t device_ptr, int64_t cap):
         """Same, but the rows are written to a caller-owned DEVICE buffer (e.g. a torch tensor feeding an RCCL all-gather).

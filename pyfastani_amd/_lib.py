@@ -64,6 +64,10 @@ class HitMapping(C.Structure):
     ]
 
 
+# fa_mapping_sink: int (*)(void *user, const fa_hit_mapping *records, int64_t n); the entry points take it as a plain pointer
+# (None = count only), so wrap a Python function as ``MAPPING_SINK(fn)`` and pass ``ctypes.cast(cb, ctypes.c_void_p)``
+MAPPING_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(HitMapping), C.c_int64)
+
 # every symbol of include/fastani_hip.h: (restype, argtypes)
 _vp, _i32, _i64, _u64, _u32, _f32, _f64 = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_uint32, C.c_float, C.c_double
 _P = C.POINTER
@@ -112,6 +116,11 @@ SIGNATURES = {
     "fa_genomes_info": (_i32, [_vp, _P(_i32), _vp, _vp, _vp]),
     "fa_mapper_query_genomes": (_i32, [_vp, _vp, _i32, _i32, _vp, _i64, _P(_i64), _i32]),
     "fa_mapper_query_genomes_mappings": (_i32, [_vp, _vp, _i32, _i32, _vp, _i64, _P(_i64), _i32, _vp, _i64, _P(_i64), _i32]),
+    "fa_mapper_query_mappings_stream": (_i32, [_vp, _P(_vp), _P(_i64), _i32, _i32, _vp, _i64, _P(_i64), _P(_i32), _P(_u64), _P(_u64),
+                                               _vp, _vp, _P(_i64)]),
+    "fa_mapper_query_genomes_mappings_stream": (_i32, [_vp, _vp, _i32, _i32, _vp, _i64, _P(_i64), _i32, _vp, _vp, _P(_i64)]),
+    "fa_mapper_set_mapping_stage": (_i32, [_vp, _i64]),
+    "fa_mapper_mapping_memory": (_i32, [_vp, _P(_i64)]),
     "fa_mapper_debug_mappings": (_i32, [_vp, _vp, _i64, _P(_i64)]),
     "fa_mapper_debug_l1": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _P(_i64)]),
     "fa_mapper_debug_query_sketch": (_i32, [_vp, _i64, _vp, _i32, _P(_i32)]),

@@ -457,6 +457,43 @@ enum TimingSlot : int { MS_STAGE = 0, MS_TOTAL = 4, MS_RECORDS, MS_LOCI, MS_EVEN
                         MS_L2_EVENTS = 16, MS_FUSED, MS_UNFUSED, MS_ORDERED, MS_L1_SORTED, MS_L1_MERGED, MS_L1_OFF_FAST, MS_TILE_LEN, MS_SLOTS };
 static_assert(MS_REPEATS == 9 && MS_ORDERED == 19 && MS_TILE_LEN == 23 && MS_SLOTS == 24, "the layout of fa_mapper_last_timings is ABI");
 
+// The way of the mapping records to the host: two buffers of `records` fa_hit_mapping in HBM, two in pinned host memory and an
+// event each.  k_map_write fills HBM buffer w & 1 with window w of a pass (fa_mapstream.h), an asynchronous copy takes it to
+// pinned buffer w & 1, and while the host consumes that the device works on window w + 1.  Their size is the mapper's
+// (fa_mapper_set_mapping_stage), not the table's; allocated by the first call that wants mappings on the host.
+struct MapStage {
+  fa_hit_mapping *dev[2] = {nullptr, nullptr}, *pin[2] = {nullptr, nullptr};
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  int64_t records = 0;
+  MapStage() = default;
+  MapStage(const MapStage &) = delete;
+  MapStage &operator=(const MapStage &) = delete;
+  ~MapStage() {
+    release();
+    for (auto &e : ev) if (e) (void)hipEventDestroy(e);
+  }
+  void release() {
+    for (int i = 0; i < 2; i++) {
+      if (dev[i]) (void)hipFree(dev[i]);
+      if (pin[i]) (void)hipHostFree(pin[i]);
+      dev[i] = pin[i] = nullptr;
+    }
+    records = 0;
+  }
+  // (the caller's stream is idle: a query call owns its workspace, and every call drains its windows before it returns)
+  void resize(int64_t n) {
+    if (n == records) return;
+    release();
+    for (int i = 0; i < 2; i++) {
+      FA_HIP(hipMalloc((void **)&dev[i], (size_t)n * sizeof(fa_hit_mapping)));
+      FA_HIP(hipHostMalloc((void **)&pin[i], (size_t)n * sizeof(fa_hit_mapping), hipHostMallocDefault));
+      if (!ev[i]) FA_HIP(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
+    }
+    records = n;
+  }
+  size_t bytes() const { return dev[0] ? 2 * (size_t)records * sizeof(fa_hit_mapping) : 0; }
+};
+
 // Everything one query call owns: its stream, every intermediate of the pipeline, its status block and timing events.
 struct Workspace {
   bool in_use = false;
@@ -482,11 +519,11 @@ struct Workspace {
   DevBuf<float> row_ident;
   DevBuf<fa_cgi_row> rows_dev;
   // only on workspaces that served a call for the mappings behind the rows (MapSink): the winner table parallel to `bins`,
-  // the chunk counts / offsets of the compaction, and the records of a call that wants them on the host
+  // the chunk counts / offsets of the compaction, and the stage through which the records reach the host
   DevBuf<MapWinner> winners;
   DevBuf<int32_t> map_chunk_count;
   DevBuf<int64_t> map_chunk_off;
-  DevBuf<fa_hit_mapping> maps_dev;
+  MapStage map_stage;
   // LUT pointers captured for the call (the mapper may publish larger tables while this call is in flight)
   const int32_t *lut_min_hits = nullptr, *lut_pass = nullptr;
   const float *lut_ident = nullptr;
@@ -554,6 +591,10 @@ struct fa_mapper {
   Workspace ws[NWS];
   std::condition_variable ws_free;
   int last_ws = 0;                    // workspace of the most recent call (stage getters, timings)
+  // records per stage buffer of the streamed mapping output (MapStage; fa_mapper_set_mapping_stage, default FA_MAP_STAGE_MB),
+  // and the workspace of the most recent call that asked for mappings (fa_mapper_mapping_memory)
+  int64_t map_stage = std::max<int64_t>(1, (int64_t)env_u64("FA_MAP_STAGE_MB", 64) * (1024 * 1024 / (int64_t)sizeof(fa_hit_mapping)));
+  int last_map_ws = -1;
   bool stage_events = false;          // fa_mapper_set_stage_events
   std::vector<DevBuf<int32_t>> retired_i32;   // LUT generations still referenced by calls in flight
   std::vector<DevBuf<float>> retired_f32;
@@ -861,13 +902,17 @@ struct L2Lds {
   size_t scan(int lanes, int bytes) const { return ((size_t)(slots + 1) * lanes * bytes + 15) / 16 * 16; }
 };
 
-// Where a call wants the mappings behind its rows (fa_mapper_query_mappings); `on` = false: it does not, and the pass
-// launches and allocates nothing for them.  Passes append: `base` records are in place.  `count` learns the number of
-// records, also when they do not fit.
+// Where a call wants the mappings behind its rows; `on` = false: it does not, and the pass launches and allocates nothing
+// for them.  Passes append: `base` records are in place.  `count` learns the number of records, also when they do not fit.
+// The destination is one of: `dev`, the caller's device buffer of `cap` records (one window per pass, straight into it);
+// `host`, the caller's host buffer of `cap` records, or `fn`, the caller's function -- both fed window by window through the
+// workspace's stage of `stage` records per window; or nothing (`count_only`: the passes count and write no record).
 struct MapSink {
-  bool on = false;
-  fa_hit_mapping *dev = nullptr;
-  int64_t cap = 0, base = 0;
+  bool on = false, count_only = false, bounded = false;     // bounded: a buffer of `cap` records, too small is an error
+  fa_hit_mapping *dev = nullptr, *host = nullptr;
+  fa_mapping_sink fn = nullptr;
+  void *user = nullptr;
+  int64_t cap = 0, base = 0, stage = 0;
   int64_t *count = nullptr;
 };
 
@@ -903,6 +948,7 @@ struct QueryPass {
   const IndexView ix;
   const int64_t npairs;
   int32_t map_chunks = 0;             // workgroups of the mapping compaction (maps.on)
+  MapEmitArgs map_args;               // of the pass's last launch_maps: the later windows are written with them (stream_maps)
   int64_t nmaps = 0;                  // result: records of the pass, whatever the room
   uint64_t items_max = 0;
   size_t qs_lds = 0;
@@ -1017,16 +1063,56 @@ struct QueryPass {
     return ra.emit != 0;
   }
   // the mappings of the whole pass, behind its last part and in front of launch_rows (whose last workgroup may hand the
-  // pass over): count per chunk, scan, write; the total goes into the status block and travels with the hand-over
+  // pass over): count per chunk, scan, and the first window of the records -- all of them for a device destination (what
+  // fits its room), the first stage's worth otherwise; the total goes into the status block and travels with the hand-over,
+  // and the host runs the windows behind the first once it knows it (stream_maps).  Rows that are formed again bring the
+  // count, the scan and the first window again.
   void launch_maps() {
-    MapEmitArgs ea;
+    MapEmitArgs &ea = map_args;
     ea.bins = w.bins.p; ea.winners = w.winners.p; ea.contig_genome = m.contig_genome.p;
     ea.n_bins = (int64_t)NQ * m.total_bins; ea.total_bins = std::max(m.total_bins, 1); ea.query_id_base = g0; ea.n_chunks = map_chunks;
     ea.chunk_count = w.map_chunk_count.p; ea.chunk_off = w.map_chunk_off.p;
-    ea.maps = maps.dev + maps.base; ea.cap = maps.cap - maps.base; ea.total_maps = &w.status.p->total_maps;
+    ea.maps = nullptr; ea.total_maps = &w.status.p->total_maps;
     if (map_chunks) hipLaunchKernelGGL(k_map_count, dim3(map_chunks), dim3(256), 0, st, ea);
     hipLaunchKernelGGL(k_map_scan, dim3(1), dim3(1024), 0, st, ea);
-    if (map_chunks) hipLaunchKernelGGL(k_map_write, dim3(map_chunks), dim3(256), 0, st, ea);
+    if (!map_chunks || maps.count_only) return;
+    int64_t hi = maps.stage;
+    ea.maps = w.map_stage.dev[0];
+    if (maps.dev) { ea.maps = maps.dev + maps.base; hi = std::max<int64_t>(0, maps.cap - maps.base); }
+    hipLaunchKernelGGL(k_map_write, dim3(map_chunks), dim3(256), 0, st, ea, (int64_t)0, hi);
+  }
+  // The records of the finished pass on their way to the host, window by window through the workspace's stage: window 0 lies
+  // in HBM stage 0 already (launch_maps); the write of window w + 1 and its copy run while the host consumes window w.  The
+  // stream is idle when this returns, so the next pass may reuse the bin and winner tables, and the next call the stage.
+  void stream_maps(MapSink &sink) {
+    MapStage &sg = w.map_stage;
+    const int64_t total = nmaps, n_win = map_windows(total, sink.stage);
+    auto issue = [&](int64_t wi) {
+      const MapWindow win = map_window(total, sink.stage, wi);
+      const int s = (int)(wi & 1);
+      if (wi > 0) {
+        MapEmitArgs ea = map_args;
+        ea.maps = sg.dev[s];
+        hipLaunchKernelGGL(k_map_write, dim3(map_chunks), dim3(256), 0, st, ea, win.lo, win.hi);
+      }
+      FA_HIP(hipMemcpyAsync(sg.pin[s], sg.dev[s], (size_t)(win.hi - win.lo) * sizeof(fa_hit_mapping), hipMemcpyDeviceToHost, st));
+      FA_HIP(hipEventRecord(sg.ev[s], st));
+    };
+    if (n_win) issue(0);
+    for (int64_t wi = 0; wi < n_win; wi++) {
+      if (wi + 1 < n_win) issue(wi + 1);
+      const MapWindow win = map_window(total, sink.stage, wi);
+      FA_HIP(hipEventSynchronize(sg.ev[wi & 1]));
+      if (sink.host) {
+        memcpy(sink.host + sink.base + win.lo, sg.pin[wi & 1], (size_t)(win.hi - win.lo) * sizeof(fa_hit_mapping));
+        continue;
+      }
+      const int rc = sink.fn(sink.user, sg.pin[wi & 1], win.hi - win.lo);
+      if (rc != 0) {
+        (void)hipStreamSynchronize(st);                          // (a window may be in flight: the stage is quiet before the call ends)
+        throw Error(FA_ERR_INVALID, "the mapping sink ended the call (it returned " + std::to_string(rc) + ")");
+      }
+    }
   }
   // what the stage launches of one part share (sized by size_part)
   struct Part {
@@ -1458,14 +1544,19 @@ static int64_t run_query_pass(fa_mapper &m, Workspace &w, const fa_genomes &g, i
   const int64_t nrows = pass.run();
   if (maps.on) {
     *maps.count = maps.base + pass.nmaps;
-    FA_REQUIRE(pass.nmaps <= maps.cap - maps.base, FA_ERR_INVALID, "mapping buffer too small");
+    if (maps.bounded) FA_REQUIRE(pass.nmaps <= maps.cap - maps.base, FA_ERR_INVALID, "mapping buffer too small");
+    if (maps.host || maps.fn) pass.stream_maps(maps);
     maps.base += pass.nmaps;
   }
   return nrows;
 }
 
-// The mappings a call asked for (fa_mapper_query_mappings): the destination as the caller gave it.
-struct MapRequest { fa_hit_mapping *maps; int64_t cap; int64_t *n_maps; bool device; };
+// The mappings a call asked for: the destination as the caller gave it -- a buffer of `cap` records on the device or the
+// host (fa_mapper_query_mappings), or, with `stream`, the function `fn` (fa_mapper_query_mappings_stream; null: count only).
+struct MapRequest {
+  fa_hit_mapping *maps; int64_t cap; int64_t *n_maps; bool device;
+  bool stream = false; fa_mapping_sink fn = nullptr; void *user = nullptr;
+};
 
 static int64_t run_query(fa_mapper &m, Workspace &w, const fa_genomes &g, int32_t first, int32_t count, fa_cgi_row *rows, int64_t cap, bool rows_device,
                          const MapRequest *want = nullptr) {
@@ -1485,9 +1576,17 @@ static int64_t run_query(fa_mapper &m, Workspace &w, const fa_genomes &g, int32_
   }
   MapSink sink;
   if (want) {
-    FA_REQUIRE(want->cap >= 0 && (want->maps || want->cap == 0) && want->n_maps, FA_ERR_INVALID, "mapping buffer missing");
-    sink.on = true; sink.cap = want->cap; sink.dev = want->maps; sink.count = want->n_maps;
-    if (!want->device) { w.maps_dev.ensure((size_t)std::max<int64_t>(want->cap, 1)); sink.dev = w.maps_dev.p; }
+    FA_REQUIRE(want->n_maps && (want->stream || (want->cap >= 0 && (want->maps || want->cap == 0))), FA_ERR_INVALID, "mapping buffer missing");
+    sink.on = true; sink.count = want->n_maps;
+    if (want->stream) { sink.fn = want->fn; sink.user = want->user; sink.count_only = !want->fn; }
+    else if (want->device) { sink.bounded = true; sink.dev = want->maps; sink.cap = want->cap; sink.count_only = !want->maps; }
+    else { sink.bounded = true; sink.host = want->maps; sink.cap = want->cap; sink.count_only = !want->maps; }   // (no buffer, no room: the count is all there is)
+    {
+      std::lock_guard<std::mutex> lock(m.mtx);
+      sink.stage = m.map_stage;
+      m.last_map_ws = (int)(&w - m.ws);
+    }
+    if (sink.host || sink.fn) w.map_stage.resize(sink.stage);
     *want->n_maps = 0;
   }
   int64_t nrows = 0;
@@ -1509,10 +1608,6 @@ static int64_t run_query(fa_mapper &m, Workspace &w, const fa_genomes &g, int32_
       FA_HIP(hipStreamSynchronize(w.stream));
     }
     memcpy(rows, w.pin_rows.p, bytes);
-  }
-  if (want && !want->device && sink.base) {
-    FA_HIP(hipMemcpyAsync(want->maps, w.maps_dev.p, (size_t)sink.base * sizeof(fa_hit_mapping), hipMemcpyDeviceToHost, w.stream));
-    FA_HIP(hipStreamSynchronize(w.stream));
   }
   return nrows;
 }
@@ -2329,6 +2424,34 @@ int fa_mapper_query_genomes_mappings(fa_mapper *m, fa_genomes *g, int32_t first,
     *n_rows = run_query(*m, *lease.w, *g, first, count, rows, cap, rows_device != 0, &want);
   });
 }
+int fa_mapper_query_genomes_mappings_stream(fa_mapper *m, fa_genomes *g, int32_t first, int32_t count, fa_cgi_row *rows, int64_t cap,
+                                            int64_t *n_rows, int rows_device, fa_mapping_sink sink, void *user, int64_t *n_maps) {
+  return guarded([&] {
+    WorkspaceLease lease(*m);
+    MapRequest want{nullptr, 0, n_maps, false};
+    want.stream = true; want.fn = sink; want.user = user;
+    *n_rows = run_query(*m, *lease.w, *g, first, count, rows, cap, rows_device != 0, &want);
+  });
+}
+int fa_mapper_set_mapping_stage(fa_mapper *m, int64_t records) {
+  return guarded([&] {
+    FA_REQUIRE(m && records >= 1, FA_ERR_INVALID, "the mapping stage holds at least one record");
+    std::lock_guard<std::mutex> lock(m->mtx);
+    m->map_stage = records;
+  });
+}
+int fa_mapper_mapping_memory(fa_mapper *m, int64_t out[4]) {
+  return guarded([&] {
+    FA_REQUIRE(m && out, FA_ERR_INVALID, "null mapper or destination");
+    std::lock_guard<std::mutex> lock(m->mtx);
+    for (int i = 0; i < 4; i++) out[i] = 0;
+    if (m->last_map_ws < 0) return;
+    const Workspace &w = m->ws[m->last_map_ws];
+    out[0] = w.map_stage.records;
+    out[1] = out[2] = (int64_t)w.map_stage.bytes();
+    out[3] = (int64_t)w.winners.block;
+  });
+}
 static int query_one(fa_mapper *m, const void *const *contigs, const int64_t *lengths, int n_contigs, int char_width,
                      fa_cgi_row *rows, int64_t cap, int64_t *n_rows, int *n_short, uint64_t *total_fragments,
                      uint64_t *total_length, const MapRequest *want) {
@@ -2359,6 +2482,13 @@ int fa_mapper_query_mappings(fa_mapper *m, const void *const *contigs, const int
                              fa_cgi_row *rows, int64_t cap, int64_t *n_rows, int *n_short, uint64_t *total_fragments,
                              uint64_t *total_length, fa_hit_mapping *maps, int64_t map_cap, int64_t *n_maps) {
   const MapRequest want{maps, map_cap, n_maps, false};
+  return query_one(m, contigs, lengths, n_contigs, char_width, rows, cap, n_rows, n_short, total_fragments, total_length, &want);
+}
+int fa_mapper_query_mappings_stream(fa_mapper *m, const void *const *contigs, const int64_t *lengths, int n_contigs, int char_width,
+                                    fa_cgi_row *rows, int64_t cap, int64_t *n_rows, int *n_short, uint64_t *total_fragments,
+                                    uint64_t *total_length, fa_mapping_sink sink, void *user, int64_t *n_maps) {
+  MapRequest want{nullptr, 0, n_maps, false};
+  want.stream = true; want.fn = sink; want.user = user;
   return query_one(m, contigs, lengths, n_contigs, char_width, rows, cap, n_rows, n_short, total_fragments, total_length, &want);
 }
 

@@ -21,6 +21,7 @@
 #pragma once
 
 #include "fa_common.h"
+#include "fa_mapstream.h"
 #include "fa_policy.h"
 #include "fa_sketch.hip.h"
 #include "fa_sketch_fast.hip.h"
@@ -2694,7 +2695,9 @@ __global__ void k_flag_nonzero(const int32_t *row_count, int64_t n, int32_t *fla
 // the (query, reference genome, bin) order in which k_cgi_rows adds the identities.  Count per chunk, scan the chunk
 // counts, write: a workgroup takes MAP_CHUNK consecutive bins, each of its waves 64 * MAP_ITERS of them in coalesced
 // 64-bin reads (issued together), and a bin's place among its wave's is the population count of the ballot below its lane.
-// A bin is mapped where the upper word of its key -- the identity -- is not zero, as in k_cgi_rows.
+// A bin is mapped where the upper word of its key -- the identity -- is not zero, as in k_cgi_rows.  The count and the scan
+// run once per pass; the write runs once per window of the records (fa_mapstream.h), so that a pass of any size leaves the
+// device through stage buffers of fixed size.
 // ----------------------------------------------------------------------------------------------------------
 constexpr int MAP_ITERS = 8, MAP_CHUNK = 256 * MAP_ITERS;
 struct MapEmitArgs {
@@ -2705,8 +2708,7 @@ struct MapEmitArgs {
   int32_t total_bins, query_id_base, n_chunks;
   int32_t *chunk_count;             // [n_chunks]
   int64_t *chunk_off;               // [n_chunks] records of the pass in front of the chunk
-  fa_hit_mapping *maps;             // the records of the pass start here
-  int64_t cap;                      // room from there on: nothing is written beyond it
+  fa_hit_mapping *maps;             // where the records of the window go (k_map_write): a stage buffer or the caller's
   int64_t *total_maps;              // in the status block: the full count, whatever the room
 };
 
@@ -2749,8 +2751,12 @@ __global__ __launch_bounds__(1024) void k_map_scan(MapEmitArgs a) {
   if (threadIdx.x == 1023) *a.total_maps = off;
 }
 
-__global__ __launch_bounds__(256) void k_map_write(MapEmitArgs a) {
+// writes the records of the pass whose places lie in the window [lo, hi) (fa_mapstream.h) to maps[place - lo]: one launch per
+// window.  A workgroup whose chunk holds no record of the window returns before it loads a key (uniform: the count and the
+// offset of the chunk are the same for all its threads)
+__global__ __launch_bounds__(256) void k_map_write(MapEmitArgs a, int64_t lo, int64_t hi) {
   __shared__ int sh_wave[4];
+  if (!map_chunk_in_window(a.chunk_off[blockIdx.x], a.chunk_count[blockIdx.x], lo, hi)) return;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int64_t base = (int64_t)blockIdx.x * MAP_CHUNK + wv * (64 * MAP_ITERS) + lane;
   unsigned long long key[MAP_ITERS];
@@ -2766,7 +2772,7 @@ __global__ __launch_bounds__(256) void k_map_write(MapEmitArgs a) {
     const unsigned long long mask = __ballot(mapped);
     const int64_t o = off + __popcll(mask & below);
     off += __popcll(mask);
-    if (!mapped || o >= a.cap) continue;
+    if (!mapped || o < lo || o >= hi) continue;
     const int64_t i = base + 64 * u;
     const MapWinner w = a.winners[i];
     fa_hit_mapping r;
@@ -2775,7 +2781,7 @@ __global__ __launch_bounds__(256) void k_map_write(MapEmitArgs a) {
     r.ref_genome_id = a.contig_genome[w.ref_seq_id];
     r.ref_seq_id = w.ref_seq_id; r.ref_start_pos = w.ref_start_pos; r.sketch_size = w.sketch_size; r.conserved = w.conserved;
     r.identity = __uint_as_float((uint32_t)(key[u] >> 32));
-    a.maps[o] = r;
+    a.maps[o - lo] = r;
   }
 }
 

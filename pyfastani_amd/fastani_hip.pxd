@@ -102,6 +102,13 @@ cdef extern from "fastani_hip.h" nogil:
     int fa_mapper_query_mappings(fa_mapper* m, const void* const* contigs, const int64_t* lengths, int n_contigs, int char_width,
                                  fa_cgi_row* rows, int64_t cap, int64_t* n_rows, int* n_short, uint64_t* total_fragments,
                                  uint64_t* total_length, fa_hit_mapping* maps, int64_t map_cap, int64_t* n_maps)
+    # the mappings window by window through a caller's function (NULL: count only); records valid during the call
+    ctypedef int (*fa_mapping_sink)(void* user, const fa_hit_mapping* records, int64_t n) noexcept nogil
+    int fa_mapper_query_mappings_stream(fa_mapper* m, const void* const* contigs, const int64_t* lengths, int n_contigs, int char_width,
+                                        fa_cgi_row* rows, int64_t cap, int64_t* n_rows, int* n_short, uint64_t* total_fragments,
+                                        uint64_t* total_length, fa_mapping_sink sink, void* user, int64_t* n_maps)
+    int fa_mapper_set_mapping_stage(fa_mapper* m, int64_t records)
+    int fa_mapper_mapping_memory(fa_mapper* m, int64_t* out)
 
     # resident batches (many-to-many extension)
     int fa_genomes_upload(fa_mapper* m, const void* const* contigs, const int64_t* lengths, const int32_t* contig_genome,
@@ -123,3 +130,6 @@ cdef extern from "fastani_hip.h" nogil:
     int fa_mapper_query_genomes_mappings(fa_mapper* m, fa_genomes* g, int32_t first, int32_t count, fa_cgi_row* rows, int64_t cap,
                                          int64_t* n_rows, int rows_device, fa_hit_mapping* maps, int64_t map_cap,
                                          int64_t* n_maps, int maps_device)
+    int fa_mapper_query_genomes_mappings_stream(fa_mapper* m, fa_genomes* g, int32_t first, int32_t count, fa_cgi_row* rows,
+                                                int64_t cap, int64_t* n_rows, int rows_device, fa_mapping_sink sink, void* user,
+                                                int64_t* n_maps)

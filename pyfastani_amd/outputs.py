@@ -71,18 +71,20 @@ MAPPING_COLUMNS = ("query", "query_fragment", "query_contig", "query_start", "qu
                    "reference_start", "identity", "conserved", "sketch_size")
 
 
-def write_mappings(path, query_names, reference_names, mappings, query_contig_lengths=None, fragment_length=None):
+def write_mappings(path, query_names, reference_names, mappings, query_contig_lengths=None, fragment_length=None, append=False):
     """The fragment mappings as a tab-separated table, one line per record in the order given, under a header line naming
     the columns (`MAPPING_COLUMNS`).  ``query_contig_lengths`` (one sequence of contig lengths per query genome, indexed by
     ``query_id``) and ``fragment_length`` place every fragment on its contig; without them the three query coordinate
     columns hold ``NA``.  ``reference_contig`` is the contig's number in the whole reference (``refSeqId``) and
     ``reference_start`` the position on that contig.  This is the project's own layout: upstream's visualisation file is
-    written by code outside the reference checkout, and no byte parity with it is claimed."""
+    written by code outside the reference checkout, and no byte parity with it is claimed.  ``append=True`` adds the lines
+    to an existing file and writes no header: the way to write a table range by range (`GenomeBatch.iter_mappings`)."""
     if (query_contig_lengths is None) != (fragment_length is None):
         raise ValueError("query_contig_lengths and fragment_length go together")
     coords = {}
-    with open(path, "w") as f:
-        f.write("\t".join(MAPPING_COLUMNS) + "\n")
+    with open(path, "a" if append else "w") as f:
+        if not append:
+            f.write("\t".join(MAPPING_COLUMNS) + "\n")
         for r in mappings:
             q, frag = int(r["query_id"]), int(r["query_seq_id"])
             where = ("NA", "NA", "NA")

@@ -16,7 +16,7 @@ import os
 
 import numpy as np
 
-from ._batch import ROW_DTYPE
+from ._batch import MAPPING_DTYPE, ROW_DTYPE
 
 
 def collectives_on(world_size):
@@ -73,6 +73,41 @@ def tensor_to_rows(t):
     return a.reshape(-1).view(ROW_DTYPE)
 
 
+def records_to_tensor(records, dtype, device="cpu"):
+    """Reinterpret structured records whose fields are all four bytes wide as an ``int32`` tensor [n, itemsize / 4]: float
+    fields travel as their bit patterns."""
+    import torch
+    records = np.ascontiguousarray(records, dtype=dtype)
+    flat = records.view(np.int32).reshape(-1, dtype.itemsize // 4).copy()
+    return torch.from_numpy(flat).to(device)
+
+
+def tensor_to_records(t, dtype):
+    a = np.ascontiguousarray(t.detach().cpu().numpy().astype(np.int32, copy=False))
+    return a.reshape(-1).view(dtype)
+
+
+def all_gather_records(local, group=None):
+    """All-gather a variable number of fixed-width records per rank: ``local`` is an int32 tensor [n_local, W] on the device
+    the process group communicates on, W the same on every rank.  The counts are gathered first and the payload is padded to
+    the largest count.  Returns an int32 tensor [sum n, W] holding the records of rank 0, 1, ... in order."""
+    import torch
+    import torch.distributed as dist
+
+    world = dist.get_world_size(group)
+    n_local, width = int(local.shape[0]), int(local.shape[1])
+    n = torch.tensor([n_local], dtype=torch.int64, device=local.device)
+    counts = [torch.zeros_like(n) for _ in range(world)]
+    dist.all_gather(counts, n, group=group)
+    counts = [int(c.item()) for c in counts]
+    n_max = max(max(counts), 1)
+    padded = torch.zeros((n_max, width), dtype=torch.int32, device=local.device)
+    padded[:n_local] = local
+    gathered = [torch.empty_like(padded) for _ in range(world)]
+    dist.all_gather(gathered, padded, group=group)
+    return torch.cat([g[:c] for g, c in zip(gathered, counts)], dim=0)
+
+
 def all_gather_rows(local, group=None, max_rows=None):
     """All-gather a variable number of rows per rank.
 
@@ -99,16 +134,7 @@ def all_gather_rows(local, group=None, max_rows=None):
         out = out.view(world, max_rows + 1, 5)
         counts = out[:, 0, 0].tolist()
         return torch.cat([out[r, 1: counts[r] + 1] for r in range(world)], dim=0)
-    n = torch.tensor([n_local], dtype=torch.int64, device=local.device)
-    counts = [torch.zeros_like(n) for _ in range(world)]
-    dist.all_gather(counts, n, group=group)
-    counts = [int(c.item()) for c in counts]
-    n_max = max(max(counts), 1)
-    padded = torch.zeros((n_max, 5), dtype=torch.int32, device=local.device)
-    padded[:n_local] = local
-    gathered = [torch.empty_like(padded) for _ in range(world)]
-    dist.all_gather(gathered, padded, group=group)
-    return torch.cat([g[:c] for g, c in zip(gathered, counts)], dim=0)
+    return all_gather_records(local, group=group)
 
 
 def remap_query_ids(rows, owned):
@@ -207,11 +233,15 @@ class ResidentHitTable:
         return flat.reshape(-1).view(ROW_DTYPE)
 
 
-def all_vs_all(mapper, genomes, rank, world_size, device=None, group=None, chunk=64, balance="fragments"):
+def all_vs_all(mapper, genomes, rank, world_size, device=None, group=None, chunk=64, balance="fragments", mappings=False):
     """Map this rank's share of ``genomes`` against ``mapper`` and return the hit table of ALL ranks.
 
     ``genomes`` is the full list (every rank holds the same list); only the owned ones are uploaded.  The share is
     balanced by fragment count (`shard_by_fragments`) unless ``balance="count"`` asks for the strided deal.
+
+    ``mappings=True``: returns ``(rows, mappings)`` -- beside the table the fragment mappings behind it
+    (`GenomeBatch.query_mappings`) of all ranks, with global query ids, in (query_id, ref_genome_id, position on the
+    reference) order.  The records of a query come from one rank and in order, so a stable sort by query puts them in place.
     """
     import torch
 
@@ -222,18 +252,29 @@ def all_vs_all(mapper, genomes, rank, world_size, device=None, group=None, chunk
     else:
         owned = shard_indices(len(genomes), rank, world_size)
     batch = mapper.upload_genomes([genomes[i] for i in owned])
-    parts = []
+    parts, map_parts = [], []
     for first in range(0, len(owned), chunk):
-        parts.append(batch.query_rows(first, min(chunk, len(owned) - first)))
+        if mappings:
+            r, m = batch.query_mappings(first, min(chunk, len(owned) - first))
+            parts.append(r)
+            map_parts.append(m)
+        else:
+            parts.append(batch.query_rows(first, min(chunk, len(owned) - first)))
     rows = np.concatenate(parts) if parts else np.zeros(0, ROW_DTYPE)
     rows = remap_query_ids(rows, owned)
+    maps = None
+    if mappings:
+        maps = remap_query_ids(np.concatenate(map_parts) if map_parts else np.zeros(0, MAPPING_DTYPE), owned)
     if not collectives_on(world_size):
-        return rows
+        return (rows, maps) if mappings else rows
     dev = device if device is not None else ("cuda" if torch.cuda.is_available() else "cpu")
     gathered = all_gather_rows(rows_to_tensor(rows, dev), group=group)
     out = tensor_to_rows(gathered)
     order = np.lexsort((out["ref_genome_id"], out["query_id"]))
-    return out[order]
+    if not mappings:
+        return out[order]
+    maps = tensor_to_records(all_gather_records(records_to_tensor(maps, MAPPING_DTYPE, dev), group=group), MAPPING_DTYPE)
+    return out[order], maps[np.argsort(maps["query_id"], kind="stable")]
 
 
 # ------------------------------------------------------------------------------------------------------------
