@@ -87,6 +87,15 @@ typedef struct fa_hit_mapping {
   float identity;           /* nucIdentity, the value the row averages */
 } fa_hit_mapping;           /* 32 bytes */
 
+/* The readings of FastANI's arithmetic that the reference's sources leave open and that move results:
+ * a setting of the mapper, not of the index -- one index can be queried under several.  fa_rules_default gives the values
+ * every mapper starts with. */
+typedef struct fa_rules {
+  float   l2_confidence;   /* 0.9f  | any value strictly inside (0, 1): the doL2Mapping site only */
+  int32_t slide_end;       /* 0 = rangeEndPos + countMinimizerWindows | 1 = rangeEndPos + fragment_length */
+  int32_t cgi_ties;        /* 0 = smallest (refSeqId, refStartPos) / querySeqId | 1 = largest */
+} fa_rules;
+
 /* ---- library ---------------------------------------------------------- */
 const char *fa_last_error(void);
 int fa_version(void);
@@ -107,6 +116,9 @@ int fa_recommended_window_size(double p_value, int k, int alphabet_size, float i
 int fa_estimate_minimum_hits_relaxed(int sketch_size, int k, float identity, int *hits);
 /* nucIdentity / nucIdentityUpperBound of skch::Map::doL2Mapping for (shared, sketch_size) */
 int fa_mapping_identity(int shared, int sketch_size, int k, float *identity, float *upper_bound);
+/* host, no device: smallest shared count of a sketch of size s whose upper-bound identity passes, at interval ci
+ * (the filter of skch::Map::doL2Mapping; sketch_size + 1 when no count passes) */
+int fa_pass_threshold(int sketch_size, int k, float identity, float ci, int *min_shared);
 /* skch::CommonFunc::getHash, include/fastani/map/common_func.pxd:12 (host twin of the device function) */
 uint32_t fa_hash(const void *kmer, int length);
 
@@ -208,6 +220,14 @@ int fa_mapper_query_mappings_stream(fa_mapper *m, const void *const *contigs, co
                                     uint64_t *total_length, fa_mapping_sink sink, void *user, int64_t *n_maps);
 /* records per stage buffer (>= 1) of the mapping calls that follow; the default is FA_MAP_STAGE_MB (64) megabytes' worth */
 int fa_mapper_set_mapping_stage(fa_mapper *m, int64_t records);
+/* The rules of the mapper (fa_rules above).  fa_mapper_set_rules: FA_ERR_INVALID for a null pointer or a value outside the
+ * ones listed, and the mapper is unchanged.  Takes the mapper lock; a query call follows the rules that were in force when it
+ * started, the calls that start afterwards the new ones; setting the rules the mapper already has does nothing.  The index
+ * does not depend on the rules.  l2_confidence reaches the percentage_identity filter of doL2Mapping only:
+ * estimateMinimumHitsRelaxed and fa_recommended_window_size stay at 0.9. */
+int fa_rules_default(fa_rules *out);
+int fa_mapper_set_rules(fa_mapper *m, const fa_rules *r);
+int fa_mapper_get_rules(fa_mapper *m, fa_rules *out);
 /* of the workspace the last mapping call used: records per stage buffer, bytes of its HBM stage, bytes of its pinned stage
  * (both 0 while no call has sent records to the host), bytes of its winner table */
 int fa_mapper_mapping_memory(fa_mapper *m, int64_t out[4]);
@@ -293,7 +313,7 @@ int fa_mapper_query_genomes_mappings_stream(fa_mapper *m, fa_genomes *g, int32_t
                                             int64_t *n_rows, int rows_device, fa_mapping_sink sink, void *user, int64_t *n_maps);
 
 /* stage-level introspection used by the parity tests */
-int fa_mapper_debug_mappings(fa_mapper *m, fa_mapping *out, int64_t cap, int64_t *n); /* L2 results of the last query call */
+int fa_mapper_debug_mappings(fa_mapper *m, fa_mapping *out, int64_t cap, int64_t *n); /* L2 results of the last query call, under its rules */
 int fa_mapper_debug_l1(fa_mapper *m, int32_t *frag, int32_t *seq_id, int32_t *range_start, int32_t *range_end,
                        int64_t cap, int64_t *n);
 int fa_mapper_debug_query_sketch(fa_mapper *m, int64_t fragment, uint32_t *hashes, int32_t cap, int32_t *sketch_size);

@@ -11,7 +11,8 @@ Beyond the reference's surface: resident query batches (``Mapper.upload_genomes`
 fragment mappings behind the hits -- ``Mapper.query_draft_mappings`` / ``query_genome_mappings`` and
 ``GenomeBatch.query_mappings`` return them as ``pyfastani_amd._batch.MAPPING_DTYPE`` records (numpy),
 ``GenomeBatch.iter_mappings`` yields them range by range for tables that should not stay in memory, and
-``pyfastani_amd.outputs`` places them on the query's contigs and writes them as a table.
+``pyfastani_amd.outputs`` places them on the query's contigs and writes them as a table.  `Rules` selects, per mapper
+(``Sketch(rules=...)``, ``Mapper.rules``), among the readings of three rules the reference's sources leave open.
 """
 try:
     from ._fastani import (
@@ -24,9 +25,11 @@ try:
         PackedGenomes,
         Minimizers,
         Position,
+        Rules,
         Sketch,
         device_count,
         device_trim,
+        pass_threshold,
         set_device,
     )
 except ImportError as exc:  # the compiled binding or libfastani_hip.so is missing: there is nothing to fall back to
@@ -37,7 +40,7 @@ except ImportError as exc:  # the compiled binding or libfastani_hip.so is missi
     ) from exc
 
 __all__ = [
-    "MAX_KMER_SIZE", "Hit", "Mapper", "MinimizerIndex", "MinimizerInfo", "Minimizers", "Position", "Sketch",
-    "GenomeBatch", "PackedGenomes", "device_count", "device_trim", "set_device",
+    "MAX_KMER_SIZE", "Hit", "Mapper", "MinimizerIndex", "MinimizerInfo", "Minimizers", "Position", "Rules", "Sketch",
+    "GenomeBatch", "PackedGenomes", "device_count", "device_trim", "pass_threshold", "set_device",
 ]
 __version__ = "0.2.0"

@@ -367,6 +367,106 @@ cdef class MinimizerIndex:
         return (MinimizerIndex, (), None, None, self.items())
 
 
+# --- Rules: the open readings of FastANI's arithmetic (no reference counterpart; DESIGN.md section 2) ---------------------
+_SLIDE_ENDS = ("windows", "fragment")
+_CGI_TIES = ("smallest", "largest")
+
+
+cdef double _f32(double v):
+    return <double> <float> v
+
+
+class Rules:
+    """The three readings of FastANI's arithmetic that the reference's sources leave open and that move results.
+
+    ``l2_confidence``: the confidence interval of the identity filter of ``doL2Mapping`` (0.9; 0.75 is the other
+    reading), any value strictly inside (0, 1), held in single precision by the engine.  ``slide_end``: the L2 slide
+    ends ``"windows"`` (the minimizer windows of a fragment) or ``"fragment"`` (a whole fragment length) behind the
+    range of the candidate region.  ``cgi_ties``: among mappings of equal identity the core-genome step keeps the
+    ``"smallest"`` or the ``"largest"`` (reference contig, position) per query fragment and query fragment per bin.
+
+    Immutable and hashable.  The rules are a setting of a `Mapper` (``Sketch(rules=...)``, ``Mapper.rules``); the index
+    does not depend on them."""
+    __slots__ = ("l2_confidence", "slide_end", "cgi_ties")
+
+    def __init__(self, l2_confidence=0.9, slide_end="windows", cgi_ties="smallest"):
+        l2_confidence = _as_float(l2_confidence, "l2_confidence")
+        if not (0.0 < l2_confidence < 1.0) or not (0.0 < _f32(l2_confidence) < 1.0):
+            raise ValueError(f"l2_confidence must lie strictly between 0 and 1, got {l2_confidence!r}")
+        if slide_end not in _SLIDE_ENDS:
+            raise ValueError(f"slide_end must be one of {_SLIDE_ENDS!r}, got {slide_end!r}")
+        if cgi_ties not in _CGI_TIES:
+            raise ValueError(f"cgi_ties must be one of {_CGI_TIES!r}, got {cgi_ties!r}")
+        object.__setattr__(self, "l2_confidence", l2_confidence)
+        object.__setattr__(self, "slide_end", str(slide_end))
+        object.__setattr__(self, "cgi_ties", str(cgi_ties))
+
+    def __setattr__(self, name, value):
+        raise AttributeError("Rules is immutable")
+
+    def __delattr__(self, name):
+        raise AttributeError("Rules is immutable")
+
+    def _key(self):
+        return (_f32(self.l2_confidence), self.slide_end, self.cgi_ties)
+
+    def __eq__(self, other):
+        if not isinstance(other, Rules):
+            return NotImplemented
+        return self._key() == other._key()
+
+    def __ne__(self, other):
+        if not isinstance(other, Rules):
+            return NotImplemented
+        return self._key() != other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return f"Rules(l2_confidence={self.l2_confidence!r}, slide_end={self.slide_end!r}, cgi_ties={self.cgi_ties!r})"
+
+    def __reduce__(self):
+        return (Rules, (self.l2_confidence, self.slide_end, self.cgi_ties))
+
+    def _asdict(self):
+        return {"l2_confidence": self.l2_confidence, "slide_end": self.slide_end, "cgi_ties": self.cgi_ties}
+
+    @property
+    def is_default(self):
+        """`bool`: whether these are the rules every mapper starts with."""
+        return self == _DEFAULT_RULES
+
+
+_DEFAULT_RULES = Rules()
+
+
+cdef object _coerce_rules(object rules):
+    """``None`` (the default), a `Rules`, or the mapping a pickled state carries."""
+    if rules is None:
+        return _DEFAULT_RULES
+    if isinstance(rules, Rules):
+        return rules
+    if isinstance(rules, dict):
+        return Rules(**rules)
+    raise TypeError(f"rules must be a Rules object or None, got {type(rules).__name__}")
+
+
+cdef int _rules_to_c(object rules, hip.fa_rules* out) except -1:
+    out.l2_confidence = <float> <double> rules.l2_confidence
+    out.slide_end = _SLIDE_ENDS.index(rules.slide_end)
+    out.cgi_ties = _CGI_TIES.index(rules.cgi_ties)
+    return 0
+
+
+def pass_threshold(int sketch_size, int k=16, float percentage_identity=80.0, float confidence=0.9):
+    """Smallest shared count of a sketch of ``sketch_size`` minimizers whose upper-bound identity at the given interval reaches
+    ``percentage_identity``: the filter `Rules.l2_confidence` moves (host arithmetic, ``fa_pass_threshold``)."""
+    cdef int c = 0
+    _check(hip.fa_pass_threshold(sketch_size, k, percentage_identity, confidence, &c))
+    return c
+
+
 # --- _Parameterized (_fastani.pyx:364-446) --------------------------------------------------------------------------
 cdef class _Parameterized:
     cdef hip.fa_params _p
@@ -540,17 +640,20 @@ cdef class Sketch(_Parameterized):
     cdef int64_t _version
     cdef readonly object minimizers
     cdef readonly object _lock
+    cdef object _rules                      # handed to the mapper by `index` (the sketch itself does not depend on them)
 
     def __cinit__(self):
         self._hs = NULL
         self._names = []
         self._version = 0
+        self._rules = _DEFAULT_RULES
         self._lock = threading.Lock()
         self.minimizers = Minimizers(self)
 
     def __init__(self, *, k=16, fragment_length=3000, minimum_fraction=0.2, p_value=1e-03, percentage_identity=80.0,
-                 reference_size=5_000_000, protein=False):
+                 reference_size=5_000_000, protein=False, rules=None):
         cdef int w = 0
+        self._rules = _coerce_rules(rules)
         k = _as_uint(k, "k", 32)
         fragment_length = _as_uint(fragment_length, "fragment_length", 32)
         minimum_fraction = _as_float(minimum_fraction, "minimum_fraction")
@@ -604,6 +707,11 @@ cdef class Sketch(_Parameterized):
         self._release()                                                      # :569-570
 
     @property
+    def rules(self):
+        """`Rules`: the readings of the open rules that mappers made by `index` start with."""
+        return self._rules
+
+    @property
     def _h(self):
         """Address of the ``fa_sketch`` handle (for the ctypes debug entry points of ``pyfastani_amd._lib``)."""
         return <uintptr_t> self._hs
@@ -632,17 +740,21 @@ cdef class Sketch(_Parameterized):
     # -- pickling (_fastani.pyx:572-591) -----------------------------------------------------------------------
     def __getstate__(self):
         lengths, sbf, counter = self._host_state()
-        return {
+        state = {
             "parameters": self._params_getstate(),
             "counter": counter,
             "lengths": lengths.tolist(),
             "names": list(self._names),
             "sketch": {"sequencesByFileInfo": sbf.tolist(), "minimizers": self.minimizers.__getstate__()},
         }
+        if not self._rules.is_default:        # (default rules: exactly the reference's state)
+            state["rules"] = self._rules._asdict()
+        return state
 
     def __setstate__(self, state):
         import numpy as np
         self._params_setstate(state["parameters"])
+        self._rules = _coerce_rules(state.get("rules"))
         self._release()
         self._version = 0
         self._names = list(state["names"])
@@ -955,6 +1067,7 @@ cdef class Sketch(_Parameterized):
             _check(code)
             mapper._p = self._p
             mapper._threads = self._threads
+            mapper._set_rules(self._rules)
             mapper._names = self._names.copy()
             self._names.clear()
             self._version += 1
@@ -976,10 +1089,12 @@ cdef class Mapper(_Parameterized):
     cdef bint _have_lengths
     cdef int64_t _version                  # bumped by __setstate__: the `Minimizers` view caches per (object, version)
     cdef readonly object minimizers
+    cdef object _rules
 
     def __cinit__(self):
         self._hm = NULL
         self._names = []
+        self._rules = _DEFAULT_RULES
         self._have_lengths = False
         self._version = 0
         self.minimizers = Minimizers(self)
@@ -999,6 +1114,28 @@ cdef class Mapper(_Parameterized):
 
     def _state_token(self):
         return ("mapper", id(self), self._version)
+
+    cdef int _set_rules(self, object rules) except -1:
+        cdef hip.fa_rules r
+        rules = _coerce_rules(rules)
+        _rules_to_c(rules, &r)
+        _check(hip.fa_mapper_set_rules(self._hm, &r))
+        self._rules = rules
+        return 0
+
+    @property
+    def rules(self):
+        """`Rules`: the readings of the open rules this mapper follows.  Assignable: a query call follows the rules that were
+        in force when it started, every entry point (`query_draft`, the mapping calls, `GenomeBatch`, the FASTA stream,
+        ``sharding``) the mapper's; the index is not rebuilt."""
+        cdef hip.fa_rules r
+        _check(hip.fa_mapper_get_rules(self._hm, &r))
+        held = Rules(r.l2_confidence, _SLIDE_ENDS[r.slide_end], _CGI_TIES[r.cgi_ties])
+        return self._rules if held == self._rules else held
+
+    @rules.setter
+    def rules(self, value):
+        self._set_rules(value)
 
     def _num_minimizers(self):
         cdef int64_t n = 0
@@ -1047,12 +1184,16 @@ cdef class Mapper(_Parameterized):
     # -- pickling (_fastani.pyx:842-865): the index is rebuilt on load ------------------------------------------
     def __getstate__(self):
         lengths, sbf = self._state_arrays()
-        return {
+        state = {
             "parameters": self._params_getstate(),
             "lengths": lengths.tolist(),
             "names": list(self._names),
             "sketch": {"sequencesByFileInfo": sbf.tolist(), "minimizers": self.minimizers.__getstate__()},
         }
+        rules = self.rules
+        if not rules.is_default:
+            state["rules"] = rules._asdict()
+        return state
 
     def __setstate__(self, state):
         cdef Sketch sk = Sketch.__new__(Sketch)
@@ -1063,6 +1204,7 @@ cdef class Mapper(_Parameterized):
             "lengths": state["lengths"],
             "names": state["names"],
             "sketch": state["sketch"],
+            "rules": state.get("rules"),
         })
         cdef Mapper other = sk.index()
         if self._hm != NULL:
@@ -1072,6 +1214,7 @@ cdef class Mapper(_Parameterized):
         self._p = other._p
         self._threads = other._threads
         self._names = other._names
+        self._rules = other._rules
         self._have_lengths = False
         self._version += 1
 

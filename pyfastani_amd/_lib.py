@@ -28,6 +28,15 @@ class Params(C.Structure):
     ]
 
 
+class RulesStruct(C.Structure):
+    # fa_rules: the open readings of the arithmetic a mapper follows (pyfastani_amd.Rules is the Python face of it)
+    _fields_ = [
+        ("l2_confidence", C.c_float),
+        ("slide_end", C.c_int32),
+        ("cgi_ties", C.c_int32),
+    ]
+
+
 class CgiRow(C.Structure):
     # cgi::CGI_Results, include/fastani/cgi/cgid_types.pxd:19-27
     _fields_ = [
@@ -80,6 +89,7 @@ SIGNATURES = {
     "fa_recommended_window_size": (_i32, [_f64, _i32, _i32, _f32, _i32, _u64, _P(_i32)]),
     "fa_estimate_minimum_hits_relaxed": (_i32, [_i32, _i32, _f32, _P(_i32)]),
     "fa_mapping_identity": (_i32, [_i32, _i32, _i32, _P(_f32), _P(_f32)]),
+    "fa_pass_threshold": (_i32, [_i32, _i32, _f32, _f32, _P(_i32)]),
     "fa_hash": (_u32, [C.c_char_p, _i32]),
     "fa_sketch_new": (_i32, [_P(Params), _P(_vp)]),
     "fa_sketch_free": (None, [_vp]),
@@ -120,6 +130,9 @@ SIGNATURES = {
                                                _vp, _vp, _P(_i64)]),
     "fa_mapper_query_genomes_mappings_stream": (_i32, [_vp, _vp, _i32, _i32, _vp, _i64, _P(_i64), _i32, _vp, _vp, _P(_i64)]),
     "fa_mapper_set_mapping_stage": (_i32, [_vp, _i64]),
+    "fa_rules_default": (_i32, [_P(RulesStruct)]),
+    "fa_mapper_set_rules": (_i32, [_vp, _P(RulesStruct)]),
+    "fa_mapper_get_rules": (_i32, [_vp, _P(RulesStruct)]),
     "fa_mapper_mapping_memory": (_i32, [_vp, _P(_i64)]),
     "fa_mapper_debug_mappings": (_i32, [_vp, _vp, _i64, _P(_i64)]),
     "fa_mapper_debug_l1": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _P(_i64)]),

@@ -494,6 +494,11 @@ struct MapStage {
   size_t bytes() const { return dev[0] ? 2 * (size_t)records * sizeof(fa_hit_mapping) : 0; }
 };
 
+static fa_rules default_rules() { fa_rules r; r.l2_confidence = kConfidence; r.slide_end = 0; r.cgi_ties = 0; return r; }
+static bool same_rules(const fa_rules &a, const fa_rules &b) {
+  return a.l2_confidence == b.l2_confidence && a.slide_end == b.slide_end && a.cgi_ties == b.cgi_ties;
+}
+
 // Everything one query call owns: its stream, every intermediate of the pipeline, its status block and timing events.
 struct Workspace {
   bool in_use = false;
@@ -527,6 +532,10 @@ struct Workspace {
   // LUT pointers captured for the call (the mapper may publish larger tables while this call is in flight)
   const int32_t *lut_min_hits = nullptr, *lut_pass = nullptr;
   const float *lut_ident = nullptr;
+  // the mapper's rules as they stood when the call started (run_query): every pass of the call follows them.  `own_pass`: the
+  // pass table of a call whose interval the mapper has left since (fa_mapper_set_rules while the call was in flight)
+  fa_rules rules = default_rules();
+  DevBuf<int32_t> own_pass;
   // last-pass bookkeeping for the debug getters
   int64_t last_F = 0;
   uint32_t last_loci = 0;             // loci of the last accepted part (all regions)
@@ -577,6 +586,8 @@ struct fa_mapper {
   std::vector<uint64_t> lengths;
   std::vector<int32_t> seqs_by_file;
   int32_t cmw = 0, qcap = 1;
+  // the open readings of the arithmetic this mapper follows (fa_mapper_set_rules); stats.ci mirrors rules.l2_confidence
+  fa_rules rules = default_rules();
   // LUTs
   StatTables stats;
   DevBuf<int32_t> d_min_hits, d_pass;
@@ -982,6 +993,15 @@ struct QueryPass {
     FA_REQUIRE(sp.smax < 32768, FA_ERR_UNSUPPORTED, "query sketch larger than 32767 minimizers");
     ensure_luts(m, sp.smax);
     w.lut_min_hits = m.d_min_hits.p; w.lut_pass = m.d_pass.p; w.lut_ident = m.d_ident.p;
+    if (w.rules.l2_confidence != m.stats.ci) {
+      // the mapper was given another interval while this call was in flight: the call keeps the one it started with
+      std::vector<int32_t> own((size_t)m.stats.smax + 1);
+      for (int s = 0; s <= m.stats.smax; s++) own[s] = stat_pass_threshold(s, m.stats.k, m.stats.pid, w.rules.l2_confidence);
+      FA_HIP(hipStreamSynchronize(st));                        // (an earlier attempt may still read the table)
+      w.own_pass.upload(own, st);
+      FA_HIP(hipStreamSynchronize(st));
+      w.lut_pass = w.own_pass.p;
+    }
   }
   void publish_spec(const Spec &sp) {
     std::lock_guard<std::mutex> lock(m.mtx);
@@ -1072,7 +1092,7 @@ struct QueryPass {
     ea.bins = w.bins.p; ea.winners = w.winners.p; ea.contig_genome = m.contig_genome.p;
     ea.n_bins = (int64_t)NQ * m.total_bins; ea.total_bins = std::max(m.total_bins, 1); ea.query_id_base = g0; ea.n_chunks = map_chunks;
     ea.chunk_count = w.map_chunk_count.p; ea.chunk_off = w.map_chunk_off.p;
-    ea.maps = nullptr; ea.total_maps = &w.status.p->total_maps;
+    ea.maps = nullptr; ea.total_maps = &w.status.p->total_maps; ea.tie = TieKey::of(w.rules.cgi_ties);
     if (map_chunks) hipLaunchKernelGGL(k_map_count, dim3(map_chunks), dim3(256), 0, st, ea);
     hipLaunchKernelGGL(k_map_scan, dim3(1), dim3(1024), 0, st, ea);
     if (!map_chunks || maps.count_only) return;
@@ -1357,6 +1377,7 @@ struct QueryPass {
       a.scan_class_div = p.scan_sorted ? lds.scan_class_div : 0;
       a.scan_hist = w.scan_hist.p; a.scan_cursor = w.scan_hist.p + LOCI_REGIONS * SCAN_CLASSES;
       a.scan_order = p.scan_sorted ? w.scan_order.p : nullptr;
+      a.slide_end = w.rules.slide_end; a.tie = TieKey::of(w.rules.cgi_ties);
       a.f_loci_lo = w.f_loci_lo.p; a.f_loci_n = w.f_loci_n.p;
       // several genomes in the pass: the workgroups of k_l2_events in offset-major order (prepare_order)
       a.frag_order = p.frag_order;
@@ -1413,6 +1434,7 @@ struct QueryPass {
       a.bin_len = m.P.fragment_length - 20;
       a.query_base = g0;                             // frag_query holds batch-wide genome numbers
       a.wide_launched = sp.redo ? 1 : 0;
+      a.tie = TieKey::of(w.rules.cgi_ties);
       a.group_bound = p.loci.n << p.loci.shift;
       hipLaunchKernelGGL(k_cgi_bins, dim3(ceil_div(l_cap, 256)), dim3(256), 0, st, a);
       if (maps.on) hipLaunchKernelGGL(k_cgi_winners, dim3(ceil_div(l_cap, 256)), dim3(256), 0, st, a, w.winners.p);
@@ -1564,6 +1586,7 @@ static int64_t run_query(fa_mapper &m, Workspace &w, const fa_genomes &g, int32_
   FA_REQUIRE(first >= 0 && count >= 0 && first + count <= g.n_genomes, FA_ERR_INVALID, "genome range out of bounds");
   for (float &x : w.last_ms) x = 0;
   w.last_forms = Forms();
+  { std::lock_guard<std::mutex> lock(m.mtx); w.rules = m.rules; }   // the rules in force when the call starts hold for all of it
   fa_cgi_row *dst = rows;
   if (!rows_device) { w.rows_dev.ensure((size_t)std::max<int64_t>(cap, 1)); dst = w.rows_dev.p; }
   // a call that is ONE pass and returns a modest number of rows to the host gets them written into pinned memory by the
@@ -2440,6 +2463,54 @@ int fa_mapper_set_mapping_stage(fa_mapper *m, int64_t records) {
     m->map_stage = records;
   });
 }
+int fa_rules_default(fa_rules *out) {
+  return guarded([&] { FA_REQUIRE(out, FA_ERR_INVALID, "null destination"); *out = default_rules(); });
+}
+static void validate_rules(const fa_rules &r) {
+  FA_REQUIRE(r.l2_confidence > 0.0f && r.l2_confidence < 1.0f, FA_ERR_INVALID, "l2_confidence must lie strictly inside (0, 1)");
+  FA_REQUIRE(r.slide_end == 0 || r.slide_end == 1, FA_ERR_INVALID, "slide_end must be 0 (windows) or 1 (fragment)");
+  FA_REQUIRE(r.cgi_ties == 0 || r.cgi_ties == 1, FA_ERR_INVALID, "cgi_ties must be 0 (smallest) or 1 (largest)");
+}
+// The interval only feeds the pass table (StatTables::pass_shared): it is rebuilt and uploaded, and the table it replaces is
+// retired like the generations ensure_luts outgrows -- calls in flight read it to their end.  The other two rules are argument
+// words of the kernels of the calls that start from now on.
+int fa_mapper_set_rules(fa_mapper *m, const fa_rules *r) {
+  return guarded([&] {
+    FA_REQUIRE(r, FA_ERR_INVALID, "null rules");
+    validate_rules(*r);
+    FA_REQUIRE(m, FA_ERR_INVALID, "null mapper");
+    std::lock_guard<std::mutex> lock(m->mtx);
+    if (same_rules(m->rules, *r)) return;
+    if (r->l2_confidence != m->stats.ci) {
+      StatTables next = m->stats;                            // (a failed upload leaves the mapper as it was)
+      next.set_ci(r->l2_confidence);
+      if (m->d_pass.p) {
+        bind_device(m->device);
+        DevBuf<int32_t> d_next;
+        d_next.upload(next.pass_shared, m->stream);
+        FA_HIP(hipStreamSynchronize(m->stream));
+        m->retired_i32.push_back(std::move(m->d_pass));
+        m->d_pass = std::move(d_next);
+      }
+      m->stats = std::move(next);
+    }
+    m->rules = *r;
+  });
+}
+int fa_mapper_get_rules(fa_mapper *m, fa_rules *out) {
+  return guarded([&] {
+    FA_REQUIRE(m && out, FA_ERR_INVALID, "null mapper or destination");
+    std::lock_guard<std::mutex> lock(m->mtx);
+    *out = m->rules;
+  });
+}
+int fa_pass_threshold(int sketch_size, int k, float identity, float ci, int *min_shared) {
+  return guarded([&] {
+    FA_REQUIRE(min_shared && sketch_size > 0 && k >= 1, FA_ERR_INVALID, "sketch_size and k must be positive");
+    FA_REQUIRE(ci > 0.0f && ci < 1.0f, FA_ERR_INVALID, "the confidence interval must lie strictly inside (0, 1)");
+    *min_shared = stat_pass_threshold(sketch_size, k, identity, ci);
+  });
+}
 int fa_mapper_mapping_memory(fa_mapper *m, int64_t out[4]) {
   return guarded([&] {
     FA_REQUIRE(m && out, FA_ERR_INVALID, "null mapper or destination");
@@ -2520,9 +2591,16 @@ int fa_mapper_debug_mappings(fa_mapper *m, fa_mapping *out, int64_t cap, int64_t
       });
       w.q_size.download(qs.data(), (size_t)w.last_F, w.stream);
       FA_HIP(hipStreamSynchronize(w.stream));
+      // (the filter of doL2Mapping at the interval the call ran with, which the mapper may have left since)
+      std::vector<int32_t> own;
+      if (w.rules.l2_confidence != m->stats.ci) {
+        own.resize(m->stats.pass_shared.size());
+        for (size_t s = 0; s < own.size(); s++) own[s] = stat_pass_threshold((int)s, m->stats.k, m->stats.pid, w.rules.l2_confidence);
+      }
+      const std::vector<int32_t> &pass_shared = own.empty() ? m->stats.pass_shared : own;
       for (uint32_t i = 0; i < L; i++) {
         int s = qs[lf[i]];
-        if (lsh[i] < m->stats.pass_shared[s]) continue;
+        if (lsh[i] < pass_shared[s]) continue;
         if (k < cap) {
           fa_mapping r;
           r.query_seq_id = lf[i]; r.ref_seq_id = ls[i]; r.ref_start_pos = lp[i]; r.sketch_size = s;

@@ -1818,6 +1818,17 @@ __global__ __launch_bounds__(L1_BIG_THREADS) void k_l1_big(L1Args a) {
 //               16-byte load per 8 events), with the per-rank state in lane-interleaved LDS.
 // `eval` marks the last event of a window position, i.e. the point where the reference compares
 // sharedSketchElements; events that are no-ops by the duplicate-linking rule carry zero deltas.
+// The low word of the two atomicMax keys of computeCGI (group_best: a locus number, bins: a querySeqId) under either tie rule
+// (fa_rules::cgi_ties): among equal high words the maximum keeps the SMALLEST number when the word holds its complement, the
+// LARGEST when it holds the number plus one -- plus one because key 0 is "empty" in both tables, and locus 0 resp. fragment 0
+// would otherwise form it.  low = (x + add) ^ flip, x = (low ^ flip) - add; uniform, so both are scalar operands.
+struct TieKey {
+  uint32_t flip, add;                // smallest: 0xFFFFFFFF, 0 (= 0xFFFFFFFF - x, never 0 below 2^32 - 1) | largest: 0, 1
+  __host__ __device__ uint32_t encode(uint32_t x) const { return (x + add) ^ flip; }
+  __host__ __device__ uint32_t decode(uint32_t low) const { return (low ^ flip) - add; }
+  static TieKey of(int largest) { TieKey t; t.flip = largest ? 0u : 0xFFFFFFFFu; t.add = largest ? 1u : 0u; return t; }
+};
+
 struct L2Args {
   IndexView ix;
   const uint32_t *q_hash;
@@ -1834,7 +1845,7 @@ struct L2Args {
   void *items;                       // uint16 or uint32 per event
   int32_t *l_shared, *l_pos;
   const int32_t *pass_lut;           // [smax+1]
-  unsigned long long *group_best;    // [groups] (shared<<32 | ~locus)
+  unsigned long long *group_best;    // [groups] (shared<<32 | tie.encode(locus))
   const uint32_t *counters;          // [2] loci overflow flag, [3] wide-state loci
   LociRegions loci;                  // which locus numbers are live (k_l2_scan)
   int32_t qcap, cmw;
@@ -1864,6 +1875,9 @@ struct L2Args {
   uint32_t *scan_hist, *scan_cursor; // [loci.n][SCAN_CLASSES] loci per class / placed so far
   uint32_t *scan_order;              // [loci capacity] locus numbers, region by region (nullptr: the identity)
   int32_t scan_class_div;            // events per class; 0 = no ordering
+  // the readings a mapper can be set to (fa_rules), the same in every lane of every wave:
+  int32_t slide_end;                 // 0: the slide ends at searchIndex(rangeEndPos + cmw) | 1: at searchIndex(rangeEndPos + fragment_length)
+  TieKey tie;                        // which of two loci with the same shared count a group keeps (step 1 of computeCGI)
 };
 
 constexpr int L2_THREADS = 64;
@@ -1950,7 +1964,15 @@ __global__ __launch_bounds__(EV_THREADS, EV_WAVES_PER_SIMD) void k_l2_events(L2A
       // searchIndex(seqId, rangeStartPos): rangeStartPos <= wpos of the first seed and wpos is strictly increasing, so
       // the answer lies within fragment_length records before that seed
       const int rfirst = a.l_rfirst[l], target = a.l_start[l], rpart = a.l_rpart[l];
-      const int last = a.ix.rec_fwd[a.l_rlast[l]];         // searchIndex(seqId, rangeEndPos + countMinimizerWindows)
+      int last = a.ix.rec_fwd[a.l_rlast[l]];               // searchIndex(seqId, rangeEndPos + countMinimizerWindows)
+      if (a.slide_end) {                                   // (uniform) searchIndex(seqId, rangeEndPos + fragment_length):
+        // at or behind that record and, wpos being strictly increasing, at most fragment_length - cmw records further on; the
+        // contig ends the search as it ends searchIndex's.  A handful of probes in the cache lines behind `last`.
+        const int tgt = wpos[a.l_rlast[l]] + a.frag_len;
+        int u = last, v = min(a.ix.contig_rec[a.l_seq[l] + 1], last + (a.frag_len - a.cmw));
+        while (u < v) { int mid = u + ((v - u) >> 1); if (wpos[mid] < tgt) u = mid + 1; else v = mid; }
+        last = u;
+      }
       int x = max(lo, rfirst - a.frag_len), y = rfirst;
       if (rpart >= 0) {
         // ... and far closer: the range starts fragment_length - 1 bases before the partner seed p that k_l1 paired with
@@ -2420,7 +2442,7 @@ __global__ __launch_bounds__(L2_THREADS) void k_l2_scan(L2Args a) {
   a.l_shared[l] = sl.best < 0 ? 0 : sl.best;
   a.l_pos[l] = (a.ix.rec_wpos[sl.opt_s] + a.ix.rec_wpos[sl.opt_e]) / 2;
   if (sl.best >= a.pass_lut[s]) {
-    unsigned long long key = ((unsigned long long)(uint32_t)sl.best << 32) | (unsigned long long)(0xFFFFFFFFu - l);
+    unsigned long long key = ((unsigned long long)(uint32_t)sl.best << 32) | (unsigned long long)a.tie.encode(l);
     atomicMax(&a.group_best[a.l_group[l]], key);
   }
 }
@@ -2430,7 +2452,7 @@ __global__ __launch_bounds__(L2_THREADS) void k_l2_scan(L2Args a) {
 // k_l2.  Step 2 (best mapping per reference bin) is an atomicMax into a dense table of bins; step 3 walks the
 // bins of every (query genome, reference genome) pair in order and averages in float32, as the reference does.
 // Tie-breaks are the canonical ones of DESIGN.md: equal identity -> smaller (refSeqId, refStartPos) in step 1,
-// smaller querySeqId in step 2.
+// smaller querySeqId in step 2 -- or the larger in both, where the mapper's rules say so (TieKey).
 // ----------------------------------------------------------------------------------------------------------
 struct CgiArgs {
   IndexView ix;
@@ -2447,6 +2469,7 @@ struct CgiArgs {
   uint32_t group_bound;         // locus numbers (= group numbers) lie below this: regions x their capacity
   int32_t wide_launched;        // the wide-state scan ran in this part (k_l2_scan<., uint16_t>): loci that left the byte state are settled
   unsigned long long *stamp;    // stage_stamp: start of the CGI stage
+  TieKey tie;                   // fa_rules::cgi_ties: the low word of the group keys (read) and of the bin keys (written)
 };
 
 // What the bin key cannot carry of a bin's winner (fa_hit_mapping): a table parallel to the bins, kept only by calls that
@@ -2465,7 +2488,7 @@ __device__ __forceinline__ bool cgi_survivor(const CgiArgs &a, uint32_t g, size_
   if (a.counters[CNT_WIDE] && !a.wide_launched) return false;
   unsigned long long best = a.group_best[g];
   if (best == 0) return false;
-  uint32_t l = 0xFFFFFFFFu - (uint32_t)(best & 0xFFFFFFFFu);
+  uint32_t l = a.tie.decode((uint32_t)(best & 0xFFFFFFFFu));
   int shared = (int)(best >> 32);
   int f = a.l_frag[l];
   int s = a.q_size[f];
@@ -2473,7 +2496,7 @@ __device__ __forceinline__ bool cgi_survivor(const CgiArgs &a, uint32_t g, size_
   int seq = a.l_seq[l];
   int pos = a.l_pos[l];
   int bin = a.ix.contig_bin[seq] + pos / a.bin_len;
-  key = ((unsigned long long)__float_as_uint(ident) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)a.frag_qseq[f]);
+  key = ((unsigned long long)__float_as_uint(ident) << 32) | (unsigned long long)a.tie.encode((uint32_t)a.frag_qseq[f]);
   idx = (size_t)(a.frag_query[f] - a.query_base) * a.ix.total_bins + bin;
   win.ref_seq_id = seq; win.ref_start_pos = pos; win.conserved = shared; win.sketch_size = s;
   return true;
@@ -2710,6 +2733,7 @@ struct MapEmitArgs {
   int64_t *chunk_off;               // [n_chunks] records of the pass in front of the chunk
   fa_hit_mapping *maps;             // where the records of the window go (k_map_write): a stage buffer or the caller's
   int64_t *total_maps;              // in the status block: the full count, whatever the room
+  TieKey tie;                       // the rule the bin keys were written under (CgiArgs::tie)
 };
 
 // keys of the wave's MAP_ITERS reads of 64 bins (0 beyond the table); returns how many are mapped
@@ -2777,7 +2801,7 @@ __global__ __launch_bounds__(256) void k_map_write(MapEmitArgs a, int64_t lo, in
     const MapWinner w = a.winners[i];
     fa_hit_mapping r;
     r.query_id = a.query_id_base + (int32_t)(i / a.total_bins);
-    r.query_seq_id = (int32_t)(0xFFFFFFFFu - (uint32_t)(key[u] & 0xFFFFFFFFu));
+    r.query_seq_id = (int32_t)a.tie.decode((uint32_t)(key[u] & 0xFFFFFFFFu));
     r.ref_genome_id = a.contig_genome[w.ref_seq_id];
     r.ref_seq_id = w.ref_seq_id; r.ref_start_pos = w.ref_start_pos; r.sketch_size = w.sketch_size; r.conserved = w.conserved;
     r.identity = __uint_as_float((uint32_t)(key[u] >> 32));

@@ -64,7 +64,7 @@ inline double stat_binomial_tail(int n, double r, int x) {
   return sum;
 }
 
-const float kConfidence = 0.9f;  // confidence interval used by estimateMinimumHitsRelaxed and doL2Mapping
+const float kConfidence = 0.9f;  // confidence interval of estimateMinimumHitsRelaxed, and the default at the doL2Mapping site
 
 // Stat::md_lower_bound
 inline float stat_md_lower_bound(float d, int s, int k, float ci) {
@@ -79,6 +79,12 @@ inline void stat_identity(int c, int s, int k, float *identity, float *upper) {
   float lo = stat_md_lower_bound(md, s, k, kConfidence);
   *identity = 100 * (1 - md);
   *upper = 100 * (1 - lo);
+}
+
+// nucIdentityUpperBound at the doL2Mapping site for an interval of the caller's (fa_rules::l2_confidence)
+inline float stat_upper_identity(int c, int s, int k, float ci) {
+  float md = stat_j2md((float)(1.0 * c / s), k);
+  return 100 * (1 - stat_md_lower_bound(md, s, k, ci));
 }
 
 inline int stat_min_hits(int s, int k, float pid) {
@@ -122,12 +128,24 @@ inline int stat_recommended_window(double cutoff, int k, int alphabet, float ide
   return -1;
 }
 
+// Smallest shared count of a sketch of size s whose upper-bound identity at interval ci reaches pid (s + 1: none does).
+// The upper-bound identity is monotone in c; the threshold is located by walking from the strict estimate.
+inline int stat_pass_threshold(int s, int k, float pid, float ci) {
+  if (s <= 0) return 1;
+  auto passes = [&](int c) { return stat_upper_identity(c, s, k, ci) >= pid; };
+  int c = std::min(std::max(stat_min_hits(s, k, pid), 0), s);
+  if (passes(c)) { while (c > 0 && passes(c - 1)) c--; }
+  else { while (c <= s && !passes(c)) c++; }
+  return c;
+}
+
 // Tables indexed by sketch size s (0..smax): minimum L1 hits, the smallest shared count whose upper-bound
 // identity passes the percentage_identity filter of doL2Mapping, and the triangular identity table
 // ident[s*(s+1)/2 + c] = nucIdentity(c, s) as float bits.
 struct StatTables {
   int k = 16;
   float pid = 80.0f;
+  float ci = kConfidence;            // interval of pass_shared only (fa_rules::l2_confidence); min_hits stays at kConfidence
   int smax = -1;
   std::vector<int32_t> min_hits;     // [s]
   std::vector<int32_t> pass_shared;  // [s]  (s+1 = nothing passes)
@@ -135,10 +153,12 @@ struct StatTables {
 
   static size_t tri(int s) { return (size_t)s * (size_t)(s + 1) / 2; }
 
-  bool passes(int c, int s) const {
-    float id, up;
-    stat_identity(c, s, k, &id, &up);
-    return up >= pid;
+  bool passes(int c, int s) const { return stat_upper_identity(c, s, k, ci) >= pid; }
+
+  // pass_shared again, for another interval (the other tables do not depend on it)
+  void set_ci(float new_ci) {
+    ci = new_ci;
+    for (int s = 1; s <= smax; s++) pass_shared[s] = stat_pass_threshold(s, k, pid, ci);
   }
 
   // grows the tables to cover sketch sizes up to new_smax; returns true if anything changed
@@ -150,11 +170,7 @@ struct StatTables {
     for (int s = std::max(smax + 1, 0); s <= new_smax; s++) {
       if (s == 0) { min_hits[0] = 0; pass_shared[0] = 1; ident[0] = 0.0f; continue; }
       min_hits[s] = stat_min_hits_relaxed(s, k, pid);
-      // The upper-bound identity is monotone in c; locate the threshold by walking from the strict estimate.
-      int c = std::min(std::max(stat_min_hits(s, k, pid), 0), s);
-      if (passes(c, s)) { while (c > 0 && passes(c - 1, s)) c--; }
-      else { while (c <= s && !passes(c, s)) c++; }
-      pass_shared[s] = c;
+      pass_shared[s] = stat_pass_threshold(s, k, pid, ci);
       for (int j = 0; j <= s; j++) ident[tri(s) + j] = 100 * (1 - stat_j2md((float)(1.0 * j / s), k));
     }
     smax = new_smax;

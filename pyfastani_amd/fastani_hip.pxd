@@ -22,6 +22,11 @@ cdef extern from "fastani_hip.h" nogil:
         double p_value
         uint64_t reference_size
 
+    ctypedef struct fa_rules:           # the open readings of the arithmetic a mapper follows (no reference counterpart)
+        float l2_confidence
+        int32_t slide_end
+        int32_t cgi_ties
+
     ctypedef struct fa_cgi_row:         # cgi::CGI_Results, include/fastani/cgi/cgid_types.pxd:19-27
         int32_t query_id
         int32_t ref_genome_id
@@ -109,6 +114,10 @@ cdef extern from "fastani_hip.h" nogil:
                                         uint64_t* total_length, fa_mapping_sink sink, void* user, int64_t* n_maps)
     int fa_mapper_set_mapping_stage(fa_mapper* m, int64_t records)
     int fa_mapper_mapping_memory(fa_mapper* m, int64_t* out)
+    int fa_rules_default(fa_rules* out)
+    int fa_mapper_set_rules(fa_mapper* m, const fa_rules* r)
+    int fa_mapper_get_rules(fa_mapper* m, fa_rules* out)
+    int fa_pass_threshold(int sketch_size, int k, float identity, float ci, int* min_shared)
 
     # resident batches (many-to-many extension)
     int fa_genomes_upload(fa_mapper* m, const void* const* contigs, const int64_t* lengths, const int32_t* contig_genome,

@@ -1,6 +1,6 @@
 """Differential fuzzing of the HIP path against the CPU oracle: random genomes with planted repeats, tandem
 duplications, inversions, N runs and low-complexity stretches; random parameters.  Every L2 mapping and every hit must
-match.  Usage: python scripts/fuzz_parity.py [--history | --domain | --contigs] [cases] [seed] [seconds] [default-cell]   (stops after `seconds` if given: a
+match.  Usage: python scripts/fuzz_parity.py [--rules l2_confidence=0.75,slide_end=fragment,cgi_ties=largest] [--history | --domain | --contigs] [cases] [seed] [seconds] [default-cell]   (stops after `seconds` if given: a
 time box; a fourth argument keeps every nucleotide case in the default cell k = 16 / fragment 3000 / 80 % with queries of plain
 ACGT -- the cell whose query passes run K1 and the fragment sketch as ONE launch, k_query_fused).  --history: one index per
 case, then 4-8 queries drawn from the generators (plain, tandem, drafts, N / IUPAC, batches) on the SAME mapper, each through
@@ -16,6 +16,25 @@ import numpy as np
 import pyfastani_amd as pf
 from pyfastani_amd import _lib, synthetic as syn
 from pyfastani_amd._lib import lib, check
+
+# --rules l2_confidence=0.75,slide_end=fragment,cgi_ties=largest (any subset): every sketch of the run gets these rules, and the
+# oracle is built with the matching FO_* switches -- oracle.oracle reads FA_ORACLE_DEFINES when it is imported, hence before it
+RULES = None
+if "--rules" in sys.argv:
+    at = sys.argv.index("--rules")
+    spec = dict(item.split("=", 1) for item in sys.argv[at + 1].split(",") if item)
+    del sys.argv[at: at + 2]
+    if "l2_confidence" in spec:
+        spec["l2_confidence"] = float(spec["l2_confidence"])
+    RULES = pf.Rules(**spec)
+    switches = []
+    if RULES.l2_confidence != 0.9:
+        switches.append(f"FO_L2_CI={RULES.l2_confidence!r}f")
+    if RULES.slide_end == "fragment":
+        switches.append("FO_SLIDE_END=1")
+    if RULES.cgi_ties == "largest":
+        switches.append("FO_CGI_TIES=1")
+    os.environ["FA_ORACLE_DEFINES"] = ",".join(switches)
 from oracle.oracle import OracleSketch
 
 def mappings(mapper):
@@ -85,7 +104,7 @@ AMINO = np.frombuffer(b"ACDEFGHIKLMNPQRSTVWY", dtype=np.uint8)
 def protein_case(g, case):
     k = int(g.choice([5, 7, 9, 12, 16])); frag = int(g.choice([60, 100, 150, 300]))
     params = dict(k=k, fragment_length=frag, protein=True, minimum_fraction=float(g.choice([0.0, 0.2])))
-    sk, osk = pf.Sketch(**params), OracleSketch(**params)
+    sk, osk = pf.Sketch(**params, rules=RULES), OracleSketch(**params)
     n_prot = int(g.integers(3, 12))
     anc = [g.integers(0, 20, int(g.integers(80, 900))) for _ in range(n_prot)]
     def mutate(p, d):
@@ -122,7 +141,7 @@ def history_case(g, case, tmp):
     osk = OracleSketch(**params)
     if osk.window_size >= frag:
         return True
-    sk = pf.Sketch(**params)
+    sk = pf.Sketch(**params, rules=RULES)
     length = int(g.integers(max(3 * frag, 8000), 60_000))
     anc = scramble(g, syn.random_codes(g, length))
     copies = int(g.choice([1, 1, 2, 8, 30]))                   # many copies of one genome: fragments with thousands of seed hits
@@ -187,7 +206,7 @@ def contigs_case(g, case):
     w = osk.window_size
     if w >= frag:
         return None
-    sk = pf.Sketch(**params)
+    sk = pf.Sketch(**params, rules=RULES)
     lengths = cd.critical_lengths(k, w, frag, (cd.k1_tile_len(w),) + cd.FORCED_TILES)
 
     def cut(codes, filler):
@@ -285,7 +304,7 @@ for case in range(cases):
         if osk.window_size >= frag:      # degenerate cell: nothing maps; covered by the unit tests
             degenerate += 1
             continue
-        sk = pf.Sketch(**params)
+        sk = pf.Sketch(**params, rules=RULES)
         # a third of the cases index with a narrow low word of the global coordinate (FA_GPOS_BITS, read when the index is built):
         # dozens of word boundaries inside these small indexes, i.e. the 64-bit form of k_l1's candidate scan
         os.environ.pop("FA_GPOS_BITS", None)
@@ -333,5 +352,5 @@ for case in range(cases):
         print(f"MISMATCH case {case} seed {seed} params {params} window {osk.window_size}: hits {hits} vs {ohits}; mappings gpu {len(gm)} oracle {len(omm)}")
         sg, so = set(gm), set(omm)
         print("   only gpu", sorted(sg - so)[:4], "only oracle", sorted(so - sg)[:4])
-print(f"{done} {'history ' if history else ''}cases (seed {seed}), {bad} mismatches, {degenerate} degenerate, {time.time() - t0:.1f} s")
+print(f"{done} {'history ' if history else ''}cases (seed {seed}{', ' + repr(RULES) if RULES else ''}), {bad} mismatches, {degenerate} degenerate, {time.time() - t0:.1f} s")
 sys.exit(1 if bad else 0)

@@ -92,6 +92,7 @@ int main(int argc, char **argv) {
   uint8_t *d_redo; CHECK(hipMalloc(&d_redo, max_loci)); a.l_redo = d_redo;
   unsigned long long *d_gb; CHECK(hipMalloc(&d_gb, 64)); CHECK(hipMemset(d_gb, 0, 64)); a.group_best = d_gb;
   a.items = d_items; a.cnt_slots = S + 17; a.lanes = 64; a.qcap = 0; a.cmw = 0;
+  a.slide_end = 0; a.tie = TieKey::of(0);                             // the default rules
   const size_t state = ((size_t)(a.cnt_slots + 1) * 64 + 15) / 16 * 16;
   unsigned long long *d_clk; CHECK(hipMalloc(&d_clk, (size_t)cus * 16));
   auto kernel = k_l2_scan<uint16_t, uint8_t, 64>;
