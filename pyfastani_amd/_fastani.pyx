@@ -872,6 +872,20 @@ cdef class Sketch(_Parameterized):
             self._add_draft(name, (sequence,))
         return self
 
+    cdef int _added(self, int code, object names, int64_t n_short) except -1:
+        """The end of a call that has added whole genomes natively (``code``: what the library returned), entered with the
+        lock held: the names follow under the same lock, which is then released -- also when the call has failed -- and
+        every short contig is reported afterwards, like `add_draft` reports it (_fastani.pyx:670-677)."""
+        try:
+            _check(code)
+            self._names.extend(names)
+            self._version += 1
+        finally:
+            self._lock.release()
+        for _ in range(n_short):
+            warnings.warn("Sketch received a short contig relative to parameters, minimizers will not be added.", UserWarning)
+        return 0
+
     def add_drafts(self, names, genomes):
         """`add_draft` for many reference genomes at once: ``genomes[i]`` is the iterable of contigs of ``names[i]``.  One call of
         the library's packer over all contigs (``fa_sketch_add_genomes``) instead of one per genome -- the host side of a
@@ -909,15 +923,14 @@ cdef class Sketch(_Parameterized):
         if ptrs.empty():
             ptrs.push_back(NULL); lens.push_back(0); cg.push_back(0)
         cdef int64_t n = <int64_t> len(keep)
-        with self._lock:
-            with nogil:
-                code = hip.fa_sketch_add_genomes(self._hs, ptrs.data(), lens.data(), cg.data(), n, gi, width, n_short.data())
-            _check(code)
-            self._names.extend(names)
-            self._version += 1
-        for i in range(gi):
-            for _ in range(n_short[i]):
-                warnings.warn("Sketch received a short contig relative to parameters, minimizers will not be added.", UserWarning)
+        cdef int64_t shorts = 0
+        cdef int32_t i
+        self._lock.acquire()
+        with nogil:
+            code = hip.fa_sketch_add_genomes(self._hs, ptrs.data(), lens.data(), cg.data(), n, gi, width, n_short.data())
+            for i in range(gi):
+                shorts += n_short[i]
+        self._added(code, names, shorts)
         return self
 
     def add_fasta(self, name, path):
@@ -926,14 +939,10 @@ cdef class Sketch(_Parameterized):
         cdef int64_t n_rec = 0, n_short = 0
         cdef bytes p = os.fsencode(path)
         cdef const char* cp = p
-        with self._lock:
-            with nogil:
-                code = hip.fa_sketch_add_fasta(self._hs, cp, &n_rec, &n_short)
-            _check(code)
-            self._names.append(name)
-            self._version += 1
-        for _ in range(n_short):
-            warnings.warn("Sketch received a short contig relative to parameters, minimizers will not be added.", UserWarning)
+        self._lock.acquire()
+        with nogil:
+            code = hip.fa_sketch_add_fasta(self._hs, cp, &n_rec, &n_short)
+        self._added(code, (name,), n_short)
         return self
 
     def add_fasta_many(self, names, paths):
@@ -954,15 +963,14 @@ cdef class Sketch(_Parameterized):
         n_rec.resize(max(n, 1)); n_short.resize(max(n, 1))
         if arr.empty():
             arr.push_back(NULL)
-        with self._lock:
-            with nogil:
-                code = hip.fa_sketch_add_fasta_many(self._hs, arr.data(), n, n_rec.data(), n_short.data())
-            _check(code)
-            self._names.extend(names)
-            self._version += 1
-        for i in range(n):
-            for _ in range(n_short[i]):
-                warnings.warn("Sketch received a short contig relative to parameters, minimizers will not be added.", UserWarning)
+        cdef int64_t shorts = 0
+        cdef int32_t i
+        self._lock.acquire()
+        with nogil:
+            code = hip.fa_sketch_add_fasta_many(self._hs, arr.data(), n, n_rec.data(), n_short.data())
+            for i in range(n):
+                shorts += n_short[i]
+        self._added(code, names, shorts)
         return self
 
     def add_packed(self, names, PackedGenomes packed, int first=0, count=None):
@@ -975,15 +983,14 @@ cdef class Sketch(_Parameterized):
         if len(names) != c:
             raise ValueError("names and the file range differ in length")
         n_rec.resize(max(c, 1)); n_short.resize(max(c, 1))
-        with self._lock:
-            with nogil:
-                code = hip.fa_sketch_add_packed(self._hs, packed._hp, first, c, n_rec.data(), n_short.data())
-            _check(code)
-            self._names.extend(names)
-            self._version += 1
-        for i in range(c):
-            for _ in range(n_short[i]):
-                warnings.warn("Sketch received a short contig relative to parameters, minimizers will not be added.", UserWarning)
+        cdef int64_t shorts = 0
+        cdef int32_t i
+        self._lock.acquire()
+        with nogil:
+            code = hip.fa_sketch_add_packed(self._hs, packed._hp, first, c, n_rec.data(), n_short.data())
+            for i in range(c):
+                shorts += n_short[i]
+        self._added(code, names, shorts)
         return self
 
     def flush(self):

@@ -1,7 +1,7 @@
 // fa_engine.hip -- host side of libfastani_hip.so: owns the HIP stream and all HBM allocations, drives the
 // kernels of fa_sketch.hip.h / fa_map.hip.h, and exports the C ABI declared in include/fastani_hip.h.
 // There is no CPU fallback anywhere in this file: without a HIP device every compute entry point fails.
-#include <cstring>
+#include <cstring>   // (before rocPRIM, whose texture_cache_iterator.hpp calls memset without including it)
 
 #include <rocprim/rocprim.hpp>
 
@@ -10,7 +10,6 @@
 #include <chrono>
 #include <climits>
 #include <cstdlib>
-#include <cstring>
 #include <memory>
 #include <condition_variable>
 #include <mutex>
@@ -23,6 +22,7 @@
 
 #include "fa_common.h"
 #include "fa_fasta.h"
+#include "fa_ingest.h"
 #include "fa_lease.h"
 #include "fa_map.hip.h"
 #include "fa_policy.h"
@@ -237,27 +237,42 @@ static void exclusive_sum_i32(DevBuf<unsigned char> &temp, const int32_t *in, in
 // ------------------------------------------------------------------------------------------------------------
 // fa_sketch: reference genomes being collected (skch::Sketch + pyfastani's counters)
 // ------------------------------------------------------------------------------------------------------------
+// the minimizer records of a sketch: three parallel device arrays that grow, fill and empty together
+struct RecArrays {
+  DevBuf<uint32_t> hash;
+  DevBuf<int32_t> seq, wpos;
+  // room for n records, the first `keep` of them preserved
+  void reserve(size_t n, size_t keep, hipStream_t st) { hash.ensure(n, true, st, keep); seq.ensure(n, true, st, keep); wpos.ensure(n, true, st, keep); }
+  // n records from host (hipMemcpyHostToDevice) or device memory replace the content
+  void load(const uint32_t *h, const int32_t *s, const int32_t *w, size_t n, hipMemcpyKind kind, hipStream_t st) {
+    hash.ensure(n); seq.ensure(n); wpos.ensure(n);
+    copy(hash.p, seq.p, wpos.p, h, s, w, n, kind, st);
+  }
+  // the first n records to host (hipMemcpyDeviceToHost) or device memory
+  void store(uint32_t *h, int32_t *s, int32_t *w, size_t n, hipMemcpyKind kind, hipStream_t st) const { copy(h, s, w, hash.p, seq.p, wpos.p, n, kind, st); }
+  static void copy(uint32_t *dh, int32_t *ds, int32_t *dw, const uint32_t *h, const int32_t *s, const int32_t *w, size_t n, hipMemcpyKind kind, hipStream_t st) {
+    if (!n) return;
+    FA_HIP(hipMemcpyAsync(dh, h, n * sizeof(uint32_t), kind, st));
+    FA_HIP(hipMemcpyAsync(ds, s, n * sizeof(int32_t), kind, st));
+    FA_HIP(hipMemcpyAsync(dw, w, n * sizeof(int32_t), kind, st));
+  }
+};
+
 struct fa_sketch {
   fa_params P;
   int device = -1;
   hipStream_t stream = nullptr;
   hipStream_t up_stream = nullptr;        // uploads of a flush (the next chunk's sequence while this one is hashed)
   HostStore pending;                      // packed contigs not yet sketched
-  std::vector<int32_t> pending_contig;    // contig id of each pending sequence
-  int64_t counter = 0;                    // contigs seen (Sketch._counter)
-  uint64_t cur_total = 0;
-  std::vector<uint64_t> lengths;          // per genome, rounded to whole fragments
-  std::vector<int32_t> seqs_by_file;      // sequencesByFileInfo
-  DevBuf<uint32_t> rec_hash;
-  DevBuf<int32_t> rec_seq, rec_wpos;
+  RefBook book;                           // the genomes' counters, and the contig id of each pending sequence (fa_ingest.h)
+  RecArrays rec;
   int64_t nrec = 0;
   SketchWork work;
   std::mutex mtx;
 
   void reset_data() {
     pending.clear(); pending.protein = P.alphabet_size != 4;
-    pending_contig.clear();
-    counter = 0; cur_total = 0; lengths.clear(); seqs_by_file.clear(); nrec = 0;
+    book.reset(); nrec = 0;
   }
 
   // sketch every pending contig on the device and append the records
@@ -287,9 +302,7 @@ struct fa_sketch {
       for (int64_t q = 0; q < nseq_all; q++) positions_all += pending.seq_len[q];
       const double per_pos = P.alphabet_size == 4 ? 2.0 / (P.window_size + 1) : 1.0;
       const size_t expect = (size_t)nrec + (size_t)((double)positions_all * std::min(1.0, per_pos * 1.25)) + 1024;
-      rec_hash.ensure(expect, true, stream, (size_t)nrec);
-      rec_seq.ensure(expect, true, stream, (size_t)nrec);
-      rec_wpos.ensure(expect, true, stream, (size_t)nrec);
+      rec.reserve(expect, (size_t)nrec, stream);
     }
     // chunk boundaries first (the copy of the next chunk is issued while this one is hashed)
     std::vector<int64_t> cuts{0};
@@ -321,7 +334,7 @@ struct fa_sketch {
       for (int64_t q = s0; q < s1; q++) {
         seq_tile_lo.push_back((int32_t)tile_total);
         tile_total += tile_count(pending.seq_len[q], P.kmer_size, tile_len);
-        seq_ids.push_back(pending_contig[q]);
+        seq_ids.push_back(book.pending_contig[q]);
       }
       seq_tile_lo.push_back((int32_t)tile_total);
       FA_REQUIRE(tile_total < (1LL << 31) - 1, FA_ERR_UNSUPPORTED, "too many tiles in one sketch chunk");
@@ -362,13 +375,11 @@ struct fa_sketch {
         FA_HIP(hipStreamSynchronize(stream));
         const int64_t nout = (int64_t)total - dropped;
         tr.mark("scan", stream);
-        rec_hash.ensure((size_t)(nrec + nout), true, stream, (size_t)nrec);
-        rec_seq.ensure((size_t)(nrec + nout), true, stream, (size_t)nrec);
-        rec_wpos.ensure((size_t)(nrec + nout), true, stream, (size_t)nrec);
+        rec.reserve((size_t)(nrec + nout), (size_t)nrec, stream);
         tr.mark("grow", stream);
         hipLaunchKernelGGL(k_compact_records, dim3(ntiles), dim3(256), 0, stream, work.tiles.p, work.tile_count.p,
                            work.tile_off.p, d_seq_tile_lo.p, d_drop.p, d_drop_off.p, work.stage_hash.p, work.stage_wpos.p,
-                           d_seq_ids.p, nrec, rec_hash.p, rec_seq.p, rec_wpos.p);
+                           d_seq_ids.p, nrec, rec.hash.p, rec.seq.p, rec.wpos.p);
         FA_HIP(hipGetLastError());
         FA_HIP(hipStreamSynchronize(stream));
         tr.mark("compact", stream);
@@ -378,7 +389,7 @@ struct fa_sketch {
     FA_HIP(hipStreamSynchronize(up_stream));
     pending.clear();
     pending.protein = P.alphabet_size != 4;
-    pending_contig.clear();
+    book.pending_contig.clear();
   }
 };
 
@@ -403,8 +414,7 @@ struct PinnedBuf {
 };
 
 // Everything the kernels read of a batch sits in ONE device allocation, filled by ONE host-to-device copy from a staging
-// image of the same layout: [packed 2-bit words | residue bytes | tiles | frag_tile_lo | frag_query | frag_qseq |
-// total_frag], every part 16-byte aligned.  Only the exception lists (rare: N runs, IUPAC codes) are separate.
+// image of the same layout (BatchLayout, fa_ingest.h).  Only the exception lists (rare: N runs, IUPAC codes) are separate.
 struct fa_genomes {
   fa_params P;
   DevBuf<unsigned char> blob;
@@ -426,6 +436,11 @@ struct fa_genomes {
   hipStream_t up_stream = nullptr;          // FASTA uploads run on the batch's own stream
   ~fa_genomes() { if (up_stream) (void)hipStreamDestroy(up_stream); }
   fa_genomes() = default;
+  // a failed refill leaves an empty (but valid) batch
+  void reset_empty() {
+    n_genomes = 0; F = 0; ntiles = 0;
+    genome_frag_lo.assign(1, 0); total_fragments.clear(); total_length.clear(); n_short.clear();
+  }
   uint64_t serial = 0;                      // a new number for every upload (caches keyed on a batch compare this, not its address)
 };
 static std::atomic<uint64_t> g_batch_serial{0};
@@ -1647,13 +1662,13 @@ struct WorkspaceLease : Lease<fa_mapper, Workspace> {
         }) {}
 };
 
-// pack + cut into fragments + tiles + upload.  `reuse` (a batch object whose device buffers are recycled, contents
-// replaced) and `pin` (pinned staging memory the image is built in, so that the one upload is a plain DMA) serve the
-// one-query-at-a-time call; without them the image is built in pageable memory.
+// pack + cut into fragments + tiles + upload, in place: `g` may be a batch object whose device buffers are recycled, contents
+// replaced.  That and `pin` (pinned staging memory the image is built in, so that the one upload is a plain DMA) serve the
+// one-query-at-a-time call; without `pin` the image is built in pageable memory.
 // `packed` (fa_genomes_upload_fasta): contig c is record packed[c] of a file that read_fasta_packed has packed already -- its
 // words are copied where `contigs` would be packed; `contigs` is not read then.
-// fill_genomes works in place (fa_genomes_reload_fasta: a batch object whose device buffers, pinned image and upload stream are
-// recycled from chunk to chunk); `sync_pinned`: wait for the upload although the image is pinned (the image is reused next).
+// `sync_pinned` (fa_genomes_reload_fasta: device buffers, pinned image and upload stream are recycled from chunk to chunk): wait
+// for the upload although the image is pinned (the image is reused next).
 static void fill_genomes(fa_genomes *g, const fa_params &P, hipStream_t st, const void *const *contigs, const int64_t *lengths,
                          const int32_t *contig_genome, int64_t n_contigs, int32_t n_genomes, int width,
                          float *host_ms, PinnedBuf *pin, const PackedRef *packed, bool sync_pinned) {
@@ -1667,83 +1682,42 @@ static void fill_genomes(fa_genomes *g, const fa_params &P, hipStream_t st, cons
   FA_REQUIRE(width == 1 || width == 2 || width == 4, FA_ERR_INVALID, "char_width must be 1, 2 or 4");
   g->P = P;
   g->serial = ++g_batch_serial;
+  // which contigs are mapped, how many whole fragments each holds, the per-genome counters and every size of the image
+  BatchPlan plan = plan_batch(P, lengths, contig_genome, n_contigs, n_genomes, TILE, sizeof(Tile));
+  const BatchLayout &at = plan.at;
+  const int64_t F = plan.F, ntiles = plan.ntiles, tiles_per_frag = plan.tiles_per_frag;
+  const int frag = P.fragment_length;
   g->n_genomes = n_genomes;
-  g->total_fragments.assign(n_genomes, 0); g->total_length.assign(n_genomes, 0); g->n_short.assign(n_genomes, 0);
-  g->total_bases = 0;
+  g->F = F; g->ntiles = ntiles; g->total_bases = plan.total_bases;
+  g->genome_frag_lo = std::move(plan.genome_frag_lo); g->contig_frag_lo = std::move(plan.contig_frag_lo);
+  g->total_fragments = std::move(plan.total_fragments); g->total_length = std::move(plan.total_length); g->n_short = std::move(plan.n_short);
   HostStore hs;
   hs.protein = P.alphabet_size != 4;
-  g->genome_frag_lo.assign((size_t)n_genomes + 1, 0);
-  g->frag_tile_lo.clear();
-  const int frag = P.fragment_length;
-  const int64_t min_len = std::min<int64_t>(std::min(P.window_size, P.kmer_size), frag);
-  // pass 1: which contigs are mapped, and how many whole fragments each holds -- this fixes every size of the image
-  std::vector<const void *> use_ptr;
-  std::vector<PackedRef> use_ref;
-  std::vector<int64_t> use_len;
-  int64_t F = 0;
-  for (int64_t c = 0; c < n_contigs; c++) {
-    const int64_t len = lengths[c];
-    if (len < min_len) continue;
-    const int64_t nfrag = len / frag;
-    if (nfrag > 0) {                                                  // the tail past the last whole fragment is never read
-      if (packed) use_ref.push_back(PackedRef{packed[c].file, packed[c].rec, nfrag * frag}); else use_ptr.push_back(contigs[c]);
-      use_len.push_back(nfrag * frag); F += nfrag;
-    }
-  }
-  const int64_t npos_frag = (int64_t)frag - P.kmer_size + 1;
-  const int64_t tiles_per_frag = npos_frag > 0 ? (npos_frag + TILE - 1) / TILE : 0;
-  const int64_t ntiles = F * tiles_per_frag;
-  FA_REQUIRE(ntiles < (1LL << 31) - 1 && F < (1LL << 31) - 1, FA_ERR_UNSUPPORTED, "too many fragments in one batch");
-  const size_t bases = (size_t)HostStore::padded_bases(use_len.data(), (int64_t)use_len.size());
-  auto al = [](size_t x) { return (x + 15) / 16 * 16; };
-  const size_t o_packed = 0, n_packed = hs.protein ? 0 : al(bases / 4 + 64);
-  const size_t o_bytes = o_packed + n_packed, n_bytes = hs.protein ? al(bases + 64) : 0;
-  const size_t o_tiles = o_bytes + n_bytes, n_tiles = al((size_t)std::max<int64_t>(ntiles, 1) * sizeof(Tile));
-  const size_t o_ftl = o_tiles + n_tiles, n_ftl = al(((size_t)F + 1) * 4);
-  const size_t o_fq = o_ftl + n_ftl, n_fq = al((size_t)std::max<int64_t>(F, 1) * 4);
-  const size_t o_fs = o_fq + n_fq, n_fs = n_fq;
-  const size_t o_tf = o_fs + n_fs, n_tf = al((size_t)std::max(n_genomes, 1) * 4);
-  const size_t image_bytes = o_tf + n_tf;
+  const size_t image_bytes = at.image_bytes, bases = plan.bases;
   unsigned char *img;
   if (pin) { pin->ensure(image_bytes); img = pin->p; }
   else { g->host_image.resize(image_bytes); img = g->host_image.data(); }
   StageTrace tr("upload_genomes");
   // the slack behind the packed words / bytes (the sketch kernel's funnel shift reads one word past the end)
-  if (!hs.protein) memset(img + o_packed + bases / 4, 0, n_packed - bases / 4); else memset(img + o_bytes + bases, 0, n_bytes - bases);
-  if (packed) place_packed(hs, use_ref.data(), (int64_t)use_ref.size(), (uint32_t *)(img + o_packed), img + o_bytes);
-  else hs.pack_many(use_ptr.data(), use_len.data(), (int64_t)use_ptr.size(), width, (uint32_t *)(img + o_packed), img + o_bytes);
+  if (!hs.protein) memset(img + at.packed.at + bases / 4, 0, at.packed.bytes - bases / 4); else memset(img + at.bytes.at + bases, 0, at.bytes.bytes - bases);
+  if (packed) {
+    std::vector<PackedRef> use_ref;
+    for (const ContigJob &cj : plan.jobs) use_ref.push_back(PackedRef{packed[cj.c].file, packed[cj.c].rec, cj.nfrag * frag});
+    place_packed(hs, use_ref.data(), (int64_t)use_ref.size(), (uint32_t *)(img + at.packed.at), img + at.bytes.at);
+  } else {
+    std::vector<const void *> use_ptr;
+    for (const ContigJob &cj : plan.jobs) use_ptr.push_back(contigs[cj.c]);
+    hs.pack_many(use_ptr.data(), plan.use_len.data(), (int64_t)use_ptr.size(), width, (uint32_t *)(img + at.packed.at), img + at.bytes.at);
+  }
   tr.mark("pack", st);
   lap(0);
-  // pass 2: fragments, tiles and per-genome bookkeeping, in contig order, written straight into the image
-  Tile *tiles = (Tile *)(img + o_tiles);
-  int32_t *frag_query = (int32_t *)(img + o_fq), *frag_qseq = (int32_t *)(img + o_fs), *tf = (int32_t *)(img + o_tf);
-  // (the bookkeeping per contig on this thread, the per-fragment tables and tiles by the host pool: 1.7 M fragments and 5 M
-  // tiles for a thousand genomes were one thread's loop)
-  struct ContigJob { int64_t si, nfrag, nf0, q0; int32_t gi; };
-  std::vector<ContigJob> jobs;
-  int32_t cur = 0;
-  size_t used = 0;
-  int64_t nf = 0;
-  for (int64_t c = 0; c < n_contigs; c++) {
-    int32_t gi = contig_genome ? contig_genome[c] : 0;
-    FA_REQUIRE(gi >= cur && gi < n_genomes, FA_ERR_INVALID, "contig_genome must be non-decreasing and < n_genomes");
-    while (cur < gi) { cur++; g->genome_frag_lo[cur] = nf; }
-    const int64_t len = lengths[c];
-    if (len < min_len) { g->n_short[gi]++; continue; }               // _fastani.pyx:1061-1070
-    const int64_t nfrag = len / frag;                                 // :1097
-    if (nfrag > 0) {
-      jobs.push_back(ContigJob{(int64_t)used++, nfrag, nf, (int64_t)g->total_fragments[gi], gi});   // querySeqId = fragments before + i, :985
-      nf += nfrag;
-    }
-    g->total_fragments[gi] += (uint64_t)nfrag;                        // :1104
-    g->total_length[gi] += (uint64_t)len;                             // :1105
-    g->total_bases += (uint64_t)(nfrag * frag);
-  }
+  // fragments and tiles, written straight into the image by the host pool (1.7 M fragments and 5 M tiles for a thousand
+  // genomes were one thread's loop)
+  Tile *tiles = (Tile *)(img + at.tiles.at);
+  int32_t *frag_query = (int32_t *)(img + at.frag_query.at), *frag_qseq = (int32_t *)(img + at.frag_qseq.at), *tf = (int32_t *)(img + at.total_frag.at);
   g->frag_tile_lo.assign((size_t)F + 1, 0);
-  g->contig_frag_lo.clear();
-  for (const ContigJob &cj : jobs) g->contig_frag_lo.push_back(cj.nf0);
-  HostPool::get().parallel_for(jobs.size(), [&](size_t j) {
-    const ContigJob &cj = jobs[j];
+  HostPool::get().parallel_for(plan.jobs.size(), [&](size_t j) {
+    const ContigJob &cj = plan.jobs[j];
     for (int64_t i = 0; i < cj.nfrag; i++) {
       const int64_t f = cj.nf0 + i;
       g->frag_tile_lo[(size_t)f] = (int32_t)(f * tiles_per_frag);
@@ -1752,13 +1726,8 @@ static void fill_genomes(fa_genomes *g, const fa_params &P, hipStream_t st, cons
       frag_query[f] = cj.gi;
     }
   });
-  const int64_t nt = nf * tiles_per_frag;
-  while (cur < n_genomes) { cur++; g->genome_frag_lo[cur] = nf; }
-  FA_REQUIRE(nf == F && nt == ntiles, FA_ERR_INTERNAL, "fragment / tile count mismatch while building the batch image");
-  g->F = F;
-  g->frag_tile_lo[(size_t)F] = (int32_t)nt;
-  g->ntiles = ntiles;
-  memcpy(img + o_ftl, g->frag_tile_lo.data(), ((size_t)F + 1) * 4);
+  g->frag_tile_lo[(size_t)F] = (int32_t)ntiles;
+  memcpy(img + at.frag_tile_lo.at, g->frag_tile_lo.data(), ((size_t)F + 1) * 4);
   for (int i = 0; i < n_genomes; i++) tf[i] = (int32_t)g->total_fragments[i];
   tr.mark("fragments_tiles", st);
   lap(1);
@@ -1769,21 +1738,21 @@ static void fill_genomes(fa_genomes *g, const fa_params &P, hipStream_t st, cons
   // tile and fragment tables (read by every stage) are copied.  FA_QUERY_ZERO_COPY=0: the whole image is copied.
   static const bool zero_copy_on = env_num("FA_QUERY_ZERO_COPY", 1) != 0;
   const bool zero_copy = zero_copy_on && pin && !sync_pinned && !hs.protein;
-  if (zero_copy) FA_HIP(hipMemcpyAsync(g->blob.p + o_tiles, img + o_tiles, image_bytes - o_tiles, hipMemcpyHostToDevice, st));
+  if (zero_copy) FA_HIP(hipMemcpyAsync(g->blob.p + at.tiles.at, img + at.tiles.at, image_bytes - at.tiles.at, hipMemcpyHostToDevice, st));
   else FA_HIP(hipMemcpyAsync(g->blob.p, img, image_bytes, hipMemcpyHostToDevice, st));
   const int64_t n_exc = (int64_t)hs.exc_pos.size();
   if (n_exc) { g->exc_pos.upload(hs.exc_pos, st); g->exc_val.upload(hs.exc_val, st); }
   g->store = StoreView();
-  g->store.packed = hs.protein ? nullptr : (const uint32_t *)((zero_copy ? img : g->blob.p) + o_packed);
-  g->store.bytes = hs.protein ? (const uint8_t *)(g->blob.p + o_bytes) : nullptr;
+  g->store.packed = hs.protein ? nullptr : (const uint32_t *)((zero_copy ? img : g->blob.p) + at.packed.at);
+  g->store.bytes = hs.protein ? (const uint8_t *)(g->blob.p + at.bytes.at) : nullptr;
   g->store.exc_pos = g->exc_pos.p; g->store.exc_val = g->exc_val.p; g->store.n_exc = n_exc;
-  g->tiles = (const Tile *)(g->blob.p + o_tiles);
-  g->d_frag_tile_lo = (const int32_t *)(g->blob.p + o_ftl);
+  g->tiles = (const Tile *)(g->blob.p + at.tiles.at);
+  g->d_frag_tile_lo = (const int32_t *)(g->blob.p + at.frag_tile_lo.at);
   // the CGI bins of a pass are indexed by the genome number relative to the first genome of the pass; passes start at
   // genome boundaries, so the per-fragment genome numbers are batch-wide and the kernel subtracts the pass's first genome
-  g->d_frag_query = (const int32_t *)(g->blob.p + o_fq);
-  g->d_frag_qseq = (const int32_t *)(g->blob.p + o_fs);
-  g->d_total_frag = (const int32_t *)(g->blob.p + o_tf);
+  g->d_frag_query = (const int32_t *)(g->blob.p + at.frag_query.at);
+  g->d_frag_qseq = (const int32_t *)(g->blob.p + at.frag_qseq.at);
+  g->d_total_frag = (const int32_t *)(g->blob.p + at.total_frag.at);
   // the staging image must stay untouched until the copy has left it (pageable copies return after staging, pinned ones
   // are asynchronous).  An image in the caller's pinned block (the one-query call: the block belongs to the workspace and
   // is not touched again before the call returns, and the pass runs on this same stream, behind the copy) needs no
@@ -1796,29 +1765,26 @@ static void fill_genomes(fa_genomes *g, const fa_params &P, hipStream_t st, cons
   lap(2);
 }
 
-static std::unique_ptr<fa_genomes> upload_genomes(const fa_params &P, hipStream_t st, const void *const *contigs, const int64_t *lengths,
-                                                  const int32_t *contig_genome, int64_t n_contigs, int32_t n_genomes, int width,
-                                                  float *host_ms = nullptr, std::unique_ptr<fa_genomes> reuse = nullptr, PinnedBuf *pin = nullptr,
-                                                  const PackedRef *packed = nullptr) {
-  std::unique_ptr<fa_genomes> g = reuse ? std::move(reuse) : std::unique_ptr<fa_genomes>(new fa_genomes());
-  fill_genomes(g.get(), P, st, contigs, lengths, contig_genome, n_contigs, n_genomes, width, host_ms, pin, packed, false);
-  return g;
-}
-
+// the records of packed files as one contig list, one genome per file
+struct PackedContigs {
+  std::vector<PackedRef> refs;
+  std::vector<int64_t> lens;
+  std::vector<int32_t> genome;
+  PackedContigs(const PackedFasta *files, int32_t n_paths) {
+    for (int32_t i = 0; i < n_paths; i++)
+      for (size_t r = 0; r < files[i].rec_len.size(); r++) { refs.push_back(PackedRef{&files[i], (int64_t)r, files[i].rec_len[r]}); lens.push_back(files[i].rec_len[r]); genome.push_back(i); }
+  }
+};
 // one genome per FASTA file, every file read + packed by its own task of the host pool (read_fasta_packed_many), then the
 // batch image assembled from the packed records and uploaded on the batch's own stream
 // genomes [first, first + count) of files packed already (one genome per file) as the batch `g`
 static void fill_genomes_from_packed(fa_mapper *m, fa_genomes *g, const PackedFasta *files, int32_t n_paths, bool pinned) {
-  std::vector<PackedRef> refs;
-  std::vector<int64_t> lens;
-  std::vector<int32_t> genome;
-  for (int32_t i = 0; i < n_paths; i++)
-    for (size_t r = 0; r < files[i].rec_len.size(); r++) { refs.push_back(PackedRef{&files[i], (int64_t)r, files[i].rec_len[r]}); lens.push_back(files[i].rec_len[r]); genome.push_back(i); }
+  const PackedContigs all(files, n_paths);
   bind_device(m->device);
   // (its own stream: a batch may be uploaded while another thread maps the previous one, Mapper.query_fasta_stream)
   if (!g->up_stream) FA_HIP(hipStreamCreateWithFlags(&g->up_stream, hipStreamNonBlocking));
-  fill_genomes(g, m->P, g->up_stream, nullptr, lens.data(), genome.data(), (int64_t)refs.size(), n_paths, 1, nullptr,
-               pinned ? &g->pin_image : nullptr, refs.data(), true);
+  fill_genomes(g, m->P, g->up_stream, nullptr, all.lens.data(), all.genome.data(), (int64_t)all.refs.size(), n_paths, 1, nullptr,
+               pinned ? &g->pin_image : nullptr, all.refs.data(), true);
 }
 static void fill_genomes_from_fasta(fa_mapper *m, fa_genomes *g, const char *const *paths, int32_t n_paths, bool pinned) {
   std::vector<PackedFasta> files;
@@ -1836,41 +1802,14 @@ struct fa_packed {
 };
 // the bookkeeping of fa_sketch_add_fasta_many over files that are packed already (s->mtx held by the caller)
 static void sketch_add_packed_files(fa_sketch *s, const PackedFasta *files, int32_t n_paths, int64_t *n_records, int64_t *n_short) {
+  const PackedContigs all(files, n_paths);
   std::vector<PackedRef> refs;
-  std::vector<int32_t> contig_ids;
-  std::vector<uint64_t> lengths;
-  std::vector<int32_t> by_file;
-  std::vector<int64_t> shorts((size_t)n_paths, 0);
-  int64_t counter = s->counter;
-  FA_REQUIRE(s->cur_total == 0 || n_paths == 0, FA_ERR_INVALID, "a genome is still open (add_contig without end_genome)");
-  for (int32_t i = 0; i < n_paths; i++) {
-    uint64_t total = 0;
-    for (size_t r = 0; r < files[i].rec_len.size(); r++) {
-      const int64_t length = files[i].rec_len[r];
-      FA_REQUIRE(length < (1LL << 31), FA_ERR_INVALID, "contig length must be below 2^31");
-      if (length >= s->P.window_size && length >= s->P.kmer_size) {      // _fastani.pyx:648
-        refs.push_back(PackedRef{&files[i], (int64_t)r, length});
-        contig_ids.push_back((int32_t)counter);
-      } else {
-        shorts[(size_t)i]++;
-      }
-      total += (uint64_t)(length / s->P.fragment_length) * s->P.fragment_length;   // :680
-      counter += 1;                                                                // :683
-    }
-    lengths.push_back(total);                            // :687
-    by_file.push_back((int32_t)counter);                 // :690
-  }
-  s->pending_contig.reserve(s->pending_contig.size() + contig_ids.size());
-  s->lengths.reserve(s->lengths.size() + lengths.size());
-  s->seqs_by_file.reserve(s->seqs_by_file.size() + by_file.size());
-  if (!refs.empty()) append_packed(s->pending, refs.data(), (int64_t)refs.size());
-  s->pending_contig.insert(s->pending_contig.end(), contig_ids.begin(), contig_ids.end());
-  s->counter = counter;
-  s->lengths.insert(s->lengths.end(), lengths.begin(), lengths.end());
-  s->seqs_by_file.insert(s->seqs_by_file.end(), by_file.begin(), by_file.end());
+  RefStage add(s->book, OpenGenome::REFUSE, n_paths);
+  add.genomes(s->P, all.lens.data(), all.genome.data(), (int64_t)all.refs.size(), n_paths, [&](int64_t c) { refs.push_back(all.refs[(size_t)c]); });
+  add.commit(s->book, [&] { if (!refs.empty()) append_packed(s->pending, refs.data(), (int64_t)refs.size()); });
   for (int32_t i = 0; i < n_paths; i++) {
     if (n_records) n_records[i] = (int64_t)files[i].rec_len.size();
-    if (n_short) n_short[i] = shorts[(size_t)i];
+    if (n_short) n_short[i] = add.n_short[(size_t)i];
   }
 }
 
@@ -1959,18 +1898,12 @@ void fa_sketch_free(fa_sketch *s) {
 int fa_sketch_add_contig(fa_sketch *s, const void *data, int64_t length, int char_width, int *added) {
   return guarded([&] {
     FA_REQUIRE(char_width == 1 || char_width == 2 || char_width == 4, FA_ERR_INVALID, "char_width must be 1, 2 or 4");
-    FA_REQUIRE(length >= 0 && length < (1LL << 31), FA_ERR_INVALID, "contig length must be below 2^31");
     std::lock_guard<std::mutex> lock(s->mtx);
     bind_device(s->device);
-    int ok = 0;
-    if (length >= s->P.window_size && length >= s->P.kmer_size) {      // _fastani.pyx:648
-      s->pending.append(data, char_width, length);
-      s->pending_contig.push_back((int32_t)s->counter);
-      ok = 1;
-    }
-    s->cur_total += (uint64_t)(length / s->P.fragment_length) * s->P.fragment_length;   // :680
-    s->counter += 1;                                                                     // :683
-    if (added) *added = ok;
+    RefStage add(s->book, OpenGenome::FOLD);
+    const bool ok = add.contig(s->P, length);
+    add.commit(s->book, [&] { if (ok) s->pending.append(data, char_width, length); });
+    if (added) *added = ok ? 1 : 0;
   });
 }
 struct fa_fasta { FastaFile f; };
@@ -2000,38 +1933,14 @@ int fa_sketch_add_fasta(fa_sketch *s, const char *path, int64_t *n_records, int6
     read_fasta_records(path, seqs);
     std::lock_guard<std::mutex> lock(s->mtx);
     bind_device(s->device);
-    // everything is validated and staged in locals first and committed only after the packer has succeeded: a record that
-    // is refused, or an allocation failure half-way, leaves the sketch exactly as it was (the reference keeps `total` in a
-    // local for the same reason, _fastani.pyx:618,680)
     std::vector<const void *> ptrs;
-    std::vector<int64_t> lens;
-    std::vector<int32_t> contig_ids;
-    int64_t shorts = 0, counter = s->counter;
-    uint64_t total = 0;
-    for (auto &q : seqs) {
-      const int64_t length = (int64_t)q.size;
-      FA_REQUIRE(length < (1LL << 31), FA_ERR_INVALID, "contig length must be below 2^31");
-      if (length >= s->P.window_size && length >= s->P.kmer_size) {      // _fastani.pyx:648
-        ptrs.push_back(q.data.get()); lens.push_back(length);
-        contig_ids.push_back((int32_t)counter);
-      } else {
-        shorts++;
-      }
-      total += (uint64_t)(length / s->P.fragment_length) * s->P.fragment_length;   // :680
-      counter += 1;                                                                // :683
-    }
-    s->pending_contig.reserve(s->pending_contig.size() + contig_ids.size());
-    s->lengths.reserve(s->lengths.size() + 1);
-    s->seqs_by_file.reserve(s->seqs_by_file.size() + 1);
-    if (!ptrs.empty()) s->pending.append_many(ptrs.data(), lens.data(), (int64_t)ptrs.size(), 1);
-    // commit (nothing below can throw: the vectors have room)
-    s->pending_contig.insert(s->pending_contig.end(), contig_ids.begin(), contig_ids.end());
-    s->counter = counter;
-    s->lengths.push_back(s->cur_total + total);          // :687
-    s->cur_total = 0;
-    s->seqs_by_file.push_back((int32_t)s->counter);      // :690
+    std::vector<int64_t> all, lens;
+    for (auto &q : seqs) all.push_back((int64_t)q.size);
+    RefStage add(s->book, OpenGenome::FOLD);
+    add.genomes(s->P, all.data(), nullptr, (int64_t)all.size(), 1, [&](int64_t c) { ptrs.push_back(seqs[(size_t)c].data.get()); lens.push_back(all[(size_t)c]); });
+    add.commit(s->book, [&] { if (!ptrs.empty()) s->pending.append_many(ptrs.data(), lens.data(), (int64_t)ptrs.size(), 1); });
     if (n_records) *n_records = (int64_t)seqs.size();
-    if (n_short) *n_short = shorts;
+    if (n_short) *n_short = add.n_short[0];
   });
 }
 // Many reference genomes at once from host buffers: contig c belongs to genome contig_genome[c] (non-decreasing); the effect of
@@ -2044,38 +1953,12 @@ int fa_sketch_add_genomes(fa_sketch *s, const void *const *contigs, const int64_
     FA_REQUIRE(n_contigs >= 0 && n_genomes >= 0 && (n_contigs == 0 || (contigs && lengths && contig_genome)), FA_ERR_INVALID, "null argument");
     std::lock_guard<std::mutex> lock(s->mtx);
     bind_device(s->device);
-    FA_REQUIRE(s->cur_total == 0 || n_genomes == 0, FA_ERR_INVALID, "a genome is still open (add_contig without end_genome)");
     std::vector<const void *> ptrs;
     std::vector<int64_t> lens;
-    std::vector<int32_t> contig_ids, by_file((size_t)n_genomes, 0), shorts((size_t)n_genomes, 0);
-    std::vector<uint64_t> totals((size_t)n_genomes, 0);
-    int64_t counter = s->counter;
-    int32_t cur = 0;
-    for (int64_t c = 0; c < n_contigs; c++) {
-      const int32_t gi = contig_genome[c];
-      FA_REQUIRE(gi >= cur && gi < n_genomes, FA_ERR_INVALID, "contig_genome must be non-decreasing and < n_genomes");
-      while (cur < gi) { by_file[(size_t)cur] = (int32_t)counter; cur++; }
-      const int64_t length = lengths[c];
-      FA_REQUIRE(length >= 0 && length < (1LL << 31), FA_ERR_INVALID, "contig length must be below 2^31");
-      if (length >= s->P.window_size && length >= s->P.kmer_size) {      // _fastani.pyx:648
-        ptrs.push_back(contigs[c]); lens.push_back(length); contig_ids.push_back((int32_t)counter);
-      } else {
-        shorts[(size_t)gi]++;
-      }
-      totals[(size_t)gi] += (uint64_t)(length / s->P.fragment_length) * s->P.fragment_length;   // :680
-      counter += 1;                                                                            // :683
-    }
-    while (cur < n_genomes) { by_file[(size_t)cur] = (int32_t)counter; cur++; }
-    s->pending_contig.reserve(s->pending_contig.size() + contig_ids.size());
-    s->lengths.reserve(s->lengths.size() + totals.size());
-    s->seqs_by_file.reserve(s->seqs_by_file.size() + by_file.size());
-    if (!ptrs.empty()) s->pending.append_many(ptrs.data(), lens.data(), (int64_t)ptrs.size(), char_width);
-    // commit (nothing below can throw: the vectors have room)
-    s->pending_contig.insert(s->pending_contig.end(), contig_ids.begin(), contig_ids.end());
-    s->counter = counter;
-    s->lengths.insert(s->lengths.end(), totals.begin(), totals.end());                           // :687
-    s->seqs_by_file.insert(s->seqs_by_file.end(), by_file.begin(), by_file.end());               // :690
-    if (n_short) for (int32_t i = 0; i < n_genomes; i++) n_short[i] = shorts[(size_t)i];
+    RefStage add(s->book, OpenGenome::REFUSE, n_genomes);
+    add.genomes(s->P, lengths, contig_genome, n_contigs, n_genomes, [&](int64_t c) { ptrs.push_back(contigs[c]); lens.push_back(lengths[c]); });
+    add.commit(s->book, [&] { if (!ptrs.empty()) s->pending.append_many(ptrs.data(), lens.data(), (int64_t)ptrs.size(), char_width); });
+    if (n_short) for (int32_t i = 0; i < n_genomes; i++) n_short[i] = (int32_t)add.n_short[(size_t)i];
   });
 }
 // Many reference genomes at once, one per FASTA file, in the order given: the files are read and packed concurrently (one
@@ -2149,26 +2032,20 @@ int fa_genomes_reload_packed(fa_mapper *m, fa_genomes *g, fa_packed *p, int32_t 
     std::shared_lock<std::shared_mutex> hold(p->mtx);
     FA_REQUIRE(first >= 0 && count >= 0 && (size_t)first + (size_t)count <= p->files.size(), FA_ERR_INVALID, "file range outside the packed set");
     FA_REQUIRE(p->protein == (m->P.alphabet_size != 4), FA_ERR_INVALID, "the files were packed for the other alphabet");
-    try {
-      fill_genomes_from_packed(m, g, p->files.data() + first, count, true);
-    } catch (...) {
-      g->n_genomes = 0; g->F = 0; g->ntiles = 0;
-      g->genome_frag_lo.assign(1, 0); g->total_fragments.clear(); g->total_length.clear(); g->n_short.clear();
-      throw;
-    }
+    try { fill_genomes_from_packed(m, g, p->files.data() + first, count, true); } catch (...) { g->reset_empty(); throw; }
   });
 }
 int fa_sketch_end_genome(fa_sketch *s) {
   return guarded([&] {
     std::lock_guard<std::mutex> lock(s->mtx);
     bind_device(s->device);
-    s->lengths.push_back(s->cur_total);                  // :687
-    s->cur_total = 0;
-    s->seqs_by_file.push_back((int32_t)s->counter);      // :690
+    RefStage add(s->book, OpenGenome::FOLD);
+    add.end_genome();
+    add.commit(s->book);
   });
 }
 int fa_sketch_abort_genome(fa_sketch *s) {
-  return guarded([&] { std::lock_guard<std::mutex> lock(s->mtx); s->cur_total = 0; });
+  return guarded([&] { std::lock_guard<std::mutex> lock(s->mtx); s->book.cur_total = 0; });
 }
 int fa_sketch_clear(fa_sketch *s) {
   return guarded([&] { std::lock_guard<std::mutex> lock(s->mtx); s->reset_data(); });
@@ -2182,43 +2059,45 @@ int fa_sketch_get_minimizers(fa_sketch *s, uint32_t *hash, int32_t *seq_id, int3
     bind_device(s->device);
     s->flush();
     if (s->nrec == 0) return;
-    s->rec_hash.download(hash, (size_t)s->nrec, s->stream);
-    s->rec_seq.download(seq_id, (size_t)s->nrec, s->stream);
-    s->rec_wpos.download(wpos, (size_t)s->nrec, s->stream);
+    s->rec.store(hash, seq_id, wpos, (size_t)s->nrec, hipMemcpyDeviceToHost, s->stream);
     FA_HIP(hipStreamSynchronize(s->stream));
   });
 }
 int fa_sketch_num_genomes(fa_sketch *s, int64_t *n) {
-  return guarded([&] { *n = (int64_t)s->lengths.size(); });
+  return guarded([&] { *n = (int64_t)s->book.lengths.size(); });
 }
 int fa_sketch_get_state(fa_sketch *s, uint64_t *lengths, int32_t *sbf, int64_t *counter) {
   return guarded([&] {
     std::lock_guard<std::mutex> lock(s->mtx);
     bind_device(s->device);
-    for (size_t i = 0; i < s->lengths.size(); i++) { lengths[i] = s->lengths[i]; sbf[i] = s->seqs_by_file[i]; }
-    *counter = s->counter;
+    for (size_t i = 0; i < s->book.lengths.size(); i++) { lengths[i] = s->book.lengths[i]; sbf[i] = s->book.seqs_by_file[i]; }
+    *counter = s->book.counter;
   });
 }
-int fa_sketch_set_state(fa_sketch *s, int64_t n_genomes, const uint64_t *lengths, const int32_t *sbf, int64_t counter,
-                        int64_t n_min, const uint32_t *hash, const int32_t *seq_id, const int32_t *wpos) {
+// the saved state of a sketch replaces its content; the records come from host (hipMemcpyHostToDevice) or device memory
+static int sketch_set_state(fa_sketch *s, int64_t n_genomes, const uint64_t *lengths, const int32_t *sbf, int64_t counter, int64_t n_min,
+                            const uint32_t *hash, const int32_t *seq_id, const int32_t *wpos, hipMemcpyKind kind) {
   return guarded([&] {
     std::lock_guard<std::mutex> lock(s->mtx);
     bind_device(s->device);
+    FA_REQUIRE(n_min >= 0 && n_genomes >= 0, FA_ERR_INVALID, "negative count");
     s->reset_data();
-    s->lengths.assign(lengths, lengths + n_genomes);
-    s->seqs_by_file.assign(sbf, sbf + n_genomes);
-    s->counter = counter;
+    s->book.lengths.assign(lengths, lengths + n_genomes);
+    s->book.seqs_by_file.assign(sbf, sbf + n_genomes);
+    s->book.counter = counter;
     if (n_min > 0) {
       require_device();
       bind_device(s->device);
       if (!s->stream) FA_HIP(hipStreamCreate(&s->stream));
-      s->rec_hash.upload(hash, (size_t)n_min, s->stream);
-      s->rec_seq.upload(seq_id, (size_t)n_min, s->stream);
-      s->rec_wpos.upload(wpos, (size_t)n_min, s->stream);
+      s->rec.load(hash, seq_id, wpos, (size_t)n_min, kind, s->stream);
       FA_HIP(hipStreamSynchronize(s->stream));
     }
     s->nrec = n_min;
   });
+}
+int fa_sketch_set_state(fa_sketch *s, int64_t n_genomes, const uint64_t *lengths, const int32_t *sbf, int64_t counter,
+                        int64_t n_min, const uint32_t *hash, const int32_t *seq_id, const int32_t *wpos) {
+  return sketch_set_state(s, n_genomes, lengths, sbf, counter, n_min, hash, seq_id, wpos, hipMemcpyHostToDevice);
 }
 
 // Device-pointer variants of the two calls above: the minimizer records never leave HBM.  Used by the multi-GPU index
@@ -2232,36 +2111,13 @@ int fa_sketch_get_minimizers_device(fa_sketch *s, int64_t cap, uint32_t *d_hash,
     s->flush();
     FA_REQUIRE(cap >= s->nrec, FA_ERR_INVALID, "destination holds fewer records than the sketch");
     if (s->nrec == 0) return;
-    const size_t n = (size_t)s->nrec;
-    FA_HIP(hipMemcpyAsync(d_hash, s->rec_hash.p, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, s->stream));
-    FA_HIP(hipMemcpyAsync(d_seq_id, s->rec_seq.p, n * sizeof(int32_t), hipMemcpyDeviceToDevice, s->stream));
-    FA_HIP(hipMemcpyAsync(d_wpos, s->rec_wpos.p, n * sizeof(int32_t), hipMemcpyDeviceToDevice, s->stream));
+    s->rec.store(d_hash, d_seq_id, d_wpos, (size_t)s->nrec, hipMemcpyDeviceToDevice, s->stream);
     FA_HIP(hipStreamSynchronize(s->stream));
   });
 }
 int fa_sketch_set_state_device(fa_sketch *s, int64_t n_genomes, const uint64_t *lengths, const int32_t *sbf, int64_t counter,
                                int64_t n_min, const uint32_t *d_hash, const int32_t *d_seq_id, const int32_t *d_wpos) {
-  return guarded([&] {
-    std::lock_guard<std::mutex> lock(s->mtx);
-    bind_device(s->device);
-    FA_REQUIRE(n_min >= 0 && n_genomes >= 0, FA_ERR_INVALID, "negative count");
-    s->reset_data();
-    s->lengths.assign(lengths, lengths + n_genomes);
-    s->seqs_by_file.assign(sbf, sbf + n_genomes);
-    s->counter = counter;
-    if (n_min > 0) {
-      require_device();
-      bind_device(s->device);
-      if (!s->stream) FA_HIP(hipStreamCreate(&s->stream));
-      const size_t n = (size_t)n_min;
-      s->rec_hash.ensure(n); s->rec_seq.ensure(n); s->rec_wpos.ensure(n);
-      FA_HIP(hipMemcpyAsync(s->rec_hash.p, d_hash, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, s->stream));
-      FA_HIP(hipMemcpyAsync(s->rec_seq.p, d_seq_id, n * sizeof(int32_t), hipMemcpyDeviceToDevice, s->stream));
-      FA_HIP(hipMemcpyAsync(s->rec_wpos.p, d_wpos, n * sizeof(int32_t), hipMemcpyDeviceToDevice, s->stream));
-      FA_HIP(hipStreamSynchronize(s->stream));
-    }
-    s->nrec = n_min;
-  });
+  return sketch_set_state(s, n_genomes, lengths, sbf, counter, n_min, d_hash, d_seq_id, d_wpos, hipMemcpyDeviceToDevice);
 }
 
 int fa_sketch_index(fa_sketch *s, fa_mapper **out) {
@@ -2276,18 +2132,14 @@ int fa_sketch_index(fa_sketch *s, fa_mapper **out) {
     m->device = s->device;
     if (m->device < 0) FA_HIP(hipGetDevice(&m->device));
     FA_HIP(hipStreamCreate(&m->stream));
-    m->rec_hash = std::move(s->rec_hash);
-    m->rec_seq = std::move(s->rec_seq);
-    m->rec_wpos = std::move(s->rec_wpos);
     m->N = s->nrec;
-    m->rec_hash.ensure((size_t)m->N + 4, true, m->stream, (size_t)m->N);
-    m->rec_seq.ensure((size_t)m->N + 4, true, m->stream, (size_t)m->N);
-    m->rec_wpos.ensure((size_t)m->N + 4, true, m->stream, (size_t)m->N);
-    m->lengths = s->lengths;
-    m->seqs_by_file = s->seqs_by_file;
-    if (!m->seqs_by_file.empty() && m->seqs_by_file.back() < (int32_t)s->counter) {
+    s->rec.reserve((size_t)m->N + 4, (size_t)m->N, m->stream);
+    m->rec_hash = std::move(s->rec.hash); m->rec_seq = std::move(s->rec.seq); m->rec_wpos = std::move(s->rec.wpos);
+    m->lengths = s->book.lengths;
+    m->seqs_by_file = s->book.seqs_by_file;
+    if (!m->seqs_by_file.empty() && m->seqs_by_file.back() < (int32_t)s->book.counter) {
       // contigs added after the last end_genome belong to no genome; keep the tables consistent
-      m->seqs_by_file.back() = (int32_t)s->counter;
+      m->seqs_by_file.back() = (int32_t)s->book.counter;
     }
     build_index(*m);
     s->reset_data();                                     // _fastani.pyx:803-804
@@ -2398,7 +2250,9 @@ int fa_genomes_upload(fa_mapper *m, const void *const *contigs, const int64_t *l
   return guarded([&] {
     std::lock_guard<std::mutex> lock(m->mtx);
     bind_device(m->device);
-    *out = upload_genomes(m->P, m->stream, contigs, lengths, contig_genome, n_contigs, n_genomes, char_width).release();
+    auto g = std::make_unique<fa_genomes>();
+    fill_genomes(g.get(), m->P, m->stream, contigs, lengths, contig_genome, n_contigs, n_genomes, char_width, nullptr, nullptr, nullptr, false);
+    *out = g.release();
   });
 }
 int fa_genomes_upload_fasta(fa_mapper *m, const char *const *paths, int32_t n_paths, fa_genomes **out) {
@@ -2412,13 +2266,7 @@ int fa_genomes_upload_fasta(fa_mapper *m, const char *const *paths, int32_t n_pa
 int fa_genomes_reload_fasta(fa_mapper *m, fa_genomes *g, const char *const *paths, int32_t n_paths) {
   return guarded([&] {
     FA_REQUIRE(g && n_paths >= 0, FA_ERR_INVALID, "null batch or negative count");
-    try {
-      fill_genomes_from_fasta(m, g, paths, n_paths, true);
-    } catch (...) {
-      g->n_genomes = 0; g->F = 0; g->ntiles = 0;                      // a failed refill leaves an empty (but valid) batch
-      g->genome_frag_lo.assign(1, 0); g->total_fragments.clear(); g->total_length.clear(); g->n_short.clear();
-      throw;
-    }
+    try { fill_genomes_from_fasta(m, g, paths, n_paths, true); } catch (...) { g->reset_empty(); throw; }
   });
 }
 void fa_genomes_free(fa_genomes *g) { delete g; }
@@ -2530,8 +2378,8 @@ static int query_one(fa_mapper *m, const void *const *contigs, const int64_t *le
     WorkspaceLease lease(*m);
     std::vector<int32_t> cg((size_t)std::max(n_contigs, 1), 0);
     float host_ms[3] = {0, 0, 0};
-    auto g = upload_genomes(m->P, lease.w->stream, contigs, lengths, cg.data(), n_contigs, 1, char_width, host_ms,
-                            std::move(lease.w->query_batch), &lease.w->pin_image);
+    std::unique_ptr<fa_genomes> g = lease.w->query_batch ? std::move(lease.w->query_batch) : std::make_unique<fa_genomes>();
+    fill_genomes(g.get(), m->P, lease.w->stream, contigs, lengths, cg.data(), n_contigs, 1, char_width, host_ms, &lease.w->pin_image, nullptr, false);
     if (n_short) *n_short = g->n_short[0];
     if (total_fragments) *total_fragments = g->total_fragments[0];
     if (total_length) *total_length = g->total_length[0];
@@ -2657,14 +2505,14 @@ int fa_debug_sketch_sequence(const fa_params *params, const void *data, int64_t 
     s.reset_data();
     if (length >= params->kmer_size) {
       s.pending.append(data, char_width, length);
-      s.pending_contig.push_back(0);
+      s.book.pending_contig.push_back(0);
     }
     s.flush();
     *n = s.nrec;
     size_t c = (size_t)std::min<int64_t>(s.nrec, cap);
     if (c) {
-      s.rec_hash.download(hash, c, s.stream);
-      s.rec_wpos.download(wpos, c, s.stream);
+      s.rec.hash.download(hash, c, s.stream);
+      s.rec.wpos.download(wpos, c, s.stream);
       FA_HIP(hipStreamSynchronize(s.stream));
     }
     if (s.stream) (void)hipStreamDestroy(s.stream);

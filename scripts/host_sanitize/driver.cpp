@@ -1,7 +1,8 @@
 // Host-side pieces of libfastani_hip under AddressSanitizer + UBSan, and (separately) ThreadSanitizer, on the CPU:
 //   the 2-bit packer (fa_host.h: AVX2 path, scalar exception path, wide characters, protein bytes) on the persistent thread
 //   pool, the memory-mapped FASTA reader (fa_fasta.h), the statistics tables (fa_stats.h), the workspace lease and the
-//   pinned-word spin (fa_lease.h), the policy of a query pass (fa_policy.h: every rule at the boundaries where it turns).  Inputs: the edge cases of tests/test_gpu_parity.py::test_minimizer_streams and
+//   pinned-word spin (fa_lease.h), the policy of a query pass (fa_policy.h: every rule at the boundaries where it turns), the contig bookkeeping of
+//   ingest (fa_ingest.h: the reference roads and the plan of a query batch against restatements of _fastani.pyx).  Inputs: the edge cases of tests/test_gpu_parity.py::test_minimizer_streams and
 //   tests/test_fasta.py, plus four concurrent clients.  No HIP: these headers are what fa_engine.hip includes for the same jobs.
 // Built and run by scripts/host_sanitize.sh; exits non-zero on any mismatch (the sanitizers abort on their own findings).
 #include <unistd.h>
@@ -15,6 +16,7 @@
 
 #include "../../pyfastani_amd/csrc/fa_fasta.h"
 #include "../../pyfastani_amd/csrc/fa_host.h"
+#include "../../pyfastani_amd/csrc/fa_ingest.h"
 #include "../../pyfastani_amd/csrc/fa_lease.h"
 #include "../../pyfastani_amd/csrc/fa_policy.h"
 #include "../../pyfastani_amd/csrc/fa_stats.h"
@@ -570,6 +572,266 @@ static void test_policy_frag_order() {
   CHECK(n == 0 || (is_perm(out, 120) && n * 1.0 <= 1.15 * 120 + 7), "uneven genomes: %u", n);
 }
 
+// ---- the contig bookkeeping of ingest (fa_ingest.h) against restatements that follow _fastani.pyx one contig at a time ----
+typedef std::vector<std::vector<int64_t>> GenomeLens;             // contig lengths, genome by genome
+static fa_params ingest_params(int k, int w, int frag, bool protein = false) {
+  fa_params P; memset(&P, 0, sizeof P);
+  P.kmer_size = k; P.window_size = w; P.fragment_length = frag; P.alphabet_size = protein ? 20 : 4;
+  return P;
+}
+static const int64_t kLenMax = (1LL << 31) - 1;
+// the lengths at which a rule turns: zero, the admission rule, whole fragments, the limit
+static std::vector<int64_t> edge_lengths(const fa_params &P) {
+  const int64_t lo = std::min(P.window_size, P.kmer_size), hi = std::max(P.window_size, P.kmer_size), f = P.fragment_length;
+  return {0, lo - 1, lo, hi - 1, hi, f - 1, f, f + 1, 2 * f - 1, kLenMax};
+}
+// a leading and a trailing empty genome, every edge length, a genome of short contigs only, empty genomes in between, random ones
+static GenomeLens ingest_genomes(const fa_params &P, uint64_t seed) {
+  std::mt19937_64 rng(seed);
+  const std::vector<int64_t> edges = edge_lengths(P);
+  GenomeLens g;
+  g.push_back({});
+  g.push_back(edges);
+  g.push_back({0, std::min(P.window_size, P.kmer_size) - 1, 0});
+  for (int i = 0; i < 12; i++) {
+    std::vector<int64_t> contigs;
+    const int n = i % 4 == 3 ? 0 : 1 + (int)(rng() % 7);
+    for (int c = 0; c < n; c++) contigs.push_back(rng() % 3 == 0 ? (int64_t)(rng() % (5 * (uint64_t)P.fragment_length)) : edges[rng() % (edges.size() - 1)]);
+    g.push_back(contigs);
+  }
+  g.push_back({});
+  return g;
+}
+static void flatten(const GenomeLens &g, size_t first, size_t count, std::vector<int64_t> &lens, std::vector<int32_t> &genome) {
+  lens.clear(); genome.clear();
+  for (size_t i = 0; i < count; i++) for (int64_t l : g[first + i]) { lens.push_back(l); genome.push_back((int32_t)i); }
+}
+
+// Sketch._add_draft, one genome (_fastani.pyx:610-690); `carried`: what earlier contigs without a genome have left
+struct PlainBook { int64_t counter = 0; uint64_t carried = 0; std::vector<uint64_t> lengths; std::vector<int32_t> by_file, sketched; std::vector<int64_t> shorts; };
+static void plain_add_draft(PlainBook &b, const fa_params &P, const std::vector<int64_t> &contigs) {
+  uint64_t total = b.carried;
+  int64_t shorts = 0;
+  for (int64_t len : contigs) {
+    if (len < P.window_size || len < P.kmer_size) shorts++;       // :648, :670-677
+    else b.sketched.push_back((int32_t)b.counter);
+    total += (uint64_t)(len - len % P.fragment_length);           // :680
+    b.counter++;                                                  // :683
+  }
+  b.carried = 0;
+  b.lengths.push_back(total);                                     // :687
+  b.by_file.push_back((int32_t)b.counter);                        // :690
+  b.shorts.push_back(shorts);
+}
+static bool same_book(const RefBook &a, const RefBook &b) {
+  return a.counter == b.counter && a.cur_total == b.cur_total && a.lengths == b.lengths && a.seqs_by_file == b.seqs_by_file && a.pending_contig == b.pending_contig;
+}
+static bool book_is(const RefBook &a, const PlainBook &w) {
+  return a.counter == w.counter && a.cur_total == w.carried && a.lengths == w.lengths && a.seqs_by_file == w.by_file && a.pending_contig == w.sketched;
+}
+// does `fn` fail with `code` and exactly `text`?
+template <class Fn> static bool refused(Fn fn, int code, const char *text) {
+  try { fn(); } catch (const Error &e) { return e.code == code && std::string(e.what()) == text; }
+  return false;
+}
+
+static void test_ingest_reference_roads(const fa_params &P, uint64_t seed) {
+  const GenomeLens genomes = ingest_genomes(P, seed);
+  PlainBook want;
+  for (auto &g : genomes) plain_add_draft(want, P, g);
+  std::vector<int64_t> lens; std::vector<int32_t> genome;
+  // contig by contig with end_genome (add_draft)
+  RefBook one;
+  for (auto &g : genomes) {
+    for (int64_t len : g) { RefStage add(one, OpenGenome::FOLD); const bool in = add.contig(P, len); add.commit(one); CHECK(in == ref_admitted(P, len), "contig(%lld) and the admission rule", (long long)len); }
+    RefStage add(one, OpenGenome::FOLD); add.end_genome(); add.commit(one);
+  }
+  CHECK(book_is(one, want), "contig by contig: the book differs from the restatement (k %d w %d)", P.kmer_size, P.window_size);
+  // all at once (add_genomes)
+  RefBook all;
+  {
+    flatten(genomes, 0, genomes.size(), lens, genome);
+    std::vector<int64_t> admitted_at;
+    RefStage add(all, OpenGenome::REFUSE, (int64_t)genomes.size());
+    add.genomes(P, lens.data(), genome.data(), (int64_t)lens.size(), (int32_t)genomes.size(), [&](int64_t c) { admitted_at.push_back(c); });
+    bool packed = false;
+    add.commit(all, [&] { packed = true; CHECK(all.counter == 0 && all.lengths.empty(), "the packer runs before anything is inserted"); });
+    CHECK(packed && add.n_short == want.shorts, "all at once: packer call and short counts");
+    CHECK(admitted_at.size() == want.sketched.size(), "all at once: %zu admitted vs %zu", admitted_at.size(), want.sketched.size());
+    for (size_t i = 0; i < admitted_at.size() && i < want.sketched.size(); i++) CHECK(admitted_at[i] == want.sketched[i], "all at once: admitted contig %zu", i);
+  }
+  CHECK(book_is(all, want), "all at once: the book differs from the restatement");
+  // file by file (add_fasta): one genome per call, no genome numbers
+  RefBook files;
+  for (size_t i = 0; i < genomes.size(); i++) {
+    RefStage add(files, OpenGenome::FOLD);
+    add.genomes(P, genomes[i].data(), nullptr, (int64_t)genomes[i].size(), 1, [](int64_t) {});
+    add.commit(files);
+    CHECK(add.n_short.size() == 1 && add.n_short[0] == want.shorts[i], "file by file: short count of genome %zu", i);
+  }
+  CHECK(book_is(files, want), "file by file: the book differs from the restatement");
+  // packed files, a few per call (add_fasta_many / add_packed)
+  RefBook packed;
+  for (size_t i = 0; i < genomes.size(); i += 4) {
+    const size_t n = std::min<size_t>(4, genomes.size() - i);
+    flatten(genomes, i, n, lens, genome);
+    RefStage add(packed, OpenGenome::REFUSE, (int64_t)n);
+    add.genomes(P, lens.data(), genome.data(), (int64_t)lens.size(), (int32_t)n, [](int64_t) {});
+    add.commit(packed);
+  }
+  CHECK(book_is(packed, want), "packed files: the book differs from the restatement");
+  CHECK(same_book(one, all) && same_book(all, files) && same_book(files, packed), "the four roads leave equal books");
+}
+
+static void test_ingest_reference_refusals(const fa_params &P) {
+  const char *too_long = "contig length must be below 2^31", *bad_genome = "contig_genome must be non-decreasing and < n_genomes",
+             *open = "a genome is still open (add_contig without end_genome)";
+  const int64_t f = P.fragment_length;
+  RefBook book;
+  { RefStage add(book, OpenGenome::FOLD); const int64_t l[3] = {3 * f, 0, f + 1}; add.genomes(P, l, nullptr, 3, 1, [](int64_t) {}); add.commit(book); }
+  const RefBook before = book;
+  auto road = [&](std::vector<int64_t> lens, std::vector<int32_t> genome, int32_t n_genomes) {
+    RefStage add(book, OpenGenome::REFUSE, n_genomes);
+    add.genomes(P, lens.data(), genome.data(), (int64_t)lens.size(), n_genomes, [](int64_t) {});
+    add.commit(book);
+  };
+  CHECK(refused([&] { road({f, 2 * f, 1LL << 31}, {0, 0, 1}, 2); }, FA_ERR_INVALID, too_long) && same_book(book, before), "2^31 is refused, the book untouched");
+  CHECK(refused([&] { road({f, 2 * f, -1}, {0, 0, 1}, 2); }, FA_ERR_INVALID, too_long) && same_book(book, before), "-1 is refused, the book untouched");
+  CHECK(refused([&] { RefStage add(book, OpenGenome::FOLD); add.contig(P, 1LL << 31); add.commit(book); }, FA_ERR_INVALID, too_long) && same_book(book, before), "one contig of 2^31");
+  CHECK(refused([&] { road({f, 2 * f, f, f}, {0, 1, 1, 0}, 2); }, FA_ERR_INVALID, bad_genome) && same_book(book, before), "a decreasing contig_genome");
+  CHECK(refused([&] { road({f, 2 * f, f, f}, {0, 1, 1, 2}, 2); }, FA_ERR_INVALID, bad_genome) && same_book(book, before), "contig_genome >= n_genomes");
+  CHECK(refused([&] { road({f}, {-1}, 2); }, FA_ERR_INVALID, bad_genome) && same_book(book, before), "a negative contig_genome");
+  // a packer that fails: the book is as before
+  bool threw = false;
+  try {
+    RefStage add(book, OpenGenome::FOLD); const int64_t l[2] = {f, 5 * f};
+    add.genomes(P, l, nullptr, 2, 1, [](int64_t) {});
+    add.commit(book, [] { throw std::bad_alloc(); });
+  } catch (const std::bad_alloc &) { threw = true; }
+  CHECK(threw && same_book(book, before), "a failing packer leaves the book as it was");
+  // a genome that add_contig left open: folded by add_fasta's policy, refused by the other
+  { RefStage add(book, OpenGenome::FOLD); add.contig(P, 2 * f + 1); add.commit(book); }
+  CHECK(book.cur_total == (uint64_t)(2 * f) && book.counter == before.counter + 1 && book.lengths == before.lengths, "an open genome carries its length");
+  const RefBook opened = book;
+  CHECK(refused([&] { road({f}, {0}, 1); }, FA_ERR_INVALID, open) && same_book(book, opened), "an open genome is refused by the batch roads");
+  CHECK(refused([&] { road({}, {}, 1); }, FA_ERR_INVALID, open) && same_book(book, opened), "... also by a batch of one genome without contigs");
+  road({}, {}, 0);
+  CHECK(same_book(book, opened), "a batch road that brings no genome changes nothing beside an open genome");
+  { RefStage add(book, OpenGenome::FOLD); const int64_t l[2] = {f, 3 * f - 1}; add.genomes(P, l, nullptr, 2, 1, [](int64_t) {}); add.commit(book); }
+  CHECK(book.cur_total == 0 && book.lengths.back() == (uint64_t)(5 * f) && book.seqs_by_file.back() == (int32_t)before.counter + 3, "add_fasta folds the open genome in");
+}
+
+// Mapper._query_draft over a batch (_fastani.pyx:985, 1061-1105), every fragment written out
+struct PlainBatch { std::vector<int32_t> frag_query, frag_qseq; std::vector<int64_t> genome_frag_lo, contig_frag_lo; std::vector<uint64_t> tf, tl; std::vector<int32_t> ns; uint64_t bases_in_frags = 0; size_t store = 0; };
+static PlainBatch plain_batch(const fa_params &P, const GenomeLens &genomes) {
+  PlainBatch b;
+  const int64_t frag = P.fragment_length;
+  for (size_t g = 0; g < genomes.size(); g++) {
+    b.genome_frag_lo.push_back((int64_t)b.frag_query.size());
+    uint64_t nfrag = 0, length = 0; int32_t shorts = 0;
+    for (int64_t len : genomes[g]) {
+      if (len < P.window_size && len < P.kmer_size && len < frag) { shorts++; continue; }              // :1061-1070
+      if (len >= frag) b.contig_frag_lo.push_back((int64_t)b.frag_query.size());
+      for (int64_t i = 0; (i + 1) * frag <= len; i++) { b.frag_query.push_back((int32_t)g); b.frag_qseq.push_back((int32_t)(nfrag + (uint64_t)i)); }   // :985
+      const int64_t n = len / frag;                                                                  // :1097
+      nfrag += (uint64_t)n; length += (uint64_t)len;                                                  // :1104, :1105
+      b.bases_in_frags += (uint64_t)(n * frag);
+      if (n > 0) b.store += (size_t)((n * frag + 63) / 64 * 64);
+    }
+    b.tf.push_back(nfrag); b.tl.push_back(length); b.ns.push_back(shorts);
+  }
+  b.genome_frag_lo.push_back((int64_t)b.frag_query.size());
+  return b;
+}
+static const int kTilePositions = 1024;                            // TILE and sizeof(Tile) of fa_sketch.hip.h
+static const size_t kTileBytes = 32;
+static void check_layout(const BatchPlan &b, bool protein, int32_t n_genomes, const char *what) {
+  const BatchLayout::Part *parts[7] = {&b.at.packed, &b.at.bytes, &b.at.tiles, &b.at.frag_tile_lo, &b.at.frag_query, &b.at.frag_qseq, &b.at.total_frag};
+  const size_t need[7] = {protein ? 0 : b.bases / 4 + 4, protein ? b.bases + 1 : 0, (size_t)b.ntiles * kTileBytes, ((size_t)b.F + 1) * 4, (size_t)b.F * 4, (size_t)b.F * 4, (size_t)n_genomes * 4};
+  size_t end = 0;
+  for (int i = 0; i < 7; i++) {
+    CHECK(parts[i]->at % 16 == 0 && parts[i]->at == end, "%s: part %d starts at %zu, the one before ends at %zu", what, i, parts[i]->at, end);
+    CHECK(parts[i]->bytes >= need[i], "%s: part %d holds %zu bytes, %zu are written", what, i, parts[i]->bytes, need[i]);
+    end = parts[i]->at + parts[i]->bytes;
+  }
+  CHECK(end == b.at.image_bytes, "%s: the parts end at %zu, the image at %zu", what, end, b.at.image_bytes);
+  CHECK((protein ? b.at.packed.bytes : b.at.bytes.bytes) == 0, "%s: the image of the other alphabet is empty", what);
+}
+static void test_ingest_batch_plan(const fa_params &P, uint64_t seed) {
+  GenomeLens genomes = ingest_genomes(P, seed);
+  const int64_t min_len = std::min<int64_t>(std::min(P.window_size, P.kmer_size), P.fragment_length);
+  if (min_len < P.fragment_length) genomes.push_back({min_len, P.fragment_length - 1});     // mapped, but no fragment
+  const bool protein = P.alphabet_size != 4;
+  const PlainBatch want = plain_batch(P, genomes);
+  std::vector<int64_t> lens; std::vector<int32_t> genome;
+  flatten(genomes, 0, genomes.size(), lens, genome);
+  const BatchPlan b = plan_batch(P, lens.data(), genome.data(), (int64_t)lens.size(), (int32_t)genomes.size(), kTilePositions, kTileBytes);
+  CHECK(b.genome_frag_lo == want.genome_frag_lo && b.contig_frag_lo == want.contig_frag_lo, "batch plan: fragment ranges of genomes and contigs");
+  CHECK(b.total_fragments == want.tf && b.total_length == want.tl && b.n_short == want.ns, "batch plan: per-genome counters");
+  CHECK(b.F == (int64_t)want.frag_query.size() && b.total_bases == want.bases_in_frags && b.bases == want.store, "batch plan: F %lld, bases %llu", (long long)b.F, (unsigned long long)b.total_bases);
+  const int64_t npos = (int64_t)P.fragment_length - P.kmer_size + 1, per = npos > 0 ? (npos + kTilePositions - 1) / kTilePositions : 0;
+  CHECK(b.tiles_per_frag == per && b.ntiles == b.F * per, "batch plan: %lld tiles", (long long)b.ntiles);
+  if (min_len < P.fragment_length) CHECK(b.n_short.back() == 0 && b.total_fragments.back() == 0 && b.total_length.back() == (uint64_t)(min_len + P.fragment_length - 1), "a contig below one fragment counts in the length only");
+  // the per-fragment tables as fill_genomes writes them from the jobs
+  std::vector<int32_t> frag_query((size_t)b.F, -1), frag_qseq((size_t)b.F, -1);
+  CHECK(b.jobs.size() == b.use_len.size() && b.jobs.size() == b.contig_frag_lo.size(), "batch plan: one entry per contig that holds fragments");
+  for (size_t j = 0; j < b.jobs.size(); j++) {
+    const ContigJob &cj = b.jobs[j];
+    CHECK(cj.si == (int64_t)j && cj.gi == genome[(size_t)cj.c] && b.use_len[j] == cj.nfrag * P.fragment_length && b.use_len[j] <= lens[(size_t)cj.c] && cj.nf0 + cj.nfrag <= b.F, "batch plan: job %zu", j);
+    if (cj.nf0 + cj.nfrag > b.F) break;
+    for (int64_t i = 0; i < cj.nfrag; i++) { frag_query[(size_t)(cj.nf0 + i)] = cj.gi; frag_qseq[(size_t)(cj.nf0 + i)] = (int32_t)(cj.q0 + i); }
+  }
+  CHECK(frag_query == want.frag_query && frag_qseq == want.frag_qseq, "batch plan: frag_query / frag_qseq");
+  check_layout(b, protein, (int32_t)genomes.size(), protein ? "protein batch" : "batch");
+}
+static void test_ingest_batch_limits() {
+  fa_params P = ingest_params(16, 24, 3000);
+  const char *bad_genome = "contig_genome must be non-decreasing and < n_genomes", *too_many = "too many fragments in one batch";
+  BatchPlan b = plan_batch(P, nullptr, nullptr, 0, 3, kTilePositions, kTileBytes);
+  CHECK(b.F == 0 && b.ntiles == 0 && b.jobs.empty() && b.genome_frag_lo == std::vector<int64_t>(4, 0) && b.n_short == std::vector<int32_t>(3, 0), "three genomes without contigs");
+  check_layout(b, false, 3, "batch without contigs");
+  b = plan_batch(P, nullptr, nullptr, 0, 0, kTilePositions, kTileBytes);
+  CHECK(b.F == 0 && b.genome_frag_lo == std::vector<int64_t>(1, 0) && b.total_fragments.empty(), "no genomes");
+  check_layout(b, false, 0, "batch without genomes");
+  const int64_t some[3] = {3000, 9000, 3000};
+  const int32_t down[3] = {0, 1, 0}, over[3] = {0, 1, 2};
+  CHECK(refused([&] { plan_batch(P, some, down, 3, 2, kTilePositions, kTileBytes); }, FA_ERR_INVALID, bad_genome), "a decreasing contig_genome in a batch");
+  CHECK(refused([&] { plan_batch(P, some, over, 3, 2, kTilePositions, kTileBytes); }, FA_ERR_INVALID, bad_genome), "contig_genome >= n_genomes in a batch");
+  CHECK(refused([&] { plan_batch(P, some, nullptr, 1, 0, kTilePositions, kTileBytes); }, FA_ERR_INVALID, bad_genome), "a contig without a genome");
+  // F: 2^31 - 2 fragments fit, 2^31 - 1 do not (one tile per fragment)
+  P = ingest_params(1, 1, 1);
+  int64_t len = kLenMax - 1;
+  b = plan_batch(P, &len, nullptr, 1, 1, kTilePositions, kTileBytes);
+  CHECK(b.F == kLenMax - 1 && b.ntiles == b.F && b.jobs.size() == 1, "2^31 - 2 fragments");
+  check_layout(b, false, 1, "largest batch");
+  len = kLenMax;
+  CHECK(refused([&] { plan_batch(P, &len, nullptr, 1, 1, kTilePositions, kTileBytes); }, FA_ERR_UNSUPPORTED, too_many), "2^31 - 1 fragments are refused");
+  const int64_t two[2] = {kLenMax - 1, 1};
+  CHECK(refused([&] { plan_batch(P, two, nullptr, 2, 1, kTilePositions, kTileBytes); }, FA_ERR_UNSUPPORTED, too_many), "... from two contigs as well");
+  // tiles: two per fragment; 2^30 - 1 fragments fit, 2^30 do not
+  P = ingest_params(16, 24, 2063);
+  const int64_t per_contig = kLenMax / 2063;
+  for (int64_t F : {(1LL << 30) - 1, 1LL << 30}) {
+    std::vector<int64_t> lens;
+    for (int64_t left = F; left > 0; left -= std::min(left, per_contig)) lens.push_back(std::min(left, per_contig) * 2063 + 7);
+    if (F < (1LL << 30)) {
+      b = plan_batch(P, lens.data(), nullptr, (int64_t)lens.size(), 1, kTilePositions, kTileBytes);
+      CHECK(b.F == F && b.tiles_per_frag == 2 && b.ntiles == (1LL << 31) - 2, "2^31 - 2 tiles");
+    } else CHECK(refused([&] { plan_batch(P, lens.data(), nullptr, (int64_t)lens.size(), 1, kTilePositions, kTileBytes); }, FA_ERR_UNSUPPORTED, too_many), "2^31 tiles are refused");
+  }
+}
+static void test_ingest() {
+  // w > k (the default sketch) and w < k; the second also at 200-base fragments, where a mapped contig may hold no fragment
+  const fa_params settings[] = {ingest_params(16, 24, 3000), ingest_params(21, 15, 200), ingest_params(5, 1, 100, true)};
+  uint64_t seed = 4100;
+  for (const fa_params &P : settings) {
+    test_ingest_reference_roads(P, seed++);
+    test_ingest_reference_refusals(P);
+    test_ingest_batch_plan(P, seed++);
+  }
+  test_ingest_batch_limits();
+}
+
 int main() {
   for (int width : {1, 2, 4}) test_packer(false, width, 1);
   test_packer(true, 1, 1);
@@ -589,6 +851,7 @@ int main() {
   test_policy_l1_plan();
   test_policy_fuse_backoff();
   test_policy_frag_order();
+  test_ingest();
   // an item that throws inside the pool reaches the caller, and the pool keeps working afterwards
   bool caught = false;
   try { HostPool::get().parallel_for(64, [](size_t i) { if (i == 13) throw Error(FA_ERR_NOMEM, "item"); }); } catch (const Error &e) { caught = e.code == FA_ERR_NOMEM; }
