@@ -312,6 +312,48 @@ int fa_mapper_query_genomes_mappings(fa_mapper *m, fa_genomes *g, int32_t first,
 int fa_mapper_query_genomes_mappings_stream(fa_mapper *m, fa_genomes *g, int32_t first, int32_t count, fa_cgi_row *rows, int64_t cap,
                                             int64_t *n_rows, int rows_device, fa_mapping_sink sink, void *user, int64_t *n_maps);
 
+/* ---- the hit table of an all-vs-all, reduced on the device ------------- */
+/* What an all-vs-all over ONE genome set is run for: the symmetric identity of every genome pair and the groups of genomes
+ * above a cut-off (species clusters at 95, dereplication at 99) -- FastANI's matrix output (cgi::outputPhylip,
+ * include/fastani/cgi/compute_core_identity.pxd:39-51) and the single-linkage step that follows it.  Genomes are numbered
+ * 0 .. n_genomes-1; query_id and ref_genome_id of the rows index the same list.
+ *   1. Filter.  A row (q, r) with q == r never forms a pair.  Another row survives iff
+ *        (float)((uint64_t)count_seq * fragment_length) >= (float)min(query_lengths[q], reference_lengths[r]) * min_fraction
+ *      in float32 (_fastani.pyx:1121-1132).  An id outside [0, n_genomes), or the same (q, r) in two rows of the table, is
+ *      FA_ERR_INVALID and nothing is returned.
+ *   2. Pair (a, b), a < b: identity_ab is the identity of the surviving row with query a and reference b, identity_ba of the
+ *      other direction, a missing direction NaN; identity is the float64 mean of the two when both survive, else the one that
+ *      does.  Pairs come out sorted by (a, b), and the same input gives the same bytes on every run.
+ *   3. Edge: a pair with identity >= (double)min_identity that, with reciprocal != 0, also has both directions.
+ *   4. Clusters: the connected components of the edges.  labels[g] is the smallest genome number in g's component (a genome
+ *      without an edge labels itself); *n_clusters is the number of g with labels[g] == g. */
+typedef struct fa_pair {
+  int32_t a, b;               /* a < b */
+  float identity_ab;          /* query a on reference b, NaN when that row is missing or filtered */
+  float identity_ba;          /* query b on reference a */
+  double identity;            /* the symmetric value */
+} fa_pair;                    /* 24 bytes */
+typedef struct fa_table_params {
+  float min_fraction;         /* minFraction of the filter */
+  int32_t fragment_length;    /* minReadLength the rows were mapped with (>= 1) */
+  float min_identity;         /* the cut-off of an edge (fa_table_clusters only) */
+  int32_t reciprocal;         /* != 0: an edge needs both directions (fa_table_clusters only) */
+} fa_table_params;            /* 16 bytes */
+/* All pairs of the table (not only the edges).  rows_device / pairs_device != 0: `rows` / `pairs` are DEVICE pointers, as on
+ * fa_mapper_query_genomes; the two length arrays (n_genomes entries each) are host memory.  pairs == NULL only counts.  A `cap`
+ * below the number of pairs is FA_ERR_INVALID: nothing is written, and *n_pairs holds the number needed (a table of n_rows
+ * rows has at most n_rows pairs).  Runs on the calling thread's current device, on a stream of its own, with memory from the
+ * device pool, and has finished when it returns; without a device it fails with FA_ERR_NO_DEVICE like every compute entry. */
+int fa_table_pairs(const fa_cgi_row *rows, int64_t n_rows, int rows_device, int32_t n_genomes, const uint64_t *query_lengths,
+                   const uint64_t *reference_lengths, const fa_table_params *p, fa_pair *pairs, int64_t cap, int64_t *n_pairs,
+                   int pairs_device);
+/* The clusters of the table: labels [n_genomes] (a DEVICE pointer when labels_device != 0).  n_clusters and stats may be
+ * NULL; stats[0] surviving rows, [1] pairs, [2] edges, [3] rounds of the component loop (the round that found nothing to
+ * lower included; 0 without an edge). */
+int fa_table_clusters(const fa_cgi_row *rows, int64_t n_rows, int rows_device, int32_t n_genomes, const uint64_t *query_lengths,
+                      const uint64_t *reference_lengths, const fa_table_params *p, int32_t *labels, int labels_device,
+                      int32_t *n_clusters, int64_t *stats);
+
 /* stage-level introspection used by the parity tests */
 int fa_mapper_debug_mappings(fa_mapper *m, fa_mapping *out, int64_t cap, int64_t *n); /* L2 results of the last query call, under its rules */
 int fa_mapper_debug_l1(fa_mapper *m, int32_t *frag, int32_t *seq_id, int32_t *range_start, int32_t *range_end,

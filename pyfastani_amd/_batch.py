@@ -20,6 +20,13 @@ MAPPING_DTYPE = np.dtype(
 )
 assert MAPPING_DTYPE.itemsize == 32
 
+# one unordered genome pair of an all-vs-all table (``fa_pair``): what `pyfastani_amd.clusters.pairs` returns.  ``a < b``;
+# ``identity_ab`` is query a on reference b, NaN where that row is missing or filtered; ``identity`` the symmetric value
+PAIR_DTYPE = np.dtype(
+    [("a", "<i4"), ("b", "<i4"), ("identity_ab", "<f4"), ("identity_ba", "<f4"), ("identity", "<f8")]
+)
+assert PAIR_DTYPE.itemsize == 24
+
 
 def pass_fragments():
     """Fragments the library maps per pass (``FA_PASS_FRAGMENTS``, read when the library starts; 49152 by default)."""

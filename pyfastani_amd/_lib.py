@@ -73,6 +73,27 @@ class HitMapping(C.Structure):
     ]
 
 
+class Pair(C.Structure):
+    # fa_pair: one unordered genome pair of an all-vs-all table (pyfastani_amd._batch.PAIR_DTYPE is the numpy face of it)
+    _fields_ = [
+        ("a", C.c_int32),
+        ("b", C.c_int32),
+        ("identity_ab", C.c_float),
+        ("identity_ba", C.c_float),
+        ("identity", C.c_double),
+    ]
+
+
+class TableParams(C.Structure):
+    # fa_table_params: the filter and the cut-off of fa_table_pairs / fa_table_clusters
+    _fields_ = [
+        ("min_fraction", C.c_float),
+        ("fragment_length", C.c_int32),
+        ("min_identity", C.c_float),
+        ("reciprocal", C.c_int32),
+    ]
+
+
 # fa_mapping_sink: int (*)(void *user, const fa_hit_mapping *records, int64_t n); the entry points take it as a plain pointer
 # (None = count only), so wrap a Python function as ``MAPPING_SINK(fn)`` and pass ``ctypes.cast(cb, ctypes.c_void_p)``
 MAPPING_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(HitMapping), C.c_int64)
@@ -134,6 +155,8 @@ SIGNATURES = {
     "fa_mapper_set_rules": (_i32, [_vp, _P(RulesStruct)]),
     "fa_mapper_get_rules": (_i32, [_vp, _P(RulesStruct)]),
     "fa_mapper_mapping_memory": (_i32, [_vp, _P(_i64)]),
+    "fa_table_pairs": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _P(TableParams), _vp, _i64, _P(_i64), _i32]),
+    "fa_table_clusters": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _P(TableParams), _vp, _i32, _P(_i32), _vp]),
     "fa_mapper_debug_mappings": (_i32, [_vp, _vp, _i64, _P(_i64)]),
     "fa_mapper_debug_l1": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _P(_i64)]),
     "fa_mapper_debug_query_sketch": (_i32, [_vp, _i64, _vp, _i32, _P(_i32)]),

@@ -1,0 +1,94 @@
+"""What an all-vs-all is run for, computed where the hit table already is: the symmetric identity of every genome pair and
+the groups of genomes above a cut-off (species clusters at 95 %, dereplication at 99 %), by ``fa_table_pairs`` /
+``fa_table_clusters`` of the library (include/fastani_hip.h has the semantics; upstream's counterpart is the matrix output,
+`outputPhylip`, include/fastani/cgi/compute_core_identity.pxd:39-51 of the reference, and whatever the user clusters it with).
+
+The rows are one genome set mapped against itself: ``query_id`` and ``ref_genome_id`` index the same list of ``n`` genomes,
+``n`` being the length of the two length arrays.  ``rows`` is either a ``ROW_DTYPE`` array -- the result is numpy -- or an
+``int32 [n_rows, 5]`` torch tensor in HBM (a `ResidentHitTable`'s table, rows left there by
+`GenomeBatch.query_rows_device`) -- it is passed by ``data_ptr()`` and the result is a tensor on that device.  There is no
+CPU path: without a HIP device both functions raise ``RuntimeError``, like every compute entry point.
+
+Not imported by the package itself (like `outputs`): it needs numpy.
+"""
+import ctypes as C
+
+import numpy as np
+
+from ._batch import PAIR_DTYPE, ROW_DTYPE
+from ._lib import TableParams, check, lib
+
+
+def _is_tensor(rows):
+    return not isinstance(rows, np.ndarray) and hasattr(rows, "data_ptr")
+
+
+class _Table:
+    """The arguments both entry points share, as ctypes values that stay alive for the call."""
+
+    def __init__(self, rows, query_lengths, reference_lengths, fragment_length, minimum_fraction, min_identity=0.0, reciprocal=False):
+        self.qlen = np.ascontiguousarray(query_lengths, dtype=np.uint64)
+        self.rlen = np.ascontiguousarray(reference_lengths, dtype=np.uint64)
+        if self.qlen.ndim != 1 or self.qlen.shape != self.rlen.shape:
+            raise ValueError("query_lengths and reference_lengths are two arrays over the same genomes")
+        self.n = int(self.qlen.shape[0])
+        self.params = TableParams(float(minimum_fraction), int(fragment_length), float(min_identity), 1 if reciprocal else 0)
+        self.torch = None
+        if _is_tensor(rows):
+            import torch
+            if rows.dtype != torch.int32 or rows.dim() != 2 or rows.shape[1] != 5 or not rows.is_cuda:
+                raise ValueError("device rows are an int32 [n_rows, 5] tensor in HBM")
+            self.torch, self.rows = torch, rows.contiguous()
+            self.n_rows, self.rows_ptr, self.device = int(rows.shape[0]), self.rows.data_ptr(), rows.device
+            torch.cuda.synchronize(self.device)          # the library runs on a stream of its own: torch's writes are done
+        else:
+            self.rows = np.ascontiguousarray(rows, dtype=ROW_DTYPE)
+            self.n_rows, self.rows_ptr = int(self.rows.shape[0]), self.rows.ctypes.data
+
+    def head(self):
+        return (C.c_void_p(self.rows_ptr), self.n_rows, 1 if self.torch else 0, self.n, C.c_void_p(self.qlen.ctypes.data),
+                C.c_void_p(self.rlen.ctypes.data), C.byref(self.params))
+
+    def on_device(self):
+        """The calling thread's current device is the one the entry points run on: the tensor's, for the call."""
+        import contextlib
+        return self.torch.cuda.device(self.device) if self.torch else contextlib.nullcontext()
+
+
+def pairs(rows, query_lengths, reference_lengths, fragment_length, minimum_fraction=0.2):
+    """Every unordered genome pair ``(a, b)``, ``a < b``, with a row that passes the reference's hit filter
+    (`outputs.filter_rows`) in at least one direction, sorted by ``(a, b)``: ``PAIR_DTYPE`` records -- an int32
+    ``[n_pairs, 6]`` tensor of their words for device rows (`sharding.tensor_to_records` reads it).  ``identity`` is bit for
+    bit the cell ``[a, b]`` of ``outputs.identity_matrix(outputs.filter_rows(...), n, n, symmetric=True)``, without the dense
+    matrix.  A genome number outside the length arrays, or the same (query, reference) twice, raises ``ValueError``."""
+    t = _Table(rows, query_lengths, reference_lengths, fragment_length, minimum_fraction)
+    n = C.c_int64(0)
+    with t.on_device():
+        if t.torch:
+            out = t.torch.empty((t.n_rows, 6), dtype=t.torch.int32, device=t.device)       # (a pair has at least one row)
+            check(lib.fa_table_pairs(*t.head(), C.c_void_p(out.data_ptr()), t.n_rows, C.byref(n), 1))
+            return out[: n.value]
+        out = np.empty(t.n_rows, dtype=PAIR_DTYPE)
+        check(lib.fa_table_pairs(*t.head(), C.c_void_p(out.ctypes.data), t.n_rows, C.byref(n), 0))
+        return out[: n.value].copy()
+
+
+def clusters(rows, query_lengths, reference_lengths, fragment_length, minimum_fraction=0.2, min_identity=95.0, reciprocal=False,
+             stats=None):
+    """Single-linkage ANI clusters: the connected components of the pairs whose symmetric identity is at least
+    ``min_identity`` (and, with ``reciprocal``, that passed the filter in both directions).  Returns ``labels``, int32
+    ``[n]``: the smallest genome number of every genome's cluster; a genome without such a pair labels itself.  ``stats``, a
+    dict, receives ``rows`` (surviving the filter), ``pairs``, ``edges``, ``rounds`` (of the component loop) and
+    ``n_clusters``."""
+    t = _Table(rows, query_lengths, reference_lengths, fragment_length, minimum_fraction, min_identity, reciprocal)
+    n_clusters, counters = C.c_int32(0), (C.c_int64 * 4)()
+    with t.on_device():
+        if t.torch:
+            labels = t.torch.empty(t.n, dtype=t.torch.int32, device=t.device)
+            check(lib.fa_table_clusters(*t.head(), C.c_void_p(labels.data_ptr()), 1, C.byref(n_clusters), counters))
+        else:
+            labels = np.empty(t.n, dtype=np.int32)
+            check(lib.fa_table_clusters(*t.head(), C.c_void_p(labels.ctypes.data), 0, C.byref(n_clusters), counters))
+    if stats is not None:
+        stats.update(rows=counters[0], pairs=counters[1], edges=counters[2], rounds=counters[3], n_clusters=n_clusters.value)
+    return labels

@@ -29,6 +29,7 @@
 #include "fa_sketch.hip.h"
 #include "fa_sketch_fast.hip.h"
 #include "fa_stats.h"
+#include "fa_table.hip.h"
 
 using namespace fa;
 
@@ -1823,6 +1824,138 @@ static void for_each_locus_slice(const Workspace &x, Fn fn) {
     if (x.last_region_count[r]) fn((size_t)r << x.loci_shift, (size_t)x.last_region_count[r]);
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// The hit table of an all-vs-all reduced to pairs and clusters (fa_table.hip.h has the semantics and the road)
+// ------------------------------------------------------------------------------------------------------------
+struct TableRequest {
+  bool clusters = false;
+  fa_pair *pairs = nullptr; int64_t cap = 0; int64_t *n_pairs = nullptr; bool pairs_device = false;
+  int32_t *labels = nullptr; bool labels_device = false; int32_t *n_clusters = nullptr; int64_t *stats = nullptr;
+};
+
+static void table_reduce(const fa_cgi_row *rows, int64_t n_rows, bool rows_device, int32_t n_genomes, const uint64_t *query_lengths,
+                         const uint64_t *reference_lengths, const fa_table_params *p, const TableRequest &want) {
+  FA_REQUIRE(p, FA_ERR_INVALID, "null table parameters");
+  FA_REQUIRE(p->fragment_length >= 1, FA_ERR_INVALID, "fragment_length must be strictly positive");
+  FA_REQUIRE(n_genomes >= 0 && n_rows >= 0, FA_ERR_INVALID, "negative table size");
+  FA_REQUIRE(n_rows == 0 || rows, FA_ERR_INVALID, "null rows");
+  FA_REQUIRE(n_genomes == 0 || (query_lengths && reference_lengths), FA_ERR_INVALID, "null genome lengths");
+  FA_REQUIRE(n_rows <= (int64_t)INT32_MAX, FA_ERR_UNSUPPORTED, "a table of more than 2^31 - 1 rows");
+  if (want.clusters) FA_REQUIRE(n_genomes == 0 || want.labels, FA_ERR_INVALID, "null labels");
+  else FA_REQUIRE(want.n_pairs && want.cap >= 0, FA_ERR_INVALID, "null pair count or negative capacity");
+  require_device();
+  struct StreamGuard {
+    hipStream_t s = nullptr;
+    ~StreamGuard() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } }
+  } stream;
+  FA_HIP(hipStreamCreate(&stream.s));
+  hipStream_t st = stream.s;
+
+  DevBuf<TableStatus> d_status;
+  d_status.ensure(1);
+  FA_HIP(hipMemsetAsync(d_status.p, 0, sizeof(TableStatus), st));
+  DevBuf<fa_cgi_row> d_rows;
+  DevBuf<uint64_t> d_len;
+  DevBuf<unsigned long long> keys, keys_sorted;
+  DevBuf<uint32_t> row_of, row_of_sorted;
+  DevBuf<unsigned char> temp;
+  DevBuf<int32_t> chunk_count;
+  DevBuf<int64_t> chunk_off;
+
+  TableArgs a{};
+  a.n_rows = n_rows; a.n_genomes = n_genomes;
+  a.fragment_length = (unsigned long long)p->fragment_length; a.min_fraction = p->min_fraction;
+  a.min_identity = (double)p->min_identity; a.reciprocal = p->reciprocal;
+  a.edges_only = want.clusters ? 1 : 0;
+  a.status = d_status.p;
+  a.n_chunks = ceil_div(n_rows, TAB_CHUNK);
+  TableStatus status{};
+  if (n_rows) {
+    if (!rows_device) { d_rows.upload(rows, (size_t)n_rows, st); a.rows = d_rows.p; }
+    else a.rows = rows;
+    d_len.ensure((size_t)n_genomes * 2);
+    FA_HIP(hipMemcpyAsync(d_len.p, query_lengths, (size_t)n_genomes * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    FA_HIP(hipMemcpyAsync(d_len.p + n_genomes, reference_lengths, (size_t)n_genomes * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    a.query_length = d_len.p; a.reference_length = d_len.p + n_genomes;
+    keys.ensure((size_t)n_rows); keys_sorted.ensure((size_t)n_rows);
+    row_of.ensure((size_t)n_rows); row_of_sorted.ensure((size_t)n_rows);
+    hipLaunchKernelGGL(k_table_keys, dim3(ceil_div(n_rows, 256)), dim3(256), 0, st, a, keys.p, row_of.p);
+    // the bits a key of this table can have set: two flag bits, 31 of b, and those of the largest a
+    const unsigned end_bit = 33u + (n_genomes > 1 ? 64u - (unsigned)__builtin_clzll((unsigned long long)(n_genomes - 1)) : 1u);
+    size_t bytes = 0;
+    FA_HIP(rocprim::radix_sort_pairs(nullptr, bytes, keys.p, keys_sorted.p, row_of.p, row_of_sorted.p, (size_t)n_rows, 0u, end_bit, st));
+    temp.ensure(bytes + 16);
+    FA_HIP(rocprim::radix_sort_pairs(temp.p, bytes, keys.p, keys_sorted.p, row_of.p, row_of_sorted.p, (size_t)n_rows, 0u, end_bit, st));
+    a.keys = keys_sorted.p; a.row_of = row_of_sorted.p;
+    chunk_count.ensure((size_t)a.n_chunks); chunk_off.ensure((size_t)a.n_chunks);
+    a.chunk_count = chunk_count.p; a.chunk_off = chunk_off.p;
+    hipLaunchKernelGGL(k_table_count, dim3(ceil_div(a.n_chunks, 4)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_table_scan, dim3(1), dim3(1024), 0, st, a);
+    FA_HIP(hipGetLastError());
+    d_status.download(&status, 1, st);
+    FA_HIP(hipStreamSynchronize(st));
+    FA_REQUIRE(!(status.flags & TAB_BAD_ID), FA_ERR_INVALID, "a row names a genome outside [0, n_genomes)");
+    FA_REQUIRE(!(status.flags & TAB_DUPLICATE), FA_ERR_INVALID, "the table holds the same (query, reference) twice");
+  }
+  const int64_t n_emit = (int64_t)status.emitted;
+
+  if (!want.clusters) {
+    *want.n_pairs = (int64_t)status.pairs;
+    if (!want.pairs) return;
+    FA_REQUIRE(n_emit <= want.cap, FA_ERR_INVALID, "the pair buffer is smaller than the number of pairs");
+    if (!n_emit) return;
+    DevBuf<fa_pair> d_pairs;
+    if (!want.pairs_device) d_pairs.ensure((size_t)n_emit);
+    a.pairs = want.pairs_device ? want.pairs : d_pairs.p;
+    a.cap = n_emit;
+    hipLaunchKernelGGL(k_table_write, dim3(ceil_div(a.n_chunks, 4)), dim3(256), 0, st, a);
+    FA_HIP(hipGetLastError());
+    if (!want.pairs_device) d_pairs.download(want.pairs, (size_t)n_emit, st);
+    FA_HIP(hipStreamSynchronize(st));
+    return;
+  }
+
+  int64_t rounds = 0;
+  unsigned int roots = 0;
+  if (n_genomes) {
+    DevBuf<int2> d_edges;
+    DevBuf<int32_t> d_labels;
+    if (!want.labels_device) d_labels.ensure((size_t)n_genomes);
+    CompArgs c{};
+    c.labels = want.labels_device ? want.labels : d_labels.p;
+    c.n_genomes = n_genomes; c.n_edges = n_emit; c.status = d_status.p;
+    const dim3 genome_grid(ceil_div(n_genomes, 256));
+    hipLaunchKernelGGL(k_comp_init, genome_grid, dim3(256), 0, st, c.labels, n_genomes);
+    if (n_emit) {
+      d_edges.ensure((size_t)n_emit);
+      a.edges = d_edges.p; a.cap = n_emit;
+      hipLaunchKernelGGL(k_table_write, dim3(ceil_div(a.n_chunks, 4)), dim3(256), 0, st, a);
+      c.edges = d_edges.p;
+      // a round lowers at least one label or is the last; labels only decrease, so the loop ends (fa_table.hip.h)
+      for (;;) {
+        c.round = (unsigned int)++rounds;
+        hipLaunchKernelGGL(k_comp_edges, dim3(ceil_div(n_emit, 256)), dim3(256), 0, st, c);
+        hipLaunchKernelGGL(k_comp_jump, genome_grid, dim3(256), 0, st, c);
+        FA_HIP(hipGetLastError());
+        unsigned int changed = 0;
+        FA_HIP(hipMemcpyAsync(&changed, &d_status.p->changed, sizeof changed, hipMemcpyDeviceToHost, st));
+        FA_HIP(hipStreamSynchronize(st));
+        if (changed != c.round) break;
+      }
+    }
+    hipLaunchKernelGGL(k_comp_roots, genome_grid, dim3(256), 0, st, c);
+    FA_HIP(hipGetLastError());
+    FA_HIP(hipMemcpyAsync(&roots, &d_status.p->roots, sizeof roots, hipMemcpyDeviceToHost, st));
+    if (!want.labels_device) d_labels.download(want.labels, (size_t)n_genomes, st);
+    FA_HIP(hipStreamSynchronize(st));
+  }
+  if (want.n_clusters) *want.n_clusters = (int32_t)roots;
+  if (want.stats) {
+    want.stats[0] = (int64_t)status.survivors; want.stats[1] = (int64_t)status.pairs;
+    want.stats[2] = (int64_t)status.edges; want.stats[3] = rounds;
+  }
+}
+
 extern "C" {
 
 const char *fa_last_error(void) { return g_last_error.c_str(); }
@@ -2302,6 +2435,25 @@ int fa_mapper_query_genomes_mappings_stream(fa_mapper *m, fa_genomes *g, int32_t
     MapRequest want{nullptr, 0, n_maps, false};
     want.stream = true; want.fn = sink; want.user = user;
     *n_rows = run_query(*m, *lease.w, *g, first, count, rows, cap, rows_device != 0, &want);
+  });
+}
+int fa_table_pairs(const fa_cgi_row *rows, int64_t n_rows, int rows_device, int32_t n_genomes, const uint64_t *query_lengths,
+                   const uint64_t *reference_lengths, const fa_table_params *p, fa_pair *pairs, int64_t cap, int64_t *n_pairs,
+                   int pairs_device) {
+  return guarded([&] {
+    TableRequest want;
+    want.pairs = pairs; want.cap = cap; want.n_pairs = n_pairs; want.pairs_device = pairs_device != 0;
+    table_reduce(rows, n_rows, rows_device != 0, n_genomes, query_lengths, reference_lengths, p, want);
+  });
+}
+int fa_table_clusters(const fa_cgi_row *rows, int64_t n_rows, int rows_device, int32_t n_genomes, const uint64_t *query_lengths,
+                      const uint64_t *reference_lengths, const fa_table_params *p, int32_t *labels, int labels_device,
+                      int32_t *n_clusters, int64_t *stats) {
+  return guarded([&] {
+    TableRequest want;
+    want.clusters = true;
+    want.labels = labels; want.labels_device = labels_device != 0; want.n_clusters = n_clusters; want.stats = stats;
+    table_reduce(rows, n_rows, rows_device != 0, n_genomes, query_lengths, reference_lengths, p, want);
   });
 }
 int fa_mapper_set_mapping_stage(fa_mapper *m, int64_t records) {

@@ -142,3 +142,24 @@ cdef extern from "fastani_hip.h" nogil:
     int fa_mapper_query_genomes_mappings_stream(fa_mapper* m, fa_genomes* g, int32_t first, int32_t count, fa_cgi_row* rows,
                                                 int64_t cap, int64_t* n_rows, int rows_device, fa_mapping_sink sink, void* user,
                                                 int64_t* n_maps)
+
+    # the hit table of an all-vs-all reduced on the device: pairs and ANI clusters (pyfastani_amd.clusters)
+    ctypedef struct fa_pair:
+        int32_t a
+        int32_t b
+        float identity_ab
+        float identity_ba
+        double identity
+
+    ctypedef struct fa_table_params:
+        float min_fraction
+        int32_t fragment_length
+        float min_identity
+        int32_t reciprocal
+
+    int fa_table_pairs(const fa_cgi_row* rows, int64_t n_rows, int rows_device, int32_t n_genomes, const uint64_t* query_lengths,
+                       const uint64_t* reference_lengths, const fa_table_params* p, fa_pair* pairs, int64_t cap, int64_t* n_pairs,
+                       int pairs_device)
+    int fa_table_clusters(const fa_cgi_row* rows, int64_t n_rows, int rows_device, int32_t n_genomes, const uint64_t* query_lengths,
+                          const uint64_t* reference_lengths, const fa_table_params* p, int32_t* labels, int labels_device,
+                          int32_t* n_clusters, int64_t* stats)

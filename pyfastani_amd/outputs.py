@@ -43,6 +43,17 @@ def write_matrix(path, names, matrix):
             f.write("\t".join([str(names[i])] + cells) + "\n")
 
 
+def write_clusters(path, names, labels):
+    """The clusters of `pyfastani_amd.clusters.clusters`: one line per genome, in genome order, with its name and the name of
+    its label -- the genome of the smallest number in its cluster, which stands for it."""
+    labels = labels.cpu().numpy() if hasattr(labels, "cpu") else np.asarray(labels)
+    if len(labels) != len(names):
+        raise ValueError("one label per name")
+    with open(path, "w") as f:
+        for name, label in zip(names, labels):
+            f.write(f"{name}\t{names[int(label)]}\n")
+
+
 def write_hits(path, query_names, reference_names, rows):
     """FastANI's tabular output: query, reference, ANI, mapped fragments, total query fragments (one line per hit,
     queries in order, hits of a query by decreasing identity)."""

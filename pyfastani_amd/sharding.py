@@ -224,6 +224,23 @@ class ResidentHitTable:
             return float(sum(a.elapsed_time(b) for a, b in marks) / len(marks))
         return float(sum(marks) / len(marks) * 1e3)
 
+    def clusters(self, tables, query_lengths, reference_lengths, fragment_length, minimum_fraction=0.2, min_identity=95.0,
+                 reciprocal=False, stats=None):
+        """`pyfastani_amd.clusters.clusters` over an exchanged table (what `step` returns) of an all-vs-all: the genomes the
+        ranks own are the references, numbered alike.  The count row of every rank is dropped on the device -- at world size 1
+        the rows are a view of the table, otherwise the ranks' rows are concatenated in HBM -- and the labels are a tensor on
+        the table's device.  (A table on the host -- the gloo runs -- goes through the library's host-pointer form.)"""
+        from . import clusters as _clusters
+        counts = [int(c) for c in tables[:, 0, 0].tolist()]
+        if len(counts) == 1:
+            rows = tables[0, 1: counts[0] + 1]
+        else:
+            rows = self.torch.cat([tables[r, 1: c + 1] for r, c in enumerate(counts)], dim=0).to(self.table_device)
+        if not rows.is_cuda:
+            rows = tensor_to_rows(rows)
+        return _clusters.clusters(rows, query_lengths, reference_lengths, fragment_length, minimum_fraction, min_identity,
+                                  reciprocal, stats)
+
     @staticmethod
     def rows_of(tables):
         """Structured rows of an exchanged table (host side, after the timed region): ranks in order."""
