@@ -354,6 +354,44 @@ int fa_table_clusters(const fa_cgi_row *rows, int64_t n_rows, int rows_device, i
                       const uint64_t *reference_lengths, const fa_table_params *p, int32_t *labels, int labels_device,
                       int32_t *n_clusters, int64_t *stats);
 
+/* ---- a query x reference hit table, reduced to every query's k best hits ---- */
+/* What a batch of queries is mapped against a reference database for: per query, the closest references that pass an identity
+ * and an aligned-fraction cut-off (species assignment: ANI >= 95 with AF >= 0.5; over one genome set with exclude_self, every
+ * genome's nearest neighbours).  Queries are numbered 0 .. n_queries-1 and references 0 .. n_references-1; the two lists are
+ * unrelated and may differ in length.
+ *   1. Survival.  A row (q, r) survives iff all four hold, each evaluated in float32 exactly as written:
+ *        not (exclude_self and q == r);
+ *        (float)((uint64_t)count_seq * fragment_length) >= (float)min(query_lengths[q], reference_lengths[r]) * min_fraction
+ *          (the filter of fa_table_pairs, _fastani.pyx:1121-1132);
+ *        the sign bit of identity is clear, it is not NaN, and identity >= min_identity;
+ *        (float)count_seq >= (float)total_query_fragments * min_aligned_fraction.
+ *   2. Order.  The survivors of a query are ordered by identity descending, ties by ref_genome_id ascending: with k >= the
+ *      number of survivors, the order of the hits query_draft returns.
+ *   3. Output.  best holds the first min(k, survivors) rows of every query -- queries ascending, a query's rows in rank order,
+ *      each a byte-for-byte copy of its input row; offsets [n_queries + 1]: query q's records are best[offsets[q] ..
+ *      offsets[q+1]), a query without survivors has an empty range, offsets[n_queries] == *n_best.  The same input gives the
+ *      same bytes on every run. */
+typedef struct fa_best_params {
+  float   min_fraction;          /* minFraction of the hit filter, as in fa_table_params */
+  int32_t fragment_length;       /* >= 1 */
+  float   min_identity;          /* >= 0, not NaN */
+  float   min_aligned_fraction;  /* >= 0, not NaN: count_seq / total_query_fragments */
+  int32_t k;                     /* >= 1: records kept per query */
+  int32_t exclude_self;          /* != 0: a row with query_id == ref_genome_id never survives */
+} fa_best_params;                /* 24 bytes */
+/* rows_device != 0: `rows` is a DEVICE pointer; out_device != 0: `best` and `offsets` are; the two length arrays are host
+ * memory.  best == NULL only counts (offsets, if given, is still written); offsets, stats and n_best may be NULL.  A `cap`
+ * below the number of records is FA_ERR_INVALID: nothing is written to best or offsets, and *n_best holds the number needed
+ * (min(n_rows, n_queries * k) always suffices).  FA_ERR_INVALID with nothing written anywhere, *n_best included: a query id
+ * outside [0, n_queries) or a reference id outside [0, n_references); the same (q, r) in two rows, surviving or not; k < 1,
+ * fragment_length < 1, a negative or NaN min_identity or min_aligned_fraction; a NULL p or NULL lengths.  stats[0] surviving
+ * rows, [1] queries with at least one record, [2] records.  Runs like fa_table_pairs: on the calling thread's current
+ * device, on a stream of its own, with memory from the device pool, finished when it returns, FA_ERR_NO_DEVICE without a
+ * device. */
+int fa_table_best(const fa_cgi_row *rows, int64_t n_rows, int rows_device, int32_t n_queries, int32_t n_references,
+                  const uint64_t *query_lengths, const uint64_t *reference_lengths, const fa_best_params *p,
+                  fa_cgi_row *best, int64_t *offsets, int64_t cap, int64_t *n_best, int out_device, int64_t *stats);
+
 /* stage-level introspection used by the parity tests */
 int fa_mapper_debug_mappings(fa_mapper *m, fa_mapping *out, int64_t cap, int64_t *n); /* L2 results of the last query call, under its rules */
 int fa_mapper_debug_l1(fa_mapper *m, int32_t *frag, int32_t *seq_id, int32_t *range_start, int32_t *range_end,

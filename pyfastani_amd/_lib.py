@@ -94,6 +94,18 @@ class TableParams(C.Structure):
     ]
 
 
+class BestParams(C.Structure):
+    # fa_best_params: the filters, the cut-offs and k of fa_table_best
+    _fields_ = [
+        ("min_fraction", C.c_float),
+        ("fragment_length", C.c_int32),
+        ("min_identity", C.c_float),
+        ("min_aligned_fraction", C.c_float),
+        ("k", C.c_int32),
+        ("exclude_self", C.c_int32),
+    ]
+
+
 # fa_mapping_sink: int (*)(void *user, const fa_hit_mapping *records, int64_t n); the entry points take it as a plain pointer
 # (None = count only), so wrap a Python function as ``MAPPING_SINK(fn)`` and pass ``ctypes.cast(cb, ctypes.c_void_p)``
 MAPPING_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(HitMapping), C.c_int64)
@@ -157,6 +169,7 @@ SIGNATURES = {
     "fa_mapper_mapping_memory": (_i32, [_vp, _P(_i64)]),
     "fa_table_pairs": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _P(TableParams), _vp, _i64, _P(_i64), _i32]),
     "fa_table_clusters": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _P(TableParams), _vp, _i32, _P(_i32), _vp]),
+    "fa_table_best": (_i32, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _P(BestParams), _vp, _vp, _i64, _P(_i64), _i32, _vp]),
     "fa_mapper_debug_mappings": (_i32, [_vp, _vp, _i64, _P(_i64)]),
     "fa_mapper_debug_l1": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _P(_i64)]),
     "fa_mapper_debug_query_sketch": (_i32, [_vp, _i64, _vp, _i32, _P(_i32)]),

@@ -30,6 +30,7 @@
 #include "fa_sketch_fast.hip.h"
 #include "fa_stats.h"
 #include "fa_table.hip.h"
+#include "fa_best.hip.h"
 
 using namespace fa;
 
@@ -1956,6 +1957,109 @@ static void table_reduce(const fa_cgi_row *rows, int64_t n_rows, bool rows_devic
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// A query x reference hit table reduced to every query's k best hits (fa_best.hip.h has the semantics and the road)
+// ------------------------------------------------------------------------------------------------------------
+static unsigned bit_width_u64(unsigned long long v) { return v ? 64u - (unsigned)__builtin_clzll(v) : 0u; }
+
+static void table_best(const fa_cgi_row *rows, int64_t n_rows, bool rows_device, int32_t n_queries, int32_t n_references,
+                       const uint64_t *query_lengths, const uint64_t *reference_lengths, const fa_best_params *p, fa_cgi_row *best,
+                       int64_t *offsets, int64_t cap, int64_t *n_best, bool out_device, int64_t *stats) {
+  FA_REQUIRE(p, FA_ERR_INVALID, "null best-hit parameters");
+  FA_REQUIRE(p->fragment_length >= 1, FA_ERR_INVALID, "fragment_length must be strictly positive");
+  FA_REQUIRE(p->k >= 1, FA_ERR_INVALID, "k must be at least 1");
+  FA_REQUIRE(p->min_identity >= 0.0f, FA_ERR_INVALID, "min_identity must be a number that is not negative");          // (false for NaN)
+  FA_REQUIRE(p->min_aligned_fraction >= 0.0f, FA_ERR_INVALID, "min_aligned_fraction must be a number that is not negative");
+  FA_REQUIRE(n_queries >= 0 && n_references >= 0 && n_rows >= 0, FA_ERR_INVALID, "negative table size");
+  FA_REQUIRE(n_rows == 0 || rows, FA_ERR_INVALID, "null rows");
+  FA_REQUIRE((n_queries == 0 || query_lengths) && (n_references == 0 || reference_lengths), FA_ERR_INVALID, "null genome lengths");
+  FA_REQUIRE(!best || cap >= 0, FA_ERR_INVALID, "negative capacity");
+  FA_REQUIRE(n_rows <= (int64_t)INT32_MAX, FA_ERR_UNSUPPORTED, "a table of more than 2^31 - 1 rows");
+  require_device();
+  struct StreamGuard {
+    hipStream_t s = nullptr;
+    ~StreamGuard() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } }
+  } stream;
+  FA_HIP(hipStreamCreate(&stream.s));
+  hipStream_t st = stream.s;
+
+  DevBuf<BestStatus> d_status;
+  d_status.ensure(1);
+  FA_HIP(hipMemsetAsync(d_status.p, 0, sizeof(BestStatus), st));
+  DevBuf<fa_cgi_row> d_rows, d_best;
+  DevBuf<uint64_t> d_len;
+  DevBuf<unsigned long long> keys, keys_sorted;
+  DevBuf<uint32_t> row_of, row_of_sorted;
+  DevBuf<unsigned char> temp;
+  DevBuf<int32_t> seg;
+  DevBuf<int64_t> d_offsets;
+
+  BestArgs a{};
+  a.n_rows = n_rows; a.n_queries = n_queries; a.n_references = n_references;
+  a.fragment_length = (unsigned long long)p->fragment_length; a.min_fraction = p->min_fraction;
+  a.min_identity = p->min_identity; a.min_aligned_fraction = p->min_aligned_fraction;
+  a.k = p->k; a.exclude_self = p->exclude_self != 0 ? 1 : 0;
+  a.ref_bits = std::max(1u, bit_width_u64(n_references > 0 ? (unsigned long long)(n_references - 1) : 0ULL));
+  a.status = d_status.p;
+  seg.ensure((size_t)n_queries * 2);
+  if (n_queries) FA_HIP(hipMemsetAsync(seg.p, 0, (size_t)n_queries * 2 * sizeof(int32_t), st));
+  a.seg_start = seg.p; a.seg_end = seg.p + n_queries;
+  d_offsets.ensure((size_t)n_queries + 1);
+  a.offsets = d_offsets.p;
+  const dim3 row_grid(ceil_div(n_rows, 256));
+  if (n_rows) {
+    if (!rows_device) { d_rows.upload(rows, (size_t)n_rows, st); a.rows = d_rows.p; }
+    else a.rows = rows;
+    d_len.ensure((size_t)n_queries + (size_t)n_references);
+    if (n_queries) FA_HIP(hipMemcpyAsync(d_len.p, query_lengths, (size_t)n_queries * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    if (n_references)
+      FA_HIP(hipMemcpyAsync(d_len.p + n_queries, reference_lengths, (size_t)n_references * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    a.query_length = d_len.p; a.reference_length = d_len.p + n_queries;
+    keys.ensure((size_t)n_rows); keys_sorted.ensure((size_t)n_rows);
+    row_of.ensure((size_t)n_rows); row_of_sorted.ensure((size_t)n_rows);
+    hipLaunchKernelGGL(k_best_keys, row_grid, dim3(256), 0, st, a, keys.p, row_of.p);
+    // first sort: the bits of r and of the largest q (rows with an id out of range land anywhere: the call fails on the flag)
+    unsigned end_bit = a.ref_bits + std::max(1u, bit_width_u64(n_queries > 0 ? (unsigned long long)(n_queries - 1) : 0ULL));
+    size_t bytes = 0;
+    FA_HIP(rocprim::radix_sort_pairs(nullptr, bytes, keys.p, keys_sorted.p, row_of.p, row_of_sorted.p, (size_t)n_rows, 0u, end_bit, st));
+    temp.ensure(bytes + 16);
+    FA_HIP(rocprim::radix_sort_pairs(temp.p, bytes, keys.p, keys_sorted.p, row_of.p, row_of_sorted.p, (size_t)n_rows, 0u, end_bit, st));
+    a.keys = keys_sorted.p; a.row_of = row_of_sorted.p;
+    hipLaunchKernelGGL(k_best_rank_keys, row_grid, dim3(256), 0, st, a, keys.p);
+    // second sort: 32 bits of identity and the bits of n_queries itself -- under them the all-ones key of a row that does
+    // not survive reads 2^bits - 1 >= n_queries, behind every query
+    end_bit = 32u + bit_width_u64((unsigned long long)n_queries);
+    bytes = 0;
+    FA_HIP(rocprim::radix_sort_pairs(nullptr, bytes, keys.p, keys_sorted.p, row_of_sorted.p, row_of.p, (size_t)n_rows, 0u, end_bit, st));
+    temp.ensure(bytes + 16);
+    FA_HIP(rocprim::radix_sort_pairs(temp.p, bytes, keys.p, keys_sorted.p, row_of_sorted.p, row_of.p, (size_t)n_rows, 0u, end_bit, st));
+    a.keys = keys_sorted.p; a.row_of = row_of.p;
+    hipLaunchKernelGGL(k_best_segments, row_grid, dim3(256), 0, st, a);
+  }
+  hipLaunchKernelGGL(k_best_scan, dim3(1), dim3(1024), 0, st, a);
+  FA_HIP(hipGetLastError());
+  BestStatus status{};
+  d_status.download(&status, 1, st);
+  FA_HIP(hipStreamSynchronize(st));
+  FA_REQUIRE(!(status.flags & TAB_BAD_ID), FA_ERR_INVALID, "a row names a query outside [0, n_queries) or a reference outside [0, n_references)");
+  FA_REQUIRE(!(status.flags & TAB_DUPLICATE), FA_ERR_INVALID, "the table holds the same (query, reference) twice");
+  const int64_t n_records = (int64_t)status.records;
+  if (n_best) *n_best = n_records;
+  FA_REQUIRE(!best || n_records <= cap, FA_ERR_INVALID, "the record buffer is smaller than the number of records");
+  if (best && n_records) {
+    if (!out_device) d_best.ensure((size_t)n_records);
+    a.best = reinterpret_cast<int32_t *>(out_device ? best : d_best.p);
+    hipLaunchKernelGGL(k_best_write, row_grid, dim3(256), 0, st, a);
+    FA_HIP(hipGetLastError());
+    if (!out_device) d_best.download(best, (size_t)n_records, st);
+  }
+  if (offsets)
+    FA_HIP(hipMemcpyAsync(offsets, d_offsets.p, ((size_t)n_queries + 1) * sizeof(int64_t),
+                          out_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+  FA_HIP(hipStreamSynchronize(st));
+  if (stats) { stats[0] = (int64_t)status.survivors; stats[1] = (int64_t)status.queries; stats[2] = n_records; }
+}
+
 extern "C" {
 
 const char *fa_last_error(void) { return g_last_error.c_str(); }
@@ -2454,6 +2558,14 @@ int fa_table_clusters(const fa_cgi_row *rows, int64_t n_rows, int rows_device, i
     want.clusters = true;
     want.labels = labels; want.labels_device = labels_device != 0; want.n_clusters = n_clusters; want.stats = stats;
     table_reduce(rows, n_rows, rows_device != 0, n_genomes, query_lengths, reference_lengths, p, want);
+  });
+}
+int fa_table_best(const fa_cgi_row *rows, int64_t n_rows, int rows_device, int32_t n_queries, int32_t n_references,
+                  const uint64_t *query_lengths, const uint64_t *reference_lengths, const fa_best_params *p, fa_cgi_row *best,
+                  int64_t *offsets, int64_t cap, int64_t *n_best, int out_device, int64_t *stats) {
+  return guarded([&] {
+    table_best(rows, n_rows, rows_device != 0, n_queries, n_references, query_lengths, reference_lengths, p, best, offsets, cap, n_best,
+               out_device != 0, stats);
   });
 }
 int fa_mapper_set_mapping_stage(fa_mapper *m, int64_t records) {

@@ -163,3 +163,16 @@ cdef extern from "fastani_hip.h" nogil:
     int fa_table_clusters(const fa_cgi_row* rows, int64_t n_rows, int rows_device, int32_t n_genomes, const uint64_t* query_lengths,
                           const uint64_t* reference_lengths, const fa_table_params* p, int32_t* labels, int labels_device,
                           int32_t* n_clusters, int64_t* stats)
+
+    # a query x reference hit table reduced to every query's k best hits (pyfastani_amd.classify)
+    ctypedef struct fa_best_params:
+        float min_fraction
+        int32_t fragment_length
+        float min_identity
+        float min_aligned_fraction
+        int32_t k
+        int32_t exclude_self
+
+    int fa_table_best(const fa_cgi_row* rows, int64_t n_rows, int rows_device, int32_t n_queries, int32_t n_references,
+                      const uint64_t* query_lengths, const uint64_t* reference_lengths, const fa_best_params* p,
+                      fa_cgi_row* best, int64_t* offsets, int64_t cap, int64_t* n_best, int out_device, int64_t* stats)

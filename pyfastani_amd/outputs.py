@@ -64,6 +64,23 @@ def write_hits(path, query_names, reference_names, rows):
                     f"{r['count_seq']}\t{r['total_query_fragments']}\n")
 
 
+def write_best_hits(path, query_names, reference_names, records, offsets):
+    """The records of `pyfastani_amd.classify.best_hits` (numpy or tensors) in the layout of `write_hits`, one line per record
+    in record order: queries ascending, a query's hits from the best down.  Returns the names of the queries without a
+    record -- the unassigned ones."""
+    if hasattr(records, "cpu"):
+        from .sharding import tensor_to_rows
+        records = tensor_to_rows(records)
+    offsets = offsets.cpu().numpy() if hasattr(offsets, "cpu") else np.asarray(offsets)
+    if len(offsets) != len(query_names) + 1 or int(offsets[-1]) != len(records):
+        raise ValueError("one offset per query name and one behind, the last the number of records")
+    with open(path, "w") as f:
+        for r in records:
+            f.write(f"{query_names[r['query_id']]}\t{reference_names[r['ref_genome_id']]}\t{r['identity']:.6g}\t"
+                    f"{r['count_seq']}\t{r['total_query_fragments']}\n")
+    return [query_names[q] for q in np.nonzero(np.diff(offsets) == 0)[0]]
+
+
 def fragment_coordinates(contig_lengths, fragment_length):
     """Where every query fragment lies in its genome: ``(contig, offset)``, two int64 arrays indexed by ``querySeqId``
     (``query_seq_id`` of a mapping).  A contig of length ``n`` holds ``n // fragment_length`` fragments, numbered on from

@@ -231,15 +231,27 @@ class ResidentHitTable:
         the rows are a view of the table, otherwise the ranks' rows are concatenated in HBM -- and the labels are a tensor on
         the table's device.  (A table on the host -- the gloo runs -- goes through the library's host-pointer form.)"""
         from . import clusters as _clusters
+        return _clusters.clusters(self._rows_in_place(tables), query_lengths, reference_lengths, fragment_length, minimum_fraction,
+                                  min_identity, reciprocal, stats)
+
+    def best(self, tables, query_lengths, reference_lengths, fragment_length, k=1, minimum_fraction=0.2, min_identity=0.0,
+             min_aligned_fraction=0.0, exclude_self=False, stats=None):
+        """`pyfastani_amd.classify.best_hits` over an exchanged table (what `step` returns): ``(records, offsets)``, every
+        query's ``k`` best hits, with the count rows dropped and the ranks joined as for `clusters`.  Query ids are the global
+        ones of ``owned``, so ``query_lengths`` covers all queries of all ranks."""
+        from . import classify as _classify
+        return _classify.best_hits(self._rows_in_place(tables), query_lengths, reference_lengths, fragment_length, k,
+                                   minimum_fraction, min_identity, min_aligned_fraction, exclude_self, stats)
+
+    def _rows_in_place(self, tables):
+        """The rows of an exchanged table without its count rows, where they are: a view at world size 1, the ranks' rows
+        concatenated in HBM otherwise; structured host rows for a table on the host."""
         counts = [int(c) for c in tables[:, 0, 0].tolist()]
         if len(counts) == 1:
             rows = tables[0, 1: counts[0] + 1]
         else:
             rows = self.torch.cat([tables[r, 1: c + 1] for r, c in enumerate(counts)], dim=0).to(self.table_device)
-        if not rows.is_cuda:
-            rows = tensor_to_rows(rows)
-        return _clusters.clusters(rows, query_lengths, reference_lengths, fragment_length, minimum_fraction, min_identity,
-                                  reciprocal, stats)
+        return rows if rows.is_cuda else tensor_to_rows(rows)
 
     @staticmethod
     def rows_of(tables):
