@@ -392,6 +392,52 @@ int fa_table_best(const fa_cgi_row *rows, int64_t n_rows, int rows_device, int32
                   const uint64_t *query_lengths, const uint64_t *reference_lengths, const fa_best_params *p,
                   fa_cgi_row *best, int64_t *offsets, int64_t cap, int64_t *n_best, int out_device, int64_t *stats);
 
+/* ---- a genome-level screen by MinHash signatures ----------------------- */
+/* What comes before mapping when a collection is larger than one index: which genomes are related at all.  Every genome is
+ * reduced to a bottom-s MinHash signature of the minimizer hashes a sketch already holds in HBM, signatures are compared pair
+ * by pair with Mash's merge rule, and the pairs above a Jaccard cut-off are grouped.
+ *   1. Signature.  Genome g owns the records whose contig id lies in [sbf[g-1], sbf[g]) (sbf = sequencesByFileInfo, sbf[-1] =
+ *      0); records are sorted by contig id.  With d_g the number of distinct hash values of g's records, the signature of g
+ *      is the min(s, d_g) smallest of them, ascending as unsigned 32-bit; count[g] = min(s, d_g), 0 for a genome without
+ *      records.  Layout: uint32 sig[n_genomes][s], int32 count[n_genomes]; entries from count[g] up to s are 0.  The count
+ *      delimits a signature, not a sentinel: 0 and 0xFFFFFFFF are legal hashes.  1 <= s <= 4096.  This is the bottom-s
+ *      sketch of the genome's winnowed minimizers, not of all its k-mers: a k-mer whose hash is among a contig's smallest
+ *      is almost always some window's minimum, so the statistic is Mash-like at the sketch's k, not that of the Mash program.
+ *   2. Pair statistic.  For signatures A and B made with the same s, U is their ascending distinct union, denom =
+ *      min(s, |U|), shared = the number of the first denom elements of U that occur in both.  denom == 0 (two empty
+ *      genomes) never forms a pair.
+ *   3. Pair filter.  A pair is kept iff denom > 0 and (int64_t)shared * jd >= (int64_t)jn * denom: jn / jd is the
+ *      caller's rational Jaccard cut-off, 0 <= jn <= jd, jd >= 1.  Integers only.
+ *   4. Output.  Records sorted by (a, b); the same input gives the same bytes on every run.  Triangular: one set, the
+ *      pairs a < b.  Rectangular: two sets, every (a, b), a indexing the first set and b the second.
+ *   5. Groups.  The connected components of triangular records; labels[g] is the smallest genome number of g's group.
+ * All three run like fa_table_best: on the calling thread's current device, on a stream of their own, with memory from the
+ * device pool, finished when they return, FA_ERR_NO_DEVICE without a device. */
+typedef struct fa_screen_pair {
+  int32_t a, b;               /* triangular: a < b */
+  int32_t shared, denom;      /* the Jaccard estimate is shared / denom */
+} fa_screen_pair;             /* 16 bytes */
+/* The genomes a workgroup of fa_screen_pairs takes per tile side at signature size s (a power of two, 2 .. 64); host only. */
+int fa_screen_tile(int32_t s, int32_t *tile);
+/* d_hash, d_seq_id (n_records each: the hash and contig id of every minimizer record), d_sig and d_count are DEVICE
+ * pointers; sbf (n_genomes entries) is host memory.  FA_ERR_INVALID with nothing written: s outside [1, 4096]; d_seq_id not
+ * ascending; a contig id outside [0, sbf[n_genomes-1]); sbf not non-decreasing. */
+int fa_screen_signatures(const uint32_t *d_hash, const int32_t *d_seq_id, int64_t n_records, const int32_t *sbf, int32_t n_genomes,
+                         int32_t s, uint32_t *d_sig, int32_t *d_count);
+/* The signature arrays are DEVICE pointers; pairs_device != 0: `pairs` is one too.  triangular != 0 requires the same
+ * pointers for both sets and n_a == n_b.  pairs == NULL only counts.  A `cap` below the number of pairs is FA_ERR_INVALID:
+ * nothing is written, and *n_pairs holds the number needed.  FA_ERR_INVALID with nothing written, *n_pairs included: a count
+ * outside [0, s]; a signature that does not ascend strictly below its count; s, jn or jd out of range.  n_pairs and stats
+ * may be NULL; stats[0] the pairs evaluated, [1] the pairs kept. */
+int fa_screen_pairs(const uint32_t *d_sig_a, const int32_t *d_count_a, int32_t n_a, const uint32_t *d_sig_b, const int32_t *d_count_b,
+                    int32_t n_b, int32_t s, int triangular, int32_t jn, int32_t jd, fa_screen_pair *pairs, int64_t cap, int64_t *n_pairs,
+                    int pairs_device, int64_t *stats);
+/* labels [n_genomes] (a DEVICE pointer when labels_device != 0, as `pairs` is under pairs_device); *n_groups, which may be
+ * NULL, is the number of g with labels[g] == g.  A record that is not 0 <= a < b < n_genomes is FA_ERR_INVALID and nothing
+ * is written. */
+int fa_screen_groups(const fa_screen_pair *pairs, int64_t n_pairs, int pairs_device, int32_t n_genomes, int32_t *labels, int labels_device,
+                     int32_t *n_groups);
+
 /* stage-level introspection used by the parity tests */
 int fa_mapper_debug_mappings(fa_mapper *m, fa_mapping *out, int64_t cap, int64_t *n); /* L2 results of the last query call, under its rules */
 int fa_mapper_debug_l1(fa_mapper *m, int32_t *frag, int32_t *seq_id, int32_t *range_start, int32_t *range_end,

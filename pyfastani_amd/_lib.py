@@ -106,6 +106,16 @@ class BestParams(C.Structure):
     ]
 
 
+class ScreenPair(C.Structure):
+    # fa_screen_pair: one genome pair of the signature screen (pyfastani_amd.screen.SCREEN_DTYPE is the numpy face of it)
+    _fields_ = [
+        ("a", C.c_int32),
+        ("b", C.c_int32),
+        ("shared", C.c_int32),
+        ("denom", C.c_int32),
+    ]
+
+
 # fa_mapping_sink: int (*)(void *user, const fa_hit_mapping *records, int64_t n); the entry points take it as a plain pointer
 # (None = count only), so wrap a Python function as ``MAPPING_SINK(fn)`` and pass ``ctypes.cast(cb, ctypes.c_void_p)``
 MAPPING_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(HitMapping), C.c_int64)
@@ -170,6 +180,10 @@ SIGNATURES = {
     "fa_table_pairs": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _P(TableParams), _vp, _i64, _P(_i64), _i32]),
     "fa_table_clusters": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _P(TableParams), _vp, _i32, _P(_i32), _vp]),
     "fa_table_best": (_i32, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _P(BestParams), _vp, _vp, _i64, _P(_i64), _i32, _vp]),
+    "fa_screen_tile": (_i32, [_i32, _P(_i32)]),
+    "fa_screen_signatures": (_i32, [_vp, _vp, _i64, _vp, _i32, _i32, _vp, _vp]),
+    "fa_screen_pairs": (_i32, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _P(_i64), _i32, _vp]),
+    "fa_screen_groups": (_i32, [_vp, _i64, _i32, _i32, _vp, _i32, _P(_i32)]),
     "fa_mapper_debug_mappings": (_i32, [_vp, _vp, _i64, _P(_i64)]),
     "fa_mapper_debug_l1": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _P(_i64)]),
     "fa_mapper_debug_query_sketch": (_i32, [_vp, _i64, _vp, _i32, _P(_i32)]),

@@ -31,6 +31,7 @@
 #include "fa_stats.h"
 #include "fa_table.hip.h"
 #include "fa_best.hip.h"
+#include "fa_screen.hip.h"
 
 using namespace fa;
 
@@ -1828,6 +1829,37 @@ static void for_each_locus_slice(const Workspace &x, Fn fn) {
 // ------------------------------------------------------------------------------------------------------------
 // The hit table of an all-vs-all reduced to pairs and clusters (fa_table.hip.h has the semantics and the road)
 // ------------------------------------------------------------------------------------------------------------
+// The connected components of an edge list over n_genomes > 0 genomes (fa_table.hip.h): labels (device) receive every genome's
+// smallest group member; returns the number of groups and, in `rounds`, those of the loop.  `status` is the call's zeroed
+// TableStatus; the stream is synchronised on return.
+static unsigned int components(const int2 *edges, int64_t n_edges, int32_t *labels, int32_t n_genomes, TableStatus *status, hipStream_t st,
+                               int64_t &rounds) {
+  CompArgs c{};
+  c.edges = edges; c.n_edges = n_edges; c.labels = labels; c.n_genomes = n_genomes; c.status = status;
+  const dim3 genome_grid(ceil_div(n_genomes, 256));
+  hipLaunchKernelGGL(k_comp_init, genome_grid, dim3(256), 0, st, c.labels, n_genomes);
+  rounds = 0;
+  if (n_edges) {
+    // a round lowers at least one label or is the last; labels only decrease, so the loop ends (fa_table.hip.h)
+    for (;;) {
+      c.round = (unsigned int)++rounds;
+      hipLaunchKernelGGL(k_comp_edges, dim3(ceil_div(n_edges, 256)), dim3(256), 0, st, c);
+      hipLaunchKernelGGL(k_comp_jump, genome_grid, dim3(256), 0, st, c);
+      FA_HIP(hipGetLastError());
+      unsigned int changed = 0;
+      FA_HIP(hipMemcpyAsync(&changed, &status->changed, sizeof changed, hipMemcpyDeviceToHost, st));
+      FA_HIP(hipStreamSynchronize(st));
+      if (changed != c.round) break;
+    }
+  }
+  unsigned int roots = 0;
+  hipLaunchKernelGGL(k_comp_roots, genome_grid, dim3(256), 0, st, c);
+  FA_HIP(hipGetLastError());
+  FA_HIP(hipMemcpyAsync(&roots, &status->roots, sizeof roots, hipMemcpyDeviceToHost, st));
+  FA_HIP(hipStreamSynchronize(st));
+  return roots;
+}
+
 struct TableRequest {
   bool clusters = false;
   fa_pair *pairs = nullptr; int64_t cap = 0; int64_t *n_pairs = nullptr; bool pairs_device = false;
@@ -1922,31 +1954,12 @@ static void table_reduce(const fa_cgi_row *rows, int64_t n_rows, bool rows_devic
     DevBuf<int2> d_edges;
     DevBuf<int32_t> d_labels;
     if (!want.labels_device) d_labels.ensure((size_t)n_genomes);
-    CompArgs c{};
-    c.labels = want.labels_device ? want.labels : d_labels.p;
-    c.n_genomes = n_genomes; c.n_edges = n_emit; c.status = d_status.p;
-    const dim3 genome_grid(ceil_div(n_genomes, 256));
-    hipLaunchKernelGGL(k_comp_init, genome_grid, dim3(256), 0, st, c.labels, n_genomes);
     if (n_emit) {
       d_edges.ensure((size_t)n_emit);
       a.edges = d_edges.p; a.cap = n_emit;
       hipLaunchKernelGGL(k_table_write, dim3(ceil_div(a.n_chunks, 4)), dim3(256), 0, st, a);
-      c.edges = d_edges.p;
-      // a round lowers at least one label or is the last; labels only decrease, so the loop ends (fa_table.hip.h)
-      for (;;) {
-        c.round = (unsigned int)++rounds;
-        hipLaunchKernelGGL(k_comp_edges, dim3(ceil_div(n_emit, 256)), dim3(256), 0, st, c);
-        hipLaunchKernelGGL(k_comp_jump, genome_grid, dim3(256), 0, st, c);
-        FA_HIP(hipGetLastError());
-        unsigned int changed = 0;
-        FA_HIP(hipMemcpyAsync(&changed, &d_status.p->changed, sizeof changed, hipMemcpyDeviceToHost, st));
-        FA_HIP(hipStreamSynchronize(st));
-        if (changed != c.round) break;
-      }
     }
-    hipLaunchKernelGGL(k_comp_roots, genome_grid, dim3(256), 0, st, c);
-    FA_HIP(hipGetLastError());
-    FA_HIP(hipMemcpyAsync(&roots, &d_status.p->roots, sizeof roots, hipMemcpyDeviceToHost, st));
+    roots = components(d_edges.p, n_emit, want.labels_device ? want.labels : d_labels.p, n_genomes, d_status.p, st, rounds);
     if (!want.labels_device) d_labels.download(want.labels, (size_t)n_genomes, st);
     FA_HIP(hipStreamSynchronize(st));
   }
@@ -2058,6 +2071,192 @@ static void table_best(const fa_cgi_row *rows, int64_t n_rows, bool rows_device,
                           out_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
   FA_HIP(hipStreamSynchronize(st));
   if (stats) { stats[0] = (int64_t)status.survivors; stats[1] = (int64_t)status.queries; stats[2] = n_records; }
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// The genome-level screen: bottom-s signatures, their pairs above a Jaccard cut-off, the groups (fa_screen.hip.h)
+// ------------------------------------------------------------------------------------------------------------
+struct CallStream {
+  hipStream_t s = nullptr;
+  CallStream() { FA_HIP(hipStreamCreate(&s)); }
+  ~CallStream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } }
+};
+
+static void screen_signatures(const uint32_t *d_hash, const int32_t *d_seq_id, int64_t n_records, const int32_t *sbf, int32_t n_genomes,
+                              int32_t s, uint32_t *d_sig, int32_t *d_count) {
+  FA_REQUIRE(s >= 1 && s <= SCR_MAX_S, FA_ERR_INVALID, "the signature size must be in [1, 4096]");
+  FA_REQUIRE(n_genomes >= 0 && n_records >= 0, FA_ERR_INVALID, "negative number of genomes or records");
+  FA_REQUIRE(n_records == 0 || (d_hash && d_seq_id), FA_ERR_INVALID, "null records");
+  FA_REQUIRE(n_genomes == 0 || (sbf && d_sig && d_count), FA_ERR_INVALID, "null sequencesByFileInfo or null outputs");
+  FA_REQUIRE(n_records == 0 || n_genomes > 0, FA_ERR_INVALID, "records without a genome");
+  FA_REQUIRE(n_records <= (int64_t)INT32_MAX, FA_ERR_UNSUPPORTED, "more than 2^31 - 1 records");
+  for (int32_t g = 0; g < n_genomes; g++)
+    FA_REQUIRE(sbf[g] >= (g ? sbf[g - 1] : 0), FA_ERR_INVALID, "sequencesByFileInfo must not decrease");
+  require_device();
+  if (!n_genomes) return;
+  CallStream stream;
+  hipStream_t st = stream.s;
+  DevBuf<TableStatus> d_status;
+  d_status.ensure(1);
+  FA_HIP(hipMemsetAsync(d_status.p, 0, sizeof(TableStatus), st));
+  DevBuf<int32_t> d_sbf;
+  DevBuf<unsigned long long> keys, keys_sorted;
+  DevBuf<uint32_t> heads, rank, segs;
+  DevBuf<unsigned char> temp;
+
+  SigArgs a{};
+  a.hash = d_hash; a.seq_id = d_seq_id; a.n_records = n_records; a.n_genomes = n_genomes; a.s = s;
+  a.n_contigs = sbf[n_genomes - 1];
+  a.sig = d_sig; a.count = d_count; a.status = d_status.p;
+  const dim3 rec_grid(ceil_div(n_records, 256));
+  if (n_records) {
+    hipLaunchKernelGGL(k_sig_check, rec_grid, dim3(256), 0, st, a);
+    FA_HIP(hipGetLastError());
+    TableStatus status{};
+    d_status.download(&status, 1, st);
+    FA_HIP(hipStreamSynchronize(st));
+    FA_REQUIRE(!(status.flags & TAB_BAD_ID), FA_ERR_INVALID, "a record's contig id lies outside [0, sequencesByFileInfo[n_genomes - 1])");
+    FA_REQUIRE(!(status.flags & SCR_NOT_ASCENDING), FA_ERR_INVALID, "the records are not sorted by contig id");
+  }
+  segs.ensure((size_t)n_genomes * 2);
+  FA_HIP(hipMemsetAsync(segs.p, 0, (size_t)n_genomes * 2 * sizeof(uint32_t), st));
+  a.first = segs.p; a.last = segs.p + n_genomes;
+  FA_HIP(hipMemsetAsync(d_sig, 0, (size_t)n_genomes * (size_t)s * sizeof(uint32_t), st));
+  if (n_records) {
+    d_sbf.upload(sbf, (size_t)n_genomes, st);
+    a.sbf = d_sbf.p;
+    keys.ensure((size_t)n_records); keys_sorted.ensure((size_t)n_records);
+    heads.ensure((size_t)n_records); rank.ensure((size_t)n_records);
+    hipLaunchKernelGGL(k_sig_keys, rec_grid, dim3(256), 0, st, a, keys.p);
+    // the bits a key can have set: 32 of the hash and those of the largest genome number
+    const unsigned end_bit = 32u + std::max(1u, bit_width_u64((unsigned long long)(n_genomes - 1)));
+    size_t bytes = 0;
+    FA_HIP(rocprim::radix_sort_keys(nullptr, bytes, keys.p, keys_sorted.p, (size_t)n_records, 0u, end_bit, st));
+    temp.ensure(bytes + 16);
+    FA_HIP(rocprim::radix_sort_keys(temp.p, bytes, keys.p, keys_sorted.p, (size_t)n_records, 0u, end_bit, st));
+    a.keys = keys_sorted.p;
+    hipLaunchKernelGGL(k_sig_heads, rec_grid, dim3(256), 0, st, a, heads.p);
+    bytes = 0;
+    FA_HIP(rocprim::exclusive_scan(nullptr, bytes, heads.p, rank.p, 0u, (size_t)n_records, rocprim::plus<uint32_t>(), st));
+    temp.ensure(bytes + 16);
+    FA_HIP(rocprim::exclusive_scan(temp.p, bytes, heads.p, rank.p, 0u, (size_t)n_records, rocprim::plus<uint32_t>(), st));
+    a.rank = rank.p;
+    hipLaunchKernelGGL(k_sig_segments, rec_grid, dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_sig_write, rec_grid, dim3(256), 0, st, a);
+  }
+  hipLaunchKernelGGL(k_sig_counts, dim3(ceil_div(n_genomes, 256)), dim3(256), 0, st, a);
+  FA_HIP(hipGetLastError());
+  FA_HIP(hipStreamSynchronize(st));
+}
+
+static void screen_pairs(const uint32_t *d_sig_a, const int32_t *d_count_a, int32_t n_a, const uint32_t *d_sig_b, const int32_t *d_count_b,
+                         int32_t n_b, int32_t s, bool triangular, int32_t jn, int32_t jd, fa_screen_pair *pairs, int64_t cap,
+                         int64_t *n_pairs, bool pairs_device, int64_t *stats) {
+  FA_REQUIRE(s >= 1 && s <= SCR_MAX_S, FA_ERR_INVALID, "the signature size must be in [1, 4096]");
+  FA_REQUIRE(jd >= 1 && jn >= 0 && jn <= jd, FA_ERR_INVALID, "the Jaccard cut-off needs 0 <= jn <= jd and jd >= 1");
+  FA_REQUIRE(n_a >= 0 && n_b >= 0, FA_ERR_INVALID, "negative number of genomes");
+  FA_REQUIRE((n_a == 0 || (d_sig_a && d_count_a)) && (n_b == 0 || (d_sig_b && d_count_b)), FA_ERR_INVALID, "null signatures");
+  FA_REQUIRE(!triangular || (d_sig_a == d_sig_b && d_count_a == d_count_b && n_a == n_b), FA_ERR_INVALID,
+             "the triangular mode takes one signature set: the same pointers and n_a == n_b");
+  FA_REQUIRE(!pairs || cap >= 0, FA_ERR_INVALID, "negative capacity");
+  require_device();
+  CallStream stream;
+  hipStream_t st = stream.s;
+  DevBuf<TableStatus> d_status;
+  d_status.ensure(1);
+  FA_HIP(hipMemsetAsync(d_status.p, 0, sizeof(TableStatus), st));
+  DevBuf<unsigned long long> mask;
+  DevBuf<int32_t> chunk_count;
+  DevBuf<int64_t> chunk_off;
+  DevBuf<fa_screen_pair> d_pairs;
+
+  ScreenArgs a{};
+  a.sig_a = d_sig_a; a.sig_b = d_sig_b; a.count_a = d_count_a; a.count_b = d_count_b;
+  a.n_a = n_a; a.n_b = n_b; a.s = s; a.triangular = triangular ? 1 : 0; a.jn = jn; a.jd = jd;
+  a.tile = screen_tile(s);
+  a.tile_shift = (int32_t)bit_width_u64((unsigned long long)a.tile) - 1;
+  a.tiles_a = ceil_div(n_a, a.tile);
+  a.words_per_row = ((int64_t)n_b + 63) / 64;
+  a.n_words = (int64_t)n_a * a.words_per_row;
+  a.status = d_status.p;
+  const int64_t n_chunks = (a.n_words + SCR_CHUNK - 1) / SCR_CHUNK;
+  FA_REQUIRE(n_chunks <= (int64_t)INT32_MAX, FA_ERR_UNSUPPORTED, "a screen of more than 2^43 pairs");
+  a.n_chunks = (int32_t)n_chunks;
+  TableStatus status{};
+  if (a.n_words) {
+    mask.ensure((size_t)a.n_words);
+    FA_HIP(hipMemsetAsync(mask.p, 0, (size_t)a.n_words * sizeof(unsigned long long), st));
+    a.mask = mask.p;
+    chunk_count.ensure((size_t)a.n_chunks); chunk_off.ensure((size_t)a.n_chunks);
+    a.chunk_count = chunk_count.p; a.chunk_off = chunk_off.p;
+    const dim3 grid((unsigned)ceil_div(n_b, a.tile), (unsigned)std::min(a.tiles_a, 65535));
+    // elements of A a lane searches at a time (measured at s = 64, 1000 and 4096, profiles/screen_pair_kernel.txt): a signature
+    // of one pass gains nothing from a second chain, long ones hide more of the reads' latency behind more chains
+    const size_t lds = (size_t)2 * a.tile * screen_stride(s) * sizeof(uint32_t);
+    if (s <= 64) hipLaunchKernelGGL(k_screen_pairs<1>, grid, dim3(SCR_THREADS), lds, st, a);
+    else if (s <= 2048) hipLaunchKernelGGL(k_screen_pairs<2>, grid, dim3(SCR_THREADS), lds, st, a);
+    else hipLaunchKernelGGL(k_screen_pairs<4>, grid, dim3(SCR_THREADS), lds, st, a);
+    hipLaunchKernelGGL(k_screen_count, dim3(ceil_div(a.n_chunks, 4)), dim3(256), 0, st, a);
+    TableArgs scan{};                                             // k_table_scan reads the chunk counts and the status only
+    scan.n_chunks = a.n_chunks; scan.chunk_count = a.chunk_count; scan.chunk_off = a.chunk_off; scan.status = d_status.p;
+    hipLaunchKernelGGL(k_table_scan, dim3(1), dim3(1024), 0, st, scan);
+    FA_HIP(hipGetLastError());
+    d_status.download(&status, 1, st);
+    FA_HIP(hipStreamSynchronize(st));
+    FA_REQUIRE(!(status.flags & SCR_BAD_COUNT), FA_ERR_INVALID, "a signature count lies outside [0, s]");
+    FA_REQUIRE(!(status.flags & SCR_NOT_ASCENDING), FA_ERR_INVALID, "a signature does not ascend strictly below its count");
+  }
+  const int64_t n_emit = (int64_t)status.emitted;
+  if (n_pairs) *n_pairs = n_emit;
+  FA_REQUIRE(!pairs || n_emit <= cap, FA_ERR_INVALID, "the pair buffer is smaller than the number of pairs");
+  if (pairs && n_emit) {
+    if (!pairs_device) d_pairs.ensure((size_t)n_emit);
+    a.pairs = pairs_device ? pairs : d_pairs.p;
+    hipLaunchKernelGGL(k_screen_write, dim3(ceil_div(a.n_chunks, 4)), dim3(256), 0, st, a);
+    FA_HIP(hipGetLastError());
+    if (!pairs_device) d_pairs.download(pairs, (size_t)n_emit, st);
+    FA_HIP(hipStreamSynchronize(st));
+  }
+  if (stats) {
+    stats[0] = triangular ? (int64_t)n_a * ((int64_t)n_a - 1) / 2 : (int64_t)n_a * (int64_t)n_b;
+    stats[1] = n_emit;
+  }
+}
+
+static void screen_groups(const fa_screen_pair *pairs, int64_t n_pairs, bool pairs_device, int32_t n_genomes, int32_t *labels,
+                          bool labels_device, int32_t *n_groups) {
+  FA_REQUIRE(n_genomes >= 0 && n_pairs >= 0, FA_ERR_INVALID, "negative number of genomes or pairs");
+  FA_REQUIRE(n_pairs == 0 || pairs, FA_ERR_INVALID, "null pairs");
+  FA_REQUIRE(n_genomes == 0 || labels, FA_ERR_INVALID, "null labels");
+  FA_REQUIRE(n_pairs <= (int64_t)INT32_MAX, FA_ERR_UNSUPPORTED, "more than 2^31 - 1 pairs");
+  require_device();
+  CallStream stream;
+  hipStream_t st = stream.s;
+  DevBuf<TableStatus> d_status;
+  d_status.ensure(1);
+  FA_HIP(hipMemsetAsync(d_status.p, 0, sizeof(TableStatus), st));
+  DevBuf<fa_screen_pair> d_pairs;
+  DevBuf<int2> d_edges;
+  DevBuf<int32_t> d_labels;
+  if (n_pairs) {
+    if (!pairs_device) { d_pairs.upload(pairs, (size_t)n_pairs, st); pairs = d_pairs.p; }
+    d_edges.ensure((size_t)n_pairs);
+    hipLaunchKernelGGL(k_screen_edges, dim3(ceil_div(n_pairs, 256)), dim3(256), 0, st, pairs, n_pairs, n_genomes, d_edges.p, d_status.p);
+    FA_HIP(hipGetLastError());
+    TableStatus status{};
+    d_status.download(&status, 1, st);
+    FA_HIP(hipStreamSynchronize(st));
+    FA_REQUIRE(!(status.flags & TAB_BAD_ID), FA_ERR_INVALID, "a pair is not 0 <= a < b < n_genomes");
+  }
+  unsigned int roots = 0;
+  if (n_genomes) {
+    if (!labels_device) d_labels.ensure((size_t)n_genomes);
+    int64_t rounds = 0;
+    roots = components(d_edges.p, n_pairs, labels_device ? labels : d_labels.p, n_genomes, d_status.p, st, rounds);
+    if (!labels_device) d_labels.download(labels, (size_t)n_genomes, st);
+    FA_HIP(hipStreamSynchronize(st));
+  }
+  if (n_groups) *n_groups = (int32_t)roots;
 }
 
 extern "C" {
@@ -2567,6 +2766,27 @@ int fa_table_best(const fa_cgi_row *rows, int64_t n_rows, int rows_device, int32
     table_best(rows, n_rows, rows_device != 0, n_queries, n_references, query_lengths, reference_lengths, p, best, offsets, cap, n_best,
                out_device != 0, stats);
   });
+}
+int fa_screen_tile(int32_t s, int32_t *tile) {
+  return guarded([&] {
+    FA_REQUIRE(tile && s >= 1 && s <= SCR_MAX_S, FA_ERR_INVALID, "the signature size must be in [1, 4096]");
+    *tile = screen_tile(s);
+  });
+}
+int fa_screen_signatures(const uint32_t *d_hash, const int32_t *d_seq_id, int64_t n_records, const int32_t *sbf, int32_t n_genomes,
+                         int32_t s, uint32_t *d_sig, int32_t *d_count) {
+  return guarded([&] { screen_signatures(d_hash, d_seq_id, n_records, sbf, n_genomes, s, d_sig, d_count); });
+}
+int fa_screen_pairs(const uint32_t *d_sig_a, const int32_t *d_count_a, int32_t n_a, const uint32_t *d_sig_b, const int32_t *d_count_b,
+                    int32_t n_b, int32_t s, int triangular, int32_t jn, int32_t jd, fa_screen_pair *pairs, int64_t cap, int64_t *n_pairs,
+                    int pairs_device, int64_t *stats) {
+  return guarded([&] {
+    screen_pairs(d_sig_a, d_count_a, n_a, d_sig_b, d_count_b, n_b, s, triangular != 0, jn, jd, pairs, cap, n_pairs, pairs_device != 0, stats);
+  });
+}
+int fa_screen_groups(const fa_screen_pair *pairs, int64_t n_pairs, int pairs_device, int32_t n_genomes, int32_t *labels, int labels_device,
+                     int32_t *n_groups) {
+  return guarded([&] { screen_groups(pairs, n_pairs, pairs_device != 0, n_genomes, labels, labels_device != 0, n_groups); });
 }
 int fa_mapper_set_mapping_stage(fa_mapper *m, int64_t records) {
   return guarded([&] {

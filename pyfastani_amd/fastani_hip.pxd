@@ -176,3 +176,19 @@ cdef extern from "fastani_hip.h" nogil:
     int fa_table_best(const fa_cgi_row* rows, int64_t n_rows, int rows_device, int32_t n_queries, int32_t n_references,
                       const uint64_t* query_lengths, const uint64_t* reference_lengths, const fa_best_params* p,
                       fa_cgi_row* best, int64_t* offsets, int64_t cap, int64_t* n_best, int out_device, int64_t* stats)
+
+    # the genome-level screen by MinHash signatures (pyfastani_amd.screen)
+    ctypedef struct fa_screen_pair:
+        int32_t a
+        int32_t b
+        int32_t shared
+        int32_t denom
+
+    int fa_screen_tile(int32_t s, int32_t* tile)
+    int fa_screen_signatures(const uint32_t* d_hash, const int32_t* d_seq_id, int64_t n_records, const int32_t* sbf, int32_t n_genomes,
+                             int32_t s, uint32_t* d_sig, int32_t* d_count)
+    int fa_screen_pairs(const uint32_t* d_sig_a, const int32_t* d_count_a, int32_t n_a, const uint32_t* d_sig_b, const int32_t* d_count_b,
+                        int32_t n_b, int32_t s, int triangular, int32_t jn, int32_t jd, fa_screen_pair* pairs, int64_t cap,
+                        int64_t* n_pairs, int pairs_device, int64_t* stats)
+    int fa_screen_groups(const fa_screen_pair* pairs, int64_t n_pairs, int pairs_device, int32_t n_genomes, int32_t* labels,
+                         int labels_device, int32_t* n_groups)

@@ -81,6 +81,17 @@ def write_best_hits(path, query_names, reference_names, records, offsets):
     return [query_names[q] for q in np.nonzero(np.diff(offsets) == 0)[0]]
 
 
+def write_screen(path, names_a, names_b, records, k):
+    """The records of `pyfastani_amd.screen.pairs` (numpy or a tensor) as the columns of ``mash dist`` without its p-value:
+    name, name, distance, shared/denom, one line per record in record order.  ``names_b`` is ``names_a`` for the pairs of one
+    set."""
+    from . import screen
+    records = screen.to_records(records)
+    with open(path, "w") as f:
+        for r, d in zip(records, screen.distance(records, k)):
+            f.write(f"{names_a[r['a']]}\t{names_b[r['b']]}\t{d:.6g}\t{r['shared']}/{r['denom']}\n")
+
+
 def fragment_coordinates(contig_lengths, fragment_length):
     """Where every query fragment lies in its genome: ``(contig, offset)``, two int64 arrays indexed by ``querySeqId``
     (``query_seq_id`` of a mapping).  A contig of length ``n`` holds ``n // fragment_length`` fragments, numbered on from

@@ -1,0 +1,193 @@
+"""Which genomes of a collection are related at all, found before anything is mapped: every genome reduced to a bottom-``s``
+MinHash signature of the minimizer hashes its `Sketch` holds in HBM, signatures compared pair by pair with Mash's merge rule,
+the pairs within a Mash distance grouped -- ``fa_screen_signatures`` / ``fa_screen_pairs`` / ``fa_screen_groups`` of the
+library (include/fastani_hip.h has the semantics).  A collection too large for one index is cut into its groups this way, and
+each group is mapped with what exists: one `Sketch` / `Mapper` / all-vs-all per group.
+
+    sketch.add_fasta_stream(names, paths)
+    sigs = screen.signatures(sketch)                       # the sketch stays usable and un-indexed; or sketch.clear(), the
+    records = screen.pairs(sigs, max_distance=0.1)         #   next chunk, and Signatures.concat
+    members = screen.partition(screen.groups(records, len(sigs)))
+
+The signature is that of the genome's *winnowed minimizers*, not of all its k-mers: the distances are Mash-like at the
+sketch's ``k``, not those of the Mash program.  Everything runs on the device; there is no CPU path, and without a HIP device
+the functions raise ``RuntimeError`` like every compute entry point.
+
+Not imported by the package itself (like `clusters` and `classify`): it needs numpy.
+"""
+import ctypes as C
+import math
+
+import numpy as np
+
+from ._lib import FA_ERR_INVALID, check, lib
+
+# fa_screen_pair: ``shared`` of the first ``denom`` elements of the two signatures' union occur in both
+SCREEN_DTYPE = np.dtype([("a", "<i4"), ("b", "<i4"), ("shared", "<i4"), ("denom", "<i4")])
+assert SCREEN_DTYPE.itemsize == 16
+
+JACCARD_DENOMINATOR = 1 << 20
+MAX_SIZE = 4096
+
+
+class Signatures:
+    """The signatures of ``len(names)`` genomes: ``sig`` int32 ``[n, size]`` (the bits of unsigned 32-bit hashes, ascending
+    as unsigned, zero from the count on) and ``count`` int32 ``[n]``, both in HBM, with the genomes' ``names`` and the
+    k-mer size ``k`` of the sketch they came from."""
+
+    def __init__(self, sig, count, names, k):
+        if sig.dim() != 2 or count.dim() != 1 or sig.shape[0] != count.shape[0] or len(names) != sig.shape[0]:
+            raise ValueError("sig is [n, size], count [n], and there is one name per genome")
+        self.sig, self.count, self.names, self.k = sig, count, list(names), int(k)
+
+    def __len__(self):
+        return len(self.names)
+
+    @property
+    def size(self):
+        return int(self.sig.shape[1])
+
+    @property
+    def device(self):
+        return self.sig.device
+
+    @staticmethod
+    def concat(parts):
+        """One set out of several of the same size, ``k`` and device, genomes in the order given: the way to screen a
+        collection that is sketched chunk by chunk (``add_fasta_stream`` + `signatures` + ``clear``)."""
+        import torch
+        parts = list(parts)
+        if not parts:
+            raise ValueError("nothing to join")
+        if len({(p.size, p.k, p.device) for p in parts}) != 1:
+            raise ValueError("signature sets of different size, k or device do not compare")
+        return Signatures(torch.cat([p.sig for p in parts]), torch.cat([p.count for p in parts]), sum((p.names for p in parts), []),
+                          parts[0].k)
+
+
+def signatures(sketch, size=1000, device="cuda"):
+    """The bottom-``size`` signatures of every genome of ``sketch`` (1 <= size <= 4096), from the records
+    `Sketch._export_records` copies HBM to HBM: the sketch is left as it is, un-indexed."""
+    import torch
+    if not 1 <= int(size) <= MAX_SIZE:
+        raise ValueError(f"the signature size must be in [1, {MAX_SIZE}]")
+    rec, (lengths, sbf, counter) = sketch._export_records(device)
+    rec = rec.contiguous()
+    n, n_records = len(sbf), int(rec.shape[1])
+    sbf = np.ascontiguousarray(sbf, dtype=np.int32)
+    sig = torch.empty((n, int(size)), dtype=torch.int32, device=rec.device)
+    count = torch.empty(n, dtype=torch.int32, device=rec.device)
+    torch.cuda.synchronize(rec.device)                   # the library runs on a stream of its own: torch's writes are done
+    with torch.cuda.device(rec.device):
+        check(lib.fa_screen_signatures(C.c_void_p(rec[0].data_ptr()), C.c_void_p(rec[1].data_ptr()), n_records,
+                                       C.c_void_p(sbf.ctypes.data), n, int(size), C.c_void_p(sig.data_ptr()), C.c_void_p(count.data_ptr())))
+    return Signatures(sig, count, sketch.names, sketch.k)
+
+
+def jaccard_cutoff(max_distance, k):
+    """``(jn, jd)``: the Jaccard index of Mash distance ``max_distance`` at k-mer size ``k``, ``1 / (2 exp(k d) - 1)``, as a
+    fraction over 2**20 rounded DOWN (and one step further, for the rounding of the float64 arithmetic itself), so that the
+    integer filter of the device keeps every pair the exact float64 cut by `distance` keeps."""
+    if not max_distance >= 0.0:
+        raise ValueError("max_distance must be a number that is not negative")
+    if max_distance >= 1.0:                              # (a pair that shares nothing has distance 1.0)
+        return 0, JACCARD_DENOMINATOR
+    j_min = 1.0 / (2.0 * math.exp(int(k) * float(max_distance)) - 1.0)
+    return max(0, min(JACCARD_DENOMINATOR, int(math.floor(j_min * JACCARD_DENOMINATOR)) - 1)), JACCARD_DENOMINATOR
+
+
+def distance(records, k):
+    """Mash's distance ``-ln(2 j / (1 + j)) / k`` of every record, ``j = shared / denom``, in float64: 1.0 for
+    ``shared == 0`` and 0.0 for ``j == 1``.  ``records`` are ``SCREEN_DTYPE`` or an int32 ``[n, 4]`` tensor."""
+    records = to_records(records)
+    shared, denom = records["shared"].astype(np.float64), records["denom"].astype(np.float64)
+    out = np.ones(len(records), dtype=np.float64)
+    some = shared > 0
+    j = shared[some] / denom[some]
+    out[some] = np.where(j >= 1.0, 0.0, -np.log(2.0 * j / (1.0 + j)) / float(k))
+    return out
+
+
+def to_records(records):
+    """``SCREEN_DTYPE`` records of an int32 ``[n, 4]`` tensor (or of records, unchanged)"""
+    if hasattr(records, "cpu"):
+        return np.ascontiguousarray(records.cpu().numpy()).view(SCREEN_DTYPE).reshape(-1)
+    return np.ascontiguousarray(records, dtype=SCREEN_DTYPE)
+
+
+def pairs(a, b=None, max_distance=0.1, device=False, stats=None):
+    """The genome pairs within Mash distance ``max_distance``, sorted by ``(a, b)``: ``SCREEN_DTYPE`` records, or with
+    ``device=True`` the int32 ``[n, 4]`` tensor of their words in HBM.  With one set (``b is None``) the pairs ``a < b`` of
+    the set; with two, every (genome of ``a``, genome of ``b``).  The device filters by the integer Jaccard cut-off of
+    `jaccard_cutoff`, which loses nothing; the survivors are then cut exactly by `distance` in float64.  ``stats``, a dict,
+    receives ``evaluated`` and ``kept`` (by the device filter)."""
+    import torch
+    other = a if b is None else b
+    if (other.size, other.k, other.device) != (a.size, a.k, a.device):
+        raise ValueError("signature sets of different size, k or device do not compare")
+    jn, jd = jaccard_cutoff(max_distance, a.k)
+    sig_a, count_a, sig_b, count_b = a.sig.contiguous(), a.count.contiguous(), other.sig.contiguous(), other.count.contiguous()
+    if b is None:
+        sig_b, count_b = sig_a, count_a
+    head = (C.c_void_p(sig_a.data_ptr()), C.c_void_p(count_a.data_ptr()), len(a), C.c_void_p(sig_b.data_ptr()),
+            C.c_void_p(count_b.data_ptr()), len(other), a.size, 1 if b is None else 0, jn, jd)
+    n, counters = C.c_int64(-1), (C.c_int64 * 2)()
+    total = len(a) * (len(a) - 1) // 2 if b is None else len(a) * len(other)
+    cap = min(total, max(4096, 16 * (len(a) + len(other))))           # a screen keeps few pairs: one pass is the rule
+    torch.cuda.synchronize(a.device)
+    with torch.cuda.device(a.device):
+        out = torch.empty((cap, 4), dtype=torch.int32, device=a.device)
+        code = lib.fa_screen_pairs(*head, C.c_void_p(out.data_ptr()), cap, C.byref(n), 1, counters)
+        if code == FA_ERR_INVALID and n.value > cap:                  # the buffer was short, and n is what it takes
+            out = torch.empty((n.value, 4), dtype=torch.int32, device=a.device)
+            torch.cuda.synchronize(a.device)
+            code = lib.fa_screen_pairs(*head, C.c_void_p(out.data_ptr()), n.value, C.byref(n), 1, counters)
+        check(code)
+        out = out[: n.value]
+    if stats is not None:
+        stats.update(evaluated=counters[0], kept=counters[1])
+    records = to_records(out)
+    keep = distance(records, a.k) <= float(max_distance)
+    if device:
+        return out if keep.all() else out[torch.from_numpy(keep).to(out.device)]
+    return records[keep]
+
+
+def groups(records, n, max_distance=None, k=None):
+    """``labels``, int32 ``[n]``: the smallest genome number of every genome's group, the groups being the connected
+    components of the triangular ``records`` -- of those within ``max_distance`` when one is given (``k``, the k-mer size,
+    is then needed for `distance`).  A tensor for records in HBM, numpy otherwise."""
+    if max_distance is not None:
+        if k is None:
+            raise ValueError("a cut by max_distance needs the k-mer size k")
+        keep = distance(records, k) <= float(max_distance)
+        if hasattr(records, "cpu"):
+            import torch
+            records = records[torch.from_numpy(keep).to(records.device)]
+        else:
+            records = np.ascontiguousarray(records, dtype=SCREEN_DTYPE)[keep]
+    n_groups = C.c_int32(0)
+    if hasattr(records, "cpu"):
+        import torch
+        if records.dtype != torch.int32 or records.dim() != 2 or records.shape[1] != 4 or not records.is_cuda:
+            raise ValueError("device records are an int32 [n, 4] tensor in HBM")
+        records = records.contiguous()
+        labels = torch.empty(int(n), dtype=torch.int32, device=records.device)
+        torch.cuda.synchronize(records.device)
+        with torch.cuda.device(records.device):
+            check(lib.fa_screen_groups(C.c_void_p(records.data_ptr()), int(records.shape[0]), 1, int(n), C.c_void_p(labels.data_ptr()), 1,
+                                       C.byref(n_groups)))
+        return labels
+    records = np.ascontiguousarray(records, dtype=SCREEN_DTYPE)
+    labels = np.empty(int(n), dtype=np.int32)
+    check(lib.fa_screen_groups(C.c_void_p(records.ctypes.data), len(records), 0, int(n), C.c_void_p(labels.ctypes.data), 0, C.byref(n_groups)))
+    return labels
+
+
+def partition(labels):
+    """The member lists of the groups, the largest group first (ties: the smaller label first), members ascending."""
+    labels = labels.cpu().numpy() if hasattr(labels, "cpu") else np.asarray(labels)
+    members = {}
+    for g, label in enumerate(labels.tolist()):
+        members.setdefault(label, []).append(g)
+    return [members[label] for label in sorted(members, key=lambda label: (-len(members[label]), label))]
