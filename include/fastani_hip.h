@@ -336,8 +336,8 @@ typedef struct fa_pair {
 typedef struct fa_table_params {
   float min_fraction;         /* minFraction of the filter */
   int32_t fragment_length;    /* minReadLength the rows were mapped with (>= 1) */
-  float min_identity;         /* the cut-off of an edge (fa_table_clusters only) */
-  int32_t reciprocal;         /* != 0: an edge needs both directions (fa_table_clusters only) */
+  float min_identity;         /* the cut-off of an edge (fa_table_clusters, fa_table_representatives) */
+  int32_t reciprocal;         /* != 0: an edge needs both directions (fa_table_clusters, fa_table_representatives) */
 } fa_table_params;            /* 16 bytes */
 /* All pairs of the table (not only the edges).  rows_device / pairs_device != 0: `rows` / `pairs` are DEVICE pointers, as on
  * fa_mapper_query_genomes; the two length arrays (n_genomes entries each) are host memory.  pairs == NULL only counts.  A `cap`
@@ -353,6 +353,29 @@ int fa_table_pairs(const fa_cgi_row *rows, int64_t n_rows, int rows_device, int3
 int fa_table_clusters(const fa_cgi_row *rows, int64_t n_rows, int rows_device, int32_t n_genomes, const uint64_t *query_lengths,
                       const uint64_t *reference_lengths, const fa_table_params *p, int32_t *labels, int labels_device,
                       int32_t *n_clusters, int64_t *stats);
+/* Greedy representative clustering of the table (GTDB species clusters, dRep's and galah's dereplicated sets): unlike the
+ * connected components, every genome is within the cut-off of the genome that stands for it.
+ *   1. Filter, pair, edge: steps 1-3 above, `reciprocal` included.  min_identity must be a number >= 0 (a negative or NaN
+ *      value is FA_ERR_INVALID, as in fa_best_params), so every edge's identity is >= 0; -0.0 is treated as +0.0.
+ *   2. Order.  `order` is a HOST array of n_genomes int32, a permutation of the genome numbers; order[0] is the most preferred
+ *      genome, NULL means genome-number order.  pos[g] is the place of g in `order`.  Anything that is not a permutation (a
+ *      value outside [0, n_genomes), a value that occurs twice) is FA_ERR_INVALID with nothing written.
+ *   3. Representatives.  Walk the genomes in `order`: a genome is a representative iff it has no edge to a representative with
+ *      a smaller pos.  Equivalently R is the one set with  g in R  <=>  no edge neighbour h with pos[h] < pos[g] is in R.
+ *   4. Assignment.  labels[g] = g for a representative.  Any other genome has at least one neighbour that is a
+ *      representative and gets the one with the largest symmetric identity, compared as float64 (not float32), ties to the
+ *      smaller pos.  identity[g] is that pair's symmetric identity, 100.0 for a representative.  *n_representatives is the
+ *      number of g with labels[g] == g.  The same input gives the same bytes on every run.
+ * labels [n_genomes] int32 and identity [n_genomes] float64 (may be NULL) are DEVICE pointers when out_device != 0.
+ * n_representatives and stats may be NULL; stats[0] surviving rows, [1] pairs, [2] edges, [3] rounds of the selection loop (at
+ * most n_genomes; 0 without an edge).  Everything else as for fa_table_clusters: a bad id or a duplicate row is
+ * FA_ERR_INVALID with nothing written, the out-parameters included; the call runs on the calling thread's current device, on
+ * a stream of its own, with memory from the device pool, has finished when it returns, and is FA_ERR_NO_DEVICE without a
+ * device. */
+int fa_table_representatives(const fa_cgi_row *rows, int64_t n_rows, int rows_device, int32_t n_genomes,
+                             const uint64_t *query_lengths, const uint64_t *reference_lengths, const fa_table_params *p,
+                             const int32_t *order, int32_t *labels, double *identity, int out_device,
+                             int32_t *n_representatives, int64_t *stats);
 
 /* ---- a query x reference hit table, reduced to every query's k best hits ---- */
 /* What a batch of queries is mapped against a reference database for: per query, the closest references that pass an identity

@@ -1,13 +1,13 @@
 """What an all-vs-all is run for, computed where the hit table already is: the symmetric identity of every genome pair and
 the groups of genomes above a cut-off (species clusters at 95 %, dereplication at 99 %), by ``fa_table_pairs`` /
-``fa_table_clusters`` of the library (include/fastani_hip.h has the semantics; upstream's counterpart is the matrix output,
+``fa_table_clusters`` / ``fa_table_representatives`` of the library (include/fastani_hip.h has the semantics; upstream's counterpart is the matrix output,
 `outputPhylip`, include/fastani/cgi/compute_core_identity.pxd:39-51 of the reference, and whatever the user clusters it with).
 
 The rows are one genome set mapped against itself: ``query_id`` and ``ref_genome_id`` index the same list of ``n`` genomes,
 ``n`` being the length of the two length arrays.  ``rows`` is either a ``ROW_DTYPE`` array -- the result is numpy -- or an
 ``int32 [n_rows, 5]`` torch tensor in HBM (a `ResidentHitTable`'s table, rows left there by
 `GenomeBatch.query_rows_device`) -- it is passed by ``data_ptr()`` and the result is a tensor on that device.  There is no
-CPU path: without a HIP device both functions raise ``RuntimeError``, like every compute entry point.
+CPU path: without a HIP device the functions raise ``RuntimeError``, like every compute entry point.
 
 Not imported by the package itself (like `outputs`): it needs numpy.
 """
@@ -24,7 +24,7 @@ def _is_tensor(rows):
 
 
 class _Table:
-    """The arguments both entry points share, as ctypes values that stay alive for the call."""
+    """The arguments the entry points share, as ctypes values that stay alive for the call."""
 
     def __init__(self, rows, query_lengths, reference_lengths, fragment_length, minimum_fraction, min_identity=0.0, reciprocal=False):
         self.qlen = np.ascontiguousarray(query_lengths, dtype=np.uint64)
@@ -92,3 +92,50 @@ def clusters(rows, query_lengths, reference_lengths, fragment_length, minimum_fr
     if stats is not None:
         stats.update(rows=counters[0], pairs=counters[1], edges=counters[2], rounds=counters[3], n_clusters=n_clusters.value)
     return labels
+
+
+def _order(order, t):
+    """``order`` as a contiguous int32 array over the genomes, or None for genome-number order."""
+    if order is None:
+        return None
+    if isinstance(order, str):
+        if order != "length":
+            raise ValueError('order is None, "length" or a permutation of the genome numbers')
+        return np.lexsort((np.arange(t.n), ~t.qlen)).astype(np.int32)      # longest first (~: descending as unsigned), ties by genome number
+    order = np.ascontiguousarray(order.cpu().numpy() if hasattr(order, "cpu") else order)
+    if order.shape != (t.n,) or order.dtype.kind not in "iu":
+        raise ValueError("order holds one genome number per genome")
+    if t.n and (int(order.min()) < 0 or int(order.max()) >= t.n):
+        raise ValueError("order is not a permutation of the genome numbers")
+    return order.astype(np.int32)
+
+
+def representatives(rows, query_lengths, reference_lengths, fragment_length, minimum_fraction=0.2, min_identity=95.0,
+                    reciprocal=False, order=None, stats=None):
+    """Greedy representative clustering (GTDB species clusters, dRep's and galah's dereplicated sets): the genomes are taken in
+    ``order`` -- a permutation of the genome numbers, the most preferred first; ``None`` is genome-number order and
+    ``"length"`` the longest ``query_lengths`` first, ties by genome number --, a genome becomes a representative unless a pair
+    at or above ``min_identity`` (the edges of `clusters`) joins it to an earlier representative, and every other genome joins
+    the representative it is closest to (ties to the earlier one).  Unlike single linkage, every genome is within the cut-off
+    of the genome that stands for it; which genomes those are depends on ``order``.  Returns ``(labels, identity)``: int32
+    ``[n]``, a representative labels itself, and float64 ``[n]``, the symmetric identity to the label (100 for a
+    representative) -- numpy for ``ROW_DTYPE`` rows, tensors on the rows' device for device rows.  ``stats``, a dict, receives
+    ``rows``, ``pairs``, ``edges``, ``rounds`` (of the selection loop) and ``n_representatives``.  An ``order`` that is no
+    permutation, or a negative or NaN ``min_identity``, raises ``ValueError``."""
+    t = _Table(rows, query_lengths, reference_lengths, fragment_length, minimum_fraction, min_identity, reciprocal)
+    order = _order(order, t)
+    order_ptr = C.c_void_p(order.ctypes.data) if order is not None else None
+    n_representatives, counters = C.c_int32(0), (C.c_int64 * 4)()
+    with t.on_device():
+        if t.torch:
+            labels = t.torch.empty(t.n, dtype=t.torch.int32, device=t.device)
+            identity = t.torch.empty(t.n, dtype=t.torch.float64, device=t.device)
+            out = (C.c_void_p(labels.data_ptr()), C.c_void_p(identity.data_ptr()), 1)
+        else:
+            labels, identity = np.empty(t.n, dtype=np.int32), np.empty(t.n, dtype=np.float64)
+            out = (C.c_void_p(labels.ctypes.data), C.c_void_p(identity.ctypes.data), 0)
+        check(lib.fa_table_representatives(*t.head(), order_ptr, *out, C.byref(n_representatives), counters))
+    if stats is not None:
+        stats.update(rows=counters[0], pairs=counters[1], edges=counters[2], rounds=counters[3],
+                     n_representatives=n_representatives.value)
+    return labels, identity

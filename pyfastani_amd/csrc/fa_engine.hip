@@ -30,6 +30,8 @@
 #include "fa_sketch_fast.hip.h"
 #include "fa_stats.h"
 #include "fa_table.hip.h"
+#include "fa_order.h"
+#include "fa_represent.hip.h"
 #include "fa_best.hip.h"
 #include "fa_screen.hip.h"
 
@@ -1860,8 +1862,53 @@ static unsigned int components(const int2 *edges, int64_t n_edges, int32_t *labe
   return roots;
 }
 
+// The representatives of a weighted edge list over n_genomes > 0 genomes and every other genome's closest one
+// (fa_represent.hip.h): labels and identity (device, identity may be null) are written once the selection has ended; returns
+// the number of representatives and, in `rounds`, those of the selection loop.  `pos` and `order` are device arrays.  `status`
+// is the call's zeroed TableStatus; the stream is synchronised on return.
+static unsigned int representatives(const TableEdge *edges, int64_t n_edges, const int32_t *pos, const int32_t *order, int32_t *labels,
+                                    double *identity, int32_t n_genomes, TableStatus *status, hipStream_t st, int64_t &rounds) {
+  DevBuf<int32_t> words;                      // state, blocked, nearest
+  DevBuf<unsigned long long> best;
+  words.ensure((size_t)n_genomes * 3);
+  best.ensure((size_t)n_genomes);
+  RepArgs r{};
+  r.edges = edges; r.n_edges = n_edges; r.n_genomes = n_genomes; r.pos = pos; r.order = order;
+  r.state = words.p; r.blocked = reinterpret_cast<unsigned int *>(words.p + n_genomes); r.nearest = words.p + 2 * (size_t)n_genomes;
+  r.best = best.p; r.labels = labels; r.identity = identity; r.status = status;
+  const dim3 genome_grid(ceil_div(n_genomes, 256)), edge_grid(ceil_div(n_edges, 256));
+  // without an edge every genome stands for itself
+  hipLaunchKernelGGL(k_rep_init, genome_grid, dim3(256), 0, st, r, n_edges ? REP_UNDECIDED : REP_CHOSEN);
+  rounds = 0;
+  if (n_edges) {
+    // a round decides at least the undecided genome of smallest pos, so there are at most n_genomes of them (fa_represent.hip.h)
+    for (;;) {
+      r.round = (unsigned int)++rounds;
+      hipLaunchKernelGGL(k_rep_edges, edge_grid, dim3(256), 0, st, r);
+      hipLaunchKernelGGL(k_rep_decide, genome_grid, dim3(256), 0, st, r);
+      FA_HIP(hipGetLastError());
+      unsigned int pending = 0;
+      FA_HIP(hipMemcpyAsync(&pending, &status->changed, sizeof pending, hipMemcpyDeviceToHost, st));
+      FA_HIP(hipStreamSynchronize(st));
+      if (pending != r.round) break;
+      FA_REQUIRE(rounds < (int64_t)n_genomes, FA_ERR_INTERNAL, "the selection of representatives did not end within n_genomes rounds");
+    }
+    hipLaunchKernelGGL(k_rep_best, edge_grid, dim3(256), 0, st, r);
+    hipLaunchKernelGGL(k_rep_nearest, edge_grid, dim3(256), 0, st, r);
+  }
+  hipLaunchKernelGGL(k_rep_write, genome_grid, dim3(256), 0, st, r);
+  FA_HIP(hipGetLastError());
+  TableStatus end{};
+  FA_HIP(hipMemcpyAsync(&end, status, sizeof end, hipMemcpyDeviceToHost, st));
+  FA_HIP(hipStreamSynchronize(st));
+  FA_REQUIRE(!(end.flags & TAB_NO_NEAREST), FA_ERR_INTERNAL, "a genome that is no representative has no representative neighbour");
+  return end.roots;
+}
+
 struct TableRequest {
   bool clusters = false;
+  bool representatives = false;            // with `clusters`: labels are representatives, not components
+  const int32_t *order = nullptr; double *identity = nullptr;
   fa_pair *pairs = nullptr; int64_t cap = 0; int64_t *n_pairs = nullptr; bool pairs_device = false;
   int32_t *labels = nullptr; bool labels_device = false; int32_t *n_clusters = nullptr; int64_t *stats = nullptr;
 };
@@ -1876,6 +1923,11 @@ static void table_reduce(const fa_cgi_row *rows, int64_t n_rows, bool rows_devic
   FA_REQUIRE(n_rows <= (int64_t)INT32_MAX, FA_ERR_UNSUPPORTED, "a table of more than 2^31 - 1 rows");
   if (want.clusters) FA_REQUIRE(n_genomes == 0 || want.labels, FA_ERR_INVALID, "null labels");
   else FA_REQUIRE(want.n_pairs && want.cap >= 0, FA_ERR_INVALID, "null pair count or negative capacity");
+  std::vector<int32_t> pos;
+  if (want.representatives) {
+    FA_REQUIRE(p->min_identity >= 0.0f, FA_ERR_INVALID, "min_identity must be a number that is not negative");          // (false for NaN)
+    FA_REQUIRE(order_positions(want.order, n_genomes, pos), FA_ERR_INVALID, "order is not a permutation of the genome numbers");
+  }
   require_device();
   struct StreamGuard {
     hipStream_t s = nullptr;
@@ -1899,7 +1951,7 @@ static void table_reduce(const fa_cgi_row *rows, int64_t n_rows, bool rows_devic
   a.n_rows = n_rows; a.n_genomes = n_genomes;
   a.fragment_length = (unsigned long long)p->fragment_length; a.min_fraction = p->min_fraction;
   a.min_identity = (double)p->min_identity; a.reciprocal = p->reciprocal;
-  a.edges_only = want.clusters ? 1 : 0;
+  a.edges_only = want.representatives ? TAB_EMIT_WEIGHTED : want.clusters ? TAB_EMIT_EDGES : TAB_EMIT_PAIRS;
   a.status = d_status.p;
   a.n_chunks = ceil_div(n_rows, TAB_CHUNK);
   TableStatus status{};
@@ -1950,7 +2002,29 @@ static void table_reduce(const fa_cgi_row *rows, int64_t n_rows, bool rows_devic
 
   int64_t rounds = 0;
   unsigned int roots = 0;
-  if (n_genomes) {
+  if (n_genomes && want.representatives) {
+    DevBuf<TableEdge> d_edges;
+    DevBuf<int32_t> d_order, d_labels;         // d_order: pos, then order
+    DevBuf<double> d_identity;
+    std::vector<int32_t> both(pos);
+    both.resize((size_t)n_genomes * 2);
+    for (int32_t g = 0; g < n_genomes; g++) both[(size_t)n_genomes + (size_t)pos[(size_t)g]] = g;
+    d_order.upload(both, st);
+    if (!want.labels_device) { d_labels.ensure((size_t)n_genomes); if (want.identity) d_identity.ensure((size_t)n_genomes); }
+    if (n_emit) {
+      d_edges.ensure((size_t)n_emit);
+      a.weighted = d_edges.p; a.cap = n_emit;
+      hipLaunchKernelGGL(k_table_write, dim3(ceil_div(a.n_chunks, 4)), dim3(256), 0, st, a);
+    }
+    double *identity = !want.identity ? nullptr : want.labels_device ? want.identity : d_identity.p;
+    roots = representatives(d_edges.p, n_emit, d_order.p, d_order.p + n_genomes, want.labels_device ? want.labels : d_labels.p, identity,
+                            n_genomes, d_status.p, st, rounds);
+    if (!want.labels_device) {
+      d_labels.download(want.labels, (size_t)n_genomes, st);
+      if (want.identity) d_identity.download(want.identity, (size_t)n_genomes, st);
+    }
+    FA_HIP(hipStreamSynchronize(st));
+  } else if (n_genomes) {
     DevBuf<int2> d_edges;
     DevBuf<int32_t> d_labels;
     if (!want.labels_device) d_labels.ensure((size_t)n_genomes);
@@ -2756,6 +2830,17 @@ int fa_table_clusters(const fa_cgi_row *rows, int64_t n_rows, int rows_device, i
     TableRequest want;
     want.clusters = true;
     want.labels = labels; want.labels_device = labels_device != 0; want.n_clusters = n_clusters; want.stats = stats;
+    table_reduce(rows, n_rows, rows_device != 0, n_genomes, query_lengths, reference_lengths, p, want);
+  });
+}
+int fa_table_representatives(const fa_cgi_row *rows, int64_t n_rows, int rows_device, int32_t n_genomes, const uint64_t *query_lengths,
+                             const uint64_t *reference_lengths, const fa_table_params *p, const int32_t *order, int32_t *labels,
+                             double *identity, int out_device, int32_t *n_representatives, int64_t *stats) {
+  return guarded([&] {
+    TableRequest want;
+    want.clusters = want.representatives = true;
+    want.order = order; want.labels = labels; want.identity = identity; want.labels_device = out_device != 0;
+    want.n_clusters = n_representatives; want.stats = stats;
     table_reduce(rows, n_rows, rows_device != 0, n_genomes, query_lengths, reference_lengths, p, want);
   });
 }

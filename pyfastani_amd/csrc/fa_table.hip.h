@@ -22,7 +22,8 @@
 // predecessor is not the surviving other direction = the head of a pair.  Heads (or, for the clusters, heads that are edges)
 // are compacted in order by count / scan / write over chunks of one wave's TAB_CHUNK consecutive rows, a head's place inside its
 // chunk being the population count of the ballots below its lane (the form of k_map_count / k_map_scan / k_map_write).
-// The same input therefore gives the same bytes on every run: no record's place depends on timing.
+// The same input therefore gives the same bytes on every run: no record's place depends on timing.  (A third form of the
+// write kernel keeps an edge's identity, TableEdge: what fa_represent.hip.h selects representatives from.)
 //
 // Components run as rounds of two launches.  k_comp_edges lowers, for every edge whose ends carry different labels, the
 // larger label's own entry and the entry of the genome that carried it to the smaller label (atomicMin); k_comp_jump
@@ -52,6 +53,14 @@ struct TableStatus {
   unsigned int pad;
 };
 
+// an edge with the symmetric identity it passed the cut-off with (the third form k_table_write emits: fa_represent.hip.h)
+struct TableEdge {
+  int32_t a, b;
+  double identity;                     // >= 0; -0.0 is stored as +0.0
+};
+
+constexpr int32_t TAB_EMIT_PAIRS = 0, TAB_EMIT_EDGES = 1, TAB_EMIT_WEIGHTED = 2;
+
 struct TableArgs {
   const fa_cgi_row *rows;
   int64_t n_rows;
@@ -64,12 +73,13 @@ struct TableArgs {
   const unsigned long long *keys;      // sorted
   const uint32_t *row_of;              // row number of every sorted key
   int32_t n_chunks;
-  int32_t edges_only;                  // compact the edges as (a, b), not the pairs as records
+  int32_t edges_only;                  // TAB_EMIT_*: the pairs as records, the edges as (a, b), the edges as (a, b, identity)
   int32_t *chunk_count;                // [n_chunks]
   int64_t *chunk_off;                  // [n_chunks]
   fa_pair *pairs;
   int2 *edges;
-  int64_t cap;                         // room behind `pairs` / `edges`
+  TableEdge *weighted;
+  int64_t cap;                         // room behind `pairs` / `edges` / `weighted`
   TableStatus *status;
 };
 
@@ -186,7 +196,11 @@ __global__ __launch_bounds__(256) void k_table_write(TableArgs a) {
     const int64_t o = off + __popcll(mask & below);
     off += __popcll(mask);
     if (!emit || o >= a.cap) continue;
-    if (a.edges_only) a.edges[o] = make_int2(t.a, t.b);
+    if (a.edges_only == TAB_EMIT_WEIGHTED) {
+      TableEdge e;
+      e.a = t.a; e.b = t.b; e.identity = t.identity == 0.0 ? 0.0 : t.identity;
+      a.weighted[o] = e;
+    } else if (a.edges_only) a.edges[o] = make_int2(t.a, t.b);
     else {
       fa_pair p;
       p.a = t.a; p.b = t.b; p.identity_ab = t.ab; p.identity_ba = t.ba; p.identity = t.identity;

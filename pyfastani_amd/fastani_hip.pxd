@@ -163,6 +163,10 @@ cdef extern from "fastani_hip.h" nogil:
     int fa_table_clusters(const fa_cgi_row* rows, int64_t n_rows, int rows_device, int32_t n_genomes, const uint64_t* query_lengths,
                           const uint64_t* reference_lengths, const fa_table_params* p, int32_t* labels, int labels_device,
                           int32_t* n_clusters, int64_t* stats)
+    int fa_table_representatives(const fa_cgi_row* rows, int64_t n_rows, int rows_device, int32_t n_genomes,
+                                 const uint64_t* query_lengths, const uint64_t* reference_lengths, const fa_table_params* p,
+                                 const int32_t* order, int32_t* labels, double* identity, int out_device,
+                                 int32_t* n_representatives, int64_t* stats)
 
     # a query x reference hit table reduced to every query's k best hits (pyfastani_amd.classify)
     ctypedef struct fa_best_params:

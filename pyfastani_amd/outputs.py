@@ -54,6 +54,19 @@ def write_clusters(path, names, labels):
             f.write(f"{name}\t{names[int(label)]}\n")
 
 
+def write_representatives(path, names, labels, identity):
+    """The result of `pyfastani_amd.clusters.representatives`: one line per genome, in genome order, with its name, the name
+    of its representative and the symmetric identity of the two (100 for a representative itself).  `write_clusters` takes
+    the same labels."""
+    labels = labels.cpu().numpy() if hasattr(labels, "cpu") else np.asarray(labels)
+    identity = identity.cpu().numpy() if hasattr(identity, "cpu") else np.asarray(identity)
+    if len(labels) != len(names) or len(identity) != len(names):
+        raise ValueError("one label and one identity per name")
+    with open(path, "w") as f:
+        for name, label, value in zip(names, labels, identity):
+            f.write(f"{name}\t{names[int(label)]}\t{float(value):.6g}\n")
+
+
 def write_hits(path, query_names, reference_names, rows):
     """FastANI's tabular output: query, reference, ANI, mapped fragments, total query fragments (one line per hit,
     queries in order, hits of a query by decreasing identity)."""

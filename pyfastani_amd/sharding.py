@@ -234,6 +234,14 @@ class ResidentHitTable:
         return _clusters.clusters(self._rows_in_place(tables), query_lengths, reference_lengths, fragment_length, minimum_fraction,
                                   min_identity, reciprocal, stats)
 
+    def representatives(self, tables, query_lengths, reference_lengths, fragment_length, minimum_fraction=0.2, min_identity=95.0,
+                        reciprocal=False, order=None, stats=None):
+        """`pyfastani_amd.clusters.representatives` over an exchanged table (what `step` returns) of an all-vs-all:
+        ``(labels, identity)``, with the count rows dropped and the ranks joined as for `clusters`."""
+        from . import clusters as _clusters
+        return _clusters.representatives(self._rows_in_place(tables), query_lengths, reference_lengths, fragment_length,
+                                         minimum_fraction, min_identity, reciprocal, order, stats)
+
     def best(self, tables, query_lengths, reference_lengths, fragment_length, k=1, minimum_fraction=0.2, min_identity=0.0,
              min_aligned_fraction=0.0, exclude_self=False, stats=None):
         """`pyfastani_amd.classify.best_hits` over an exchanged table (what `step` returns): ``(records, offsets)``, every
