@@ -11,14 +11,13 @@ device.  There is no CPU path: without a HIP device `best_hits` raises ``Runtime
 
 Not imported by the package itself (like `clusters` and `outputs`): it needs numpy.
 """
-import contextlib
 import ctypes as C
 
 import numpy as np
 
 from ._batch import ROW_DTYPE
 from ._lib import BestParams, check, lib
-from .clusters import _is_tensor
+from .clusters import _Rows
 
 
 def best_hits(rows, query_lengths, reference_lengths, fragment_length, k=1, minimum_fraction=0.2, min_identity=0.0,
@@ -41,27 +40,18 @@ def best_hits(rows, query_lengths, reference_lengths, fragment_length, k=1, mini
     params = BestParams(float(minimum_fraction), int(fragment_length), float(min_identity), float(min_aligned_fraction), int(k),
                         1 if exclude_self else 0)
     n, counters = C.c_int64(0), (C.c_int64 * 3)()
-    lengths = (n_queries, n_references, C.c_void_p(qlen.ctypes.data), C.c_void_p(rlen.ctypes.data), C.byref(params))
-    if _is_tensor(rows):
-        import torch
-        if rows.dtype != torch.int32 or rows.dim() != 2 or rows.shape[1] != 5 or not rows.is_cuda:
-            raise ValueError("device rows are an int32 [n_rows, 5] tensor in HBM")
-        rows = rows.contiguous()
-        n_rows, on_device = int(rows.shape[0]), torch.cuda.device(rows.device)
-        cap = min(n_rows, n_queries * max(int(k), 0))
-        records = torch.empty((cap, 5), dtype=torch.int32, device=rows.device)
-        offsets = torch.empty(n_queries + 1, dtype=torch.int64, device=rows.device)
-        torch.cuda.synchronize(rows.device)              # the library runs on a stream of its own: torch's writes are done
-        out = (C.c_void_p(rows.data_ptr()), n_rows, 1) + lengths + (C.c_void_p(records.data_ptr()), C.c_void_p(offsets.data_ptr()))
-    else:
-        rows = np.ascontiguousarray(rows, dtype=ROW_DTYPE)
-        n_rows, on_device = int(rows.shape[0]), contextlib.nullcontext()
-        cap = min(n_rows, n_queries * max(int(k), 0))
-        records = np.empty(cap, dtype=ROW_DTYPE)
-        offsets = np.empty(n_queries + 1, dtype=np.int64)
-        out = (C.c_void_p(rows.ctypes.data), n_rows, 0) + lengths + (C.c_void_p(records.ctypes.data), C.c_void_p(offsets.ctypes.data))
-    with on_device:
-        check(lib.fa_table_best(*out, cap, C.byref(n), 0 if isinstance(rows, np.ndarray) else 1, counters))
+    r = _Rows(rows)
+    cap = min(r.n_rows, n_queries * max(int(k), 0))
+    with r.on_device():
+        if r.is_device:
+            records = r.torch.empty((cap, 5), dtype=r.torch.int32, device=r.device)
+            offsets = r.torch.empty(n_queries + 1, dtype=r.torch.int64, device=r.device)
+            out = (C.c_void_p(records.data_ptr()), C.c_void_p(offsets.data_ptr()))
+        else:
+            records, offsets = np.empty(cap, dtype=ROW_DTYPE), np.empty(n_queries + 1, dtype=np.int64)
+            out = (C.c_void_p(records.ctypes.data), C.c_void_p(offsets.ctypes.data))
+        check(lib.fa_table_best(C.c_void_p(r.ptr), r.n_rows, 1 if r.is_device else 0, n_queries, n_references, C.c_void_p(qlen.ctypes.data),
+                                C.c_void_p(rlen.ctypes.data), C.byref(params), *out, cap, C.byref(n), 1 if r.is_device else 0, counters))
     if stats is not None:
         stats.update(rows=counters[0], queries=counters[1], records=counters[2])
-    return (records[: n.value].copy() if isinstance(records, np.ndarray) else records[: n.value]), offsets
+    return (records[: n.value] if r.is_device else records[: n.value].copy()), offsets

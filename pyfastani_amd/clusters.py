@@ -23,7 +23,31 @@ def _is_tensor(rows):
     return not isinstance(rows, np.ndarray) and hasattr(rows, "data_ptr")
 
 
-class _Table:
+class _Rows:
+    """The one reading of a ``rows`` argument: a ``ROW_DTYPE`` array on the host or an int32 ``[n_rows, 5]`` tensor in HBM,
+    contiguous and alive for the call, as ``ptr``, ``n_rows`` and ``is_device`` (then ``torch`` and ``device`` are set)."""
+
+    def __init__(self, rows):
+        self.torch = self.device = None
+        if _is_tensor(rows):
+            import torch
+            if rows.dtype != torch.int32 or rows.dim() != 2 or rows.shape[1] != 5 or not rows.is_cuda:
+                raise ValueError("device rows are an int32 [n_rows, 5] tensor in HBM")
+            self.torch, self.rows, self.device = torch, rows.contiguous(), rows.device
+            self.n_rows, self.ptr = int(rows.shape[0]), self.rows.data_ptr()
+            torch.cuda.synchronize(self.device)          # the library runs on a stream of its own: torch's writes are done
+        else:
+            self.rows = np.ascontiguousarray(rows, dtype=ROW_DTYPE)
+            self.n_rows, self.ptr = int(self.rows.shape[0]), self.rows.ctypes.data
+        self.is_device = self.torch is not None
+
+    def on_device(self):
+        """The calling thread's current device is the one the entry points run on: the tensor's, for the call."""
+        import contextlib
+        return self.torch.cuda.device(self.device) if self.is_device else contextlib.nullcontext()
+
+
+class _Table(_Rows):
     """The arguments the entry points share, as ctypes values that stay alive for the call."""
 
     def __init__(self, rows, query_lengths, reference_lengths, fragment_length, minimum_fraction, min_identity=0.0, reciprocal=False):
@@ -33,26 +57,11 @@ class _Table:
             raise ValueError("query_lengths and reference_lengths are two arrays over the same genomes")
         self.n = int(self.qlen.shape[0])
         self.params = TableParams(float(minimum_fraction), int(fragment_length), float(min_identity), 1 if reciprocal else 0)
-        self.torch = None
-        if _is_tensor(rows):
-            import torch
-            if rows.dtype != torch.int32 or rows.dim() != 2 or rows.shape[1] != 5 or not rows.is_cuda:
-                raise ValueError("device rows are an int32 [n_rows, 5] tensor in HBM")
-            self.torch, self.rows = torch, rows.contiguous()
-            self.n_rows, self.rows_ptr, self.device = int(rows.shape[0]), self.rows.data_ptr(), rows.device
-            torch.cuda.synchronize(self.device)          # the library runs on a stream of its own: torch's writes are done
-        else:
-            self.rows = np.ascontiguousarray(rows, dtype=ROW_DTYPE)
-            self.n_rows, self.rows_ptr = int(self.rows.shape[0]), self.rows.ctypes.data
+        super().__init__(rows)
 
     def head(self):
-        return (C.c_void_p(self.rows_ptr), self.n_rows, 1 if self.torch else 0, self.n, C.c_void_p(self.qlen.ctypes.data),
+        return (C.c_void_p(self.ptr), self.n_rows, 1 if self.is_device else 0, self.n, C.c_void_p(self.qlen.ctypes.data),
                 C.c_void_p(self.rlen.ctypes.data), C.byref(self.params))
-
-    def on_device(self):
-        """The calling thread's current device is the one the entry points run on: the tensor's, for the call."""
-        import contextlib
-        return self.torch.cuda.device(self.device) if self.torch else contextlib.nullcontext()
 
 
 def pairs(rows, query_lengths, reference_lengths, fragment_length, minimum_fraction=0.2):

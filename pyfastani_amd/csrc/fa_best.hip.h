@@ -103,7 +103,7 @@ __global__ __launch_bounds__(256) void k_best_segments(BestArgs a) {
 }
 
 // exclusive 64-bit sum of min(k, survivors) over the queries by one workgroup (thread t owns a run of consecutive queries, the
-// form of k_table_scan) + the total behind it + the counters
+// form of k_chunk_scan, fa_compact.hip.h) + the total behind it + the counters
 __global__ __launch_bounds__(1024) void k_best_scan(BestArgs a) {
   __shared__ long long sh_wave[16], sh_survivors[16], sh_queries[16];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;

@@ -155,4 +155,71 @@ struct DevBuf {
   }
 };
 
+inline void require_device() {
+  int n = 0;
+  hipError_t e = hipGetDeviceCount(&n);
+  if (e != hipSuccess || n <= 0) {
+    (void)hipGetLastError();
+    throw Error(FA_ERR_NO_DEVICE, "no HIP device available: libfastani_hip has no CPU fallback");
+  }
+}
+
+// a stream of one call's own: synchronised and destroyed when the call returns or throws
+struct CallStream {
+  hipStream_t s = nullptr;
+  CallStream() { FA_HIP(hipStreamCreate(&s)); }
+  CallStream(const CallStream &) = delete;
+  ~CallStream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } }
+};
+
+// rocPRIM's two calls with the argument list written once: fn(nullptr, bytes) sizes the temporary storage, fn(temp, bytes) runs
+template <typename Fn>
+void with_temp(DevBuf<unsigned char> &temp, Fn fn) {
+  size_t bytes = 0;
+  FA_HIP(fn(nullptr, bytes));
+  temp.ensure(bytes + 16);
+  FA_HIP(fn(temp.p, bytes));
+}
+
+// the status block of one call: a device T zeroed on the stream before the first launch; read() = its host copy, synchronised
+template <typename T>
+struct StatusBlock {
+  T *p;
+  explicit StatusBlock(hipStream_t st) {
+    buf.ensure(1);
+    p = buf.p;
+    FA_HIP(hipMemsetAsync(p, 0, sizeof(T), st));
+  }
+  T read(hipStream_t st) const {
+    T host{};
+    buf.download(&host, 1, st);
+    FA_HIP(hipStreamSynchronize(st));
+    return host;
+  }
+ private:
+  DevBuf<T> buf;
+};
+
+// an output of n elements behind the caller's pointer: dev() is that pointer when it is a device one, else a staged copy
+// that finish() sends to the host on the stream (the caller synchronises)
+template <typename T>
+struct Staged {
+  Staged(T *out, bool device, size_t n) : out_(out), device_(device), n_(n) { if (out && !device) buf_.ensure(n); }
+  T *dev() const { return !out_ ? nullptr : device_ ? out_ : buf_.p; }
+  void finish(hipStream_t st) const { if (out_ && !device_) buf_.download(out_, n_, st); }
+ private:
+  T *out_;
+  bool device_;
+  size_t n_;
+  DevBuf<T> buf_;
+};
+
+// an input of n elements on the device: the caller's pointer when it is a device one, else its copy in `stage`
+template <typename T>
+const T *on_device(const T *in, bool device, size_t n, DevBuf<T> &stage, hipStream_t st) {
+  if (device) return in;
+  stage.upload(in, n, st);
+  return stage.p;
+}
+
 }  // namespace fa

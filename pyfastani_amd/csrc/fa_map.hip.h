@@ -21,6 +21,7 @@
 #pragma once
 
 #include "fa_common.h"
+#include "fa_compact.hip.h"
 #include "fa_mapstream.h"
 #include "fa_policy.h"
 #include "fa_sketch.hip.h"
@@ -2719,7 +2720,7 @@ __global__ void k_flag_nonzero(const int32_t *row_count, int64_t n, int32_t *fla
 // counts, write: a workgroup takes MAP_CHUNK consecutive bins, each of its waves 64 * MAP_ITERS of them in coalesced
 // 64-bin reads (issued together), and a bin's place among its wave's is the population count of the ballot below its lane.
 // A bin is mapped where the upper word of its key -- the identity -- is not zero, as in k_cgi_rows.  The count and the scan
-// run once per pass; the write runs once per window of the records (fa_mapstream.h), so that a pass of any size leaves the
+// (k_chunk_scan, fa_compact.hip.h) run once per pass; the write runs once per window of the records (fa_mapstream.h), so that a pass of any size leaves the
 // device through stage buffers of fixed size.
 // ----------------------------------------------------------------------------------------------------------
 constexpr int MAP_ITERS = 8, MAP_CHUNK = 256 * MAP_ITERS;
@@ -2732,7 +2733,6 @@ struct MapEmitArgs {
   int32_t *chunk_count;             // [n_chunks]
   int64_t *chunk_off;               // [n_chunks] records of the pass in front of the chunk
   fa_hit_mapping *maps;             // where the records of the window go (k_map_write): a stage buffer or the caller's
-  int64_t *total_maps;              // in the status block: the full count, whatever the room
   TieKey tie;                       // the rule the bin keys were written under (CgiArgs::tie)
 };
 
@@ -2754,25 +2754,6 @@ __global__ __launch_bounds__(256) void k_map_count(MapEmitArgs a) {
   if (lane == 0) sh_wave[wv] = n;
   __syncthreads();
   if (threadIdx.x == 0) a.chunk_count[blockIdx.x] = sh_wave[0] + sh_wave[1] + sh_wave[2] + sh_wave[3];
-}
-
-// exclusive 64-bit sum of the chunk counts by one workgroup (thread t owns a run of consecutive chunks) + the pass's total
-__global__ __launch_bounds__(1024) void k_map_scan(MapEmitArgs a) {
-  __shared__ long long sh_wave[16];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int per = (a.n_chunks + 1023) / 1024;
-  const int c0 = min(a.n_chunks, (int)threadIdx.x * per), c1 = min(a.n_chunks, c0 + per);
-  long long mine = 0;
-  for (int c = c0; c < c1; c++) mine += a.chunk_count[c];
-  long long incl = mine;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) { const long long v = __shfl_up(incl, d); if (lane >= d) incl += v; }
-  if (lane == 63) sh_wave[wv] = incl;
-  __syncthreads();
-  long long off = incl - mine;
-  for (int w = 0; w < wv; w++) off += sh_wave[w];
-  for (int c = c0; c < c1; c++) { a.chunk_off[c] = off; off += a.chunk_count[c]; }
-  if (threadIdx.x == 1023) *a.total_maps = off;
 }
 
 // writes the records of the pass whose places lie in the window [lo, hi) (fa_mapstream.h) to maps[place - lo]: one launch per

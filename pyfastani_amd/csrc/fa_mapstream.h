@@ -1,7 +1,7 @@
 // fa_mapstream.h -- the window arithmetic of the streamed mapping output: plain C++, no HIP
 // (scripts/host_sanitize/mapstream.cpp checks it on the CPU).
 //
-// The records of a pass (fa_hit_mapping, k_map_count / k_map_scan / k_map_write in fa_map.hip.h) have places 0 .. total - 1 in
+// The records of a pass (fa_hit_mapping, k_map_count / k_chunk_scan / k_map_write in fa_map.hip.h) have places 0 .. total - 1 in
 // (query, reference genome, bin) order.  They leave the device in windows of `stage` records: window w holds the places
 // [w * stage, min(total, (w + 1) * stage)), written to the front of a stage buffer of fixed size.  k_map_write is launched once
 // per window; a workgroup, which owns one chunk of consecutive bins and knows the place of its first record and their number,

@@ -77,7 +77,7 @@ enum PinfoSlot : int {
 struct PassStatus {
   int32_t stats[4];                 // StatSlot
   int32_t total_rows, pad0;
-  int64_t total_maps;               // fa_hit_mapping records of the pass (a call that asked for mappings; k_map_scan)
+  int64_t total_maps;               // fa_hit_mapping records of the pass (a call that asked for mappings; k_chunk_scan)
   uint64_t totals[4];               // TotalSlot
   uint32_t counters[8];             // CounterSlot
   unsigned long long pinfo[4];      // PinfoSlot

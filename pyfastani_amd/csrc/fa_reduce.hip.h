@@ -1,0 +1,488 @@
+// fa_reduce.hip.h -- the host drivers of the reductions over results the mapper already holds: a hit table to pairs,
+// clusters and representatives (fa_table.hip.h, fa_represent.hip.h), to every query's k best hits (fa_best.hip.h), and the
+// signature screen (fa_screen.hip.h).  They use nothing of the sketch, the mapper or the workspace; fa_engine.hip wraps each
+// in its extern "C" entry point.
+//
+// Every driver has the same frame (the pieces are in fa_common.h): it checks its arguments, then require_device(), then
+//   - runs on a stream of the call's own (CallStream), declared before every buffer so that it outlives them;
+//   - owns a status block (StatusBlock) zeroed on that stream before the first launch, and turns the flags it reads back
+//     into the entry point's own error messages;
+//   - takes every input as the caller's device pointer or uploads it (on_device), and writes every output to the caller's
+//     device pointer or to a staged copy that is downloaded at the end (Staged);
+//   - sizes its sort keys with bit_width_u64 / id_bits and calls rocPRIM through with_temp;
+//   - is synchronised when it returns: host outputs are complete, device outputs are written.
+#pragma once
+
+#include <rocprim/rocprim.hpp>
+
+#include <algorithm>
+#include <climits>
+#include <vector>
+
+#include "fa_best.hip.h"
+#include "fa_common.h"
+#include "fa_order.h"
+#include "fa_represent.hip.h"
+#include "fa_screen.hip.h"
+#include "fa_table.hip.h"
+
+namespace fa {
+
+// ------------------------------------------------------------------------------------------------------------
+// The hit table of an all-vs-all reduced to pairs and clusters (fa_table.hip.h has the semantics and the road)
+// ------------------------------------------------------------------------------------------------------------
+// The connected components of an edge list over n_genomes > 0 genomes (fa_table.hip.h): labels (device) receive every genome's
+// smallest group member; returns the number of groups and, in `rounds`, those of the loop.  `status` is the call's zeroed
+// TableStatus; the stream is synchronised on return.
+inline unsigned int components(const int2 *edges, int64_t n_edges, int32_t *labels, int32_t n_genomes, TableStatus *status, hipStream_t st,
+                               int64_t &rounds) {
+  CompArgs c{};
+  c.edges = edges; c.n_edges = n_edges; c.labels = labels; c.n_genomes = n_genomes; c.status = status;
+  const dim3 genome_grid(ceil_div(n_genomes, 256));
+  hipLaunchKernelGGL(k_comp_init, genome_grid, dim3(256), 0, st, c.labels, n_genomes);
+  rounds = 0;
+  if (n_edges) {
+    // a round lowers at least one label or is the last; labels only decrease, so the loop ends (fa_table.hip.h)
+    for (;;) {
+      c.round = (unsigned int)++rounds;
+      hipLaunchKernelGGL(k_comp_edges, dim3(ceil_div(n_edges, 256)), dim3(256), 0, st, c);
+      hipLaunchKernelGGL(k_comp_jump, genome_grid, dim3(256), 0, st, c);
+      FA_HIP(hipGetLastError());
+      unsigned int changed = 0;
+      FA_HIP(hipMemcpyAsync(&changed, &status->changed, sizeof changed, hipMemcpyDeviceToHost, st));
+      FA_HIP(hipStreamSynchronize(st));
+      if (changed != c.round) break;
+    }
+  }
+  unsigned int roots = 0;
+  hipLaunchKernelGGL(k_comp_roots, genome_grid, dim3(256), 0, st, c);
+  FA_HIP(hipGetLastError());
+  FA_HIP(hipMemcpyAsync(&roots, &status->roots, sizeof roots, hipMemcpyDeviceToHost, st));
+  FA_HIP(hipStreamSynchronize(st));
+  return roots;
+}
+
+// The representatives of a weighted edge list over n_genomes > 0 genomes and every other genome's closest one
+// (fa_represent.hip.h): labels and identity (device, identity may be null) are written once the selection has ended; returns
+// the number of representatives and, in `rounds`, those of the selection loop.  `pos` and `order` are device arrays.  `status`
+// is the call's zeroed TableStatus; the stream is synchronised on return.
+inline unsigned int representatives(const TableEdge *edges, int64_t n_edges, const int32_t *pos, const int32_t *order, int32_t *labels,
+                                    double *identity, int32_t n_genomes, TableStatus *status, hipStream_t st, int64_t &rounds) {
+  DevBuf<int32_t> words;                      // state, blocked, nearest
+  DevBuf<unsigned long long> best;
+  words.ensure((size_t)n_genomes * 3);
+  best.ensure((size_t)n_genomes);
+  RepArgs r{};
+  r.edges = edges; r.n_edges = n_edges; r.n_genomes = n_genomes; r.pos = pos; r.order = order;
+  r.state = words.p; r.blocked = reinterpret_cast<unsigned int *>(words.p + n_genomes); r.nearest = words.p + 2 * (size_t)n_genomes;
+  r.best = best.p; r.labels = labels; r.identity = identity; r.status = status;
+  const dim3 genome_grid(ceil_div(n_genomes, 256)), edge_grid(ceil_div(n_edges, 256));
+  // without an edge every genome stands for itself
+  hipLaunchKernelGGL(k_rep_init, genome_grid, dim3(256), 0, st, r, n_edges ? REP_UNDECIDED : REP_CHOSEN);
+  rounds = 0;
+  if (n_edges) {
+    // a round decides at least the undecided genome of smallest pos, so there are at most n_genomes of them (fa_represent.hip.h)
+    for (;;) {
+      r.round = (unsigned int)++rounds;
+      hipLaunchKernelGGL(k_rep_edges, edge_grid, dim3(256), 0, st, r);
+      hipLaunchKernelGGL(k_rep_decide, genome_grid, dim3(256), 0, st, r);
+      FA_HIP(hipGetLastError());
+      unsigned int pending = 0;
+      FA_HIP(hipMemcpyAsync(&pending, &status->changed, sizeof pending, hipMemcpyDeviceToHost, st));
+      FA_HIP(hipStreamSynchronize(st));
+      if (pending != r.round) break;
+      FA_REQUIRE(rounds < (int64_t)n_genomes, FA_ERR_INTERNAL, "the selection of representatives did not end within n_genomes rounds");
+    }
+    hipLaunchKernelGGL(k_rep_best, edge_grid, dim3(256), 0, st, r);
+    hipLaunchKernelGGL(k_rep_nearest, edge_grid, dim3(256), 0, st, r);
+  }
+  hipLaunchKernelGGL(k_rep_write, genome_grid, dim3(256), 0, st, r);
+  FA_HIP(hipGetLastError());
+  TableStatus end{};
+  FA_HIP(hipMemcpyAsync(&end, status, sizeof end, hipMemcpyDeviceToHost, st));
+  FA_HIP(hipStreamSynchronize(st));
+  FA_REQUIRE(!(end.flags & TAB_NO_NEAREST), FA_ERR_INTERNAL, "a genome that is no representative has no representative neighbour");
+  return end.roots;
+}
+
+struct TableRequest {
+  bool clusters = false;
+  bool representatives = false;            // with `clusters`: labels are representatives, not components
+  const int32_t *order = nullptr; double *identity = nullptr;
+  fa_pair *pairs = nullptr; int64_t cap = 0; int64_t *n_pairs = nullptr; bool pairs_device = false;
+  int32_t *labels = nullptr; bool labels_device = false; int32_t *n_clusters = nullptr; int64_t *stats = nullptr;
+};
+
+inline void table_reduce(const fa_cgi_row *rows, int64_t n_rows, bool rows_device, int32_t n_genomes, const uint64_t *query_lengths,
+                         const uint64_t *reference_lengths, const fa_table_params *p, const TableRequest &want) {
+  FA_REQUIRE(p, FA_ERR_INVALID, "null table parameters");
+  FA_REQUIRE(p->fragment_length >= 1, FA_ERR_INVALID, "fragment_length must be strictly positive");
+  FA_REQUIRE(n_genomes >= 0 && n_rows >= 0, FA_ERR_INVALID, "negative table size");
+  FA_REQUIRE(n_rows == 0 || rows, FA_ERR_INVALID, "null rows");
+  FA_REQUIRE(n_genomes == 0 || (query_lengths && reference_lengths), FA_ERR_INVALID, "null genome lengths");
+  FA_REQUIRE(n_rows <= (int64_t)INT32_MAX, FA_ERR_UNSUPPORTED, "a table of more than 2^31 - 1 rows");
+  if (want.clusters) FA_REQUIRE(n_genomes == 0 || want.labels, FA_ERR_INVALID, "null labels");
+  else FA_REQUIRE(want.n_pairs && want.cap >= 0, FA_ERR_INVALID, "null pair count or negative capacity");
+  std::vector<int32_t> pos;
+  if (want.representatives) {
+    FA_REQUIRE(p->min_identity >= 0.0f, FA_ERR_INVALID, "min_identity must be a number that is not negative");          // (false for NaN)
+    FA_REQUIRE(order_positions(want.order, n_genomes, pos), FA_ERR_INVALID, "order is not a permutation of the genome numbers");
+  }
+  require_device();
+  CallStream stream;
+  hipStream_t st = stream.s;
+  StatusBlock<TableStatus> d_status(st);
+  DevBuf<fa_cgi_row> d_rows;
+  DevBuf<uint64_t> d_len;
+  DevBuf<unsigned long long> keys, keys_sorted;
+  DevBuf<uint32_t> row_of, row_of_sorted;
+  DevBuf<unsigned char> temp;
+  DevBuf<int32_t> chunk_count;
+  DevBuf<int64_t> chunk_off;
+
+  TableArgs a{};
+  a.n_rows = n_rows; a.n_genomes = n_genomes;
+  a.fragment_length = (unsigned long long)p->fragment_length; a.min_fraction = p->min_fraction;
+  a.min_identity = (double)p->min_identity; a.reciprocal = p->reciprocal;
+  a.edges_only = want.representatives ? TAB_EMIT_WEIGHTED : want.clusters ? TAB_EMIT_EDGES : TAB_EMIT_PAIRS;
+  a.status = d_status.p;
+  a.n_chunks = ceil_div(n_rows, TAB_CHUNK);
+  TableStatus status{};
+  if (n_rows) {
+    a.rows = on_device(rows, rows_device, (size_t)n_rows, d_rows, st);
+    d_len.ensure((size_t)n_genomes * 2);
+    FA_HIP(hipMemcpyAsync(d_len.p, query_lengths, (size_t)n_genomes * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    FA_HIP(hipMemcpyAsync(d_len.p + n_genomes, reference_lengths, (size_t)n_genomes * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    a.query_length = d_len.p; a.reference_length = d_len.p + n_genomes;
+    keys.ensure((size_t)n_rows); keys_sorted.ensure((size_t)n_rows);
+    row_of.ensure((size_t)n_rows); row_of_sorted.ensure((size_t)n_rows);
+    hipLaunchKernelGGL(k_table_keys, dim3(ceil_div(n_rows, 256)), dim3(256), 0, st, a, keys.p, row_of.p);
+    // the bits a key of this table can have set: two flag bits, 31 of b, and those of the largest a
+    const unsigned end_bit = 33u + id_bits(n_genomes);
+    with_temp(temp, [&](void *t, size_t &bytes) {
+      return rocprim::radix_sort_pairs(t, bytes, keys.p, keys_sorted.p, row_of.p, row_of_sorted.p, (size_t)n_rows, 0u, end_bit, st);
+    });
+    a.keys = keys_sorted.p; a.row_of = row_of_sorted.p;
+    chunk_count.ensure((size_t)a.n_chunks); chunk_off.ensure((size_t)a.n_chunks);
+    a.chunk_count = chunk_count.p; a.chunk_off = chunk_off.p;
+    hipLaunchKernelGGL(k_table_count, dim3(ceil_div(a.n_chunks, 4)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_chunk_scan, dim3(1), dim3(1024), 0, st, a.chunk_count, a.chunk_off, a.n_chunks, &d_status.p->emitted);
+    FA_HIP(hipGetLastError());
+    status = d_status.read(st);
+    FA_REQUIRE(!(status.flags & TAB_BAD_ID), FA_ERR_INVALID, "a row names a genome outside [0, n_genomes)");
+    FA_REQUIRE(!(status.flags & TAB_DUPLICATE), FA_ERR_INVALID, "the table holds the same (query, reference) twice");
+  }
+  const int64_t n_emit = (int64_t)status.emitted;
+  // the n_emit records of the call's form (a.edges_only), once their destination is set in `a`
+  auto emit = [&] {
+    a.cap = n_emit;
+    hipLaunchKernelGGL(k_table_write, dim3(ceil_div(a.n_chunks, 4)), dim3(256), 0, st, a);
+  };
+
+  if (!want.clusters) {
+    *want.n_pairs = (int64_t)status.pairs;
+    if (!want.pairs) return;
+    FA_REQUIRE(n_emit <= want.cap, FA_ERR_INVALID, "the pair buffer is smaller than the number of pairs");
+    if (!n_emit) return;
+    Staged<fa_pair> pairs(want.pairs, want.pairs_device, (size_t)n_emit);
+    a.pairs = pairs.dev();
+    emit();
+    FA_HIP(hipGetLastError());
+    pairs.finish(st);
+    FA_HIP(hipStreamSynchronize(st));
+    return;
+  }
+
+  int64_t rounds = 0;
+  unsigned int roots = 0;
+  if (n_genomes && want.representatives) {
+    DevBuf<TableEdge> d_edges;
+    DevBuf<int32_t> d_order;                   // pos, then order
+    std::vector<int32_t> both(pos);
+    both.resize((size_t)n_genomes * 2);
+    for (int32_t g = 0; g < n_genomes; g++) both[(size_t)n_genomes + (size_t)pos[(size_t)g]] = g;
+    d_order.upload(both, st);
+    Staged<int32_t> labels(want.labels, want.labels_device, (size_t)n_genomes);
+    Staged<double> identity(want.identity, want.labels_device, (size_t)n_genomes);
+    if (n_emit) {
+      d_edges.ensure((size_t)n_emit);
+      a.weighted = d_edges.p;
+      emit();
+    }
+    roots = representatives(d_edges.p, n_emit, d_order.p, d_order.p + n_genomes, labels.dev(), identity.dev(), n_genomes, d_status.p, st, rounds);
+    labels.finish(st);
+    identity.finish(st);
+    FA_HIP(hipStreamSynchronize(st));
+  } else if (n_genomes) {
+    DevBuf<int2> d_edges;
+    Staged<int32_t> labels(want.labels, want.labels_device, (size_t)n_genomes);
+    if (n_emit) {
+      d_edges.ensure((size_t)n_emit);
+      a.edges = d_edges.p;
+      emit();
+    }
+    roots = components(d_edges.p, n_emit, labels.dev(), n_genomes, d_status.p, st, rounds);
+    labels.finish(st);
+    FA_HIP(hipStreamSynchronize(st));
+  }
+  if (want.n_clusters) *want.n_clusters = (int32_t)roots;
+  if (want.stats) {
+    want.stats[0] = (int64_t)status.survivors; want.stats[1] = (int64_t)status.pairs;
+    want.stats[2] = (int64_t)status.edges; want.stats[3] = rounds;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// A query x reference hit table reduced to every query's k best hits (fa_best.hip.h has the semantics and the road)
+// ------------------------------------------------------------------------------------------------------------
+inline void table_best(const fa_cgi_row *rows, int64_t n_rows, bool rows_device, int32_t n_queries, int32_t n_references,
+                       const uint64_t *query_lengths, const uint64_t *reference_lengths, const fa_best_params *p, fa_cgi_row *best,
+                       int64_t *offsets, int64_t cap, int64_t *n_best, bool out_device, int64_t *stats) {
+  FA_REQUIRE(p, FA_ERR_INVALID, "null best-hit parameters");
+  FA_REQUIRE(p->fragment_length >= 1, FA_ERR_INVALID, "fragment_length must be strictly positive");
+  FA_REQUIRE(p->k >= 1, FA_ERR_INVALID, "k must be at least 1");
+  FA_REQUIRE(p->min_identity >= 0.0f, FA_ERR_INVALID, "min_identity must be a number that is not negative");          // (false for NaN)
+  FA_REQUIRE(p->min_aligned_fraction >= 0.0f, FA_ERR_INVALID, "min_aligned_fraction must be a number that is not negative");
+  FA_REQUIRE(n_queries >= 0 && n_references >= 0 && n_rows >= 0, FA_ERR_INVALID, "negative table size");
+  FA_REQUIRE(n_rows == 0 || rows, FA_ERR_INVALID, "null rows");
+  FA_REQUIRE((n_queries == 0 || query_lengths) && (n_references == 0 || reference_lengths), FA_ERR_INVALID, "null genome lengths");
+  FA_REQUIRE(!best || cap >= 0, FA_ERR_INVALID, "negative capacity");
+  FA_REQUIRE(n_rows <= (int64_t)INT32_MAX, FA_ERR_UNSUPPORTED, "a table of more than 2^31 - 1 rows");
+  require_device();
+  CallStream stream;
+  hipStream_t st = stream.s;
+  StatusBlock<BestStatus> d_status(st);
+  DevBuf<fa_cgi_row> d_rows;
+  DevBuf<uint64_t> d_len;
+  DevBuf<unsigned long long> keys, keys_sorted;
+  DevBuf<uint32_t> row_of, row_of_sorted;
+  DevBuf<unsigned char> temp;
+  DevBuf<int32_t> seg;
+  DevBuf<int64_t> d_offsets;
+
+  BestArgs a{};
+  a.n_rows = n_rows; a.n_queries = n_queries; a.n_references = n_references;
+  a.fragment_length = (unsigned long long)p->fragment_length; a.min_fraction = p->min_fraction;
+  a.min_identity = p->min_identity; a.min_aligned_fraction = p->min_aligned_fraction;
+  a.k = p->k; a.exclude_self = p->exclude_self != 0 ? 1 : 0;
+  a.ref_bits = id_bits(n_references);
+  a.status = d_status.p;
+  seg.ensure((size_t)n_queries * 2);
+  if (n_queries) FA_HIP(hipMemsetAsync(seg.p, 0, (size_t)n_queries * 2 * sizeof(int32_t), st));
+  a.seg_start = seg.p; a.seg_end = seg.p + n_queries;
+  d_offsets.ensure((size_t)n_queries + 1);
+  a.offsets = d_offsets.p;
+  const dim3 row_grid(ceil_div(n_rows, 256));
+  if (n_rows) {
+    a.rows = on_device(rows, rows_device, (size_t)n_rows, d_rows, st);
+    d_len.ensure((size_t)n_queries + (size_t)n_references);
+    if (n_queries) FA_HIP(hipMemcpyAsync(d_len.p, query_lengths, (size_t)n_queries * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    if (n_references)
+      FA_HIP(hipMemcpyAsync(d_len.p + n_queries, reference_lengths, (size_t)n_references * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    a.query_length = d_len.p; a.reference_length = d_len.p + n_queries;
+    keys.ensure((size_t)n_rows); keys_sorted.ensure((size_t)n_rows);
+    row_of.ensure((size_t)n_rows); row_of_sorted.ensure((size_t)n_rows);
+    hipLaunchKernelGGL(k_best_keys, row_grid, dim3(256), 0, st, a, keys.p, row_of.p);
+    // first sort: the bits of r and of the largest q (rows with an id out of range land anywhere: the call fails on the flag)
+    unsigned end_bit = a.ref_bits + id_bits(n_queries);
+    with_temp(temp, [&](void *t, size_t &bytes) {
+      return rocprim::radix_sort_pairs(t, bytes, keys.p, keys_sorted.p, row_of.p, row_of_sorted.p, (size_t)n_rows, 0u, end_bit, st);
+    });
+    a.keys = keys_sorted.p; a.row_of = row_of_sorted.p;
+    hipLaunchKernelGGL(k_best_rank_keys, row_grid, dim3(256), 0, st, a, keys.p);
+    // second sort: 32 bits of identity and the bits of n_queries itself -- under them the all-ones key of a row that does
+    // not survive reads 2^bits - 1 >= n_queries, behind every query
+    end_bit = 32u + bit_width_u64((unsigned long long)n_queries);
+    with_temp(temp, [&](void *t, size_t &bytes) {
+      return rocprim::radix_sort_pairs(t, bytes, keys.p, keys_sorted.p, row_of_sorted.p, row_of.p, (size_t)n_rows, 0u, end_bit, st);
+    });
+    a.keys = keys_sorted.p; a.row_of = row_of.p;
+    hipLaunchKernelGGL(k_best_segments, row_grid, dim3(256), 0, st, a);
+  }
+  hipLaunchKernelGGL(k_best_scan, dim3(1), dim3(1024), 0, st, a);
+  FA_HIP(hipGetLastError());
+  const BestStatus status = d_status.read(st);
+  FA_REQUIRE(!(status.flags & TAB_BAD_ID), FA_ERR_INVALID, "a row names a query outside [0, n_queries) or a reference outside [0, n_references)");
+  FA_REQUIRE(!(status.flags & TAB_DUPLICATE), FA_ERR_INVALID, "the table holds the same (query, reference) twice");
+  const int64_t n_records = (int64_t)status.records;
+  if (n_best) *n_best = n_records;
+  FA_REQUIRE(!best || n_records <= cap, FA_ERR_INVALID, "the record buffer is smaller than the number of records");
+  Staged<fa_cgi_row> records(best, out_device, (size_t)n_records);
+  if (best && n_records) {
+    a.best = reinterpret_cast<int32_t *>(records.dev());
+    hipLaunchKernelGGL(k_best_write, row_grid, dim3(256), 0, st, a);
+    FA_HIP(hipGetLastError());
+    records.finish(st);
+  }
+  if (offsets)
+    FA_HIP(hipMemcpyAsync(offsets, d_offsets.p, ((size_t)n_queries + 1) * sizeof(int64_t),
+                          out_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+  FA_HIP(hipStreamSynchronize(st));
+  if (stats) { stats[0] = (int64_t)status.survivors; stats[1] = (int64_t)status.queries; stats[2] = n_records; }
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// The genome-level screen: bottom-s signatures, their pairs above a Jaccard cut-off, the groups (fa_screen.hip.h)
+// ------------------------------------------------------------------------------------------------------------
+inline void screen_signatures(const uint32_t *d_hash, const int32_t *d_seq_id, int64_t n_records, const int32_t *sbf, int32_t n_genomes,
+                              int32_t s, uint32_t *d_sig, int32_t *d_count) {
+  FA_REQUIRE(s >= 1 && s <= SCR_MAX_S, FA_ERR_INVALID, "the signature size must be in [1, 4096]");
+  FA_REQUIRE(n_genomes >= 0 && n_records >= 0, FA_ERR_INVALID, "negative number of genomes or records");
+  FA_REQUIRE(n_records == 0 || (d_hash && d_seq_id), FA_ERR_INVALID, "null records");
+  FA_REQUIRE(n_genomes == 0 || (sbf && d_sig && d_count), FA_ERR_INVALID, "null sequencesByFileInfo or null outputs");
+  FA_REQUIRE(n_records == 0 || n_genomes > 0, FA_ERR_INVALID, "records without a genome");
+  FA_REQUIRE(n_records <= (int64_t)INT32_MAX, FA_ERR_UNSUPPORTED, "more than 2^31 - 1 records");
+  for (int32_t g = 0; g < n_genomes; g++)
+    FA_REQUIRE(sbf[g] >= (g ? sbf[g - 1] : 0), FA_ERR_INVALID, "sequencesByFileInfo must not decrease");
+  require_device();
+  if (!n_genomes) return;
+  CallStream stream;
+  hipStream_t st = stream.s;
+  StatusBlock<TableStatus> d_status(st);
+  DevBuf<int32_t> d_sbf;
+  DevBuf<unsigned long long> keys, keys_sorted;
+  DevBuf<uint32_t> heads, rank, segs;
+  DevBuf<unsigned char> temp;
+
+  SigArgs a{};
+  a.hash = d_hash; a.seq_id = d_seq_id; a.n_records = n_records; a.n_genomes = n_genomes; a.s = s;
+  a.n_contigs = sbf[n_genomes - 1];
+  a.sig = d_sig; a.count = d_count; a.status = d_status.p;
+  const dim3 rec_grid(ceil_div(n_records, 256));
+  if (n_records) {
+    // the verdict on the records is read before an output is touched
+    hipLaunchKernelGGL(k_sig_check, rec_grid, dim3(256), 0, st, a);
+    FA_HIP(hipGetLastError());
+    const TableStatus status = d_status.read(st);
+    FA_REQUIRE(!(status.flags & TAB_BAD_ID), FA_ERR_INVALID, "a record's contig id lies outside [0, sequencesByFileInfo[n_genomes - 1])");
+    FA_REQUIRE(!(status.flags & SCR_NOT_ASCENDING), FA_ERR_INVALID, "the records are not sorted by contig id");
+  }
+  segs.ensure((size_t)n_genomes * 2);
+  FA_HIP(hipMemsetAsync(segs.p, 0, (size_t)n_genomes * 2 * sizeof(uint32_t), st));
+  a.first = segs.p; a.last = segs.p + n_genomes;
+  FA_HIP(hipMemsetAsync(d_sig, 0, (size_t)n_genomes * (size_t)s * sizeof(uint32_t), st));
+  if (n_records) {
+    d_sbf.upload(sbf, (size_t)n_genomes, st);
+    a.sbf = d_sbf.p;
+    keys.ensure((size_t)n_records); keys_sorted.ensure((size_t)n_records);
+    heads.ensure((size_t)n_records); rank.ensure((size_t)n_records);
+    hipLaunchKernelGGL(k_sig_keys, rec_grid, dim3(256), 0, st, a, keys.p);
+    // the bits a key can have set: 32 of the hash and those of the largest genome number
+    const unsigned end_bit = 32u + id_bits(n_genomes);
+    with_temp(temp, [&](void *t, size_t &bytes) {
+      return rocprim::radix_sort_keys(t, bytes, keys.p, keys_sorted.p, (size_t)n_records, 0u, end_bit, st);
+    });
+    a.keys = keys_sorted.p;
+    hipLaunchKernelGGL(k_sig_heads, rec_grid, dim3(256), 0, st, a, heads.p);
+    with_temp(temp, [&](void *t, size_t &bytes) {
+      return rocprim::exclusive_scan(t, bytes, heads.p, rank.p, 0u, (size_t)n_records, rocprim::plus<uint32_t>(), st);
+    });
+    a.rank = rank.p;
+    hipLaunchKernelGGL(k_sig_segments, rec_grid, dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_sig_write, rec_grid, dim3(256), 0, st, a);
+  }
+  hipLaunchKernelGGL(k_sig_counts, dim3(ceil_div(n_genomes, 256)), dim3(256), 0, st, a);
+  FA_HIP(hipGetLastError());
+  FA_HIP(hipStreamSynchronize(st));
+}
+
+inline void screen_pairs(const uint32_t *d_sig_a, const int32_t *d_count_a, int32_t n_a, const uint32_t *d_sig_b, const int32_t *d_count_b,
+                         int32_t n_b, int32_t s, bool triangular, int32_t jn, int32_t jd, fa_screen_pair *pairs, int64_t cap,
+                         int64_t *n_pairs, bool pairs_device, int64_t *stats) {
+  FA_REQUIRE(s >= 1 && s <= SCR_MAX_S, FA_ERR_INVALID, "the signature size must be in [1, 4096]");
+  FA_REQUIRE(jd >= 1 && jn >= 0 && jn <= jd, FA_ERR_INVALID, "the Jaccard cut-off needs 0 <= jn <= jd and jd >= 1");
+  FA_REQUIRE(n_a >= 0 && n_b >= 0, FA_ERR_INVALID, "negative number of genomes");
+  FA_REQUIRE((n_a == 0 || (d_sig_a && d_count_a)) && (n_b == 0 || (d_sig_b && d_count_b)), FA_ERR_INVALID, "null signatures");
+  FA_REQUIRE(!triangular || (d_sig_a == d_sig_b && d_count_a == d_count_b && n_a == n_b), FA_ERR_INVALID,
+             "the triangular mode takes one signature set: the same pointers and n_a == n_b");
+  FA_REQUIRE(!pairs || cap >= 0, FA_ERR_INVALID, "negative capacity");
+  require_device();
+  CallStream stream;
+  hipStream_t st = stream.s;
+  StatusBlock<TableStatus> d_status(st);
+  DevBuf<unsigned long long> mask;
+  DevBuf<int32_t> chunk_count;
+  DevBuf<int64_t> chunk_off;
+
+  ScreenArgs a{};
+  a.sig_a = d_sig_a; a.sig_b = d_sig_b; a.count_a = d_count_a; a.count_b = d_count_b;
+  a.n_a = n_a; a.n_b = n_b; a.s = s; a.triangular = triangular ? 1 : 0; a.jn = jn; a.jd = jd;
+  a.tile = screen_tile(s);
+  a.tile_shift = (int32_t)bit_width_u64((unsigned long long)a.tile) - 1;
+  a.tiles_a = ceil_div(n_a, a.tile);
+  a.words_per_row = ((int64_t)n_b + 63) / 64;
+  a.n_words = (int64_t)n_a * a.words_per_row;
+  a.status = d_status.p;
+  const int64_t n_chunks = (a.n_words + SCR_CHUNK - 1) / SCR_CHUNK;
+  FA_REQUIRE(n_chunks <= (int64_t)INT32_MAX, FA_ERR_UNSUPPORTED, "a screen of more than 2^43 pairs");
+  a.n_chunks = (int32_t)n_chunks;
+  TableStatus status{};
+  if (a.n_words) {
+    mask.ensure((size_t)a.n_words);
+    FA_HIP(hipMemsetAsync(mask.p, 0, (size_t)a.n_words * sizeof(unsigned long long), st));
+    a.mask = mask.p;
+    chunk_count.ensure((size_t)a.n_chunks); chunk_off.ensure((size_t)a.n_chunks);
+    a.chunk_count = chunk_count.p; a.chunk_off = chunk_off.p;
+    const dim3 grid((unsigned)ceil_div(n_b, a.tile), (unsigned)std::min(a.tiles_a, 65535));
+    // elements of A a lane searches at a time (measured at s = 64, 1000 and 4096, profiles/screen_pair_kernel.txt): a signature
+    // of one pass gains nothing from a second chain, long ones hide more of the reads' latency behind more chains
+    const size_t lds = (size_t)2 * a.tile * screen_stride(s) * sizeof(uint32_t);
+    if (s <= 64) hipLaunchKernelGGL(k_screen_pairs<1>, grid, dim3(SCR_THREADS), lds, st, a);
+    else if (s <= 2048) hipLaunchKernelGGL(k_screen_pairs<2>, grid, dim3(SCR_THREADS), lds, st, a);
+    else hipLaunchKernelGGL(k_screen_pairs<4>, grid, dim3(SCR_THREADS), lds, st, a);
+    hipLaunchKernelGGL(k_screen_count, dim3(ceil_div(a.n_chunks, 4)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_chunk_scan, dim3(1), dim3(1024), 0, st, a.chunk_count, a.chunk_off, a.n_chunks, &d_status.p->emitted);
+    FA_HIP(hipGetLastError());
+    status = d_status.read(st);
+    FA_REQUIRE(!(status.flags & SCR_BAD_COUNT), FA_ERR_INVALID, "a signature count lies outside [0, s]");
+    FA_REQUIRE(!(status.flags & SCR_NOT_ASCENDING), FA_ERR_INVALID, "a signature does not ascend strictly below its count");
+  }
+  const int64_t n_emit = (int64_t)status.emitted;
+  if (n_pairs) *n_pairs = n_emit;
+  FA_REQUIRE(!pairs || n_emit <= cap, FA_ERR_INVALID, "the pair buffer is smaller than the number of pairs");
+  if (pairs && n_emit) {
+    Staged<fa_screen_pair> out(pairs, pairs_device, (size_t)n_emit);
+    a.pairs = out.dev();
+    hipLaunchKernelGGL(k_screen_write, dim3(ceil_div(a.n_chunks, 4)), dim3(256), 0, st, a);
+    FA_HIP(hipGetLastError());
+    out.finish(st);
+    FA_HIP(hipStreamSynchronize(st));
+  }
+  if (stats) {
+    stats[0] = triangular ? (int64_t)n_a * ((int64_t)n_a - 1) / 2 : (int64_t)n_a * (int64_t)n_b;
+    stats[1] = n_emit;
+  }
+}
+
+inline void screen_groups(const fa_screen_pair *pairs, int64_t n_pairs, bool pairs_device, int32_t n_genomes, int32_t *labels,
+                          bool labels_device, int32_t *n_groups) {
+  FA_REQUIRE(n_genomes >= 0 && n_pairs >= 0, FA_ERR_INVALID, "negative number of genomes or pairs");
+  FA_REQUIRE(n_pairs == 0 || pairs, FA_ERR_INVALID, "null pairs");
+  FA_REQUIRE(n_genomes == 0 || labels, FA_ERR_INVALID, "null labels");
+  FA_REQUIRE(n_pairs <= (int64_t)INT32_MAX, FA_ERR_UNSUPPORTED, "more than 2^31 - 1 pairs");
+  require_device();
+  CallStream stream;
+  hipStream_t st = stream.s;
+  StatusBlock<TableStatus> d_status(st);
+  DevBuf<fa_screen_pair> d_pairs;
+  DevBuf<int2> d_edges;
+  if (n_pairs) {
+    pairs = on_device(pairs, pairs_device, (size_t)n_pairs, d_pairs, st);
+    d_edges.ensure((size_t)n_pairs);
+    hipLaunchKernelGGL(k_screen_edges, dim3(ceil_div(n_pairs, 256)), dim3(256), 0, st, pairs, n_pairs, n_genomes, d_edges.p, d_status.p);
+    FA_HIP(hipGetLastError());
+    const TableStatus status = d_status.read(st);
+    FA_REQUIRE(!(status.flags & TAB_BAD_ID), FA_ERR_INVALID, "a pair is not 0 <= a < b < n_genomes");
+  }
+  unsigned int roots = 0;
+  if (n_genomes) {
+    Staged<int32_t> out(labels, labels_device, (size_t)n_genomes);
+    int64_t rounds = 0;
+    roots = components(d_edges.p, n_pairs, out.dev(), n_genomes, d_status.p, st, rounds);
+    out.finish(st);
+    FA_HIP(hipStreamSynchronize(st));
+  }
+  if (n_groups) *n_groups = (int32_t)roots;
+}
+
+}  // namespace fa

@@ -44,7 +44,7 @@
 // elements at a time, their reads issued together (E is the engine's choice by s; profiles/EXPERIMENTS.md has the
 // measurements).  A kept pair sets bit b of row a in a bit mask of n_a x n_b (atomicOr: the outcome does not depend on
 // order).  The pairs then come out in (a, b) order by count / scan / write over chunks of SCR_CHUNK mask words (the form of
-// k_table_count / k_table_scan / k_table_write; k_table_scan itself is reused): a chunk's wave walks its set bits in order
+// k_table_count / k_chunk_scan / k_table_write, the scan being the same kernel): a chunk's wave walks its set bits in order
 // and evaluates each kept pair again, straight from global memory, for its two counts -- the mask costs one bit per pair
 // where the statistics would cost eight bytes, and kept pairs are few where a screen is of use.  No atomic decides a
 // record's place.

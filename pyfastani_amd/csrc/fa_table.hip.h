@@ -21,7 +21,8 @@
 // row needs to know is in its two neighbours: equal keys but for the last bit = a duplicate; a surviving row whose
 // predecessor is not the surviving other direction = the head of a pair.  Heads (or, for the clusters, heads that are edges)
 // are compacted in order by count / scan / write over chunks of one wave's TAB_CHUNK consecutive rows, a head's place inside its
-// chunk being the population count of the ballots below its lane (the form of k_map_count / k_map_scan / k_map_write).
+// chunk being the population count of the ballots below its lane (the form of k_map_count / k_chunk_scan / k_map_write;
+// the scan is the one kernel of fa_compact.hip.h).
 // The same input therefore gives the same bytes on every run: no record's place depends on timing.  (A third form of the
 // write kernel keeps an edge's identity, TableEdge: what fa_represent.hip.h selects representatives from.)
 //
@@ -36,6 +37,7 @@
 #pragma once
 
 #include "fa_common.h"
+#include "fa_compact.hip.h"
 
 namespace fa {
 
@@ -46,7 +48,7 @@ constexpr unsigned long long TAB_KEY_NONE = ~0ULL;
 // one per call, zeroed before the first launch
 struct TableStatus {
   unsigned long long survivors, pairs, edges;   // k_table_count
-  long long emitted;                            // k_table_scan: records the write kernel produces
+  int64_t emitted;                              // k_chunk_scan: records the write kernel produces
   unsigned int flags;                           // TAB_BAD_ID | TAB_DUPLICATE
   unsigned int changed;                         // the last round (1-based) in which a label was lowered
   unsigned int roots;                           // k_comp_roots
@@ -160,25 +162,6 @@ __global__ __launch_bounds__(256) void k_table_count(TableArgs a) {
   if (survivors) atomicAdd(&a.status->survivors, (unsigned long long)survivors);
   if (pairs) atomicAdd(&a.status->pairs, (unsigned long long)pairs);
   if (edges) atomicAdd(&a.status->edges, (unsigned long long)edges);
-}
-
-// exclusive 64-bit sum of the chunk counts by one workgroup (thread t owns a run of consecutive chunks) + the total
-__global__ __launch_bounds__(1024) void k_table_scan(TableArgs a) {
-  __shared__ long long sh_wave[16];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int per = (a.n_chunks + 1023) / 1024;
-  const int c0 = min(a.n_chunks, (int)threadIdx.x * per), c1 = min(a.n_chunks, c0 + per);
-  long long mine = 0;
-  for (int c = c0; c < c1; c++) mine += a.chunk_count[c];
-  long long incl = mine;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) { const long long v = __shfl_up(incl, d); if (lane >= d) incl += v; }
-  if (lane == 63) sh_wave[wv] = incl;
-  __syncthreads();
-  long long off = incl - mine;
-  for (int w = 0; w < wv; w++) off += sh_wave[w];
-  for (int c = c0; c < c1; c++) { a.chunk_off[c] = off; off += a.chunk_count[c]; }
-  if (threadIdx.x == 1023) a.status->emitted = off;
 }
 
 __global__ __launch_bounds__(256) void k_table_write(TableArgs a) {

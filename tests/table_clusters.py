@@ -97,6 +97,27 @@ def shuffled_table(n_rows, n=64, seed=1):
     return make_case(rows, n, shuffle=False)
 
 
+def one_direction_table(n_rows, n, seed=3):
+    """(case, pairs): n_rows distinct cells a < b over n genomes, one row each in a random direction, all passing the filter,
+    shuffled; and the pairs the table reduces to, in closed form (restate walks the rows in Python: too slow for a table
+    that gives one thread of the chunk scan two chunks)"""
+    g = np.random.default_rng(seed + n_rows)
+    a, b = np.triu_indices(n, 1)
+    assert n_rows <= len(a)
+    cells = np.sort(g.permutation(len(a))[:n_rows])                  # (sorted: the cells in (a, b) order)
+    a, b = a[cells].astype(np.int32), b[cells].astype(np.int32)
+    flip = g.random(n_rows) < 0.5                                    # the row's query is b
+    identity = (90.0 + 10.0 * g.random(n_rows)).astype(np.float32)
+    rows = np.zeros(n_rows, dtype=ROW_DTYPE)
+    rows["query_id"], rows["ref_genome_id"] = np.where(flip, b, a), np.where(flip, a, b)
+    rows["count_seq"], rows["total_query_fragments"], rows["identity"] = KEEP, 1000, identity
+    pairs = np.zeros(n_rows, dtype=PAIR_DTYPE)
+    pairs["a"], pairs["b"] = a, b
+    pairs["identity_ab"], pairs["identity_ba"] = np.where(flip, NAN32, identity), np.where(flip, identity, NAN32)
+    pairs["identity"] = identity.astype(np.float64)
+    return make_case(rows[g.permutation(n_rows)], n, shuffle=False), pairs
+
+
 def graph_case(edges, n, seed):
     """one row per edge, in a random direction, all passing the filter at identity 97: the edges of the components"""
     g = np.random.default_rng(seed)

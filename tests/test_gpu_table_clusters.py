@@ -101,6 +101,17 @@ def test_pairs_match_the_restatement(name):
     assert (code, n) == (FA_OK, len(expected(name, False)[0]))
 
 
+def test_pairs_of_a_table_whose_chunk_scan_gives_a_thread_two_chunks():
+    """524 289 rows are 1025 chunks of 512: a thread of k_chunk_scan (1024 of them) owns two chunks, the branch that the
+    mappings and the screen share with this table.  Against the closed form of tests/table_clusters.py, byte for byte."""
+    n_rows = 1024 * 512 + 1
+    case, want = tc.one_direction_table(n_rows, 1100)
+    code, buf, n = lib_pairs(case)
+    assert code == FA_OK, _lib.last_error()
+    assert n == n_rows == len(want)
+    assert buf.tobytes() == want.tobytes()
+
+
 @pytest.mark.parametrize("reciprocal", [False, True])
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_clusters_match_the_restatement(name, reciprocal):

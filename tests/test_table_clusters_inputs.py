@@ -106,6 +106,15 @@ def test_row_count_cases():
             assert np.any(rows["query_id"] == rows["ref_genome_id"]) and len(set(rows["count_seq"].tolist())) == 2
 
 
+def test_one_direction_table_closed_form_equals_the_restatement():
+    case, pairs = tc.one_direction_table(300, 40)
+    assert len(case["rows"]) == 300 and case["n"] == 40
+    assert pairs.tobytes() == tc.restate(case, False)[0].tobytes()
+    assert np.any(np.isnan(pairs["identity_ab"])) and np.any(np.isnan(pairs["identity_ba"]))          # both directions occur
+    q, r = case["rows"]["query_id"].astype(np.int64), case["rows"]["ref_genome_id"].astype(np.int64)
+    assert np.any(np.diff(np.minimum(q, r) * 40 + np.maximum(q, r)) < 0)                              # shuffled
+
+
 def test_small_cases_have_their_property():
     pairs, labels, n_clusters, counts = tc.restate(CASES["one_genome"], False)
     assert len(pairs) == 0 and labels.tolist() == [0] and n_clusters == 1
