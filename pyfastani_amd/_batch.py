@@ -29,7 +29,8 @@ assert PAIR_DTYPE.itemsize == 24
 
 
 def pass_fragments():
-    """Fragments the library maps per pass (``FA_PASS_FRAGMENTS``, read when the library starts; 49152 by default)."""
+    """Fragments the library maps per pass (``FA_PASS_FRAGMENTS``; 49152 by default, as in ``csrc/fa_knobs.h``).  The library
+    reads the variable once, at its first pass; this reads it on every call, so set it before the first query."""
     return int(os.environ.get("FA_PASS_FRAGMENTS") or 48 * 1024)
 
 

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "fa_error.h"
+#include "fa_knobs.h"
 
 namespace fa {
 
@@ -96,10 +97,9 @@ class DevPool {
   // then).  Other allocators of the process (torch tensors, RCCL buffers) never make the pool trim, so it must not sit on most of
   // a device; `fa_device_trim` gives everything back on request.
   void size_cap() {
-    const char *e = getenv("FA_POOL_MAX_GB");
-    double gb = 96.0;
-    if (e) gb = atof(e);
-    else {
+    double gb = knob::pool_max_gb();
+    if (knob::unset(gb)) {
+      gb = 96.0;
       size_t free_b = 0, total_b = 0;
       if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && total_b > 0) gb = std::min(96.0, 0.30 * (double)total_b / (1024.0 * 1024.0 * 1024.0));
       else (void)hipGetLastError();

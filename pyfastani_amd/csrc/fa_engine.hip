@@ -25,6 +25,7 @@
 #include "fa_common.h"
 #include "fa_fasta.h"
 #include "fa_ingest.h"
+#include "fa_knobs.h"
 #include "fa_lease.h"
 #include "fa_map.hip.h"
 #include "fa_policy.h"
@@ -80,19 +81,6 @@ static void validate_params(const fa_params &p) {
              "window_size/kmer_size too large for the LDS-staged sketch kernel (tile + 2w + k must fit 160 KiB)");
 }
 
-// FA_* knobs: env_set = the knob is set (to anything); env_num = its value (atof), `unset` when it is not set; env_u64 = a
-// positive count, else `dflt`
-static bool env_set(const char *name) { return getenv(name) != nullptr; }
-static double env_num(const char *name, double unset) {
-  const char *e = getenv(name);
-  return e ? atof(e) : unset;
-}
-static uint64_t env_u64(const char *name, uint64_t dflt) {
-  const char *e = getenv(name);
-  long long x = e ? atoll(e) : 0;
-  return x > 0 ? (uint64_t)x : dflt;
-}
-
 // launches `kernel` with `lds` bytes of dynamic LDS; above 64 KB the kernel has to be allowed them first
 template <typename Kernel, typename... Args>
 static void launch_lds(Kernel kernel, dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args &...args) {
@@ -118,8 +106,10 @@ struct StageTrace {
   const char *what;
   std::chrono::steady_clock::time_point t0, t;
   std::vector<std::pair<std::string, double>> acc;
-  explicit StageTrace(const char *w) : on(env_set("FA_TRACE")), what(w) {
-    live = on && env_num("FA_TRACE", 0) >= 2;
+  explicit StageTrace(const char *w) : what(w) {
+    const double level = knob::trace();
+    on = !knob::unset(level);
+    live = on && level >= 2;
     t0 = t = std::chrono::steady_clock::now();
   }
   void mark(const char *stage, hipStream_t st) {
@@ -167,7 +157,7 @@ static bool launch_sketch_tiles(const fa_params &P, const StoreView &store, cons
   a.protein = P.alphabet_size != 4;
   a.npos_cap = TILE + 2 * P.window_size - 2;
   // FA_K1_GENERAL=1: every tile through the 64-bit form of the window minimum (tests compare the two)
-  static const bool k1_general = env_num("FA_K1_GENERAL", 0) != 0;
+  const bool k1_general = knob::k1_general() != 0;
   a.fast = (!k1_general && P.window_size >= 3 && P.window_size <= 1000) ? 1 : 0;   // (three padded arrays in the LDS of two key arrays)
   size_t lds = sketch_lds_bytes(P.kmer_size, P.window_size);
   size_t image = lds - ((size_t)a.npos_cap * 16 + ((size_t)a.npos_cap / 64 + 1) * 8 + (TILE / 64) * 8 + (TILE / 64 + 1) * 4 + 16 + 4 * 256 * 8);
@@ -190,7 +180,7 @@ static bool launch_sketch_tiles(const fa_params &P, const StoreView &store, cons
     // staging arrays FIRST (a launch whose other workgroups exit at once, and which carries the zeroing workgroups of the pass);
     // the fused kernel takes their records from there.  The run-time-w forms of the fused kernel do not fit the registers of seven waves per
     // SIMD -- a few words would go to scratch memory, which the runtime then keeps per stream for good -- and are not built.
-    static const bool fuse_on = env_num("FA_QUERY_FUSED", 1) != 0;
+    const bool fuse_on = knob::query_fused() != 0;
     const bool may_fuse = fuse && fuse_on && (int64_t)5 * P.fragment_length / (P.window_size + 1) <= QF_CAP;
     auto launch_fast = [&](auto kernel) {
       hipLaunchKernelGGL(kernel, dim3(ntiles + extra), dim3(SK_THREADS), flds, st, a);
@@ -455,8 +445,7 @@ static PublishArgs publish_args(PassStatus *dev, PassStatus *host_mapped, uint32
 }
 // host side of k_publish_status: polls for FA_SPIN_US microseconds (default 20 000), then sleeps on the stream
 static void wait_published(const PassStatus *h, uint32_t seq, hipStream_t st) {
-  static const uint64_t spin_us = env_u64("FA_SPIN_US", 20000);
-  if (spin_for_seq(&h->seq, seq, spin_us)) return;
+  if (spin_for_seq(&h->seq, seq, knob::spin_us())) return;
   FA_HIP(hipStreamSynchronize(st));
   FA_REQUIRE(__atomic_load_n(&h->seq, __ATOMIC_ACQUIRE) == seq, FA_ERR_INTERNAL, "the status of the pass was not published");
 }
@@ -590,8 +579,8 @@ struct fa_mapper {
   int32_t n_wraps = 0, gpos_bits = 32;
   bool packed_geo = false;
   // k_l2_events reads the packed record layout (rec_hg, rec_prev16) when the index has one; FA_NO_PACKED_GEO=1 takes the
-  // plain arrays on any index (the tests reach the unpacked form on small indices that way)
-  bool events_packed() const { return packed_geo && !env_set("FA_NO_PACKED_GEO"); }
+  // plain arrays on any index (the tests reach the unpacked form on small indices that way).  Asked once per part (QueryPass::ev_packed)
+  bool events_packed() const { return packed_geo && !knob::no_packed_geo(); }
   int64_t N = 0, U = 0;
   int32_t C = 0, G = 0, table_bits = 4, freq_threshold = INT_MAX, total_bins = 0;
   std::vector<uint64_t> lengths;
@@ -615,7 +604,7 @@ struct fa_mapper {
   int last_ws = 0;                    // workspace of the most recent call (stage getters, timings)
   // records per stage buffer of the streamed mapping output (MapStage; fa_mapper_set_mapping_stage, default FA_MAP_STAGE_MB),
   // and the workspace of the most recent call that asked for mappings (fa_mapper_mapping_memory)
-  int64_t map_stage = std::max<int64_t>(1, (int64_t)env_u64("FA_MAP_STAGE_MB", 64) * (1024 * 1024 / (int64_t)sizeof(fa_hit_mapping)));
+  int64_t map_stage = std::max<int64_t>(1, (int64_t)knob::map_stage_mb() * (1024 * 1024 / (int64_t)sizeof(fa_hit_mapping)));
   int last_map_ws = -1;
   bool stage_events = false;          // fa_mapper_set_stage_events
   std::vector<DevBuf<int32_t>> retired_i32;   // LUT generations still referenced by calls in flight
@@ -732,7 +721,7 @@ static void build_index(fa_mapper &m) {
     top.reserve((size_t)M);
     {
       // (FA_FREQ_OVER_CAP: the tests shrink the room for long lists -- 1 = none fits -- so that the sort is exercised too)
-      const uint32_t OVER_CAP = (uint32_t)std::min<uint64_t>(1u << 16, env_u64("FA_FREQ_OVER_CAP", 1u << 16));
+      const uint32_t OVER_CAP = (uint32_t)knob::freq_over_cap();
       DevBuf<unsigned long long> d_hist;
       DevBuf<uint32_t> d_over;
       d_hist.ensure(FREQ_BINS + 1); d_over.ensure(OVER_CAP);
@@ -790,7 +779,7 @@ static void build_index(fa_mapper &m) {
         hipLaunchKernelGGL(k_window_links<false>, dim3(ceil_div(N, WL_TILE)), dim3(WL_THREADS), (size_t)(WL_TILE + 2 * halo) * sizeof(int32_t), st, m.rec_seq.p,
                            m.rec_wpos.p, m.contig_rec.p, N, m.cmw, halo, m.rec_fwd.p, m.rec_bwd.p, m.rec_flags.p);
       // (FA_LINK_BLOCK_BITS: the tests shrink the blocks so that a small index has blocks inside a contig AND straddling ones)
-      const int shift = (int)std::min<uint64_t>(20, std::max<uint64_t>(2, env_u64("FA_LINK_BLOCK_BITS", 10)));
+      const int shift = (int)knob::link_block_bits();
       const int64_t blocks = (N + ((int64_t)1 << shift) - 1) >> shift;
       blk_lo.ensure((size_t)blocks + 1);
       hipLaunchKernelGGL(k_block_contig, dim3(ceil_div(blocks, 256)), dim3(256), 0, st, m.rec_seq.p, m.contig_rec.p, N, shift, blk_lo.p);
@@ -816,7 +805,7 @@ static void build_index(fa_mapper &m) {
       m.rec_gpos.ensure((size_t)N + 4);
       m.wrap_rec.ensure(GPOS_MAX_WRAPS);
       // (FA_GPOS_BITS: the tests shrink the low word so that a small index crosses many of its boundaries)
-      m.gpos_bits = (int)std::min<uint64_t>(32, std::max<uint64_t>(12, env_u64("FA_GPOS_BITS", 32)));
+      m.gpos_bits = (int)knob::gpos_bits();
       FA_REQUIRE(m.gpos_bits == 32 || (1LL << m.gpos_bits) > 2 * (int64_t)m.P.fragment_length, FA_ERR_INVALID, "FA_GPOS_BITS too small for the fragment length");
       hipLaunchKernelGGL(k_rec_gpos, dim3(ceil_div(N, 256)), dim3(256), 0, st, m.rec_seq.p, m.rec_wpos.p, base.p, N, m.gpos_bits, m.rec_gpos.p, m.wrap_rec.p, d_wraps.p);
       d_wraps.download(&m.n_wraps, 1, st);
@@ -887,18 +876,14 @@ struct ClearList {
 
 // FA_DEBUG_SYNC=1: synchronise after every stage of a query pass and name the stage that failed
 static void debug_sync(hipStream_t st, const char *stage) {
-  static const bool on = env_set("FA_DEBUG_SYNC");
-  if (!on) return;
+  if (!knob::debug_sync()) return;
   fprintf(stderr, "[fa] %s ...\n", stage);
   hipError_t e = hipStreamSynchronize(st);
   if (e != hipSuccess) throw Error(FA_ERR_NO_DEVICE, std::string("stage ") + stage + " failed: " + hipGetErrorString(e));
 }
 
 // fragments mapped per pass (bounds the workspace); FA_PASS_FRAGMENTS overrides it (tests force several passes)
-static int64_t pass_fragments() {
-  static const int64_t v = (int64_t)env_u64("FA_PASS_FRAGMENTS", 48 * 1024);
-  return v;
-}
+static int64_t pass_fragments() { return (int64_t)knob::pass_fragments(); }
 
 // Dynamic LDS of k_l2_events and k_l2_scan at a sketch bound (their tables hold cnt_slots = smax + 1 ranks) for the fragments
 // of an index: what scan_occupancy asks the runtime about is what launch_l2_stage launches with.
@@ -976,6 +961,7 @@ struct QueryPass {
   // publishes what it learnt (bounds only ever grow, except the LDS seed slots, which follow the latest pass)
   Spec sp;
   bool bins_cleared = false;
+  bool ev_packed = false;             // the part in flight reads the packed record layout (fa_mapper::events_packed, asked once per part)
   std::deque<Range> todo;
   bool rows_valid = false;
   unsigned long long t_begin = ~0ULL, t_end = 0;
@@ -993,8 +979,7 @@ struct QueryPass {
     // (FA_SMAX_INIT: development, a smaller first guess for small fragments; FA_LOCI_CAP_MIN: the tests force the retry path
     // with a tiny value)
     if (!ms.init)
-      ms = spec_first_use((int)env_u64("FA_SMAX_INIT", 256), (int64_t)env_u64("FA_LOCI_CAP_MIN", 1u << 18), env_u64("FA_EVENTS_CAP_MIN", 1u << 26),
-                          pass_fragments());
+      ms = spec_first_use((int)knob::smax_init(), (int64_t)knob::loci_cap_min(), knob::events_cap_min(), pass_fragments());
     sp = ms;
     sp.fuse_off = ms.fuse_skip > 0;
     FA_REQUIRE(sp.smax < 32768, FA_ERR_UNSUPPORTED, "query sketch larger than 32767 minimizers");
@@ -1023,7 +1008,7 @@ struct QueryPass {
     if (lds_scan > 64 * 1024 || lds_ev > 64 * 1024) return 0;
     int n_scan = 0, n_ev = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n_scan, (const void *)k_l2_scan<uint16_t, uint8_t, 64>, L2_THREADS, lds_scan) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&n_ev, m.events_packed() ? (const void *)k_l2_events<uint16_t, true> : (const void *)k_l2_events<uint16_t, false>,
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&n_ev, ev_packed ? (const void *)k_l2_events<uint16_t, true> : (const void *)k_l2_events<uint16_t, false>,
                                                      EV_THREADS, lds_ev) != hipSuccess) {
       (void)hipGetLastError();
       return 0;
@@ -1034,7 +1019,7 @@ struct QueryPass {
   // ================================================ the plan of the pass =======================================
   void plan() {
     // event offsets are 32-bit: at most this many slide events per part (FA_EVENTS_CAP_MAX: the tests force the split)
-    items_max = env_u64("FA_EVENTS_CAP_MAX", (1ULL << 32) - 64);
+    items_max = knob::events_cap_max();
     w.bins.ensure((size_t)NQ * std::max(m.total_bins, 1) + 2);
     w.row_count.ensure((size_t)npairs + 1); w.row_ident.ensure((size_t)npairs + 1);
     w.row_flag.ensure((size_t)npairs + 1); w.row_off.ensure((size_t)npairs + 1);
@@ -1071,8 +1056,7 @@ struct QueryPass {
     // workgroup pays for it with a device-scope fence, which writes its XCD's L2 back: ~1 us each, one after another per XCD.
     // Break-even at 400-800 pairs (profiles/r05_emit_threshold.txt); at the 12-14 000 pairs of a 24-genome chunk against 500
     // references the fences were 0.44 of the 0.52 ms of the kernel.  (FA_ROWS_EMIT_MAX: the measurement's knob, <= 16384)
-    static const int64_t emit_max = (int64_t)env_u64("FA_ROWS_EMIT_MAX", 512);
-    ra.emit = npairs <= std::min<int64_t>(emit_max, 16384);
+    ra.emit = npairs <= (int64_t)knob::rows_emit_max();
     ra.pub = pub;
     if (!ra.emit) ra.pub.seq = 0;
     ra.done = &d_counters[CNT_ROWS_DONE]; ra.query_total_frag = g.d_total_frag + g0; ra.query_id_base = g0;
@@ -1168,6 +1152,7 @@ struct QueryPass {
     const Spec &sp = p.sp;
     const int64_t f0 = p.f0, F = p.F;
     w.last_F = 0; w.last_loci = 0;                                  // (filled in when the part is accepted)
+    ev_packed = m.events_packed();
     const int ntiles = p.ntiles;
     // buffers whose size depends only on the geometry of the part
     w.sk.stage_hash.ensure((size_t)std::max(ntiles, 1) * TILE);
@@ -1185,10 +1170,9 @@ struct QueryPass {
     const int smax = p.smax;
     const int64_t l_cap = p.l_cap;
     {
-      static const L1Knobs knobs{(int)env_num("FA_L1_PREFILTER", -1), (float)env_num("FA_L1_THIN_SMALL", -1.0), (float)env_num("FA_L1_THIN_MID", 0.05)};
+      const L1Knobs knobs{(int)knob::l1_prefilter(), (float)knob::l1_thin_small(), (float)knob::l1_thin_mid()};
       p.l1 = plan_l1(sp, m.N, knobs);
-      static const bool dbg_l1 = env_set("FA_DEBUG_L1");
-      if (dbg_l1) fprintf(stderr, "k_l1 classes: need=%u tiny=%.3f small=%.3f mid=%.3f prefilter=%d -> %d launch(es)\n", p.l1.need, sp.l1_tiny_share, sp.l1_small_share, sp.l1_mid_share, (int)p.l1.prefilter, p.l1.n);
+      if (knob::debug_l1()) fprintf(stderr, "k_l1 classes: need=%u tiny=%.3f small=%.3f mid=%.3f prefilter=%d -> %d launch(es)\n", p.l1.need, sp.l1_tiny_share, sp.l1_small_share, sp.l1_mid_share, (int)p.l1.prefilter, p.l1.n);
     }
     w.l_frag.ensure((size_t)l_cap); w.l_seq.ensure((size_t)l_cap); w.l_start.ensure((size_t)l_cap); w.l_end.ensure((size_t)l_cap + 4);
     w.l_rfirst.ensure((size_t)l_cap); w.l_rlast.ensure((size_t)l_cap + 4); w.l_rpart.ensure((size_t)l_cap);
@@ -1196,8 +1180,7 @@ struct QueryPass {
     w.group_best.ensure((size_t)l_cap + 2);
     w.l_beg.ensure((size_t)l_cap); w.l_end0.ensure((size_t)l_cap); w.l_last.ensure((size_t)l_cap); w.l_ndrop.ensure((size_t)l_cap);
     w.l_nev.ensure((size_t)l_cap); w.l_ioff.ensure((size_t)l_cap); w.l_redo.ensure((size_t)l_cap + 4);
-    static const int scan_order_knob = (int)env_num("FA_L2_SCAN_ORDER", -1);
-    p.scan_sorted = scan_sorted(sp, scan_order_knob);
+    p.scan_sorted = scan_sorted(sp, (int)knob::l2_scan_order());
     w.scan_hist.ensure((size_t)2 * LOCI_REGIONS * SCAN_CLASSES);
     if (p.scan_sorted) w.scan_order.ensure((size_t)l_cap + 64);
     w.ovf_buf.ensure((size_t)sp.scratch_words + 4);
@@ -1224,9 +1207,8 @@ struct QueryPass {
   // The workgroup order of k_l2_events (frag_order_gate, build_frag_order), built on the host, cached per (batch, fragment
   // range) and uploaded behind K1.
   void prepare_order(Part &p) {
-    static const bool order_on = env_num("FA_FRAG_ORDER", 1) != 0;
-    static const bool order_one = env_num("FA_FRAG_ORDER_ONE", 1) != 0;   // (A/B of the one-genome order)
-    if (!frag_order_gate(order_on, order_one, NQ, p.F)) return;
+    // (FA_FRAG_ORDER_ONE: the A/B of the one-genome order)
+    if (!frag_order_gate(knob::frag_order() != 0, knob::frag_order_one() != 0, NQ, p.F)) return;
     if (w.order_batch != g.serial || w.order_f0 != p.f0 || w.order_f1 != p.f1) {
       std::vector<int32_t> ord;
       w.order_len = build_frag_order(g.genome_frag_lo.data(), g0, p.f0, p.f1, ord);       // 0: the lists cannot be balanced, identity order
@@ -1266,7 +1248,7 @@ struct QueryPass {
       a.q_hash = w.q_hash.p; a.q_size = w.q_size.p; a.qcap = qcap;
       a.ix = ix; a.q_off = w.q_off.p; a.q_cnt = w.q_cnt.p; a.n_seeds = w.n_seeds.p;
       a.sort_cap = (int32_t)(qs_lds / 4);
-      a.rec_cap = (int)std::max(0.0, std::min((double)QF_CAP, env_num("FA_QF_CAP", QF_CAP)));
+      a.rec_cap = (int)std::max(0.0, std::min((double)QF_CAP, knob::qf_cap()));
       a.exc_tiles = 0;                                 // (set by launch_sketch_tiles for the fused kernel)
       // ---- K1 (its extra workgroups zero the ranges above beside the hashing) + per-fragment sort / unique / index lookup:
       //      one launch where the pass qualifies (k_query_fused), else k_sketch_fast / k_sketch_tiles, then k_query_sketch ----
@@ -1308,17 +1290,15 @@ struct QueryPass {
       a.counters = d_counters; a.loci = p.loci; a.qcap = qcap; a.frag_len = m.P.fragment_length; a.l_cap = (int32_t)l_cap;
       a.lds_seed_cap = seed_slots; a.totals_seed_cap = seed_slots; a.n_lo = 0; a.n_hi = 0xFFFFFFFFu; a.pinfo = d_pinfo; a.lut_smax = smax; a.scratch_words = sp.scratch_words;
       a.f_loci_lo = w.f_loci_lo.p; a.f_loci_n = w.f_loci_n.p;
-      static const bool l1_block_sort_on = env_num("FA_L1_BLOCK_SORT", 1) != 0;
-      static const bool l1_stats = env_num("FA_L1_STATS", 0) != 0;
-      static const int l1_near_knob = (int)env_num("FA_L1_NEAR", -1);
-      const bool l1_near_on = l1_near(m.N, l1_near_knob);
+      const bool l1_block_sort_on = knob::l1_block_sort() != 0, l1_stats = knob::l1_stats() != 0;
+      const bool l1_near_on = l1_near(m.N, (int)knob::l1_near());
       const bool l1_pf_on = p.l1.prefilter;             // (decided with the size classes, when the part was planned)
       a.block_sort = (l1_block_sort_on ? 1 : 0) | (l1_stats ? 2 : 0) | (l1_near_on ? 4 : 0) | (l1_pf_on ? 8 : 0);
       const uint32_t l1_grid = (uint32_t)F;             // (the offset-major order of k_l2_events applied here measured nothing: 75.9 / 75.5 ms on config 3)
       a.dbg = w.status.p->dbg;
       // fragments with more hits than LDS holds (seen before on this mapper: scratch is reserved for them) are cut
       // into LDS-sized chunks at contig boundaries by k_l1_big first; what it cannot cut stays with k_l1's HBM path
-      static const bool l1_big = env_num("FA_L1_BIG", 1) != 0;
+      const bool l1_big = knob::l1_big() != 0;
       a.big_state = nullptr; a.big_enabled = 0; a.big_cap = 0;
       const int64_t big_room = (int64_t)160 * 1024 - 2048 - ((int64_t)smax + 2) * 16 - (int64_t)L1_BIG_THREADS * 8;   // LDS left for a chunk's seeds
       if (l1_big && sp.scratch_words > 0 && big_room >= 4 * 2048) {
@@ -1332,8 +1312,7 @@ struct QueryPass {
         constexpr int NTT = decltype(nt_tag)::value;
         const size_t lds = l1_lds_bytes(c.slots, smax, NTT);
         FA_REQUIRE(lds + 1024 <= 160 * 1024, FA_ERR_UNSUPPORTED, "query sketch too large for the LDS tables of the L1 kernel");
-        static const bool dbg = env_set("FA_DEBUG_L1");
-        if (dbg) fprintf(stderr, "k_l1<%d>: F=%lld hits %u..%u seed_slots=%u smax=%d lds=%zu\n", NTT, (long long)F, c.n_lo, c.n_hi, c.slots, smax, lds);
+        if (knob::debug_l1()) fprintf(stderr, "k_l1<%d>: F=%lld hits %u..%u seed_slots=%u smax=%d lds=%zu\n", NTT, (long long)F, c.n_lo, c.n_hi, c.slots, smax, lds);
         L1Args b = a;
         b.lds_seed_cap = c.slots; b.n_lo = c.n_lo; b.n_hi = c.n_hi; b.fold_totals = fold ? 1 : 0;
         // (plan_l1 gives a 256-thread class L1_SMALL_HITS = 16 x 256 slots at most: it has no 32-hits-per-thread form)
@@ -1417,7 +1396,7 @@ struct QueryPass {
         a.lanes = lanes16;
         launch_lds(lanes16 == L2_THREADS ? scan16 : scan16_rt, dim3(scan_grid(lanes16)), dim3(L2_THREADS), lds16, st, a);
       };
-      const bool pk = m.events_packed();
+      const bool pk = ev_packed;
       if (wide) launch(pk ? k_l2_events<uint32_t, true> : k_l2_events<uint32_t, false>, k_l2_scan<uint32_t, uint8_t, 64>, k_l2_scan<uint32_t, uint8_t, 0>, k_l2_scan<uint32_t, uint16_t, 64>, k_l2_scan<uint32_t, uint16_t, 0>);
       else launch(pk ? k_l2_events<uint16_t, true> : k_l2_events<uint16_t, false>, k_l2_scan<uint16_t, uint8_t, 64>, k_l2_scan<uint16_t, uint8_t, 0>, k_l2_scan<uint16_t, uint16_t, 64>, k_l2_scan<uint16_t, uint16_t, 0>);
     }
@@ -1728,8 +1707,7 @@ static void fill_genomes(fa_genomes *g, const fa_params &P, hipStream_t st, cons
   // packed words STRAIGHT from the pinned image over PCIe -- every word is read once, by the workgroup that hashes it, and the
   // kernel is bound by its hashing, so the 1.25 MB travel inside its 67 us instead of in a 28 us copy in front of it; only the
   // tile and fragment tables (read by every stage) are copied.  FA_QUERY_ZERO_COPY=0: the whole image is copied.
-  static const bool zero_copy_on = env_num("FA_QUERY_ZERO_COPY", 1) != 0;
-  const bool zero_copy = zero_copy_on && pin && !sync_pinned && !hs.protein;
+  const bool zero_copy = knob::query_zero_copy() != 0 && pin && !sync_pinned && !hs.protein;
   if (zero_copy) FA_HIP(hipMemcpyAsync(g->blob.p + at.tiles.at, img + at.tiles.at, image_bytes - at.tiles.at, hipMemcpyHostToDevice, st));
   else FA_HIP(hipMemcpyAsync(g->blob.p, img, image_bytes, hipMemcpyHostToDevice, st));
   const int64_t n_exc = (int64_t)hs.exc_pos.size();

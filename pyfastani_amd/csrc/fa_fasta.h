@@ -402,8 +402,7 @@ struct FileBytes {
   FileBytes &operator=(const FileBytes &) = delete;
   ~FileBytes() { if (map) munmap(map, map_len); }
   void open(const char *path) {
-    static const bool use_mmap = [] { const char *e = getenv("FA_FASTA_IO"); return e && std::string(e) == "mmap"; }();
-    if (!use_mmap) {
+    if (knob::fasta_io() != "mmap") {
       std::vector<char> &buf = fasta_detail::io_buffer();
       size = fasta_detail::slurp(path, buf);
       data = buf.data();
@@ -431,7 +430,7 @@ struct FileBytes {
 
 inline void read_fasta_packed(const char *path, bool protein, PackedFasta &out, const std::shared_ptr<HostArena> &arena = nullptr) {
   using namespace fasta_detail;
-  static const bool timed = getenv("FA_TRACE") != nullptr;
+  const bool timed = !knob::unset(knob::trace());
   const auto t0 = std::chrono::steady_clock::now();
   FileBytes fb;
   fb.open(path);
@@ -495,7 +494,7 @@ inline void read_fasta_packed(const char *path, bool protein, PackedFasta &out, 
 
 // (FA_FASTA_THREADS=<n>: pool workers that take files; default: the pool's usual two dozen -- on tmpfs 128 readers spent 70 ms
 //  per 5 MB file inside read(), 25 readers 3-4 ms)
-inline int fasta_pool_helpers() { static const int v = [] { const char *e = getenv("FA_FASTA_THREADS"); const int x = e ? atoi(e) : 0; return x > 0 ? x : 24; }(); return v; }
+inline int fasta_pool_helpers() { return (int)std::min<uint64_t>(knob::fasta_threads(), INT_MAX); }
 
 // Many files at once: one task per file on the pool (a file never waits for the one before it).
 inline void read_fasta_packed_many(const char *const *paths, size_t n, bool protein, std::vector<PackedFasta> &out) {

@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <climits>
 #include <condition_variable>
 #include <cstdlib>
 #include <exception>
@@ -20,6 +21,7 @@
 #include <vector>
 
 #include "fa_error.h"
+#include "fa_knobs.h"
 
 namespace fa {
 
@@ -55,8 +57,7 @@ static const uint8_t kCodeOf[256] = {
 // with 256 hardware threads start 32 packer threads each, not 8 x 128)
 inline int host_threads() {
   static const int v = [] {
-    const char *e = getenv("FA_HOST_THREADS");
-    int x = e ? atoi(e) : 0;
+    int x = (int)std::min<uint64_t>(knob::host_threads(), INT_MAX);
     if (x <= 0) {
       const char *lw = getenv("LOCAL_WORLD_SIZE");
       const unsigned ranks = (unsigned)std::max(1, lw ? atoi(lw) : 1);
@@ -166,7 +167,7 @@ __attribute__((target("avx2"))) inline bool pack32_avx2(const uint8_t *src, uint
   return true;
 }
 inline bool host_has_avx2() {
-  static const bool v = __builtin_cpu_supports("avx2") && !getenv("FA_NO_AVX2");
+  static const bool v = __builtin_cpu_supports("avx2") && !knob::no_avx2();
   return v;
 }
 
@@ -250,7 +251,7 @@ struct HostStore {
     std::vector<Chunk> chunks;
     // bases per chunk (multiple of 64): fine enough to spread one 5 Mb genome over the helpers, coarse enough that waking
     // a helper (tens of microseconds) is worth it -- the AVX2 loop packs 64 Kbases in ~8 us, the table loop in ~60 us
-    static const int64_t ch_env = [] { const char *e = getenv("FA_PACK_CHUNK"); long long x = e ? atoll(e) : 0; return (int64_t)(x > 0 ? (x + 63) / 64 * 64 : 0); }();
+    const int64_t ch_env = (int64_t)knob::pack_chunk();
     const bool avx2 = host_has_avx2() && width == 1 && !protein;
     const int64_t CH = ch_env ? ch_env : (avx2 ? (1 << 18) : (1 << 16));
     seq_off.reserve(seq_off.size() + (size_t)n); seq_len.reserve(seq_len.size() + (size_t)n);

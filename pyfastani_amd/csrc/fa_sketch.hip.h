@@ -145,8 +145,8 @@ inline void make_tiles(std::vector<Tile> &tiles, const HostStore &hs, int64_t of
 // 3 x 4 for 976-position tiles, 4 x 3 for 722, 6 x 2 for 466.)  Query fragments keep whole tiles: 2 985 positions do not fit
 // three four-trip tiles (2 980), and a fourth tile costs more than the fifth trip.  FA_K1_TILE = 1024 restores the full tile (A/B).
 inline int k1_tile_len(int w) {
-  static const int forced = [] { const char *e = getenv("FA_K1_TILE"); const int x = e ? atoi(e) : 0; return (x >= 256 && x <= TILE && x % 4 == 0) ? x : 0; }();
-  if (forced) return forced;
+  const uint64_t forced = knob::k1_tile();
+  if (forced >= 256 && forced <= (uint64_t)TILE && forced % 4 == 0) return (int)forced;
   return std::max(256, (TILE - (2 * w - 2)) & ~3);
 }
 

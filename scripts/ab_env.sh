@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B kernel durations of ONE library build under different environment settings, on the same box:
-#   scripts/ab_env.sh "FA_SCAN_ORDER=0" "FA_SCAN_ORDER=1" "FA_SCAN_ORDER=2"
+#   scripts/ab_env.sh "FA_L2_SCAN_ORDER=0" "FA_L2_SCAN_ORDER=1"
 # (every argument is a space-separated list of VAR=value settings; per-kernel averages of rocprofv3 over scripts/time_pass.py)
 export TMPDIR=/tmp
 i=0

@@ -1,5 +1,5 @@
 #!/bin/bash
-# The host-only pieces of libfastani_hip (fa_host.h packer + thread pool, fa_fasta.h, fa_stats.h, fa_lease.h, fa_policy.h, fa_ingest.h, fa_mapstream.h, fa_order.h) under
+# The host-only pieces of libfastani_hip (fa_host.h packer + thread pool, fa_fasta.h, fa_stats.h, fa_lease.h, fa_policy.h, fa_ingest.h, fa_mapstream.h, fa_order.h, fa_knobs.h) under
 # AddressSanitizer + UndefinedBehaviorSanitizer and, separately, ThreadSanitizer -- on the CPU, g++ only (no GPU sanitizer,
 # no XNACK).  Every build runs with the AVX2 packer and with FA_NO_AVX2=1 (the scalar paths), with 8 and with 3 host threads.
 #   bash scripts/host_sanitize.sh [log]        (default log: profiles/r06_host_sanitizers.txt)
@@ -39,6 +39,17 @@ status=0
     rc=${PIPESTATUS[0]}
     echo "exit status $rc"
     [ "$rc" = 0 ] || status=1
+  else echo "BUILD FAILED"; status=1; fi
+  # the knob table (fa_knobs.h): what every accessor makes of a value and when it reads it; ASan + UBSan only.  Two runs: a ONCE
+  # accessor answers one question per process
+  echo "## build: g++ -std=c++17 -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=all scripts/host_sanitize/knobs.cpp"
+  if g++ -std=c++17 -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=all scripts/host_sanitize/knobs.cpp -o "$OUT/knobs" 2>&1; then
+    for mode in "" defaults; do
+      "$OUT/knobs" $mode 2>&1 | tail -5
+      rc=${PIPESTATUS[0]}
+      echo "exit status $rc"
+      [ "$rc" = 0 ] || status=1
+    done
   else echo "BUILD FAILED"; status=1; fi
   echo "# overall: $([ $status = 0 ] && echo clean || echo FINDINGS)"
 } | tee "$LOG"

@@ -1,5 +1,5 @@
 #!/bin/bash
-# SQ counters of one kernel (all launches summed) under environment settings:  scripts/pmc_kernel.sh k_l1 "FA_X=0" "FA_X=1"
+# SQ counters of one kernel (all launches summed) under environment settings:  scripts/pmc_kernel.sh k_l1 "FA_L1_BLOCK_SORT=0" "FA_L1_BLOCK_SORT=1"
 # (program behind `--` directly; counters in their own passes, never with a trace domain)
 export TMPDIR=/tmp
 KERNEL=$1; shift
