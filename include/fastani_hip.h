@@ -158,6 +158,32 @@ int fa_sketch_set_state_device(fa_sketch *s, int64_t n_genomes, const uint64_t *
  * mapper and the sketch is left cleared but usable. */
 int fa_sketch_index(fa_sketch *s, fa_mapper **out);
 
+/* ---- a collection mapped group by group out of one resident sketch ---- */
+/* What comes between the screen and a mapper when a collection is larger than one index: a Sketch holds 12 bytes per record
+ * and an index is bound to 2^31 of them, so a collection sketched once is cut into its groups here, each group indexed and
+ * mapped on its own, and the frequency filter of the WHOLE collection installed in every group's mapper
+ * (fa_mapper_set_global_frequency) -- the group's rows are then the rows the one big index would give for its references.
+ * No reference counterpart.  With sbf = sequencesByFileInfo of s, first(g) = g ? sbf[g-1] : 0, c(g) = sbf[g] - first(g):
+ *   1. Selection.  genomes[0..n) is a HOST array, strictly ascending, every entry in [0, n_genomes).  *out is a new sketch
+ *      with the fa_params of s, on its device, that holds those genomes:  lengths'[i] = lengths[genomes[i]],
+ *      sbf'[i] = sum over j <= i of c(genomes[j]),  counter' = sbf'[n-1] (0 for n == 0).
+ *   2. Records.  The records of genome g are those with contig id in [first(g), sbf[g]): a contiguous range, records being
+ *      sorted by contig id.  The records of genomes[i] are copied in their order with hash and window position unchanged;
+ *      their contig id becomes  seq_id - first(genomes[i]) + first'(i).  n == 0 gives an empty sketch.
+ *   3. Frequency.  *threshold is what fa_mapper_freq_threshold of fa_sketch_index(s) would return (INT_MAX: nothing is
+ *      ignored); the distinct hashes with at least *threshold records, ascending as unsigned 32-bit, go to the DEVICE array
+ *      d_drop_keys and their number to *n_drop (0 at INT_MAX).  No index is built: at most 2^32 - 1 records
+ *      (FA_ERR_UNSUPPORTED beyond), not the 2^31 of an index.
+ * Both flush the pending contigs of s first, as fa_sketch_get_minimizers_device does, and otherwise only read it: s holds
+ * the same records afterwards and indexes to the same mapper.  The cost of fa_sketch_select goes with the selected records,
+ * not with the records of s.  FA_ERR_INVALID from fa_sketch_select: an entry outside [0, n_genomes), a list that does not
+ * ascend strictly, contigs behind the last fa_sketch_end_genome of s; *out is then untouched.  A `cap` below the number of
+ * keys is FA_ERR_INVALID from fa_sketch_frequency: nothing is written, and *n_drop holds the number needed (as
+ * fa_screen_pairs does).  Both run on the sketch's stream, have finished when they return, and are FA_ERR_NO_DEVICE without
+ * a device like every compute entry point. */
+int fa_sketch_select(fa_sketch *s, const int32_t *genomes, int32_t n, fa_sketch **out);
+int fa_sketch_frequency(fa_sketch *s, int *threshold, int64_t cap, uint32_t *d_drop_keys, int64_t *n_drop);
+
 /* ---- Mapper: query side ------------------------------------------------ */
 void fa_mapper_free(fa_mapper *m);
 /* Sketch_t::getFreqThreshold, include/fastani/map/win_sketch.pxd:40 */

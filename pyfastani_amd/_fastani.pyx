@@ -1060,6 +1060,33 @@ cdef class Sketch(_Parameterized):
             self._version += 1
         return self
 
+    def select(self, genomes):
+        """A new `Sketch` that holds the genomes ``genomes`` of this one (their numbers, strictly ascending), with their
+        names and this sketch's parameters and `rules`: the records are cut out on the device (``fa_sketch_select``), this
+        sketch is only read and stays usable -- `index` consumes the selection, not the collection.  No reference
+        counterpart; `pyfastani_amd.groups` maps a screened collection group by group this way."""
+        import numpy as np
+        cdef Sketch out = Sketch.__new__(Sketch)
+        cdef int code
+        cdef int32_t n
+        cdef uintptr_t p
+        wanted = [operator.index(g) for g in genomes]
+        with self._lock:
+            if any(g < 0 or g >= len(self._names) for g in wanted):
+                raise ValueError(f"a selected genome is outside [0, {len(self._names)})")
+            if any(b <= a for a, b in zip(wanted, wanted[1:])):
+                raise ValueError("the selected genomes must ascend strictly")
+            arr = np.ascontiguousarray(wanted, dtype=np.int32)
+            p, n = arr.ctypes.data, len(wanted)
+            with nogil:
+                code = hip.fa_sketch_select(self._hs, <const int32_t*> p, n, &out._hs)
+            _check(code)
+            out._p = self._p
+            out._threads = self._threads
+            out._rules = self._rules
+            out._names = [self._names[g] for g in wanted]
+        return out
+
     cpdef Mapper index(self):
         """Index the reference genomes for fast lookups using the minimizers (_fastani.pyx:769-806).
 

@@ -148,6 +148,8 @@ SIGNATURES = {
     "fa_sketch_get_minimizers_device": (_i32, [_vp, _i64, _vp, _vp, _vp]),
     "fa_sketch_set_state_device": (_i32, [_vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     "fa_sketch_index": (_i32, [_vp, _P(_vp)]),
+    "fa_sketch_select": (_i32, [_vp, _vp, _i32, _P(_vp)]),
+    "fa_sketch_frequency": (_i32, [_vp, _P(_i32), _i64, _vp, _P(_i64)]),
     "fa_mapper_free": (None, [_vp]),
     "fa_mapper_freq_threshold": (_i32, [_vp, _P(_i32)]),
     "fa_mapper_lookup_export_device": (_i32, [_vp, _i64, _vp, _vp]),

@@ -38,6 +38,7 @@
 #include "fa_best.hip.h"
 #include "fa_screen.hip.h"
 #include "fa_reduce.hip.h"
+#include "fa_select.hip.h"
 
 using namespace fa;
 
@@ -632,6 +633,61 @@ __global__ void k_contig_bins(const int32_t *contig_rec, const int32_t *rec_wpos
   nbins[c] = n;
 }
 
+// Sketch_t::computeFreqHist on the device: the frequency threshold of U position lists of the lengths `counts` (a device
+// array), INT_MAX when nothing is ignored.  The one copy of the walk: build_index and fa_sketch_frequency both call it.
+static int frequency_threshold(const uint32_t *counts, int64_t U, DevBuf<unsigned char> &temp, hipStream_t st) {
+  int threshold = INT_MAX;
+  DevBuf<uint32_t> counts_sorted;
+  // frequency threshold (computeFreqHist): walk the distinct list lengths from the most frequent down
+  int64_t to_ignore = (int64_t)((float)U * 0.001f / 100);
+  int64_t M = std::min<int64_t>(U, to_ignore + 1);
+  // the M largest list lengths, in descending order: from a histogram of the short lists plus the long ones verbatim
+  // (k_length_histogram); only an index with more than 65 536 lists of 4 096 positions and more sorts all lengths instead
+  std::vector<uint32_t> top;
+  top.reserve((size_t)M);
+  {
+    // (FA_FREQ_OVER_CAP: the tests shrink the room for long lists -- 1 = none fits -- so that the sort is exercised too)
+    const uint32_t OVER_CAP = (uint32_t)knob::freq_over_cap();
+    DevBuf<unsigned long long> d_hist;
+    DevBuf<uint32_t> d_over;
+    d_hist.ensure(FREQ_BINS + 1); d_over.ensure(OVER_CAP);
+    FA_HIP(hipMemsetAsync(d_hist.p, 0, (FREQ_BINS + 1) * sizeof(unsigned long long), st));
+    uint32_t *d_over_n = (uint32_t *)(d_hist.p + FREQ_BINS);
+    hipLaunchKernelGGL(k_length_histogram, dim3((unsigned)std::min<int64_t>(ceil_div(U, 256), 4096)), dim3(256), 0, st, counts, U, d_hist.p,
+                       d_over.p, OVER_CAP, d_over_n);
+    std::vector<unsigned long long> h_hist(FREQ_BINS + 1);
+    d_hist.download(h_hist.data(), FREQ_BINS + 1, st);
+    FA_HIP(hipStreamSynchronize(st));
+    const uint32_t n_over = (uint32_t)(h_hist[FREQ_BINS] & 0xFFFFFFFFu);
+    if (n_over < OVER_CAP || n_over == 0) {
+      std::vector<uint32_t> h_over(n_over);
+      if (n_over) { d_over.download(h_over.data(), n_over, st); FA_HIP(hipStreamSynchronize(st)); }
+      std::sort(h_over.begin(), h_over.end(), std::greater<uint32_t>());
+      for (uint32_t i = 0; i < n_over && (int64_t)top.size() < M; i++) top.push_back(h_over[i]);
+      for (int b = FREQ_BINS - 1; b >= 0 && (int64_t)top.size() < M; b--)
+        for (unsigned long long c = h_hist[(size_t)b]; c > 0 && (int64_t)top.size() < M; c--) top.push_back((uint32_t)b);
+    } else {
+      counts_sorted.ensure((size_t)U);
+      with_temp(temp, [&](void *t, size_t &bytes) {
+        return rocprim::radix_sort_keys_desc(t, bytes, counts, counts_sorted.p, (size_t)U, 0u, 32u, st);
+      });
+      top.resize((size_t)M);
+      counts_sorted.download(top.data(), (size_t)M, st);
+      FA_HIP(hipStreamSynchronize(st));
+    }
+  }
+  FA_REQUIRE((int64_t)top.size() == M, FA_ERR_INTERNAL, "list-length histogram does not add up");
+  for (int64_t i = 0; i < M;) {
+    int64_t j = i;
+    while (j < M && top[j] == top[i]) j++;
+    if (j == M && M < U) break;   // the run continues past the prefix: sum would exceed to_ignore
+    if (j < to_ignore) { threshold = (int)top[i]; i = j; }
+    else if (j == to_ignore) { threshold = (int)top[i]; break; }
+    else break;
+  }
+  return threshold;
+}
+
 // Sketch_t::index() + computeFreqHist() on the device
 static void build_index(fa_mapper &m) {
   hipStream_t st = m.stream;
@@ -689,7 +745,7 @@ static void build_index(fa_mapper &m) {
   m.U = 0;
   m.freq_threshold = INT_MAX;
   if (N > 0) {
-    DevBuf<uint32_t> iota, sorted_hash, counts, counts_sorted, blk_lo;
+    DevBuf<uint32_t> iota, sorted_hash, counts, blk_lo;
     DevBuf<int32_t> num_runs;
     iota.ensure((size_t)N); sorted_hash.ensure((size_t)N); counts.ensure((size_t)N + 1); num_runs.ensure(1);
     tr.mark("alloc", st);
@@ -712,53 +768,7 @@ static void build_index(fa_mapper &m) {
       return rocprim::exclusive_scan(t, bytes, counts.p, m.uniq_off.p, 0u, (size_t)U + 1, rocprim::plus<uint32_t>(), st);
     });
     tr.mark("rle_scan", st);
-    // frequency threshold (computeFreqHist): walk the distinct list lengths from the most frequent down
-    int64_t to_ignore = (int64_t)((float)(int64_t)U * 0.001f / 100);
-    int64_t M = std::min<int64_t>(U, to_ignore + 1);
-    // the M largest list lengths, in descending order: from a histogram of the short lists plus the long ones verbatim
-    // (k_length_histogram); only an index with more than 65 536 lists of 4 096 positions and more sorts all lengths instead
-    std::vector<uint32_t> top;
-    top.reserve((size_t)M);
-    {
-      // (FA_FREQ_OVER_CAP: the tests shrink the room for long lists -- 1 = none fits -- so that the sort is exercised too)
-      const uint32_t OVER_CAP = (uint32_t)knob::freq_over_cap();
-      DevBuf<unsigned long long> d_hist;
-      DevBuf<uint32_t> d_over;
-      d_hist.ensure(FREQ_BINS + 1); d_over.ensure(OVER_CAP);
-      FA_HIP(hipMemsetAsync(d_hist.p, 0, (FREQ_BINS + 1) * sizeof(unsigned long long), st));
-      uint32_t *d_over_n = (uint32_t *)(d_hist.p + FREQ_BINS);
-      hipLaunchKernelGGL(k_length_histogram, dim3((unsigned)std::min<int64_t>(ceil_div(U, 256), 4096)), dim3(256), 0, st, counts.p, (int64_t)U, d_hist.p,
-                         d_over.p, OVER_CAP, d_over_n);
-      std::vector<unsigned long long> h_hist(FREQ_BINS + 1);
-      d_hist.download(h_hist.data(), FREQ_BINS + 1, st);
-      FA_HIP(hipStreamSynchronize(st));
-      const uint32_t n_over = (uint32_t)(h_hist[FREQ_BINS] & 0xFFFFFFFFu);
-      if (n_over < OVER_CAP || n_over == 0) {
-        std::vector<uint32_t> h_over(n_over);
-        if (n_over) { d_over.download(h_over.data(), n_over, st); FA_HIP(hipStreamSynchronize(st)); }
-        std::sort(h_over.begin(), h_over.end(), std::greater<uint32_t>());
-        for (uint32_t i = 0; i < n_over && (int64_t)top.size() < M; i++) top.push_back(h_over[i]);
-        for (int b = FREQ_BINS - 1; b >= 0 && (int64_t)top.size() < M; b--)
-          for (unsigned long long c = h_hist[(size_t)b]; c > 0 && (int64_t)top.size() < M; c--) top.push_back((uint32_t)b);
-      } else {
-        counts_sorted.ensure((size_t)U);
-        with_temp(temp, [&](void *t, size_t &bytes) {
-          return rocprim::radix_sort_keys_desc(t, bytes, counts.p, counts_sorted.p, (size_t)U, 0u, 32u, st);
-        });
-        top.resize((size_t)M);
-        counts_sorted.download(top.data(), (size_t)M, st);
-        FA_HIP(hipStreamSynchronize(st));
-      }
-    }
-    FA_REQUIRE((int64_t)top.size() == M, FA_ERR_INTERNAL, "list-length histogram does not add up");
-    for (int64_t i = 0; i < M;) {
-      int64_t j = i;
-      while (j < M && top[j] == top[i]) j++;
-      if (j == M && M < U) break;   // the run continues past the prefix: sum would exceed to_ignore
-      if (j < to_ignore) { m.freq_threshold = (int)top[i]; i = j; }
-      else if (j == to_ignore) { m.freq_threshold = (int)top[i]; break; }
-      else break;
-    }
+    m.freq_threshold = frequency_threshold(counts.p, (int64_t)U, temp, st);
     tr.mark("threshold", st);
     // lookup table at load factor <= 1/2
     m.table_bits = std::max(4, floor_log2(std::max(U, 1)) + 2);
@@ -2088,6 +2098,135 @@ int fa_sketch_get_minimizers_device(fa_sketch *s, int64_t cap, uint32_t *d_hash,
 int fa_sketch_set_state_device(fa_sketch *s, int64_t n_genomes, const uint64_t *lengths, const int32_t *sbf, int64_t counter,
                                int64_t n_min, const uint32_t *d_hash, const int32_t *d_seq_id, const int32_t *d_wpos) {
   return sketch_set_state(s, n_genomes, lengths, sbf, counter, n_min, d_hash, d_seq_id, d_wpos, hipMemcpyDeviceToDevice);
+}
+
+// A subset of the genomes as a sketch of its own, and the frequency filter an index of the sketch would have: what maps a
+// collection group by group out of one resident sketch (fa_select.hip.h has the semantics and the road).  Both run on the
+// sketch's stream and have finished when they return.
+int fa_sketch_select(fa_sketch *s, const int32_t *genomes, int32_t n, fa_sketch **out) {
+  return guarded([&] {
+    FA_REQUIRE(s && out && n >= 0 && (genomes || n == 0), FA_ERR_INVALID, "null sketch, list or destination, or a negative count");
+    std::lock_guard<std::mutex> lock(s->mtx);
+    bind_device(s->device);
+    const RefBook &book = s->book;
+    const int64_t G = (int64_t)book.lengths.size();
+    FA_REQUIRE(book.counter == (G ? (int64_t)book.seqs_by_file.back() : 0), FA_ERR_INVALID, "a genome is still open (add_contig without end_genome)");
+    for (int32_t i = 0; i < n; i++) {
+      FA_REQUIRE(genomes[i] >= 0 && genomes[i] < G, FA_ERR_INVALID, "a selected genome is outside [0, n_genomes)");
+      FA_REQUIRE(i == 0 || genomes[i] > genomes[i - 1], FA_ERR_INVALID, "the selected genomes must ascend strictly");
+    }
+    require_device();
+    s->flush();
+    bind_device(s->device);
+    struct Free { void operator()(fa_sketch *p) const { fa_sketch_free(p); } };
+    std::unique_ptr<fa_sketch, Free> o(new fa_sketch());
+    o->P = s->P;
+    o->device = s->device;
+    o->reset_data();
+    // one segment per selected genome: its contig range in the source and what its contig ids move by
+    std::vector<int32_t> contig_lo((size_t)n), contig_hi((size_t)n), delta((size_t)n);
+    int32_t contigs = 0;
+    for (int32_t i = 0; i < n; i++) {
+      const int32_t g = genomes[i];
+      contig_lo[(size_t)i] = g ? book.seqs_by_file[(size_t)g - 1] : 0;
+      contig_hi[(size_t)i] = book.seqs_by_file[(size_t)g];
+      delta[(size_t)i] = contigs - contig_lo[(size_t)i];
+      contigs += contig_hi[(size_t)i] - contig_lo[(size_t)i];
+      o->book.lengths.push_back(book.lengths[(size_t)g]);
+      o->book.seqs_by_file.push_back(contigs);
+    }
+    o->book.counter = contigs;
+    if (n > 0 && s->nrec > 0) {
+      require_device();
+      if (!s->stream) FA_HIP(hipStreamCreate(&s->stream));
+      hipStream_t st = s->stream;
+      DevBuf<int32_t> d_contig_lo, d_contig_hi, d_delta;
+      DevBuf<int64_t> d_rec, d_off;                             // d_rec: [n] first records, then [n] ends
+      d_contig_lo.upload(contig_lo, st); d_contig_hi.upload(contig_hi, st);
+      d_rec.ensure(2 * (size_t)n);
+      hipLaunchKernelGGL(k_select_bounds, dim3(ceil_div(2 * (int64_t)n, 256)), dim3(256), 0, st, s->rec.seq.p, s->nrec, d_contig_lo.p, d_contig_hi.p, n,
+                         d_rec.p, d_rec.p + n);
+      FA_HIP(hipGetLastError());
+      std::vector<int64_t> rec(2 * (size_t)n), off((size_t)n + 1);
+      d_rec.download(rec.data(), rec.size(), st);
+      FA_HIP(hipStreamSynchronize(st));
+      int64_t total = 0;
+      for (int32_t i = 0; i < n; i++) {
+        const int64_t lo = rec[(size_t)i], hi = rec[(size_t)n + (size_t)i];
+        FA_REQUIRE(0 <= lo && lo <= hi && hi <= s->nrec, FA_ERR_INTERNAL, "the records of the sketch are not sorted by contig id");
+        off[(size_t)i] = total;
+        total += hi - lo;
+      }
+      off[(size_t)n] = total;
+      if (total > 0) {
+        o->rec.hash.ensure((size_t)total); o->rec.seq.ensure((size_t)total); o->rec.wpos.ensure((size_t)total);
+        d_off.upload(off, st); d_delta.upload(delta, st);
+        SelectArgs a;
+        a.src_hash = s->rec.hash.p; a.src_seq = s->rec.seq.p; a.src_wpos = s->rec.wpos.p;
+        a.dst_hash = o->rec.hash.p; a.dst_seq = o->rec.seq.p; a.dst_wpos = o->rec.wpos.p;
+        a.dst_off = d_off.p; a.src_lo = d_rec.p; a.delta = d_delta.p; a.n = n; a.total = total;
+        const int64_t tiles = (total + SEL_TILE - 1) / SEL_TILE;
+        hipLaunchKernelGGL(k_select_copy, dim3((unsigned)std::min<int64_t>(tiles, SEL_MAX_BLOCKS)), dim3(SEL_THREADS), 0, st, a);
+        FA_HIP(hipGetLastError());
+        FA_HIP(hipStreamSynchronize(st));
+      }
+      o->nrec = total;
+    }
+    *out = o.release();
+  });
+}
+
+int fa_sketch_frequency(fa_sketch *s, int *threshold, int64_t cap, uint32_t *d_drop_keys, int64_t *n_drop) {
+  return guarded([&] {
+    FA_REQUIRE(s && threshold && n_drop && cap >= 0 && (d_drop_keys || cap == 0), FA_ERR_INVALID, "null sketch or destination, or a negative capacity");
+    std::lock_guard<std::mutex> lock(s->mtx);
+    bind_device(s->device);
+    require_device();
+    s->flush();
+    bind_device(s->device);
+    const int64_t N = s->nrec;
+    // (the list lengths are uint32, as in the index; nothing here is a record NUMBER, so 2^31 is no bound)
+    FA_REQUIRE(N <= (int64_t)UINT32_MAX, FA_ERR_UNSUPPORTED, "more than 2^32 - 1 minimizers in one sketch");
+    int thr = INT_MAX;
+    int64_t dropped = 0;
+    DevBuf<uint32_t> sorted_hash, uniq, counts, num_runs;
+    if (N > 0) {
+      if (!s->stream) FA_HIP(hipStreamCreate(&s->stream));
+      hipStream_t st = s->stream;
+      DevBuf<unsigned char> temp;
+      DevBuf<size_t> n_selected;
+      sorted_hash.ensure((size_t)N); uniq.ensure((size_t)N); counts.ensure((size_t)N); num_runs.ensure(1); n_selected.ensure(1);
+      with_temp(temp, [&](void *t, size_t &bytes) { return rocprim::radix_sort_keys(t, bytes, s->rec.hash.p, sorted_hash.p, (size_t)N, 0u, 32u, st); });
+      with_temp(temp, [&](void *t, size_t &bytes) {
+        return rocprim::run_length_encode(t, bytes, sorted_hash.p, (size_t)N, uniq.p, counts.p, num_runs.p, st);
+      });
+      uint32_t U = 0;
+      num_runs.download(&U, 1, st);
+      FA_HIP(hipStreamSynchronize(st));
+      thr = frequency_threshold(counts.p, (int64_t)U, temp, st);
+      if (thr < INT_MAX) {
+        // the distinct hashes ascend, and so do the ones kept; the sorted copy has served and takes them
+        with_temp(temp, [&](void *t, size_t &bytes) {
+          return rocprim::select(t, bytes, uniq.p, rocprim::make_transform_iterator(counts.p, ListAtLeast{(uint32_t)thr}), sorted_hash.p, n_selected.p,
+                                 (size_t)U, st);
+        });
+        size_t kept = 0;
+        n_selected.download(&kept, 1, st);
+        FA_HIP(hipStreamSynchronize(st));
+        dropped = (int64_t)kept;
+      }
+      if (dropped > cap) {
+        *n_drop = dropped;
+        FA_REQUIRE(false, FA_ERR_INVALID, "destination holds fewer keys than reach the threshold (*n_drop is what it takes)");
+      }
+      if (dropped > 0) {
+        FA_HIP(hipMemcpyAsync(d_drop_keys, sorted_hash.p, (size_t)dropped * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+        FA_HIP(hipStreamSynchronize(st));
+      }
+    }
+    *threshold = thr;
+    *n_drop = dropped;
+  });
 }
 
 int fa_sketch_index(fa_sketch *s, fa_mapper **out) {

@@ -21,8 +21,9 @@
 //   ONCE  read at the first call of THIS accessor and cached for the life of the process (a function-local static): tests that
 //         force such a knob start a child process
 //   LIVE  the environment is consulted on every call.  FA_QF_CAP, FA_NO_PACKED_GEO and FA_EVENTS_CAP_MAX are read by every query
-//         pass (once per part), FA_GPOS_BITS / FA_LINK_BLOCK_BITS / FA_FREQ_OVER_CAP by every index build, FA_TRACE wherever a
-//         traced stage starts; FA_SMAX_INIT / FA_LOCI_CAP_MIN / FA_EVENTS_CAP_MIN at the first query of every mapper and
+//         pass (once per part), FA_GPOS_BITS / FA_LINK_BLOCK_BITS / FA_FREQ_OVER_CAP by every index build (the last also by
+//         fa_sketch_frequency, through the same function), FA_TRACE wherever a traced stage starts; FA_SMAX_INIT /
+//         FA_LOCI_CAP_MIN / FA_EVENTS_CAP_MIN at the first query of every mapper and
 //         FA_MAP_STAGE_MB when a mapper is built (call sites that run once per object)
 #pragma once
 

@@ -86,6 +86,9 @@ cdef extern from "fastani_hip.h" nogil:
     int fa_sketch_add_genomes(fa_sketch* s, const void* const* contigs, const int64_t* lengths, const int32_t* contig_genome, int64_t n_contigs, int32_t n_genomes, int char_width, int32_t* n_short)
     int fa_sketch_add_fasta_many(fa_sketch* s, const char* const* paths, int32_t n_paths, int64_t* n_records, int64_t* n_short)
     int fa_sketch_index(fa_sketch* s, fa_mapper** out)                                        # :790-791 (+ ownership move :793-806)
+    # a subset of the genomes as a sketch of its own / the frequency filter an index of the sketch would have (no reference counterpart)
+    int fa_sketch_select(fa_sketch* s, const int32_t* genomes, int32_t n, fa_sketch** out)
+    int fa_sketch_frequency(fa_sketch* s, int* threshold, int64_t cap, uint32_t* d_drop_keys, int64_t* n_drop)
 
     # Sketch_t after index() + skch::Map
     void fa_mapper_free(fa_mapper* m)                                                         # :839-840
