@@ -1,13 +1,20 @@
-// fa_common.h -- shared host-side plumbing of libfastani_hip: error type, HIP checks, device buffers.
+// fa_common.h -- shared host-side plumbing of libfastani_hip: error type, HIP checks, device buffers, and the owning types of
+// streams, events and pinned memory.
 #pragma once
 
+#include <cstring>   // (before rocPRIM, whose texture_cache_iterator.hpp calls memset without including it)
+
 #include <hip/hip_runtime.h>
+#include <rocprim/rocprim.hpp>
 
 #include <algorithm>
+#include <atomic>
+#include <chrono>
 #include <cstdint>
 #include <cstdlib>
 #include <map>
 #include <mutex>
+#include <string>
 #include <utility>
 #include <vector>
 
@@ -164,12 +171,90 @@ inline void require_device() {
   }
 }
 
-// a stream of one call's own: synchronised and destroyed when the call returns or throws
-struct CallStream {
+// An owned stream: created on first use (get), destroyed with its owner.  Move-only.  Destruction needs no current device.
+struct Stream {
   hipStream_t s = nullptr;
-  CallStream() { FA_HIP(hipStreamCreate(&s)); }
-  CallStream(const CallStream &) = delete;
-  ~CallStream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } }
+  Stream() = default;
+  Stream(Stream &&o) noexcept : s(o.s) { o.s = nullptr; }
+  ~Stream() { if (s) (void)hipStreamDestroy(s); }
+  hipStream_t get(unsigned flags = hipStreamDefault) {
+    if (!s) FA_HIP(hipStreamCreateWithFlags(&s, flags));
+    return s;
+  }
+  operator hipStream_t() const { return s; }
+};
+// a stream of one call's own: synchronised and destroyed when the call returns or throws
+struct CallStream : Stream {
+  CallStream() { get(); }
+  ~CallStream() { if (s) (void)hipStreamSynchronize(s); }
+};
+// An owned event, the same shape: get(flags) creates it on first use.
+struct Event {
+  hipEvent_t e = nullptr;
+  Event() = default;
+  Event(Event &&o) noexcept : e(o.e) { o.e = nullptr; }
+  ~Event() { if (e) (void)hipEventDestroy(e); }
+  hipEvent_t get(unsigned flags = hipEventDefault) {
+    if (!e) FA_HIP(hipEventCreateWithFlags(&e, flags));
+    return e;
+  }
+  operator hipEvent_t() const { return e; }
+};
+
+// Pinned host staging memory (grows, never shrinks; one per workspace / upload).  `flags`: hipHostMalloc's, e.g. mapped and
+// coherent for a block that a kernel writes and the host polls
+struct PinnedBuf {
+  unsigned char *p = nullptr;
+  size_t cap = 0;
+  PinnedBuf() = default;
+  PinnedBuf(const PinnedBuf &) = delete;
+  PinnedBuf &operator=(const PinnedBuf &) = delete;
+  ~PinnedBuf() { if (p) (void)hipHostFree(p); }
+  void ensure(size_t n, unsigned flags = hipHostMallocDefault) {
+    if (n <= cap) return;
+    if (p) { (void)hipHostFree(p); p = nullptr; cap = 0; }
+    const size_t ncap = std::max(n, cap * 2);
+    FA_HIP(hipHostMalloc((void **)&p, ncap, flags));
+    cap = ncap;
+  }
+};
+
+// The device chosen with fa_set_device (-1: whatever the calling thread has current).  HIP's current device is a
+// per-thread setting, and sketches / mappers are used from any host thread: each object remembers its device and every
+// entry point binds it again.
+inline std::atomic<int> g_device{-1};
+inline void bind_device(int device) {
+  if (device >= 0) FA_HIP(hipSetDevice(device));
+}
+
+// FA_TRACE=1: wall-clock of the host-visible stages of sketching and index construction on stderr
+struct StageTrace {
+  bool on, live = false;
+  const char *what;
+  std::chrono::steady_clock::time_point t0, t;
+  std::vector<std::pair<std::string, double>> acc;
+  explicit StageTrace(const char *w) : what(w) {
+    const double level = knob::trace();
+    on = !knob::unset(level);
+    live = on && level >= 2;
+    t0 = t = std::chrono::steady_clock::now();
+  }
+  void mark(const char *stage, hipStream_t st) {
+    if (!on) return;
+    (void)hipStreamSynchronize(st);
+    auto now = std::chrono::steady_clock::now();
+    double ms = std::chrono::duration<double, std::milli>(now - t).count();
+    t = now;
+    if (live) { fprintf(stderr, "[fa trace] %s: %s done after %.1f ms\n", what, stage, ms); fflush(stderr); }   // FA_TRACE=2: as it happens
+    for (auto &a : acc) if (a.first == stage) { a.second += ms; return; }
+    acc.emplace_back(stage, ms);
+  }
+  ~StageTrace() {
+    if (!on) return;
+    fprintf(stderr, "[fa trace] %s: %.1f ms total;", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    for (auto &a : acc) fprintf(stderr, " %s %.1f", a.first.c_str(), a.second);
+    fprintf(stderr, "\n");
+  }
 };
 
 // rocPRIM's two calls with the argument list written once: fn(nullptr, bytes) sizes the temporary storage, fn(temp, bytes) runs
@@ -179,6 +264,11 @@ void with_temp(DevBuf<unsigned char> &temp, Fn fn) {
   FA_HIP(fn(nullptr, bytes));
   temp.ensure(bytes + 16);
   FA_HIP(fn(temp.p, bytes));
+}
+
+// rocPRIM directly (device-wide scan / radix sort / run-length encode; sizes are size_t)
+inline void exclusive_sum_i32(DevBuf<unsigned char> &temp, const int32_t *in, int32_t *out, size_t n, hipStream_t st) {
+  with_temp(temp, [&](void *t, size_t &bytes) { return rocprim::exclusive_scan(t, bytes, in, out, (int32_t)0, n, rocprim::plus<int32_t>(), st); });
 }
 
 // the status block of one call: a device T zeroed on the stream before the first launch; read() = its host copy, synchronised

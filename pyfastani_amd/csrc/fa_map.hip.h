@@ -2157,11 +2157,9 @@ __global__ __launch_bounds__(EV_THREADS, EV_WAVES_PER_SIMD) void k_l2_events(L2A
     for (int u = 0; u < R; u++) {
       const int i = t0 + lane + 64 * u;
       if (i >= hi) continue;
-      uint32_t flags; bool prev_in; int32_t bwd, fwd1;
-      if (PACKED) {
-        flags = t.geo[u] >> (2 * GEO_BITS); prev_in = t.pd[u] <= (uint32_t)(i - beg);
-        bwd = i - (int32_t)((t.geo[u] >> GEO_BITS) & ((1u << GEO_BITS) - 1u)); fwd1 = i + 1 + (int32_t)(t.geo[u] & ((1u << GEO_BITS) - 1u));
-      } else { flags = t.rf[u]; prev_in = t.pv[u] >= beg; bwd = t.bw[u]; fwd1 = t.fw[u]; }
+      const uint32_t flags = t.rf[u];                   // (the packed layout has returned above)
+      const bool prev_in = t.pv[u] >= beg;
+      const int32_t bwd = t.bw[u], fwd1 = t.fw[u];
       // both events carry slot = rank + 1 and ONE signed delta: of the matched bit when the hash is in the query
       // sketch (a sentinel is not a match), of the window-only count otherwise
       const uint32_t base = (uint32_t)(x[u] + 1) << EV_SLOT;
@@ -2485,7 +2483,7 @@ __device__ __forceinline__ bool cgi_survivor(const CgiArgs &a, uint32_t g, size_
                                                                       //  group maxima is cleared per pass: no maximum, no group)
   // A void part must leave no trace in the bin table, which later parts and the repeat of this one accumulate into: when a
   // locus overflowed the one-byte slide state and the wide pass was not launched, the group maxima lack that locus, and a
-  // lesser locus of its group could land in a bin the true best never touches (the host repeats the part, fa_engine.hip)
+  // lesser locus of its group could land in a bin the true best never touches (the host repeats the part, fa_query.hip.h)
   if (a.counters[CNT_WIDE] && !a.wide_launched) return false;
   unsigned long long best = a.group_best[g];
   if (best == 0) return false;
@@ -2529,7 +2527,7 @@ __global__ void k_cgi_winners(CgiArgs a, MapWinner *winners) {
 // of eight 64-bin chunks are fetched together so that the sequential chain waits for HBM once per 512 bins, and
 // chunks without any mapping are skipped (x + 0.0f == x).  When `emit` is set (small passes) the last workgroup to
 // finish also forms the rows -- flag the non-empty pairs, scan, write in (query, genome) order -- which saves a launch.
-// Hand-over of a pass to the host (fa_engine.hip, k_publish_status): the status block and, for a one-query call, the hit
+// Hand-over of a pass to the host (fa_query.hip.h, k_publish_status): the status block and, for a one-query call, the hit
 // rows are copied into pinned host memory, then the pass number is released for the host that polls it.  Run by one
 // workgroup: the last one of k_cgi_rows when that kernel also forms the rows, else a kernel of its own.
 constexpr int ROWS_INLINE_MAX = 256;    // rows the publishing workgroup writes into pinned host memory itself

@@ -5,7 +5,7 @@
 // (query, reference genome, bin) order.  They leave the device in windows of `stage` records: window w holds the places
 // [w * stage, min(total, (w + 1) * stage)), written to the front of a stage buffer of fixed size.  k_map_write is launched once
 // per window; a workgroup, which owns one chunk of consecutive bins and knows the place of its first record and their number,
-// asks map_chunk_in_window whether any of them falls into the window before it loads a key.  fa_engine.hip (QueryPass) owns the
+// asks map_chunk_in_window whether any of them falls into the window before it loads a key.  fa_query.hip.h (QueryPass) owns the
 // stage buffers and the launches; everything here is pure arithmetic.
 #pragma once
 

@@ -4,7 +4,7 @@
 // hits, the loci, the slide events -- are speculated from earlier parts (Spec), checked by the kernels, which raise SPEC_*
 // flags in the status block (PassStatus), and judged here once the part is done: accepted, or void and run again with a
 // grown record, or cut into smaller parts.  The same record picks the forms of the next part (the k_l1 size classes, the
-// block pre-filter, the sorted scan, the wide state, the back-off of the fused sketch kernel).  fa_engine.hip (QueryPass)
+// block pre-filter, the sorted scan, the wide state, the back-off of the fused sketch kernel).  fa_query.hip.h (QueryPass)
 // owns the buffers, the launches and the locking; everything here is pure arithmetic over plain structs.
 #pragma once
 

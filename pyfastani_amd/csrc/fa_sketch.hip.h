@@ -408,12 +408,13 @@ struct SketchArgs {
 
 // LDS carve-up (dynamic): [image: code_words*4 B][keyA: npos_cap*8][keyB: npos_cap*8][valid: (npos_cap/64+1)*8]
 //                         [emit: (TILE/64)*8][prefix: (TILE/64+1)*4]
-inline size_t sketch_lds_bytes(int k, int w) {
+struct SketchLayout { size_t image, total; };
+inline SketchLayout sketch_layout(int k, int w) {
   size_t npos_cap = (size_t)TILE + 2 * (size_t)w - 2;
   size_t span = npos_cap + (size_t)k - 1 + 64;            // bases (or bytes) staged, with slack for get16 over-read
   size_t image = ((span + 3) / 4 + 4) * 4;                // byte image is the larger of the two
   image = (image + 15) / 16 * 16;
-  return image + npos_cap * 16 + (npos_cap / 64 + 1) * 8 + (TILE / 64) * 8 + (TILE / 64 + 1) * 4 + 16 + 4 * 256 * 8;
+  return SketchLayout{image, image + npos_cap * 16 + (npos_cap / 64 + 1) * 8 + (TILE / 64) * 8 + (TILE / 64 + 1) * 4 + 16 + 4 * 256 * 8};
 }
 
 // BYTES = false: tiles of plain ACGT, hashed from the 2-bit image (the hot kernel, kept free of the byte path so that it

@@ -155,6 +155,12 @@ struct StatTables {
 
   bool passes(int c, int s) const { return stat_upper_identity(c, s, k, ci) >= pid; }
 
+  // the pass table at the interval of a call that the mapper has left since (fa_mapper_set_rules while the call was in flight)
+  std::vector<int32_t> pass_shared_at(float call_ci) const {
+    std::vector<int32_t> own((size_t)smax + 1);
+    for (int s = 0; s <= smax; s++) own[s] = stat_pass_threshold(s, k, pid, call_ci);
+    return own;
+  }
   // pass_shared again, for another interval (the other tables do not depend on it)
   void set_ci(float new_ci) {
     ci = new_ci;

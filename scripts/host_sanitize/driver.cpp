@@ -3,7 +3,7 @@
 //   pool, the memory-mapped FASTA reader (fa_fasta.h), the statistics tables (fa_stats.h), the workspace lease and the
 //   pinned-word spin (fa_lease.h), the policy of a query pass (fa_policy.h: every rule at the boundaries where it turns), the contig bookkeeping of
 //   ingest (fa_ingest.h: the reference roads and the plan of a query batch against restatements of _fastani.pyx).  Inputs: the edge cases of tests/test_gpu_parity.py::test_minimizer_streams and
-//   tests/test_fasta.py, plus four concurrent clients.  No HIP: these headers are what fa_engine.hip includes for the same jobs.
+//   tests/test_fasta.py, plus four concurrent clients.  No HIP: these headers are what the library's one translation unit (fa_engine.hip and the fa_*.hip.h it includes) uses for the same jobs.
 // Built and run by scripts/host_sanitize.sh; exits non-zero on any mismatch (the sanitizers abort on their own findings).
 #include <unistd.h>
 

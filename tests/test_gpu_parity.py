@@ -1370,7 +1370,7 @@ def test_device_memory_is_stable():
 ])
 def test_unpacked_record_geometry(params, env, monkeypatch):
     # k_l2_events<T, false> (records from the plain arrays, occupancy-word ranks like the packed form): the form every index
-    # takes whose fragment length leaves no room for the 13-bit distances of rec_hg (fa_engine.hip, packed_geo), and
+    # takes whose fragment length leaves no room for the 13-bit distances of rec_hg (fa_index.hip.h, packed_geo), and
     # FA_NO_PACKED_GEO forces on any index
     for key, val in env.items():
         monkeypatch.setenv(key, val)

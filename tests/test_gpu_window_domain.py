@@ -31,7 +31,7 @@ WINDOWS = [1, 2, 3, 4, 5, 63, 64, 65, 127, 128, 129, 255, 256, 257, 384, 385, 38
 KS = [11, 14, 16, 21, 32, 33]
 DEFINITION_WINDOWS = [1, 2, 3, 4, 64, 65, 385, 1000, 1001, 2049]
 TILE = 1024
-FUSED_CELLS = {(14, 12), (14, 37), (14, 50), (16, 13), (16, 24), (16, 40), (21, 15), (21, 25)}   # FA_KW_CELLS, fa_engine.hip
+FUSED_CELLS = {(14, 12), (14, 37), (14, 50), (16, 13), (16, 24), (16, 40), (21, 15), (21, 25)}   # FA_KW_CELLS, fa_k1.hip.h
 
 
 def k1_tile_len(w):
