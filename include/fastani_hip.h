@@ -487,6 +487,40 @@ int fa_screen_pairs(const uint32_t *d_sig_a, const int32_t *d_count_a, int32_t n
 int fa_screen_groups(const fa_screen_pair *pairs, int64_t n_pairs, int pairs_device, int32_t n_genomes, int32_t *labels, int labels_device,
                      int32_t *n_groups);
 
+/* ---- the screen's containment road -------------------------------------- */
+/* The Jaccard estimate of fa_screen_pairs collapses when two genomes differ in size: the bottom s of the union is filled by the
+ * larger one, and a contig, a plasmid or an incomplete genome looks distant from the complete relative it lies inside.  The
+ * containment of a query's signature in a reference's FULL set of distinct hashes (what `mash screen` computes) does not.
+ *   1. Contents of a collection.  Genome g owns the records whose contig id lies in [sbf[g-1], sbf[g]), exactly as for
+ *      signatures.  The contents are the distinct pairs (hash, genome) of the records, sorted ascending by hash as unsigned
+ *      32-bit, then by genome.  Layout: uint32 ent_hash[m], int32 ent_genome[m]; m <= n_records; a genome without records has
+ *      no entry; 0 and 0xFFFFFFFF are legal hashes.
+ *   2. Statistic.  For a signature A (ascending, distinct, count_a long) and a reference genome b: shared = the number of
+ *      elements x of A that have an entry (x, b); denom = count_a.  denom == 0 never forms a pair.
+ *   3. Filter.  A pair is kept iff denom > 0 and (int64_t)shared * cd >= (int64_t)cn * denom: cn / cd is the caller's
+ *      rational containment cut-off, 0 <= cn <= cd, cd >= 1.  Integers only.
+ *   4. Output.  fa_screen_pair records sorted by (a, b), a indexing the signature set and b the collection; every pair is
+ *      rectangular.  The same input gives the same bytes on every run.
+ * Both calls run like fa_screen_pairs: on the calling thread's current device, on a stream of their own, with memory from the
+ * device pool, finished when they return, FA_ERR_NO_DEVICE without a device. */
+/* d_hash, d_seq_id, d_ent_hash and d_ent_genome are DEVICE pointers; sbf is host memory.  d_ent_hash == d_ent_genome == NULL
+ * only counts.  A `cap` below the number of entries is FA_ERR_INVALID: nothing is written, and *n_entries (which may be NULL)
+ * holds the number needed; n_records entries always suffice.  FA_ERR_INVALID with nothing written, *n_entries included:
+ * d_seq_id not ascending; a contig id outside [0, sbf[n_genomes-1]); sbf not non-decreasing. */
+int fa_screen_contents(const uint32_t *d_hash, const int32_t *d_seq_id, int64_t n_records, const int32_t *sbf, int32_t n_genomes,
+                       uint32_t *d_ent_hash, int32_t *d_ent_genome, int64_t cap, int64_t *n_entries);
+/* The references a workgroup of fa_screen_contained counts at a time: a collection of more is taken slice by slice; host only. */
+int fa_screen_contain_slice(int32_t *slice);
+/* The signature and entry arrays are DEVICE pointers; pairs_device != 0: `pairs` is one too.  pairs == NULL only counts.  A
+ * `cap` below the number of pairs is FA_ERR_INVALID: nothing is written, and *n_pairs holds the number needed.
+ * FA_ERR_INVALID with nothing written, *n_pairs included: s outside [1, 4096]; a count outside [0, s]; a signature that does
+ * not ascend strictly below its count; entries that do not ascend strictly by (hash, genome); an entry's genome outside
+ * [0, n_b); cn or cd out of range.  n_pairs and stats may be NULL; stats[0] the pairs evaluated, n_a * n_b, [1] the pairs
+ * kept, [2] the directory entries visited: the entries (x, b) with x in A, summed over the signatures A. */
+int fa_screen_contained(const uint32_t *d_sig, const int32_t *d_count, int32_t n_a, int32_t s, const uint32_t *d_ent_hash,
+                        const int32_t *d_ent_genome, int64_t n_entries, int32_t n_b, int32_t cn, int32_t cd, fa_screen_pair *pairs,
+                        int64_t cap, int64_t *n_pairs, int pairs_device, int64_t *stats);
+
 /* stage-level introspection used by the parity tests */
 int fa_mapper_debug_mappings(fa_mapper *m, fa_mapping *out, int64_t cap, int64_t *n); /* L2 results of the last query call, under its rules */
 int fa_mapper_debug_l1(fa_mapper *m, int32_t *frag, int32_t *seq_id, int32_t *range_start, int32_t *range_end,

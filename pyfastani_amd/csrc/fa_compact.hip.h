@@ -1,6 +1,7 @@
 // fa_compact.hip.h -- the middle step of every ordered compaction of the library (count per chunk, scan the chunk counts,
-// write): the mappings of a pass (fa_map.hip.h), the pairs and edges of a hit table (fa_table.hip.h) and the pairs of a
-// screen (fa_screen.hip.h) count and write in their own kernels and share this scan.
+// write): the mappings of a pass (fa_map.hip.h), the pairs and edges of a hit table (fa_table.hip.h), the pairs of a
+// screen (fa_screen.hip.h) and the entries and records of its containment road (fa_contain.hip.h) count and write in their
+// own kernels and share this scan.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -543,6 +543,23 @@ int fa_screen_groups(const fa_screen_pair *pairs, int64_t n_pairs, int pairs_dev
                      int32_t *n_groups) {
   return guarded([&] { screen_groups(pairs, n_pairs, pairs_device != 0, n_genomes, labels, labels_device != 0, n_groups); });
 }
+int fa_screen_contents(const uint32_t *d_hash, const int32_t *d_seq_id, int64_t n_records, const int32_t *sbf, int32_t n_genomes,
+                       uint32_t *d_ent_hash, int32_t *d_ent_genome, int64_t cap, int64_t *n_entries) {
+  return guarded([&] { screen_contents(d_hash, d_seq_id, n_records, sbf, n_genomes, d_ent_hash, d_ent_genome, cap, n_entries); });
+}
+int fa_screen_contain_slice(int32_t *slice) {
+  return guarded([&] {
+    FA_REQUIRE(slice, FA_ERR_INVALID, "null destination");
+    *slice = CNT_SLICE;
+  });
+}
+int fa_screen_contained(const uint32_t *d_sig, const int32_t *d_count, int32_t n_a, int32_t s, const uint32_t *d_ent_hash,
+                        const int32_t *d_ent_genome, int64_t n_entries, int32_t n_b, int32_t cn, int32_t cd, fa_screen_pair *pairs,
+                        int64_t cap, int64_t *n_pairs, int pairs_device, int64_t *stats) {
+  return guarded([&] {
+    screen_contained(d_sig, d_count, n_a, s, d_ent_hash, d_ent_genome, n_entries, n_b, cn, cd, pairs, cap, n_pairs, pairs_device != 0, stats);
+  });
+}
 int fa_mapper_set_mapping_stage(fa_mapper *m, int64_t records) {
   return guarded([&] {
     FA_REQUIRE(m && records >= 1, FA_ERR_INVALID, "the mapping stage holds at least one record");

@@ -1,6 +1,6 @@
 // fa_reduce.hip.h -- the host drivers of the reductions over results the mapper already holds: a hit table to pairs,
-// clusters and representatives (fa_table.hip.h, fa_represent.hip.h), to every query's k best hits (fa_best.hip.h), and the
-// signature screen (fa_screen.hip.h).  They use nothing of the sketch, the mapper or the workspace; fa_engine.hip wraps each
+// clusters and representatives (fa_table.hip.h, fa_represent.hip.h), to every query's k best hits (fa_best.hip.h), the
+// signature screen (fa_screen.hip.h) and its containment road (fa_contain.hip.h).  They use nothing of the sketch, the mapper or the workspace; fa_engine.hip wraps each
 // in its extern "C" entry point.
 //
 // Every driver has the same frame (the pieces are in fa_common.h): it checks its arguments, then require_device(), then
@@ -21,6 +21,7 @@
 
 #include "fa_best.hip.h"
 #include "fa_common.h"
+#include "fa_contain.hip.h"
 #include "fa_order.h"
 #include "fa_represent.hip.h"
 #include "fa_screen.hip.h"
@@ -366,7 +367,7 @@ inline void screen_signatures(const uint32_t *d_hash, const int32_t *d_seq_id, i
     a.sbf = d_sbf.p;
     keys.ensure((size_t)n_records); keys_sorted.ensure((size_t)n_records);
     heads.ensure((size_t)n_records); rank.ensure((size_t)n_records);
-    hipLaunchKernelGGL(k_sig_keys, rec_grid, dim3(256), 0, st, a, keys.p);
+    hipLaunchKernelGGL(k_sig_keys<false>, rec_grid, dim3(256), 0, st, a, keys.p);
     // the bits a key can have set: 32 of the hash and those of the largest genome number
     const unsigned end_bit = 32u + id_bits(n_genomes);
     with_temp(temp, [&](void *t, size_t &bytes) {
@@ -483,6 +484,156 @@ inline void screen_groups(const fa_screen_pair *pairs, int64_t n_pairs, bool pai
     FA_HIP(hipStreamSynchronize(st));
   }
   if (n_groups) *n_groups = (int32_t)roots;
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// The containment road of the screen: a collection's contents as a sorted directory, signatures looked up in it
+// (fa_contain.hip.h has the semantics and the road)
+// ------------------------------------------------------------------------------------------------------------
+inline void screen_contents(const uint32_t *d_hash, const int32_t *d_seq_id, int64_t n_records, const int32_t *sbf, int32_t n_genomes,
+                            uint32_t *d_ent_hash, int32_t *d_ent_genome, int64_t cap, int64_t *n_entries) {
+  FA_REQUIRE(n_genomes >= 0 && n_records >= 0, FA_ERR_INVALID, "negative number of genomes or records");
+  FA_REQUIRE(n_records == 0 || (d_hash && d_seq_id), FA_ERR_INVALID, "null records");
+  FA_REQUIRE(n_genomes == 0 || sbf, FA_ERR_INVALID, "null sequencesByFileInfo");
+  FA_REQUIRE(n_records == 0 || n_genomes > 0, FA_ERR_INVALID, "records without a genome");
+  FA_REQUIRE((d_ent_hash == nullptr) == (d_ent_genome == nullptr), FA_ERR_INVALID, "the entries' hashes and genomes come together or not at all");
+  FA_REQUIRE(!d_ent_hash || cap >= 0, FA_ERR_INVALID, "negative capacity");
+  FA_REQUIRE(n_records <= (int64_t)INT32_MAX, FA_ERR_UNSUPPORTED, "more than 2^31 - 1 records");
+  for (int32_t g = 0; g < n_genomes; g++)
+    FA_REQUIRE(sbf[g] >= (g ? sbf[g - 1] : 0), FA_ERR_INVALID, "sequencesByFileInfo must not decrease");
+  require_device();
+  if (!n_records) {
+    if (n_entries) *n_entries = 0;
+    return;
+  }
+  CallStream stream;
+  hipStream_t st = stream.s;
+  StatusBlock<TableStatus> d_status(st);
+  DevBuf<int32_t> d_sbf;
+  DevBuf<unsigned long long> keys, keys_sorted;
+  DevBuf<uint32_t> heads;
+  DevBuf<unsigned char> temp;
+  DevBuf<int32_t> chunk_count;
+  DevBuf<int64_t> chunk_off;
+
+  SigArgs a{};
+  a.hash = d_hash; a.seq_id = d_seq_id; a.n_records = n_records; a.n_genomes = n_genomes;
+  a.n_contigs = sbf[n_genomes - 1];
+  a.status = d_status.p;
+  const dim3 rec_grid(ceil_div(n_records, 256));
+  // the verdict on the records is read before anything else runs
+  hipLaunchKernelGGL(k_sig_check, rec_grid, dim3(256), 0, st, a);
+  FA_HIP(hipGetLastError());
+  TableStatus status = d_status.read(st);
+  FA_REQUIRE(!(status.flags & TAB_BAD_ID), FA_ERR_INVALID, "a record's contig id lies outside [0, sequencesByFileInfo[n_genomes - 1])");
+  FA_REQUIRE(!(status.flags & SCR_NOT_ASCENDING), FA_ERR_INVALID, "the records are not sorted by contig id");
+  d_sbf.upload(sbf, (size_t)n_genomes, st);
+  a.sbf = d_sbf.p;
+  keys.ensure((size_t)n_records); keys_sorted.ensure((size_t)n_records);
+  heads.ensure((size_t)n_records);
+  // the bits a key can have set: those of the largest genome number and 32 of the hash above them
+  a.genome_bits = (int32_t)id_bits(n_genomes);
+  const unsigned end_bit = 32u + (unsigned)a.genome_bits;
+  hipLaunchKernelGGL(k_sig_keys<true>, rec_grid, dim3(256), 0, st, a, keys.p);
+  with_temp(temp, [&](void *t, size_t &bytes) {
+    return rocprim::radix_sort_keys(t, bytes, keys.p, keys_sorted.p, (size_t)n_records, 0u, end_bit, st);
+  });
+  a.keys = keys_sorted.p;
+  hipLaunchKernelGGL(k_sig_heads, rec_grid, dim3(256), 0, st, a, heads.p);
+  EntArgs e{};
+  e.keys = keys_sorted.p; e.heads = heads.p; e.n_records = n_records;
+  e.n_chunks = ceil_div(n_records, ENT_CHUNK); e.genome_bits = a.genome_bits;
+  chunk_count.ensure((size_t)e.n_chunks); chunk_off.ensure((size_t)e.n_chunks);
+  e.chunk_count = chunk_count.p; e.chunk_off = chunk_off.p;
+  hipLaunchKernelGGL(k_ent_count, dim3(ceil_div(e.n_chunks, 4)), dim3(256), 0, st, e);
+  hipLaunchKernelGGL(k_chunk_scan, dim3(1), dim3(1024), 0, st, e.chunk_count, e.chunk_off, e.n_chunks, &d_status.p->emitted);
+  FA_HIP(hipGetLastError());
+  status = d_status.read(st);
+  const int64_t m = (int64_t)status.emitted;
+  if (n_entries) *n_entries = m;
+  if (!d_ent_hash) return;
+  FA_REQUIRE(m <= cap, FA_ERR_INVALID, "the entry buffers are smaller than the number of entries");
+  e.ent_hash = d_ent_hash; e.ent_genome = d_ent_genome;
+  hipLaunchKernelGGL(k_ent_write, dim3(ceil_div(e.n_chunks, 4)), dim3(256), 0, st, e);
+  FA_HIP(hipGetLastError());
+  FA_HIP(hipStreamSynchronize(st));
+}
+
+inline void screen_contained(const uint32_t *d_sig, const int32_t *d_count, int32_t n_a, int32_t s, const uint32_t *d_ent_hash,
+                             const int32_t *d_ent_genome, int64_t n_entries, int32_t n_b, int32_t cn, int32_t cd, fa_screen_pair *pairs,
+                             int64_t cap, int64_t *n_pairs, bool pairs_device, int64_t *stats) {
+  FA_REQUIRE(s >= 1 && s <= SCR_MAX_S, FA_ERR_INVALID, "the signature size must be in [1, 4096]");
+  FA_REQUIRE(cd >= 1 && cn >= 0 && cn <= cd, FA_ERR_INVALID, "the containment cut-off needs 0 <= cn <= cd and cd >= 1");
+  FA_REQUIRE(n_a >= 0 && n_b >= 0 && n_entries >= 0, FA_ERR_INVALID, "negative number of genomes or entries");
+  FA_REQUIRE(n_a == 0 || (d_sig && d_count), FA_ERR_INVALID, "null signatures");
+  FA_REQUIRE(n_entries == 0 || (d_ent_hash && d_ent_genome), FA_ERR_INVALID, "null entries");
+  FA_REQUIRE(!pairs || cap >= 0, FA_ERR_INVALID, "negative capacity");
+  const int64_t n_slices = std::max<int64_t>(1, ((int64_t)n_b + CNT_SLICE - 1) / CNT_SLICE);
+  const int64_t n_groups = (int64_t)n_a * n_slices;
+  FA_REQUIRE(n_groups <= (int64_t)INT32_MAX, FA_ERR_UNSUPPORTED, "more than 2^31 - 1 (query, slice of references) workgroups");
+  require_device();
+  CallStream stream;
+  hipStream_t st = stream.s;
+  StatusBlock<ContainStatus> d_status(st);
+  DevBuf<int32_t> group_count;
+  DevBuf<int64_t> group_off;
+
+  ContainArgs a{};
+  a.sig = d_sig; a.count = d_count; a.n_a = n_a; a.s = s;
+  a.ent_hash = d_ent_hash; a.ent_genome = d_ent_genome; a.m = n_entries; a.n_b = n_b; a.n_slices = (int32_t)n_slices;
+  a.cn = cn; a.cd = cd; a.status = d_status.p;
+  ContainStatus status{};
+  const int64_t to_check = std::max((int64_t)n_a * s, n_entries);
+  if (to_check) {
+    // the verdict on both inputs is read before a counting kernel is launched: those rely on it
+    hipLaunchKernelGGL(k_contain_check, dim3((unsigned)std::min<int64_t>((to_check + 255) / 256, 1 << 20)), dim3(256), 0, st, a);
+    FA_HIP(hipGetLastError());
+    status = d_status.read(st);
+    FA_REQUIRE(!(status.flags & SCR_BAD_COUNT), FA_ERR_INVALID, "a signature count lies outside [0, s]");
+    FA_REQUIRE(!(status.flags & SCR_NOT_ASCENDING), FA_ERR_INVALID, "a signature does not ascend strictly below its count");
+    FA_REQUIRE(!(status.flags & TAB_BAD_ID), FA_ERR_INVALID, "an entry names a genome outside [0, n_b)");
+    FA_REQUIRE(!(status.flags & CNT_UNORDERED), FA_ERR_INVALID, "the entries do not ascend strictly by (hash, genome)");
+  }
+  // the COUNT or the WRITE form; elements of A a thread searches at a time: as many chains as a signature of size s gives a
+  // thread of CNT_THREADS, four at the most (not measured yet: scripts/time_contain.py)
+  const size_t lds = (size_t)((std::min<int64_t>(n_b, CNT_SLICE) + 1) / 2) * sizeof(uint32_t);
+  auto launch = [&](bool write) {
+    const dim3 grid((unsigned)n_groups), block(CNT_THREADS);
+    if (s <= CNT_THREADS) {
+      if (write) hipLaunchKernelGGL((k_contain<1, true>), grid, block, lds, st, a);
+      else hipLaunchKernelGGL((k_contain<1, false>), grid, block, lds, st, a);
+    } else if (s <= 2 * CNT_THREADS) {
+      if (write) hipLaunchKernelGGL((k_contain<2, true>), grid, block, lds, st, a);
+      else hipLaunchKernelGGL((k_contain<2, false>), grid, block, lds, st, a);
+    } else {
+      if (write) hipLaunchKernelGGL((k_contain<4, true>), grid, block, lds, st, a);
+      else hipLaunchKernelGGL((k_contain<4, false>), grid, block, lds, st, a);
+    }
+  };
+  if (n_a && n_b) {
+    group_count.ensure((size_t)n_groups); group_off.ensure((size_t)n_groups);
+    a.group_count = group_count.p; a.group_off = group_off.p;
+    launch(false);
+    hipLaunchKernelGGL(k_chunk_scan, dim3(1), dim3(1024), 0, st, a.group_count, a.group_off, (int32_t)n_groups, &d_status.p->emitted);
+    FA_HIP(hipGetLastError());
+    status = d_status.read(st);
+  }
+  const int64_t n_emit = status.emitted;
+  if (n_pairs) *n_pairs = n_emit;
+  FA_REQUIRE(!pairs || n_emit <= cap, FA_ERR_INVALID, "the pair buffer is smaller than the number of pairs");
+  if (pairs && n_emit) {
+    Staged<fa_screen_pair> out(pairs, pairs_device, (size_t)n_emit);
+    a.pairs = out.dev();
+    launch(true);
+    FA_HIP(hipGetLastError());
+    out.finish(st);
+    FA_HIP(hipStreamSynchronize(st));
+  }
+  if (stats) {
+    stats[0] = (int64_t)n_a * (int64_t)n_b;
+    stats[1] = n_emit;
+    stats[2] = (int64_t)status.visited;
+  }
 }
 
 }  // namespace fa

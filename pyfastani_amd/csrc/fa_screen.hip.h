@@ -26,10 +26,11 @@
 //
 // Signatures.  k_sig_check raises a flag for a contig id that descends or lies outside [0, sbf[n_genomes-1]) -- the host
 // reads it before anything is written.  k_sig_keys finds every record's genome by binary search in sbf and packs
-// genome << 32 | hash; one radix sort over 32 bits plus those of the largest genome number orders every genome's hashes;
-// a head is a key that differs from its predecessor; an exclusive scan of the heads ranks them, the rank of a genome's
-// first key (always a head) is the base of its segment (k_sig_segments: the one thread that sees a boundary writes it),
-// and k_sig_write stores the heads of segment rank below s.
+// genome << 32 | hash (its other form packs the hash above the genome: the contents of fa_contain.hip.h); one radix sort
+// over 32 bits plus those of the largest genome number orders every genome's hashes; a head is a key that differs from
+// its predecessor; an exclusive scan of the heads ranks them, the rank of a genome's first key (always a head) is the base
+// of its segment (k_sig_segments: the one thread that sees a boundary writes it), and k_sig_write stores the heads of
+// segment rank below s.
 //
 // Pairs, the hot path.  A workgroup of SCR_WAVES waves owns a tile of T x T genomes and stages the 2 T signatures once in
 // LDS, checking on the way that counts lie in [0, s] and signatures ascend strictly.  A row of LDS is screen_stride(s) words,
@@ -83,6 +84,7 @@ struct SigArgs {
   const int32_t *sbf;                  // device copy
   int32_t n_genomes, s;
   int32_t n_contigs;                   // sbf[n_genomes - 1]
+  int32_t genome_bits;                 // k_sig_keys<true>: the bits of the largest genome number, below the hash
   const unsigned long long *keys;      // sorted
   const uint32_t *rank;                // exclusive scan of the heads
   uint32_t *first, *last;              // [n_genomes], zeroed: head ranks [first, last) of every genome with records
@@ -101,6 +103,8 @@ __global__ __launch_bounds__(256) void k_sig_check(SigArgs a) {
   if (flags) atomicOr(&a.status->flags, flags);
 }
 
+// HASH_MAJOR: hash << genome_bits | genome, the order of a collection's contents (fa_contain.hip.h); else genome << 32 | hash
+template <bool HASH_MAJOR>
 __global__ __launch_bounds__(256) void k_sig_keys(SigArgs a, unsigned long long *keys) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= a.n_records) return;
@@ -110,7 +114,8 @@ __global__ __launch_bounds__(256) void k_sig_keys(SigArgs a, unsigned long long 
     const int mid = (lo + hi) >> 1;
     if (a.sbf[mid] > c) hi = mid; else lo = mid + 1;
   }
-  keys[i] = (unsigned long long)(uint32_t)min(lo, a.n_genomes - 1) << 32 | a.hash[i];
+  const unsigned long long g = (unsigned long long)(uint32_t)min(lo, a.n_genomes - 1), h = a.hash[i];
+  keys[i] = HASH_MAJOR ? h << a.genome_bits | g : g << 32 | h;
 }
 
 __global__ __launch_bounds__(256) void k_sig_heads(SigArgs a, uint32_t *heads) {

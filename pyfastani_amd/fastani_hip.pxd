@@ -199,3 +199,10 @@ cdef extern from "fastani_hip.h" nogil:
                         int64_t* n_pairs, int pairs_device, int64_t* stats)
     int fa_screen_groups(const fa_screen_pair* pairs, int64_t n_pairs, int pairs_device, int32_t n_genomes, int32_t* labels,
                          int labels_device, int32_t* n_groups)
+    # the screen's containment road: a collection's contents as a sorted directory, signatures looked up in it
+    int fa_screen_contents(const uint32_t* d_hash, const int32_t* d_seq_id, int64_t n_records, const int32_t* sbf, int32_t n_genomes,
+                           uint32_t* d_ent_hash, int32_t* d_ent_genome, int64_t cap, int64_t* n_entries)
+    int fa_screen_contain_slice(int32_t* slice)
+    int fa_screen_contained(const uint32_t* d_sig, const int32_t* d_count, int32_t n_a, int32_t s, const uint32_t* d_ent_hash,
+                            const int32_t* d_ent_genome, int64_t n_entries, int32_t n_b, int32_t cn, int32_t cd, fa_screen_pair* pairs,
+                            int64_t cap, int64_t* n_pairs, int pairs_device, int64_t* stats)

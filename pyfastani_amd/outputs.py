@@ -105,6 +105,16 @@ def write_screen(path, names_a, names_b, records, k):
             f.write(f"{names_a[r['a']]}\t{names_b[r['b']]}\t{d:.6g}\t{r['shared']}/{r['denom']}\n")
 
 
+def write_containment(path, query_names, reference_names, records, k):
+    """The records of `pyfastani_amd.screen.contained` (numpy or a tensor) in the format of `write_screen`: query, reference,
+    containment identity, shared/denom, one line per record in record order."""
+    from . import screen
+    records = screen.to_records(records)
+    with open(path, "w") as f:
+        for r, i in zip(records, screen.identity(records, k)):
+            f.write(f"{query_names[r['a']]}\t{reference_names[r['b']]}\t{i:.6g}\t{r['shared']}/{r['denom']}\n")
+
+
 def fragment_coordinates(contig_lengths, fragment_length):
     """Where every query fragment lies in its genome: ``(contig, offset)``, two int64 arrays indexed by ``querySeqId``
     (``query_seq_id`` of a mapping).  A contig of length ``n`` holds ``n // fragment_length`` fragments, numbered on from

@@ -9,8 +9,16 @@ each group is mapped with what exists: one `Sketch` / `Mapper` / all-vs-all per 
     records = screen.pairs(sigs, max_distance=0.1)         #   next chunk, and Signatures.concat
     members = screen.partition(screen.groups(records, len(sigs)))
 
+The Jaccard estimate of `pairs` collapses when two genomes differ in size (a contig, a plasmid, an incomplete genome against
+its complete relative).  The containment road is for those: ``fa_screen_contents`` / ``fa_screen_contained``, what ``mash
+screen`` computes.
+
+    contents = screen.contents(sketch)                     # every genome's FULL distinct hash set, one sorted directory in HBM
+    found = screen.contained(query_sigs, contents, min_identity=0.9)       # a: query, b: genome; `identity` of each record
+    records = screen.fold(screen.contained(sigs, contents))                # a collection in itself, as triangular records
+
 The signature is that of the genome's *winnowed minimizers*, not of all its k-mers: the distances are Mash-like at the
-sketch's ``k``, not those of the Mash program.  Everything runs on the device; there is no CPU path, and without a HIP device
+sketch's ``k``, not those of the Mash program.  Everything but `fold` runs on the device; there is no CPU path, and without a HIP device
 the functions raise ``RuntimeError`` like every compute entry point.
 
 Not imported by the package itself (like `clusters` and `classify`): it needs numpy.
@@ -151,6 +159,129 @@ def pairs(a, b=None, max_distance=0.1, device=False, stats=None):
     if device:
         return out if keep.all() else out[torch.from_numpy(keep).to(out.device)]
     return records[keep]
+
+
+# ---- the containment road ----------------------------------------------------------------------------------------------
+class Contents:
+    """The contents of a collection of ``len(names)`` genomes: its distinct (hash, genome) pairs as ``hash`` and ``genome``,
+    int32 ``[m]`` each (``hash`` holds the bits of unsigned 32-bit values), in HBM and sorted by hash as unsigned, then by
+    genome -- the directory `contained` looks signatures up in -- with the genomes' ``names`` and the k-mer size ``k``."""
+
+    def __init__(self, hash, genome, names, k):
+        if hash.dim() != 1 or genome.dim() != 1 or hash.shape[0] != genome.shape[0]:
+            raise ValueError("hash and genome are [m], one of each per entry")
+        self.hash, self.genome, self.names, self.k = hash, genome, list(names), int(k)
+
+    def __len__(self):
+        return len(self.names)
+
+    @property
+    def entries(self):
+        return int(self.hash.shape[0])
+
+    @property
+    def device(self):
+        return self.hash.device
+
+
+def contents(sketch, device="cuda"):
+    """The `Contents` of every genome of ``sketch``, from the records `Sketch._export_records` copies HBM to HBM: the sketch
+    is left as it is, un-indexed.  Where a `Signatures` keeps the bottom ``size`` of a genome's hashes, this keeps them all."""
+    import torch
+    rec, (lengths, sbf, counter) = sketch._export_records(device)
+    rec = rec.contiguous()
+    n, n_records = len(sbf), int(rec.shape[1])
+    sbf = np.ascontiguousarray(sbf, dtype=np.int32)
+    ent_hash = torch.empty(n_records, dtype=torch.int32, device=rec.device)          # n_records entries always suffice
+    ent_genome = torch.empty(n_records, dtype=torch.int32, device=rec.device)
+    m = C.c_int64(0)
+    torch.cuda.synchronize(rec.device)                   # the library runs on a stream of its own: torch's writes are done
+    with torch.cuda.device(rec.device):
+        check(lib.fa_screen_contents(C.c_void_p(rec[0].data_ptr()), C.c_void_p(rec[1].data_ptr()), n_records, C.c_void_p(sbf.ctypes.data), n,
+                                     C.c_void_p(ent_hash.data_ptr()), C.c_void_p(ent_genome.data_ptr()), n_records, C.byref(m)))
+    return Contents(ent_hash[: m.value].clone(), ent_genome[: m.value].clone(), sketch.names, sketch.k)
+
+
+def containment_cutoff(min_identity, k):
+    """``(cn, cd)``: the containment of identity ``min_identity`` at k-mer size ``k``, ``min_identity ** k``, as a fraction
+    over 2**20 rounded DOWN (and one step further, for the rounding of the float64 arithmetic itself), so that the integer
+    filter of the device keeps every pair the exact float64 cut by `identity` keeps: a pair below ``cn / cd`` has a
+    containment at least 2**-20 below ``min_identity ** k``, hence (the k-th root has slope >= 1 / k on [0, 1]) an identity
+    at least 2**-20 / k below ``min_identity``, far beyond what float64 rounds."""
+    if not 0.0 <= min_identity <= 1.0:
+        raise ValueError("min_identity must be a number in [0, 1]")
+    c_min = float(min_identity) ** int(k)
+    return max(0, min(JACCARD_DENOMINATOR, int(math.floor(c_min * JACCARD_DENOMINATOR)) - 1)), JACCARD_DENOMINATOR
+
+
+def identity(records, k):
+    """``(shared / denom) ** (1 / k)`` of every record in float64 -- the identity at which a k-mer of the query survives in
+    the reference with probability ``shared / denom`` (Mash's containment index) -- and 0.0 for ``shared == 0``."""
+    records = to_records(records)
+    shared, denom = records["shared"].astype(np.float64), records["denom"].astype(np.float64)
+    out = np.zeros(len(records), dtype=np.float64)
+    some = shared > 0
+    out[some] = (shared[some] / denom[some]) ** (1.0 / float(k))
+    return out
+
+
+def contained(sigs, contents, min_identity=0.9, device=False, stats=None):
+    """The (signature of ``sigs``, genome of ``contents``) pairs of containment identity at least ``min_identity``, sorted by
+    ``(a, b)``: ``SCREEN_DTYPE`` records with ``shared`` of the signature's ``denom`` elements found in the genome, or with
+    ``device=True`` the int32 ``[n, 4]`` tensor of their words in HBM.  The device filters by the integer cut-off of
+    `containment_cutoff`, which loses nothing; the survivors are then cut exactly by `identity` in float64.  ``stats``, a
+    dict, receives ``evaluated``, ``kept`` (by the device filter) and ``visited`` (directory entries)."""
+    import torch
+    if (sigs.k, sigs.device) != (contents.k, contents.device):
+        raise ValueError("signatures and contents of different k or device do not compare")
+    cn, cd = containment_cutoff(min_identity, sigs.k)
+    sig, count = sigs.sig.contiguous(), sigs.count.contiguous()
+    ent_hash, ent_genome = contents.hash.contiguous(), contents.genome.contiguous()
+    head = (C.c_void_p(sig.data_ptr()), C.c_void_p(count.data_ptr()), len(sigs), sigs.size, C.c_void_p(ent_hash.data_ptr()),
+            C.c_void_p(ent_genome.data_ptr()), contents.entries, len(contents), cn, cd)
+    n, counters = C.c_int64(-1), (C.c_int64 * 3)()
+    cap = min(len(sigs) * len(contents), max(4096, 16 * (len(sigs) + len(contents))))      # a screen keeps few pairs: one pass is the rule
+    torch.cuda.synchronize(sigs.device)
+    with torch.cuda.device(sigs.device):
+        out = torch.empty((cap, 4), dtype=torch.int32, device=sigs.device)
+        code = lib.fa_screen_contained(*head, C.c_void_p(out.data_ptr()), cap, C.byref(n), 1, counters)
+        if code == FA_ERR_INVALID and n.value > cap:                  # the buffer was short, and n is what it takes
+            out = torch.empty((n.value, 4), dtype=torch.int32, device=sigs.device)
+            torch.cuda.synchronize(sigs.device)
+            code = lib.fa_screen_contained(*head, C.c_void_p(out.data_ptr()), n.value, C.byref(n), 1, counters)
+        check(code)
+        out = out[: n.value]
+    if stats is not None:
+        stats.update(evaluated=counters[0], kept=counters[1], visited=counters[2])
+    records = to_records(out)
+    keep = identity(records, sigs.k) >= float(min_identity)
+    if device:
+        return out if keep.all() else out[torch.from_numpy(keep).to(out.device)]
+    return records[keep]
+
+
+def fold(records):
+    """The records of a collection contained in itself (`contained` of its own signatures) as triangular records `groups`
+    takes: ``a == b`` is dropped, and of the two directions of an unordered pair the one with the larger ``shared / denom``
+    is kept (compared by integer cross-multiplication; on a tie the record whose own ``a < b``), written as
+    ``(min, max, shared, denom)`` and sorted by ``(a, b)``.  On the host, with numpy."""
+    records = to_records(records)
+    records = records[records["a"] != records["b"]]
+    lo, hi = np.minimum(records["a"], records["b"]), np.maximum(records["a"], records["b"])
+    forward = records["a"] < records["b"]
+    order = np.lexsort((~forward, hi, lo))                            # by (lo, hi), the record whose own a < b first
+    records, lo, hi = records[order], lo[order], hi[order]
+    first = np.ones(len(records), dtype=bool)
+    first[1:] = (lo[1:] != lo[:-1]) | (hi[1:] != hi[:-1])
+    take = np.nonzero(first)[0]
+    other = np.minimum(take + 1, len(records) - 1)
+    paired = (other != take) & ~first[other]                          # the pair has a second record, right behind the first
+    s0, d0 = records["shared"][take].astype(np.int64), records["denom"][take].astype(np.int64)
+    s1, d1 = records["shared"][other].astype(np.int64), records["denom"][other].astype(np.int64)
+    take = np.where(paired & (s1 * d0 > s0 * d1), other, take)        # the second only when strictly larger
+    out = np.zeros(len(take), dtype=SCREEN_DTYPE)
+    out["a"], out["b"], out["shared"], out["denom"] = lo[take], hi[take], records["shared"][take], records["denom"][take]
+    return out
 
 
 def groups(records, n, max_distance=None, k=None):
