@@ -520,6 +520,30 @@ int fa_screen_contain_slice(int32_t *slice);
 int fa_screen_contained(const uint32_t *d_sig, const int32_t *d_count, int32_t n_a, int32_t s, const uint32_t *d_ent_hash,
                         const int32_t *d_ent_genome, int64_t n_entries, int32_t n_b, int32_t cn, int32_t cd, fa_screen_pair *pairs,
                         int64_t cap, int64_t *n_pairs, int pairs_device, int64_t *stats);
+/* Winner take all: fa_screen_contained with every element of a query credited to ONE reference, so that of a species'
+ * many strains the one that explains the query best keeps its containment and the others fall to what they alone explain.
+ * This is the library's integer restatement of `mash screen -w`, over the winnowed minimizers like everything here; it has
+ * not been checked against the Mash program.  weight[b] >= 0 is per reference; d_weight == NULL: every weight is 0.
+ *   1. First pass.  first[b] = the number of x in A with an entry (x, b): the `shared` of fa_screen_contained, over all the
+ *      references of the collection.
+ *   2. Winner.  For every x in A with at least one entry, winner(x) is the reference with the largest first[b] among those
+ *      that have an entry (x, b) -- whether they pass the cut-off or not; ties go to the largest weight[b], remaining ties
+ *      to the smallest b.  denom is the same for every b, so comparing first[] compares the identities exactly: integers only.
+ *   3. Statistic.  won[b] = the number of x in A with winner(x) == b; denom = count_a.  The won[b] of a query sum to the
+ *      number of its elements that occur anywhere in the collection.
+ *   4. Filter and output.  Those of fa_screen_contained with `won` in the place of `shared`: kept iff denom > 0 and
+ *      (int64_t)won * cd >= (int64_t)cn * denom, so cn == 0 keeps the references with won == 0; records {a, b, won, denom}
+ *      sorted by (a, b); the same input gives the same bytes on every run.
+ * Everything else is fa_screen_contained's contract: the pointers, counting only, a short `cap`, the causes of
+ * FA_ERR_INVALID with nothing written -- and a negative weight is one more.  stats[0] is n_a * n_b, [1] the records kept,
+ * [2] the directory entries visited by the first pass (the sum of first[], fa_screen_contained's [2]), [3] the elements
+ * assigned (the sum of won[]): stats has four entries. */
+int fa_screen_contained_winner(const uint32_t *d_sig, const int32_t *d_count, int32_t n_a, int32_t s, const uint32_t *d_ent_hash,
+                               const int32_t *d_ent_genome, int64_t n_entries, int32_t n_b, const int32_t *d_weight, int32_t cn,
+                               int32_t cd, fa_screen_pair *pairs, int64_t cap, int64_t *n_pairs, int pairs_device, int64_t *stats);
+/* development: the threads of a workgroup of fa_screen_contained_winner's first kernel, 512 or 1024 (0: the default), for
+ * the process; the results do not depend on it (scripts/time_contain_winner.py times both); host only */
+int fa_debug_contain_winner_threads(int32_t threads);
 
 /* stage-level introspection used by the parity tests */
 int fa_mapper_debug_mappings(fa_mapper *m, fa_mapping *out, int64_t cap, int64_t *n); /* L2 results of the last query call, under its rules */

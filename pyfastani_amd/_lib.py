@@ -190,6 +190,8 @@ SIGNATURES = {
     "fa_screen_contents": (_i32, [_vp, _vp, _i64, _vp, _i32, _vp, _vp, _i64, _P(_i64)]),
     "fa_screen_contain_slice": (_i32, [_P(_i32)]),
     "fa_screen_contained": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _i64, _P(_i64), _i32, _vp]),
+    "fa_screen_contained_winner": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _i64, _i32, _vp, _i32, _i32, _vp, _i64, _P(_i64), _i32, _vp]),
+    "fa_debug_contain_winner_threads": (_i32, [_i32]),
     "fa_mapper_debug_mappings": (_i32, [_vp, _vp, _i64, _P(_i64)]),
     "fa_mapper_debug_l1": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _P(_i64)]),
     "fa_mapper_debug_query_sketch": (_i32, [_vp, _i64, _vp, _i32, _P(_i32)]),

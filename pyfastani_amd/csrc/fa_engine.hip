@@ -557,7 +557,22 @@ int fa_screen_contained(const uint32_t *d_sig, const int32_t *d_count, int32_t n
                         const int32_t *d_ent_genome, int64_t n_entries, int32_t n_b, int32_t cn, int32_t cd, fa_screen_pair *pairs,
                         int64_t cap, int64_t *n_pairs, int pairs_device, int64_t *stats) {
   return guarded([&] {
-    screen_contained(d_sig, d_count, n_a, s, d_ent_hash, d_ent_genome, n_entries, n_b, cn, cd, pairs, cap, n_pairs, pairs_device != 0, stats);
+    screen_contained(d_sig, d_count, n_a, s, d_ent_hash, d_ent_genome, n_entries, n_b, false, nullptr, cn, cd, pairs, cap, n_pairs,
+                     pairs_device != 0, stats);
+  });
+}
+int fa_screen_contained_winner(const uint32_t *d_sig, const int32_t *d_count, int32_t n_a, int32_t s, const uint32_t *d_ent_hash,
+                               const int32_t *d_ent_genome, int64_t n_entries, int32_t n_b, const int32_t *d_weight, int32_t cn, int32_t cd,
+                               fa_screen_pair *pairs, int64_t cap, int64_t *n_pairs, int pairs_device, int64_t *stats) {
+  return guarded([&] {
+    screen_contained(d_sig, d_count, n_a, s, d_ent_hash, d_ent_genome, n_entries, n_b, true, d_weight, cn, cd, pairs, cap, n_pairs,
+                     pairs_device != 0, stats);
+  });
+}
+int fa_debug_contain_winner_threads(int32_t threads) {
+  return guarded([&] {
+    FA_REQUIRE(threads == 0 || threads == 512 || threads == 1024, FA_ERR_INVALID, "512 or 1024 threads, or 0 for the default");
+    g_winner_threads.store(threads ? threads : WIN_THREADS);
   });
 }
 int fa_mapper_set_mapping_stage(fa_mapper *m, int64_t records) {

@@ -559,9 +559,14 @@ inline void screen_contents(const uint32_t *d_hash, const int32_t *d_seq_id, int
   FA_HIP(hipStreamSynchronize(st));
 }
 
+// the threads of a k_contain_winner workgroup, 512 or 1024: WIN_THREADS unless fa_debug_contain_winner_threads has set the other
+inline std::atomic<int> g_winner_threads{WIN_THREADS};
+
+// fa_screen_contained, and with `winner` fa_screen_contained_winner (d_weight: its optional weights): the same call but for the
+// statistic the records carry -- the elements a reference holds, or those it wins
 inline void screen_contained(const uint32_t *d_sig, const int32_t *d_count, int32_t n_a, int32_t s, const uint32_t *d_ent_hash,
-                             const int32_t *d_ent_genome, int64_t n_entries, int32_t n_b, int32_t cn, int32_t cd, fa_screen_pair *pairs,
-                             int64_t cap, int64_t *n_pairs, bool pairs_device, int64_t *stats) {
+                             const int32_t *d_ent_genome, int64_t n_entries, int32_t n_b, bool winner, const int32_t *d_weight, int32_t cn,
+                             int32_t cd, fa_screen_pair *pairs, int64_t cap, int64_t *n_pairs, bool pairs_device, int64_t *stats) {
   FA_REQUIRE(s >= 1 && s <= SCR_MAX_S, FA_ERR_INVALID, "the signature size must be in [1, 4096]");
   FA_REQUIRE(cd >= 1 && cn >= 0 && cn <= cd, FA_ERR_INVALID, "the containment cut-off needs 0 <= cn <= cd and cd >= 1");
   FA_REQUIRE(n_a >= 0 && n_b >= 0 && n_entries >= 0, FA_ERR_INVALID, "negative number of genomes or entries");
@@ -577,13 +582,15 @@ inline void screen_contained(const uint32_t *d_sig, const int32_t *d_count, int3
   StatusBlock<ContainStatus> d_status(st);
   DevBuf<int32_t> group_count;
   DevBuf<int64_t> group_off;
+  DevBuf<int32_t> winners;
 
   ContainArgs a{};
+  a.weight = winner ? d_weight : nullptr;
   a.sig = d_sig; a.count = d_count; a.n_a = n_a; a.s = s;
   a.ent_hash = d_ent_hash; a.ent_genome = d_ent_genome; a.m = n_entries; a.n_b = n_b; a.n_slices = (int32_t)n_slices;
   a.cn = cn; a.cd = cd; a.status = d_status.p;
   ContainStatus status{};
-  const int64_t to_check = std::max((int64_t)n_a * s, n_entries);
+  const int64_t to_check = std::max({(int64_t)n_a * s, n_entries, a.weight ? (int64_t)n_b : (int64_t)0});
   if (to_check) {
     // the verdict on both inputs is read before a counting kernel is launched: those rely on it
     hipLaunchKernelGGL(k_contain_check, dim3((unsigned)std::min<int64_t>((to_check + 255) / 256, 1 << 20)), dim3(256), 0, st, a);
@@ -593,13 +600,17 @@ inline void screen_contained(const uint32_t *d_sig, const int32_t *d_count, int3
     FA_REQUIRE(!(status.flags & SCR_NOT_ASCENDING), FA_ERR_INVALID, "a signature does not ascend strictly below its count");
     FA_REQUIRE(!(status.flags & TAB_BAD_ID), FA_ERR_INVALID, "an entry names a genome outside [0, n_b)");
     FA_REQUIRE(!(status.flags & CNT_UNORDERED), FA_ERR_INVALID, "the entries do not ascend strictly by (hash, genome)");
+    FA_REQUIRE(!(status.flags & CNT_BAD_WEIGHT), FA_ERR_INVALID, "a weight is negative");
   }
   // the COUNT or the WRITE form; elements of A a thread searches at a time: as many chains as a signature of size s gives a
   // thread of CNT_THREADS, four at the most (not measured yet: scripts/time_contain.py)
   const size_t lds = (size_t)((std::min<int64_t>(n_b, CNT_SLICE) + 1) / 2) * sizeof(uint32_t);
   auto launch = [&](bool write) {
     const dim3 grid((unsigned)n_groups), block(CNT_THREADS);
-    if (s <= CNT_THREADS) {
+    if (winner) {
+      if (write) hipLaunchKernelGGL(k_contain_won<true>, grid, block, lds, st, a);
+      else hipLaunchKernelGGL(k_contain_won<false>, grid, block, lds, st, a);
+    } else if (s <= CNT_THREADS) {
       if (write) hipLaunchKernelGGL((k_contain<1, true>), grid, block, lds, st, a);
       else hipLaunchKernelGGL((k_contain<1, false>), grid, block, lds, st, a);
     } else if (s <= 2 * CNT_THREADS) {
@@ -613,6 +624,28 @@ inline void screen_contained(const uint32_t *d_sig, const int32_t *d_count, int3
   if (n_a && n_b) {
     group_count.ensure((size_t)n_groups); group_off.ensure((size_t)n_groups);
     a.group_count = group_count.p; a.group_off = group_off.p;
+    if (winner) {
+      // every element's winner, once for both forms: one workgroup per query, the slices' counters and 20 bytes per element
+      // of the signature in LDS -- beyond 64 KiB for a large collection, one workgroup per CU either way
+      winners.ensure((size_t)n_a * (size_t)s);
+      a.winner = winners.p;
+      const size_t lds_w = lds + (size_t)s * 20;
+      const int threads = g_winner_threads.load();
+      auto go = [&](auto kernel) {
+        if (lds_w > 64 * 1024) FA_HIP(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_w));
+        hipLaunchKernelGGL(kernel, dim3((unsigned)n_a), dim3((unsigned)threads), lds_w, st, a);
+      };
+      const int chains = (s + threads - 1) / threads;                 // searches a thread has in flight, four at the most
+      if (threads == 512) {
+        if (chains <= 1) go(k_contain_winner<512, 1>);
+        else if (chains <= 2) go(k_contain_winner<512, 2>);
+        else go(k_contain_winner<512, 4>);
+      } else {
+        if (chains <= 1) go(k_contain_winner<1024, 1>);
+        else if (chains <= 2) go(k_contain_winner<1024, 2>);
+        else go(k_contain_winner<1024, 4>);
+      }
+    }
     launch(false);
     hipLaunchKernelGGL(k_chunk_scan, dim3(1), dim3(1024), 0, st, a.group_count, a.group_off, (int32_t)n_groups, &d_status.p->emitted);
     FA_HIP(hipGetLastError());
@@ -633,6 +666,7 @@ inline void screen_contained(const uint32_t *d_sig, const int32_t *d_count, int3
     stats[0] = (int64_t)n_a * (int64_t)n_b;
     stats[1] = n_emit;
     stats[2] = (int64_t)status.visited;
+    if (winner) stats[3] = (int64_t)status.assigned;
   }
 }
 

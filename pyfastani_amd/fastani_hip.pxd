@@ -206,3 +206,6 @@ cdef extern from "fastani_hip.h" nogil:
     int fa_screen_contained(const uint32_t* d_sig, const int32_t* d_count, int32_t n_a, int32_t s, const uint32_t* d_ent_hash,
                             const int32_t* d_ent_genome, int64_t n_entries, int32_t n_b, int32_t cn, int32_t cd, fa_screen_pair* pairs,
                             int64_t cap, int64_t* n_pairs, int pairs_device, int64_t* stats)
+    int fa_screen_contained_winner(const uint32_t* d_sig, const int32_t* d_count, int32_t n_a, int32_t s, const uint32_t* d_ent_hash,
+                                   const int32_t* d_ent_genome, int64_t n_entries, int32_t n_b, const int32_t* d_weight, int32_t cn,
+                                   int32_t cd, fa_screen_pair* pairs, int64_t cap, int64_t* n_pairs, int pairs_device, int64_t* stats)

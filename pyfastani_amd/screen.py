@@ -16,9 +16,16 @@ screen`` computes.
     contents = screen.contents(sketch)                     # every genome's FULL distinct hash set, one sorted directory in HBM
     found = screen.contained(query_sigs, contents, min_identity=0.9)       # a: query, b: genome; `identity` of each record
     records = screen.fold(screen.contained(sigs, contents))                # a collection in itself, as triangular records
+    one = screen.contained(query_sigs, contents, winner_take_all=True, weights="length")     # every hash credited to ONE genome
 
-The signature is that of the genome's *winnowed minimizers*, not of all its k-mers: the distances are Mash-like at the
-sketch's ``k``, not those of the Mash program.  Everything but `fold` runs on the device; there is no CPU path, and without a HIP device
+A query of a well-sampled species is contained in every one of its strains.  With ``winner_take_all`` every hash of the query
+is credited to one genome only -- of those that hold it the one holding the most of the query's hashes (``first``, the plain
+``shared``); ties go to the larger weight, then to the smaller genome number -- and a record carries what its genome *won*:
+redundant relatives fall to what they alone explain and drop below the cut-off.  The rule is this library's integer
+restatement of ``mash screen -w`` (``fa_screen_contained_winner``); it has not been checked against the Mash program.
+
+The signature is that of the genome's *winnowed minimizers*, not of all its k-mers, and so is every statistic here, the
+winner-take-all one included: the distances are Mash-like at the sketch's ``k``, not those of the Mash program.  Everything but `fold` runs on the device; there is no CPU path, and without a HIP device
 the functions raise ``RuntimeError`` like every compute entry point.
 
 Not imported by the package itself (like `clusters` and `classify`): it needs numpy.
@@ -165,12 +172,17 @@ def pairs(a, b=None, max_distance=0.1, device=False, stats=None):
 class Contents:
     """The contents of a collection of ``len(names)`` genomes: its distinct (hash, genome) pairs as ``hash`` and ``genome``,
     int32 ``[m]`` each (``hash`` holds the bits of unsigned 32-bit values), in HBM and sorted by hash as unsigned, then by
-    genome -- the directory `contained` looks signatures up in -- with the genomes' ``names`` and the k-mer size ``k``."""
+    genome -- the directory `contained` looks signatures up in -- with the genomes' ``names`` and the k-mer size ``k``.
+    ``lengths``, when known, is every genome's total length as numpy int64 -- as the sketch counts it, every contig in whole
+    fragments -- the weights ``"length"`` of `contained`."""
 
-    def __init__(self, hash, genome, names, k):
+    def __init__(self, hash, genome, names, k, lengths=None):
         if hash.dim() != 1 or genome.dim() != 1 or hash.shape[0] != genome.shape[0]:
             raise ValueError("hash and genome are [m], one of each per entry")
         self.hash, self.genome, self.names, self.k = hash, genome, list(names), int(k)
+        self.lengths = None if lengths is None else np.ascontiguousarray(lengths).astype(np.int64)
+        if self.lengths is not None and self.lengths.shape != (len(self.names),):
+            raise ValueError("there is one length per genome")
 
     def __len__(self):
         return len(self.names)
@@ -199,7 +211,7 @@ def contents(sketch, device="cuda"):
     with torch.cuda.device(rec.device):
         check(lib.fa_screen_contents(C.c_void_p(rec[0].data_ptr()), C.c_void_p(rec[1].data_ptr()), n_records, C.c_void_p(sbf.ctypes.data), n,
                                      C.c_void_p(ent_hash.data_ptr()), C.c_void_p(ent_genome.data_ptr()), n_records, C.byref(m)))
-    return Contents(ent_hash[: m.value].clone(), ent_genome[: m.value].clone(), sketch.names, sketch.k)
+    return Contents(ent_hash[: m.value].clone(), ent_genome[: m.value].clone(), sketch.names, sketch.k, lengths)
 
 
 def containment_cutoff(min_identity, k):
@@ -225,34 +237,66 @@ def identity(records, k):
     return out
 
 
-def contained(sigs, contents, min_identity=0.9, device=False, stats=None):
+def _winner_weights(weights, contents):
+    """``weights`` of `contained` as contiguous int32 numpy, one per genome of ``contents``"""
+    if isinstance(weights, str):
+        if weights != "length":
+            raise ValueError('weights are a sequence of integers, or "length"')
+        if contents.lengths is None:
+            raise ValueError("these contents do not know their genomes' lengths")
+        return np.minimum(contents.lengths, np.iinfo(np.int32).max).astype(np.int32)
+    values = np.asarray(weights.cpu() if hasattr(weights, "cpu") else weights)
+    if values.shape != (len(contents),) or not (np.issubdtype(values.dtype, np.integer) or values.size == 0):
+        raise ValueError("weights are one integer per genome of the contents")
+    if values.size and (int(values.min()) < 0 or int(values.max()) > np.iinfo(np.int32).max):
+        raise ValueError("a weight is an integer in [0, 2**31 - 1]")
+    return np.ascontiguousarray(values, dtype=np.int32)
+
+
+def contained(sigs, contents, min_identity=0.9, device=False, stats=None, winner_take_all=False, weights=None):
     """The (signature of ``sigs``, genome of ``contents``) pairs of containment identity at least ``min_identity``, sorted by
     ``(a, b)``: ``SCREEN_DTYPE`` records with ``shared`` of the signature's ``denom`` elements found in the genome, or with
     ``device=True`` the int32 ``[n, 4]`` tensor of their words in HBM.  The device filters by the integer cut-off of
     `containment_cutoff`, which loses nothing; the survivors are then cut exactly by `identity` in float64.  ``stats``, a
-    dict, receives ``evaluated``, ``kept`` (by the device filter) and ``visited`` (directory entries)."""
+    dict, receives ``evaluated``, ``kept`` (by the device filter) and ``visited`` (directory entries).
+
+    With ``winner_take_all`` every element of a signature is credited to one genome only (the module docstring has the rule)
+    and ``shared`` is what the genome won; ``stats`` also receives ``assigned``, the elements that found a genome.
+    ``weights`` break the ties of that rule: ``None`` (none), one non-negative integer per genome (a sequence, numpy or a
+    tensor), or ``"length"`` for ``contents.lengths`` clipped to int32 -- Mash's own tie rule, the longer reference."""
     import torch
     if (sigs.k, sigs.device) != (contents.k, contents.device):
         raise ValueError("signatures and contents of different k or device do not compare")
+    if weights is not None and not winner_take_all:
+        raise ValueError("weights break the ties of winner_take_all and mean nothing without it")
+    if weights is not None:
+        weights = _winner_weights(weights, contents)
     cn, cd = containment_cutoff(min_identity, sigs.k)
     sig, count = sigs.sig.contiguous(), sigs.count.contiguous()
     ent_hash, ent_genome = contents.hash.contiguous(), contents.genome.contiguous()
     head = (C.c_void_p(sig.data_ptr()), C.c_void_p(count.data_ptr()), len(sigs), sigs.size, C.c_void_p(ent_hash.data_ptr()),
             C.c_void_p(ent_genome.data_ptr()), contents.entries, len(contents), cn, cd)
-    n, counters = C.c_int64(-1), (C.c_int64 * 3)()
+    call = lib.fa_screen_contained
+    if winner_take_all:
+        call = lib.fa_screen_contained_winner
+        d_weights = None if weights is None else torch.from_numpy(weights).to(sigs.device)
+        head = head[:8] + (None if d_weights is None or not len(contents) else C.c_void_p(d_weights.data_ptr()),) + head[8:]
+    n, counters = C.c_int64(-1), (C.c_int64 * 4)()
     cap = min(len(sigs) * len(contents), max(4096, 16 * (len(sigs) + len(contents))))      # a screen keeps few pairs: one pass is the rule
     torch.cuda.synchronize(sigs.device)
     with torch.cuda.device(sigs.device):
         out = torch.empty((cap, 4), dtype=torch.int32, device=sigs.device)
-        code = lib.fa_screen_contained(*head, C.c_void_p(out.data_ptr()), cap, C.byref(n), 1, counters)
+        code = call(*head, C.c_void_p(out.data_ptr()), cap, C.byref(n), 1, counters)
         if code == FA_ERR_INVALID and n.value > cap:                  # the buffer was short, and n is what it takes
             out = torch.empty((n.value, 4), dtype=torch.int32, device=sigs.device)
             torch.cuda.synchronize(sigs.device)
-            code = lib.fa_screen_contained(*head, C.c_void_p(out.data_ptr()), n.value, C.byref(n), 1, counters)
+            code = call(*head, C.c_void_p(out.data_ptr()), n.value, C.byref(n), 1, counters)
         check(code)
         out = out[: n.value]
     if stats is not None:
         stats.update(evaluated=counters[0], kept=counters[1], visited=counters[2])
+        if winner_take_all:
+            stats.update(assigned=counters[3])
     records = to_records(out)
     keep = identity(records, sigs.k) >= float(min_identity)
     if device:
