@@ -402,6 +402,40 @@ int fa_table_representatives(const fa_cgi_row *rows, int64_t n_rows, int rows_de
                              const uint64_t *query_lengths, const uint64_t *reference_lengths, const fa_table_params *p,
                              const int32_t *order, int32_t *labels, double *identity, int out_device,
                              int32_t *n_representatives, int64_t *stats);
+/* Average-linkage (UPGMA) clusters of the table at one cut-off -- dRep's default for both of its steps, and what is run on
+ * FastANI's matrix output with scipy's linkage(method="average") and fcluster(criterion="distance"): unlike the connected
+ * components it does not chain, and unlike the representatives it does not depend on an order the caller brings.
+ *   1. Filter and pair: steps 1-2 above.  A pair is PRESENT iff it exists after the filter and, with reciprocal != 0, has
+ *      both directions.
+ *   2. Weight.  A present pair's weight is w = rint(identity * 2^20) as int64, ties to even, identity being the pair's float64
+ *      symmetric identity: exact for what FastANI reports (a float32 at or above 16 is a multiple of 2^-19, a mean of two a
+ *      multiple of 2^-20).  `missing` is the identity assumed for every pair that is not present (dRep: 0; or the floor
+ *      below which FastANI reports nothing): qm = rint((double)missing * 2^20).  qc = rint((double)min_identity * 2^20).
+ *   3. State.  A cluster's label is its smallest genome number; every genome starts alone.  For two clusters A and B, c(A,B)
+ *      is the number of present pairs between them, S(A,B) = sum of their w + qm * (|A||B| - c(A,B)), and the average is
+ *      S(A,B) / (|A||B|).  Only cluster pairs with c > 0 are candidates.
+ *   4. Order.  Candidate (A,B) comes before (C,D) iff its average is larger, compared exactly as S(A,B) * |C||D| against
+ *      S(C,D) * |A||B| in integers (128 bits; never float64); ties go to the smaller min(label), then to the smaller max(label).
+ *   5. Merge.  While the first candidate in that order has S >= qc * |A||B|, merge it: sums and counts add, the label is the
+ *      smaller one.
+ *   6. Result.  labels[g] is the label of g's cluster, *n_clusters the number of g with labels[g] == g.  The same input gives
+ *      the same bytes on every run.  (The library merges every mutual first pair of a round at once; the labels are those of
+ *      the sequential walk.)
+ *   7. FA_ERR_INVALID with nothing written, the out-parameters included: everything fa_table_clusters rejects; min_identity
+ *      or missing negative or NaN; missing >= min_identity, compared as qm >= qc; a present pair whose identity is NaN or
+ *      outside [0, 128].  n_genomes > 2^18 is FA_ERR_UNSUPPORTED: S stays below 2^62 and the cross products below 2^128.
+ * labels [n_genomes] is a DEVICE pointer when labels_device != 0.  n_clusters and stats may be NULL; stats[0] surviving rows,
+ * [1] pairs, [2] present pairs, [3] rounds (those that merged a pair: at most n_genomes - 1; a block of exactly tied genomes
+ * merges one pair per round), [4] merges = n_genomes - *n_clusters.  Runs like fa_table_clusters: on the calling thread's
+ * current device, on a stream of its own, with memory from the device pool, finished when it returns, FA_ERR_NO_DEVICE
+ * without a device.  Only the partition at one cut-off is returned: no merge list, no tree. */
+int fa_table_linkage(const fa_cgi_row *rows, int64_t n_rows, int rows_device, int32_t n_genomes, const uint64_t *query_lengths,
+                     const uint64_t *reference_lengths, const fa_table_params *p, float missing, int32_t *labels, int labels_device,
+                     int32_t *n_clusters, int64_t *stats);
+/* The order of step 4 on two candidates a and b = {S, |A||B|, lo, hi} (S >= 0, |A||B| >= 1, labels >= 0, else
+ * FA_ERR_INVALID): *first = 1 when a comes before b, 0 when b comes before a, 2 when they are equal.  Host only; it calls the
+ * comparator the kernels use. */
+int fa_debug_linkage_order(const int64_t a[4], const int64_t b[4], int *first);
 
 /* ---- a query x reference hit table, reduced to every query's k best hits ---- */
 /* What a batch of queries is mapped against a reference database for: per query, the closest references that pass an identity

@@ -182,6 +182,8 @@ SIGNATURES = {
     "fa_table_pairs": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _P(TableParams), _vp, _i64, _P(_i64), _i32]),
     "fa_table_clusters": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _P(TableParams), _vp, _i32, _P(_i32), _vp]),
     "fa_table_representatives": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _P(TableParams), _vp, _vp, _vp, _i32, _P(_i32), _vp]),
+    "fa_table_linkage": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _P(TableParams), _f32, _vp, _i32, _P(_i32), _vp]),
+    "fa_debug_linkage_order": (_i32, [_P(_i64), _P(_i64), _P(_i32)]),
     "fa_table_best": (_i32, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _P(BestParams), _vp, _vp, _i64, _P(_i64), _i32, _vp]),
     "fa_screen_tile": (_i32, [_i32, _P(_i32)]),
     "fa_screen_signatures": (_i32, [_vp, _vp, _i64, _vp, _i32, _i32, _vp, _vp]),

@@ -1,6 +1,6 @@
 """What an all-vs-all is run for, computed where the hit table already is: the symmetric identity of every genome pair and
 the groups of genomes above a cut-off (species clusters at 95 %, dereplication at 99 %), by ``fa_table_pairs`` /
-``fa_table_clusters`` / ``fa_table_representatives`` of the library (include/fastani_hip.h has the semantics; upstream's counterpart is the matrix output,
+``fa_table_clusters`` / ``fa_table_representatives`` / ``fa_table_linkage`` of the library (include/fastani_hip.h has the semantics; upstream's counterpart is the matrix output,
 `outputPhylip`, include/fastani/cgi/compute_core_identity.pxd:39-51 of the reference, and whatever the user clusters it with).
 
 The rows are one genome set mapped against itself: ``query_id`` and ``ref_genome_id`` index the same list of ``n`` genomes,
@@ -100,6 +100,33 @@ def clusters(rows, query_lengths, reference_lengths, fragment_length, minimum_fr
             check(lib.fa_table_clusters(*t.head(), C.c_void_p(labels.ctypes.data), 0, C.byref(n_clusters), counters))
     if stats is not None:
         stats.update(rows=counters[0], pairs=counters[1], edges=counters[2], rounds=counters[3], n_clusters=n_clusters.value)
+    return labels
+
+
+def average_linkage(rows, query_lengths, reference_lengths, fragment_length, minimum_fraction=0.2, min_identity=95.0, reciprocal=False,
+                    missing=0.0, stats=None):
+    """Average-linkage (UPGMA) ANI clusters at the cut-off ``min_identity`` (``fa_table_linkage``): the two clusters with the
+    largest mean identity over all their genome pairs are merged while that mean is at least ``min_identity``.  A pair
+    without a row that passes the filter (with ``reciprocal``: in both directions) counts as ``missing`` -- 0 as in dRep, or
+    the floor below which nothing is reported; it must lie below ``min_identity``.  Unlike single linkage the clusters do not
+    chain, and unlike `representatives` they do not depend on an order.  Means are compared exactly (fixed point, integers);
+    ties go to the pair with the smaller genome numbers.  Returns ``labels``, int32 ``[n]``: the smallest genome number of
+    every genome's cluster -- numpy for ``ROW_DTYPE`` rows, a tensor on the rows' device for device rows.  ``stats``, a dict,
+    receives ``rows``, ``pairs``, ``present``, ``rounds``, ``merges`` and ``n_clusters``.  Only this partition is returned:
+    no tree.  A negative or NaN ``min_identity`` or ``missing``, or an identity outside [0, 128], raises ``ValueError``; more
+    than 2^18 genomes ``NotImplementedError``."""
+    t = _Table(rows, query_lengths, reference_lengths, fragment_length, minimum_fraction, min_identity, reciprocal)
+    n_clusters, counters = C.c_int32(0), (C.c_int64 * 5)()
+    with t.on_device():
+        if t.torch:
+            labels = t.torch.empty(t.n, dtype=t.torch.int32, device=t.device)
+            check(lib.fa_table_linkage(*t.head(), float(missing), C.c_void_p(labels.data_ptr()), 1, C.byref(n_clusters), counters))
+        else:
+            labels = np.empty(t.n, dtype=np.int32)
+            check(lib.fa_table_linkage(*t.head(), float(missing), C.c_void_p(labels.ctypes.data), 0, C.byref(n_clusters), counters))
+    if stats is not None:
+        stats.update(rows=counters[0], pairs=counters[1], present=counters[2], rounds=counters[3], merges=counters[4],
+                     n_clusters=n_clusters.value)
     return labels
 
 

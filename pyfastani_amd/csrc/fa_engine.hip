@@ -514,6 +514,27 @@ int fa_table_representatives(const fa_cgi_row *rows, int64_t n_rows, int rows_de
     table_reduce(rows, n_rows, rows_device != 0, n_genomes, query_lengths, reference_lengths, p, want);
   });
 }
+int fa_table_linkage(const fa_cgi_row *rows, int64_t n_rows, int rows_device, int32_t n_genomes, const uint64_t *query_lengths,
+                     const uint64_t *reference_lengths, const fa_table_params *p, float missing, int32_t *labels, int labels_device,
+                     int32_t *n_clusters, int64_t *stats) {
+  return guarded([&] {
+    TableRequest want;
+    want.clusters = want.linkage = true;
+    want.missing = missing;
+    want.labels = labels; want.labels_device = labels_device != 0; want.n_clusters = n_clusters; want.stats = stats;
+    table_reduce(rows, n_rows, rows_device != 0, n_genomes, query_lengths, reference_lengths, p, want);
+  });
+}
+int fa_debug_linkage_order(const int64_t a[4], const int64_t b[4], int *first) {
+  return guarded([&] {
+    FA_REQUIRE(a && b && first, FA_ERR_INVALID, "null candidate or destination");
+    FA_REQUIRE(a[0] >= 0 && b[0] >= 0 && a[1] >= 1 && b[1] >= 1, FA_ERR_INVALID, "a candidate has S >= 0 and |A||B| >= 1");
+    FA_REQUIRE(a[2] >= 0 && a[2] <= INT32_MAX && a[3] >= 0 && a[3] <= INT32_MAX && b[2] >= 0 && b[2] <= INT32_MAX && b[3] >= 0 &&
+                   b[3] <= INT32_MAX, FA_ERR_INVALID, "a label is a genome number");
+    const LinkCand x{a[0], a[1], (int32_t)a[2], (int32_t)a[3]}, y{b[0], b[1], (int32_t)b[2], (int32_t)b[3]};
+    *first = link_order(x, y);
+  });
+}
 int fa_table_best(const fa_cgi_row *rows, int64_t n_rows, int rows_device, int32_t n_queries, int32_t n_references,
                   const uint64_t *query_lengths, const uint64_t *reference_lengths, const fa_best_params *p, fa_cgi_row *best,
                   int64_t *offsets, int64_t cap, int64_t *n_best, int out_device, int64_t *stats) {

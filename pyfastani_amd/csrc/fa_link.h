@@ -1,0 +1,71 @@
+// fa_link.h -- the integer arithmetic of average-linkage clustering (fa_table_linkage, fa_linkage.hip.h): plain C++, no HIP.
+// The kernels and fa_debug_linkage_order call the same functions, so the exactness of the order is testable without a GPU.
+//
+// Identities are fixed point, 20 fractional bits: w = rint(identity * 2^20), ties to even.  A float32 at or above 16 is a
+// multiple of 2^-19, so the float64 mean of two of them is a multiple of 2^-20 and the conversion is exact for everything
+// FastANI reports.  A candidate is a pair of clusters {A, B} with
+//     s = sum of w over the present pairs between them + qm * (|A||B| - their number),     n = |A||B|,
+// and its average is s / n.  With at most 2^18 genomes n <= 2^34 and, w being at most 128 * 2^20, s <= 2^61: the cross
+// products that compare two averages stay below 2^96 and are taken in 128 bits.  No floating point decides an order.
+#pragma once
+
+#include <cmath>
+#include <cstdint>
+
+#if defined(__HIPCC__)
+#define FA_LINK_FN __host__ __device__ inline
+#else
+#define FA_LINK_FN inline
+#endif
+
+namespace fa {
+
+constexpr int32_t LINK_MAX_GENOMES = 1 << 18;
+constexpr double LINK_SCALE = 1048576.0;                   // 2^20
+constexpr double LINK_MAX_IDENTITY = 128.0;
+constexpr long long LINK_MAX_W = 128LL << 20;
+
+// the sum over the present pairs between two clusters and their number: what a merge adds up
+struct LinkSum {
+  long long w, c;
+};
+struct LinkSumPlus {
+  FA_LINK_FN LinkSum operator()(const LinkSum &x, const LinkSum &y) const { return LinkSum{x.w + y.w, x.c + y.c}; }
+};
+
+// a candidate under the order of step 4; n == 0 stands for "none" and comes after every candidate
+struct LinkCand {
+  long long s, n;
+  int32_t lo, hi;
+};
+
+// whether an identity can be converted at all (false for NaN)
+FA_LINK_FN bool link_identity_ok(double identity) { return identity >= 0.0 && identity <= LINK_MAX_IDENTITY; }
+
+// rint(x * 2^20), ties to even; x in [0, 2^40]
+FA_LINK_FN long long link_fixed(double x) { return (long long)rint(x * LINK_SCALE); }
+
+FA_LINK_FN long long link_s(const LinkSum &sum, long long n, long long qm) { return sum.w + qm * (n - sum.c); }
+
+// s / n >= qc
+FA_LINK_FN bool link_passes(long long s, long long n, long long qc) { return s >= qc * n; }
+
+// 1: a comes before b; 0: b comes before a; 2: they are the same candidate.  Larger average first, compared as
+// a.s * b.n against b.s * a.n in 128 bits; ties to the smaller lo, then to the smaller hi.  s >= 0, n >= 1.
+FA_LINK_FN int link_order(const LinkCand &a, const LinkCand &b) {
+  const unsigned __int128 x = (unsigned __int128)(unsigned long long)a.s * (unsigned long long)b.n;
+  const unsigned __int128 y = (unsigned __int128)(unsigned long long)b.s * (unsigned long long)a.n;
+  if (x != y) return x > y ? 1 : 0;
+  if (a.lo != b.lo) return a.lo < b.lo ? 1 : 0;
+  if (a.hi != b.hi) return a.hi < b.hi ? 1 : 0;
+  return 2;
+}
+
+// the same with "none" on either side: whether b replaces a as the best so far
+FA_LINK_FN bool link_better(const LinkCand &b, const LinkCand &a) {
+  if (b.n == 0) return false;
+  if (a.n == 0) return true;
+  return link_order(b, a) == 1;
+}
+
+}  // namespace fa

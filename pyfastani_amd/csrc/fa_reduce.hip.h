@@ -1,5 +1,5 @@
 // fa_reduce.hip.h -- the host drivers of the reductions over results the mapper already holds: a hit table to pairs,
-// clusters and representatives (fa_table.hip.h, fa_represent.hip.h), to every query's k best hits (fa_best.hip.h), the
+// clusters, representatives and average-linkage clusters (fa_table.hip.h, fa_represent.hip.h, fa_linkage.hip.h), to every query's k best hits (fa_best.hip.h), the
 // signature screen (fa_screen.hip.h) and its containment road (fa_contain.hip.h).  They use nothing of the sketch, the mapper or the workspace; fa_engine.hip wraps each
 // in its extern "C" entry point.
 //
@@ -22,6 +22,7 @@
 #include "fa_best.hip.h"
 #include "fa_common.h"
 #include "fa_contain.hip.h"
+#include "fa_linkage.hip.h"
 #include "fa_order.h"
 #include "fa_represent.hip.h"
 #include "fa_screen.hip.h"
@@ -106,9 +107,75 @@ inline unsigned int representatives(const TableEdge *edges, int64_t n_edges, con
   return end.roots;
 }
 
+// The average-linkage clusters of the present pairs of a table over n_genomes > 0 genomes (fa_linkage.hip.h): labels (device)
+// receive every genome's smallest cluster member; returns the number of clusters and, in `rounds`, the rounds that merged a
+// pair.  `emit_into(keys, sums)` has k_table_write put the two directed entries of each of the n_pairs present pairs there.
+// `status` is the call's zeroed TableStatus; the stream is synchronised on return.
+template <typename Emit>
+inline unsigned int linkage(Emit emit_into, int64_t n_pairs, int32_t *labels, int32_t n_genomes, long long qm, long long qc,
+                            TableStatus *status, hipStream_t st, int64_t &rounds) {
+  FA_REQUIRE(n_pairs <= (int64_t)(1 << 30), FA_ERR_UNSUPPORTED, "more than 2^30 present pairs");
+  StatusBlock<LinkStatus> d_link(st);
+  DevBuf<unsigned long long> keys[3];         // the entries to sort, sorted, reduced to distinct keys
+  DevBuf<LinkSum> sums[3];
+  DevBuf<int32_t> words;                      // seg_start, seg_end, size, parent, best
+  DevBuf<unsigned char> temp;
+  const size_t n = (size_t)n_genomes;
+  words.ensure(n * 5);
+  LinkArgs l{};
+  l.n_genomes = n_genomes; l.bits = (int32_t)id_bits(n_genomes); l.qm = qm; l.qc = qc;
+  l.seg_start = words.p; l.seg_end = words.p + n; l.size = words.p + 2 * n; l.parent = words.p + 3 * n; l.best = words.p + 4 * n;
+  l.labels = labels; l.status = d_link.p;
+  const dim3 genome_grid(ceil_div(n_genomes, 256));
+  hipLaunchKernelGGL(k_link_init, genome_grid, dim3(256), 0, st, l);
+  rounds = 0;
+  int64_t n_in = 2 * n_pairs;
+  if (n_in) {
+    for (int i = 0; i < 3; i++) { keys[i].ensure((size_t)n_in); sums[i].ensure((size_t)n_in); }
+    emit_into(keys[0].p, sums[0].p);
+    l.keys = keys[2].p; l.sums = sums[2].p; l.next_keys = keys[0].p; l.next_sums = sums[0].p;
+    // the bits a key can have set: two genome numbers and, above them, the bit of a dropped entry
+    const unsigned end_bit = 2u * (unsigned)l.bits + 1u;
+    // a round that merges leaves one cluster fewer at least, so at most n_genomes - 1 of them merge
+    while (n_in) {
+      with_temp(temp, [&](void *t, size_t &bytes) {
+        return rocprim::radix_sort_pairs(t, bytes, keys[0].p, keys[1].p, sums[0].p, sums[1].p, (size_t)n_in, 0u, end_bit, st);
+      });
+      with_temp(temp, [&](void *t, size_t &bytes) {
+        return rocprim::reduce_by_key(t, bytes, keys[1].p, sums[1].p, (size_t)n_in, keys[2].p, sums[2].p, &d_link.p->unique, LinkSumPlus(),
+                                      rocprim::equal_to<unsigned long long>(), st);
+      });
+      FA_HIP(hipMemsetAsync(l.seg_start, 0, n * 2 * sizeof(int32_t), st));
+      l.bound = n_in; l.round = (unsigned int)rounds + 1u;
+      const dim3 entry_grid(ceil_div(n_in, 256));
+      hipLaunchKernelGGL(k_link_segments, entry_grid, dim3(256), 0, st, l);
+      hipLaunchKernelGGL(k_link_best, genome_grid, dim3(256), 0, st, l);
+      hipLaunchKernelGGL(k_link_merge, genome_grid, dim3(256), 0, st, l);
+      hipLaunchKernelGGL(k_link_labels, genome_grid, dim3(256), 0, st, l);
+      hipLaunchKernelGGL(k_link_relabel, entry_grid, dim3(256), 0, st, l);
+      FA_HIP(hipGetLastError());
+      const LinkStatus now = d_link.read(st);
+      if (now.changed != l.round) break;
+      rounds++;
+      FA_REQUIRE(rounds < (int64_t)n_genomes, FA_ERR_INTERNAL, "average linkage merged in more rounds than there are genomes");
+      n_in = (int64_t)now.live;
+    }
+  }
+  CompArgs c{};
+  c.labels = labels; c.n_genomes = n_genomes; c.status = status;
+  unsigned int roots = 0;
+  hipLaunchKernelGGL(k_comp_roots, genome_grid, dim3(256), 0, st, c);
+  FA_HIP(hipGetLastError());
+  FA_HIP(hipMemcpyAsync(&roots, &status->roots, sizeof roots, hipMemcpyDeviceToHost, st));
+  FA_HIP(hipStreamSynchronize(st));
+  return roots;
+}
+
 struct TableRequest {
   bool clusters = false;
   bool representatives = false;            // with `clusters`: labels are representatives, not components
+  bool linkage = false;                    // with `clusters`: labels are average-linkage clusters, `missing` their missing identity
+  float missing = 0.0f;
   const int32_t *order = nullptr; double *identity = nullptr;
   fa_pair *pairs = nullptr; int64_t cap = 0; int64_t *n_pairs = nullptr; bool pairs_device = false;
   int32_t *labels = nullptr; bool labels_device = false; int32_t *n_clusters = nullptr; int64_t *stats = nullptr;
@@ -129,6 +196,17 @@ inline void table_reduce(const fa_cgi_row *rows, int64_t n_rows, bool rows_devic
     FA_REQUIRE(p->min_identity >= 0.0f, FA_ERR_INVALID, "min_identity must be a number that is not negative");          // (false for NaN)
     FA_REQUIRE(order_positions(want.order, n_genomes, pos), FA_ERR_INVALID, "order is not a permutation of the genome numbers");
   }
+  long long qm = 0, qc = 0;
+  if (want.linkage) {
+    FA_REQUIRE(p->min_identity >= 0.0f, FA_ERR_INVALID, "min_identity must be a number that is not negative");          // (false for NaN)
+    FA_REQUIRE(want.missing >= 0.0f, FA_ERR_INVALID, "missing must be a number that is not negative");
+    const double dm = rint((double)want.missing * LINK_SCALE), dc = rint((double)p->min_identity * LINK_SCALE);
+    FA_REQUIRE(dm < dc, FA_ERR_INVALID, "missing must lie below min_identity");
+    FA_REQUIRE(n_genomes <= LINK_MAX_GENOMES, FA_ERR_UNSUPPORTED, "average linkage over more than 2^18 genomes");
+    // no weight exceeds LINK_MAX_W: a cut-off above it merges nothing whatever its value, and neither does the clamped one
+    qc = (long long)std::min(dc, (double)(LINK_MAX_W + 1));
+    qm = (long long)std::min(dm, (double)LINK_MAX_W);
+  }
   require_device();
   CallStream stream;
   hipStream_t st = stream.s;
@@ -145,7 +223,8 @@ inline void table_reduce(const fa_cgi_row *rows, int64_t n_rows, bool rows_devic
   a.n_rows = n_rows; a.n_genomes = n_genomes;
   a.fragment_length = (unsigned long long)p->fragment_length; a.min_fraction = p->min_fraction;
   a.min_identity = (double)p->min_identity; a.reciprocal = p->reciprocal;
-  a.edges_only = want.representatives ? TAB_EMIT_WEIGHTED : want.clusters ? TAB_EMIT_EDGES : TAB_EMIT_PAIRS;
+  a.edges_only = want.linkage ? TAB_EMIT_LINK : want.representatives ? TAB_EMIT_WEIGHTED : want.clusters ? TAB_EMIT_EDGES : TAB_EMIT_PAIRS;
+  a.link_bits = (int32_t)id_bits(n_genomes);
   a.status = d_status.p;
   a.n_chunks = ceil_div(n_rows, TAB_CHUNK);
   TableStatus status{};
@@ -172,6 +251,7 @@ inline void table_reduce(const fa_cgi_row *rows, int64_t n_rows, bool rows_devic
     status = d_status.read(st);
     FA_REQUIRE(!(status.flags & TAB_BAD_ID), FA_ERR_INVALID, "a row names a genome outside [0, n_genomes)");
     FA_REQUIRE(!(status.flags & TAB_DUPLICATE), FA_ERR_INVALID, "the table holds the same (query, reference) twice");
+    FA_REQUIRE(!(status.flags & TAB_BAD_IDENTITY), FA_ERR_INVALID, "a present pair has an identity that is NaN or outside [0, 128]");
   }
   const int64_t n_emit = (int64_t)status.emitted;
   // the n_emit records of the call's form (a.edges_only), once their destination is set in `a`
@@ -196,7 +276,16 @@ inline void table_reduce(const fa_cgi_row *rows, int64_t n_rows, bool rows_devic
 
   int64_t rounds = 0;
   unsigned int roots = 0;
-  if (n_genomes && want.representatives) {
+  if (n_genomes && want.linkage) {
+    Staged<int32_t> labels(want.labels, want.labels_device, (size_t)n_genomes);
+    auto emit_into = [&](unsigned long long *link_keys, LinkSum *link_sums) {
+      a.link_keys = link_keys; a.link_sums = link_sums;
+      emit();
+    };
+    roots = linkage(emit_into, n_emit, labels.dev(), n_genomes, qm, qc, d_status.p, st, rounds);
+    labels.finish(st);
+    FA_HIP(hipStreamSynchronize(st));
+  } else if (n_genomes && want.representatives) {
     DevBuf<TableEdge> d_edges;
     DevBuf<int32_t> d_order;                   // pos, then order
     std::vector<int32_t> both(pos);
@@ -230,6 +319,7 @@ inline void table_reduce(const fa_cgi_row *rows, int64_t n_rows, bool rows_devic
   if (want.stats) {
     want.stats[0] = (int64_t)status.survivors; want.stats[1] = (int64_t)status.pairs;
     want.stats[2] = (int64_t)status.edges; want.stats[3] = rounds;
+    if (want.linkage) want.stats[4] = (int64_t)n_genomes - (int64_t)roots;
   }
 }
 

@@ -24,7 +24,9 @@
 // chunk being the population count of the ballots below its lane (the form of k_map_count / k_chunk_scan / k_map_write;
 // the scan is the one kernel of fa_compact.hip.h).
 // The same input therefore gives the same bytes on every run: no record's place depends on timing.  (A third form of the
-// write kernel keeps an edge's identity, TableEdge: what fa_represent.hip.h selects representatives from.)
+// write kernel keeps an edge's identity, TableEdge: what fa_represent.hip.h selects representatives from.  A fourth takes
+// every pair that is present -- no cut-off, `reciprocal` applied -- as the two directed entries (a -> b, b -> a) with its
+// fixed-point weight: what fa_linkage.hip.h agglomerates; its count kernel also refuses an identity that has no weight.)
 //
 // Components run as rounds of two launches.  k_comp_edges lowers, for every edge whose ends carry different labels, the
 // larger label's own entry and the entry of the genome that carried it to the smaller label (atomicMin); k_comp_jump
@@ -38,11 +40,13 @@
 
 #include "fa_common.h"
 #include "fa_compact.hip.h"
+#include "fa_link.h"
 
 namespace fa {
 
 constexpr int TAB_ITERS = 8, TAB_CHUNK = 64 * TAB_ITERS;          // rows per wave; a workgroup of four waves takes 4 * TAB_CHUNK
 constexpr unsigned TAB_BAD_ID = 1u, TAB_DUPLICATE = 2u;
+constexpr unsigned TAB_BAD_IDENTITY = 64u;      // (TAB_EMIT_LINK) a present pair whose identity is NaN or outside [0, 128]
 constexpr unsigned long long TAB_KEY_NONE = ~0ULL;
 
 // one per call, zeroed before the first launch
@@ -61,7 +65,7 @@ struct TableEdge {
   double identity;                     // >= 0; -0.0 is stored as +0.0
 };
 
-constexpr int32_t TAB_EMIT_PAIRS = 0, TAB_EMIT_EDGES = 1, TAB_EMIT_WEIGHTED = 2;
+constexpr int32_t TAB_EMIT_PAIRS = 0, TAB_EMIT_EDGES = 1, TAB_EMIT_WEIGHTED = 2, TAB_EMIT_LINK = 3;
 
 struct TableArgs {
   const fa_cgi_row *rows;
@@ -75,13 +79,17 @@ struct TableArgs {
   const unsigned long long *keys;      // sorted
   const uint32_t *row_of;              // row number of every sorted key
   int32_t n_chunks;
-  int32_t edges_only;                  // TAB_EMIT_*: the pairs as records, the edges as (a, b), the edges as (a, b, identity)
+  int32_t edges_only;                  // TAB_EMIT_*: the pairs as records, the edges as (a, b), the edges as (a, b, identity),
+                                       // the present pairs as directed entries
+  int32_t link_bits;                   // (TAB_EMIT_LINK) a directed entry's key is from << link_bits | to
   int32_t *chunk_count;                // [n_chunks]
   int64_t *chunk_off;                  // [n_chunks]
   fa_pair *pairs;
   int2 *edges;
   TableEdge *weighted;
-  int64_t cap;                         // room behind `pairs` / `edges` / `weighted`
+  unsigned long long *link_keys;       // [2 * cap]
+  LinkSum *link_sums;                  // [2 * cap]
+  int64_t cap;                         // room behind `pairs` / `edges` / `weighted`; half of that behind link_keys / link_sums
   TableStatus *status;
 };
 
@@ -137,7 +145,8 @@ __device__ __forceinline__ TableItem table_item(const TableArgs &a, int64_t i) {
     }
   }
   t.identity = both ? ((double)t.ab + (double)t.ba) / 2.0 : (double)own;
-  t.edge = t.identity >= a.min_identity && (both || a.reciprocal == 0);
+  // (TAB_EMIT_LINK: a pair is present whatever its identity)
+  t.edge = (a.edges_only == TAB_EMIT_LINK || t.identity >= a.min_identity) && (both || a.reciprocal == 0);
   return t;
 }
 
@@ -147,7 +156,7 @@ __global__ __launch_bounds__(256) void k_table_count(TableArgs a) {
   if (chunk >= a.n_chunks) return;                                  // (wave-uniform)
   const int64_t base = (int64_t)chunk * TAB_CHUNK + lane;
   int survivors = 0, pairs = 0, edges = 0;
-  bool duplicate = false;
+  bool duplicate = false, bad_identity = false;
 #pragma unroll
   for (int u = 0; u < TAB_ITERS; u++) {
     const TableItem t = table_item(a, base + 64 * u);
@@ -155,8 +164,10 @@ __global__ __launch_bounds__(256) void k_table_count(TableArgs a) {
     pairs += __popcll(__ballot(t.head));
     edges += __popcll(__ballot(t.edge));
     duplicate |= t.duplicate;
+    bad_identity |= a.edges_only == TAB_EMIT_LINK && t.edge && !link_identity_ok(t.identity);
   }
   if (__any(duplicate) && lane == 0) atomicOr(&a.status->flags, TAB_DUPLICATE);
+  if (__any(bad_identity) && lane == 0) atomicOr(&a.status->flags, TAB_BAD_IDENTITY);
   if (lane != 0) return;
   a.chunk_count[chunk] = a.edges_only ? edges : pairs;
   if (survivors) atomicAdd(&a.status->survivors, (unsigned long long)survivors);
@@ -179,7 +190,13 @@ __global__ __launch_bounds__(256) void k_table_write(TableArgs a) {
     const int64_t o = off + __popcll(mask & below);
     off += __popcll(mask);
     if (!emit || o >= a.cap) continue;
-    if (a.edges_only == TAB_EMIT_WEIGHTED) {
+    if (a.edges_only == TAB_EMIT_LINK) {
+      const LinkSum one{link_fixed(t.identity), 1};
+      a.link_keys[2 * o] = (unsigned long long)t.a << a.link_bits | (unsigned long long)t.b;
+      a.link_keys[2 * o + 1] = (unsigned long long)t.b << a.link_bits | (unsigned long long)t.a;
+      a.link_sums[2 * o] = one;
+      a.link_sums[2 * o + 1] = one;
+    } else if (a.edges_only == TAB_EMIT_WEIGHTED) {
       TableEdge e;
       e.a = t.a; e.b = t.b; e.identity = t.identity == 0.0 ? 0.0 : t.identity;
       a.weighted[o] = e;

@@ -234,6 +234,14 @@ class ResidentHitTable:
         return _clusters.clusters(self._rows_in_place(tables), query_lengths, reference_lengths, fragment_length, minimum_fraction,
                                   min_identity, reciprocal, stats)
 
+    def average_linkage(self, tables, query_lengths, reference_lengths, fragment_length, minimum_fraction=0.2, min_identity=95.0,
+                        reciprocal=False, missing=0.0, stats=None):
+        """`pyfastani_amd.clusters.average_linkage` over an exchanged table (what `step` returns) of an all-vs-all: the labels,
+        with the count rows dropped and the ranks joined as for `clusters`."""
+        from . import clusters as _clusters
+        return _clusters.average_linkage(self._rows_in_place(tables), query_lengths, reference_lengths, fragment_length,
+                                         minimum_fraction, min_identity, reciprocal, missing, stats)
+
     def representatives(self, tables, query_lengths, reference_lengths, fragment_length, minimum_fraction=0.2, min_identity=95.0,
                         reciprocal=False, order=None, stats=None):
         """`pyfastani_amd.clusters.representatives` over an exchanged table (what `step` returns) of an all-vs-all:

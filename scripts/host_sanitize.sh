@@ -1,5 +1,5 @@
 #!/bin/bash
-# The host-only pieces of libfastani_hip (fa_host.h packer + thread pool, fa_fasta.h, fa_stats.h, fa_lease.h, fa_policy.h, fa_ingest.h, fa_mapstream.h, fa_order.h, fa_knobs.h) under
+# The host-only pieces of libfastani_hip (fa_host.h packer + thread pool, fa_fasta.h, fa_stats.h, fa_lease.h, fa_policy.h, fa_ingest.h, fa_mapstream.h, fa_order.h, fa_link.h, fa_knobs.h) under
 # AddressSanitizer + UndefinedBehaviorSanitizer and, separately, ThreadSanitizer -- on the CPU, g++ only (no GPU sanitizer,
 # no XNACK).  Every build runs with the AVX2 packer and with FA_NO_AVX2=1 (the scalar paths), with 8 and with 3 host threads.
 #   bash scripts/host_sanitize.sh [log]        (default log: profiles/r06_host_sanitizers.txt)
@@ -36,6 +36,14 @@ status=0
   echo "## build: g++ -std=c++17 -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=all scripts/host_sanitize/order.cpp"
   if g++ -std=c++17 -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=all scripts/host_sanitize/order.cpp -o "$OUT/order" 2>&1; then
     "$OUT/order" 2>&1 | tail -5
+    rc=${PIPESTATUS[0]}
+    echo "exit status $rc"
+    [ "$rc" = 0 ] || status=1
+  else echo "BUILD FAILED"; status=1; fi
+  # the fixed point, the order and the cut-off test of fa_table_linkage (fa_link.h) at the ends of their range: ASan + UBSan only
+  echo "## build: g++ -std=c++17 -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=all scripts/host_sanitize/link.cpp"
+  if g++ -std=c++17 -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=all scripts/host_sanitize/link.cpp -o "$OUT/link" 2>&1; then
+    "$OUT/link" 2>&1 | tail -5
     rc=${PIPESTATUS[0]}
     echo "exit status $rc"
     [ "$rc" = 0 ] || status=1

@@ -1,0 +1,68 @@
+// The arithmetic of fa_table_linkage (pyfastani_amd/csrc/fa_link.h) at the ends of its range, on the CPU: build with
+//   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all link.cpp  and run.
+//
+// Under UBSan a signed overflow in a sum, a product or the cut-off test is a finding of its own.  The largest case the
+// library admits is 2^18 genomes: two clusters of 2^17, every pair present at identity 128 or every pair missing at the
+// largest `missing`, against the largest cut-off the driver passes on (LINK_MAX_W + 1).  The order is also held against a
+// second comparison that divides instead of multiplying (quotient, then remainders by cross products that fit 128 bits).
+#include <cstdint>
+#include <cstdio>
+
+#include "../../pyfastani_amd/csrc/fa_link.h"
+
+static int failures = 0;
+#define CHECK(cond, ...) \
+  do { if (!(cond)) { if (failures++ < 20) { fprintf(stderr, "FAILED %s:%d: %s: ", __FILE__, __LINE__, #cond); fprintf(stderr, __VA_ARGS__); fprintf(stderr, "\n"); } } } while (0)
+
+static uint64_t rng_state = 88172645463325252ULL;
+static uint64_t rnd() { rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_state ^= rng_state << 17; return rng_state; }
+
+// s1 / n1 against s2 / n2 without the 128-bit product of the sums: 1, 0 or 2 (equal averages)
+static int by_division(const fa::LinkCand &a, const fa::LinkCand &b) {
+  const long long qa = a.s / a.n, qb = b.s / b.n;
+  if (qa != qb) return qa > qb ? 1 : 0;
+  const unsigned __int128 x = (unsigned __int128)(a.s % a.n) * (unsigned long long)b.n, y = (unsigned __int128)(b.s % b.n) * (unsigned long long)a.n;
+  return x == y ? 2 : x > y ? 1 : 0;
+}
+
+int main() {
+  using namespace fa;
+  CHECK(link_fixed(0.0) == 0 && link_fixed(128.0) == LINK_MAX_W && link_fixed(95.0) == 95LL << 20, "fixed point of round values");
+  CHECK(link_fixed(0.5 / LINK_SCALE) == 0 && link_fixed(1.5 / LINK_SCALE) == 2 && link_fixed(2.5 / LINK_SCALE) == 2, "ties go to even");
+  CHECK(link_identity_ok(0.0) && link_identity_ok(-0.0) && link_identity_ok(128.0), "the ends of the identity range");
+  CHECK(!link_identity_ok(-1e-300) && !link_identity_ok(128.0000001) && !link_identity_ok(0.0 / 0.0), "outside it, and NaN");
+
+  const long long half = (long long)LINK_MAX_GENOMES / 2, pairs = half * half;                  // 2^34
+  const LinkSum full{LINK_MAX_W * pairs, pairs}, none{0, 0};
+  const long long s_full = link_s(full, pairs, LINK_MAX_W), s_none = link_s(none, pairs, LINK_MAX_W);
+  CHECK(s_full == LINK_MAX_W * pairs && s_none == s_full && s_full < (1LL << 62), "the largest sums stay below 2^62");
+  CHECK(!link_passes(s_full, pairs, LINK_MAX_W + 1) && link_passes(s_full, pairs, LINK_MAX_W), "the largest cut-off");
+  const LinkCand top{s_full, pairs, 0, 1}, below{s_full - 1, pairs, 0, 2}, tied{LINK_MAX_W * (pairs - 1), pairs - 1, 2, 3};
+  CHECK(link_order(top, below) == 1 && link_order(below, top) == 0, "one unit of the sum decides");
+  CHECK(link_order(top, tied) == 1 && link_order(tied, top) == 0 && link_order(top, top) == 2, "equal averages: the labels decide");
+  const LinkCand nothing{0, 0, 0, 0};
+  CHECK(link_better(top, nothing) && !link_better(nothing, top) && !link_better(nothing, nothing) && !link_better(top, top), "none comes last");
+
+  long checked = 0;
+  for (int trial = 0; trial < 200000; trial++) {
+    LinkCand a, b;
+    a.n = 1 + (long long)(rnd() % (uint64_t)pairs); b.n = trial % 3 ? 1 + (long long)(rnd() % (uint64_t)pairs) : a.n + (long long)(rnd() % 3);
+    const long long w = (long long)(rnd() % (uint64_t)(LINK_MAX_W + 1));
+    a.s = w * a.n; b.s = w * b.n;
+    if (trial % 2) {
+      const long long da = (long long)(rnd() % 3), db = (long long)(rnd() % 3);
+      if (da <= a.s) a.s -= da;
+      if (db <= b.s) b.s -= db;
+    }
+    a.lo = (int32_t)(rnd() % 5); a.hi = a.lo + 1 + (int32_t)(rnd() % 5); b.lo = (int32_t)(rnd() % 5); b.hi = b.lo + 1 + (int32_t)(rnd() % 5);
+    int want = by_division(a, b);
+    if (want == 2) want = a.lo != b.lo ? (a.lo < b.lo) : a.hi != b.hi ? (a.hi < b.hi) : 2;
+    CHECK(link_order(a, b) == want, "trial %d: %lld / %lld against %lld / %lld", trial, a.s, a.n, b.s, b.n);
+    CHECK(link_order(b, a) == (want == 2 ? 2 : 1 - want), "trial %d: not antisymmetric", trial);
+    checked++;
+  }
+  printf("%ld random pairs of candidates ordered\n", checked);
+  if (failures) { printf("%d checks FAILED\n", failures); return 1; }
+  printf("all checks passed\n");
+  return 0;
+}
