@@ -117,7 +117,9 @@ int fa_estimate_minimum_hits_relaxed(int sketch_size, int k, float identity, int
 /* nucIdentity / nucIdentityUpperBound of skch::Map::doL2Mapping for (shared, sketch_size) */
 int fa_mapping_identity(int shared, int sketch_size, int k, float *identity, float *upper_bound);
 /* host, no device: smallest shared count of a sketch of size s whose upper-bound identity passes, at interval ci
- * (the filter of skch::Map::doL2Mapping; sketch_size + 1 when no count passes) */
+ * (the filter of skch::Map::doL2Mapping; sketch_size + 1 when no count passes).  FA_ERR_UNSUPPORTED where a mapping of NO
+ * shared record passes while one of a single shared record does not (k <= 7, sketches of hundreds of records, identities below
+ * ~18 %): no threshold states that filter, and a mapper refuses a query or fa_mapper_set_rules under such parameters */
 int fa_pass_threshold(int sketch_size, int k, float identity, float ci, int *min_shared);
 /* skch::CommonFunc::getHash, include/fastani/map/common_func.pxd:12 (host twin of the device function) */
 uint32_t fa_hash(const void *kmer, int length);

@@ -624,6 +624,7 @@ int fa_mapper_set_rules(fa_mapper *m, const fa_rules *r) {
     if (r->l2_confidence != m->stats.ci) {
       StatTables next = m->stats;                            // (a failed upload leaves the mapper as it was)
       next.set_ci(r->l2_confidence);
+      require_no_zero_pass(next);                           // (refused: the mapper keeps its rules)
       if (m->d_pass.p) {
         bind_device(m->device);
         DevBuf<int32_t> d_next;
@@ -648,6 +649,8 @@ int fa_pass_threshold(int sketch_size, int k, float identity, float ci, int *min
   return guarded([&] {
     FA_REQUIRE(min_shared && sketch_size > 0 && k >= 1, FA_ERR_INVALID, "sketch_size and k must be positive");
     FA_REQUIRE(ci > 0.0f && ci < 1.0f, FA_ERR_INVALID, "the confidence interval must lie strictly inside (0, 1)");
+    FA_REQUIRE(!stat_zero_passes_alone(sketch_size, k, identity, ci), FA_ERR_UNSUPPORTED,
+               "a mapping of no shared record passes alone: no threshold states this filter (a mapper refuses these parameters)");
     *min_shared = stat_pass_threshold(sketch_size, k, identity, ci);
   });
 }

@@ -413,6 +413,14 @@ static void build_index(fa_mapper &m) {
   m.stats.smax = -1;
 }
 
+// fa_stats.h: stat_zero_passes_alone.  Checked on every call (a mapper whose tables grew into such a sketch size stays refused).
+static void require_no_zero_pass(const StatTables &t) {
+  if (t.zero_pass)
+    throw Error(FA_ERR_UNSUPPORTED, "percentage_identity " + std::to_string(t.pid) + " at l2_confidence " + std::to_string(t.ci) +
+                " passes a mapping of no shared record, and none of one shared record, at sketch size " + std::to_string(t.zero_pass) +
+                ", which the mapping tables cannot carry");
+}
+
 // (Re)builds the LUTs for sketches up to smax.  Called with m.mtx held; calls in flight keep the tables they captured
 // (older generations are retired, not freed), so the tables can grow while other workspaces are busy.
 static void ensure_luts(fa_mapper &m, int smax) {
@@ -423,6 +431,7 @@ static void ensure_luts(fa_mapper &m, int smax) {
     m.d_ident.upload(m.stats.ident, m.stream);
     FA_HIP(hipStreamSynchronize(m.stream));
   }
+  require_no_zero_pass(m.stats);
 }
 
 static int64_t host_find(fa_mapper *m, uint32_t hash, uint32_t *off, uint32_t *cnt) {

@@ -129,7 +129,9 @@ inline int stat_recommended_window(double cutoff, int k, int alphabet, float ide
 }
 
 // Smallest shared count of a sketch of size s whose upper-bound identity at interval ci reaches pid (s + 1: none does).
-// The upper-bound identity is monotone in c; the threshold is located by walking from the strict estimate.
+// The upper-bound identity is monotone in c from c = 1 on; the threshold is located by walking from the strict estimate.
+// c = 0 stands outside: j2md(0) is DEFINED as 1 while j2md(1 / s) exceeds 1 once 2 / (s + 1) < e^-k, so the bound of 0 can
+// lie ABOVE the bound of 1 (k <= 7, s of a few hundred and more, identities below ~18 %), and the walk never finds it.
 inline int stat_pass_threshold(int s, int k, float pid, float ci) {
   if (s <= 0) return 1;
   auto passes = [&](int c) { return stat_upper_identity(c, s, k, ci) >= pid; };
@@ -137,6 +139,15 @@ inline int stat_pass_threshold(int s, int k, float pid, float ci) {
   if (passes(c)) { while (c > 0 && passes(c - 1)) c--; }
   else { while (c <= s && !passes(c)) c++; }
   return c;
+}
+
+// True where doL2Mapping's filter passes a mapping of NO shared record that `shared >= stat_pass_threshold` refuses (the
+// case above).  Such a mapping exists -- a minimum hit count of 0 is raised to 1, one chance seed makes a locus, and its
+// best window need not hold the seed among the s smallest of the union -- and no threshold states that filter: a mapper
+// refuses parameters under which this holds for a sketch size its tables cover.  (Where the count 1 passes as well the
+// threshold is 0 and the table is right; what becomes of a mapping of identity 0 after the filter is DESIGN.md section 2.)
+inline bool stat_zero_passes_alone(int s, int k, float pid, float ci) {
+  return s > 0 && stat_upper_identity(0, s, k, ci) >= pid && stat_pass_threshold(s, k, pid, ci) > 0;
 }
 
 // Tables indexed by sketch size s (0..smax): minimum L1 hits, the smallest shared count whose upper-bound
@@ -150,6 +161,7 @@ struct StatTables {
   std::vector<int32_t> min_hits;     // [s]
   std::vector<int32_t> pass_shared;  // [s]  (s+1 = nothing passes)
   std::vector<float> ident;          // triangular
+  int zero_pass = 0;                // smallest s <= smax with stat_zero_passes_alone at (k, pid, ci); 0: none
 
   static size_t tri(int s) { return (size_t)s * (size_t)(s + 1) / 2; }
 
@@ -164,7 +176,11 @@ struct StatTables {
   // pass_shared again, for another interval (the other tables do not depend on it)
   void set_ci(float new_ci) {
     ci = new_ci;
-    for (int s = 1; s <= smax; s++) pass_shared[s] = stat_pass_threshold(s, k, pid, ci);
+    zero_pass = 0;
+    for (int s = 1; s <= smax; s++) {
+      pass_shared[s] = stat_pass_threshold(s, k, pid, ci);
+      if (!zero_pass && pass_shared[s] > 0 && stat_upper_identity(0, s, k, ci) >= pid) zero_pass = s;
+    }
   }
 
   // grows the tables to cover sketch sizes up to new_smax; returns true if anything changed
@@ -177,6 +193,7 @@ struct StatTables {
       if (s == 0) { min_hits[0] = 0; pass_shared[0] = 1; ident[0] = 0.0f; continue; }
       min_hits[s] = stat_min_hits_relaxed(s, k, pid);
       pass_shared[s] = stat_pass_threshold(s, k, pid, ci);
+      if (!zero_pass && pass_shared[s] > 0 && stat_upper_identity(0, s, k, ci) >= pid) zero_pass = s;
       for (int j = 0; j <= s; j++) ident[tri(s) + j] = 100 * (1 - stat_j2md((float)(1.0 * j / s), k));
     }
     smax = new_smax;

@@ -144,8 +144,8 @@ def plant_repeats(contigs, k, w, frag):
     return out
 
 
-def build_inputs(cell):
-    """The genomes of a cell, as lists of bytes.  refs["whole"]: three relatives of one ancestor and an unrelated genome, one
+def build_inputs(cell, divergences=(0.01, 0.04, 0.08)):
+    """The genomes of a cell, as lists of bytes.  refs["whole"]: three relatives of one ancestor (at `divergences`) and an unrelated genome, one
     contig each.  refs["frag"]: the relatives cut by `cut_at` with repeats planted inside contigs (`plant_repeats`), the
     unrelated genome whole, a genome with no contig in the middle
     and a genome of contigs too short for a record at the end (the first contig of the index has length 0: the index begins
@@ -155,7 +155,7 @@ def build_inputs(cell):
     g = syn.rng(cell["seed"])
     lengths = cell_lengths(cell)
     anc = _random(g, cell["length"], protein)
-    rel = [_ascii(_mutate(g, anc, d, protein), protein) for d in (0.01, 0.04, 0.08)]
+    rel = [_ascii(_mutate(g, anc, d, protein), protein) for d in divergences]
     unrelated = _ascii(_random(g, cell["length"] // 2, protein), protein)
     too_short = [_ascii(_random(g, n, protein), protein) for n in (k - 1, 0, 1, max(0, w - 1), k - 1, min(k, w) - 1 if min(k, w) else 0)]
     refs = {

@@ -185,43 +185,44 @@ def rows_of(maps):
 
 
 # ---- expected values ----------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def expected(case, reading):
-    """What the oracle of a reading gives for a case, computed once per process: per cell, per query
+def expected_cell(cell, reading):
+    """What the oracle of a reading gives for one cell {"params", "refs", "queries"}: per query
     {"hits", "l2": every L2 mapping (qseq, rseq, rstart, sketch, shared), sorted, "rows": [(genome, count, float32 identity)],
      "kept": the records of the restated computeCGI under the reading's tie direction}."""
     mod = oracle(reading)
     largest = READINGS[reading].get("cgi_ties") == "largest"
-    out = []
-    for cell in inputs(case):
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore")
-            osk = mod.OracleSketch(**cell["params"])
-        sbf, n = [], 0
-        for i, contigs in enumerate(cell["refs"]):
-            osk.add_draft(i, contigs)
-            n += len(contigs)
-            sbf.append(n)
-        osk.index()
-        per_query = []
-        for q, contigs in enumerate(cell["queries"]):
-            hits, det = osk.query_draft(contigs, threads=8, details=True)
-            m, r = det["mappings"], det["rows"]
-            per_query.append({
-                "hits": hits,
-                "l2": sorted(zip(m["qseq"].tolist(), m["rseq"].tolist(), m["rstart"].tolist(), m["sketch"].tolist(), m["shared"].tolist())),
-                "rows": [(int(g), int(c), np.float32(x)) for g, c, x in zip(r["genome"], r["count"], r["identity"])],
-                "kept": kept_mappings(m, sbf, fragment_length(cell), largest, q),
-            })
-        out.append(per_query)
-    return out
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        osk = mod.OracleSketch(**cell["params"])
+    sbf, n = [], 0
+    for i, contigs in enumerate(cell["refs"]):
+        osk.add_draft(i, contigs)
+        n += len(contigs)
+        sbf.append(n)
+    osk.index()
+    per_query = []
+    for q, contigs in enumerate(cell["queries"]):
+        hits, det = osk.query_draft(contigs, threads=8, details=True)
+        m, r = det["mappings"], det["rows"]
+        per_query.append({
+            "hits": hits,
+            "l2": sorted(zip(m["qseq"].tolist(), m["rseq"].tolist(), m["rstart"].tolist(), m["sketch"].tolist(), m["shared"].tolist())),
+            "rows": [(int(g), int(c), np.float32(x)) for g, c, x in zip(r["genome"], r["count"], r["identity"])],
+            "kept": kept_mappings(m, sbf, fragment_length(cell), largest, q),
+        })
+    return per_query
 
 
-def moved(case, reading):
-    """What a reading moves against the default oracle, summed over the cells and queries of a case:
+@functools.lru_cache(maxsize=None)
+def expected(case, reading):
+    """`expected_cell` of every cell of a case, computed once per process."""
+    return [expected_cell(cell, reading) for cell in inputs(case)]
+
+
+def moved_between(a, b):
+    """What differs between two answers of the form of `expected` (per cell, per query), summed over cells and queries:
     {"l2": mappings (as multisets), "rows": rows, "hits": queries whose hit list differs}."""
     from collections import Counter
-    a, b = expected(case, "default"), expected(case, reading)
     out = {"l2": 0, "rows": 0, "hits": 0, "l2_per_cell": [], "rows_per_cell": []}
     for ca, cb in zip(a, b):
         l2 = rows = 0
@@ -236,6 +237,27 @@ def moved(case, reading):
         out["l2_per_cell"].append(l2)
         out["rows_per_cell"].append(rows)
     return out
+
+
+def moved(case, reading):
+    """What a reading moves against the default oracle in a case (`moved_between`)."""
+    return moved_between(expected(case, "default"), expected(case, reading))
+
+
+def oracle_upper(olib, c, s, k, ci):
+    """nucIdentityUpperBound of c shared records of a sketch of s at interval ci, by the oracle's doL2Mapping arithmetic (float32
+    throughout)."""
+    md = olib.fo_j2md(np.float32(c / s), k)
+    lower = np.float32(olib.fo_md_lower_bound(md, s, k, ci))
+    return np.float32(100) * (np.float32(1) - lower)
+
+
+def oracle_threshold(olib, s, k, pid, ci):
+    """Smallest shared count whose upper-bound identity passes (s + 1: none does)."""
+    for c in range(s + 1):
+        if oracle_upper(olib, c, s, k, ci) >= np.float32(pid):
+            return c
+    return s + 1
 
 
 # ---- the device side ------------------------------------------------------------------------------------------------------
@@ -315,9 +337,10 @@ def pack(results):
     return out
 
 
-def unpack(z, case):
+def unpack(z, cells):
+    """The inverse of `pack` for the cells that were mapped (e.g. `inputs(case)`)."""
     out = []
-    for c, cell in enumerate(inputs(case)):
+    for c, cell in enumerate(cells):
         per_query = []
         for q in range(len(cell["queries"])):
             per_query.append({

@@ -90,3 +90,33 @@ def test_fuzz_contig_domain_against_oracle():
     last = res.stdout.strip().splitlines()[-1].split()
     assert "0 mismatches" in res.stdout and int(last[0]) == cases, res.stdout[-500:]
     assert int(last[last.index("degenerate,") - 1]) <= cases // 4, res.stdout[-500:]
+
+
+ALL_RULES = "l2_confidence=0.75,slide_end=fragment,cgi_ties=largest"
+
+
+def test_fuzz_window_domain_under_the_other_readings():
+    """The --domain leg with every sketch under the three non-default readings (`--rules`), against the oracle built with the
+    matching switches: the longer slide, the other interval and the other tie direction at w = 2-4 and at sketches of a
+    handful of records, on genomes with repeats, inversions, N runs and drafts."""
+    seed = (source_seed() ^ 0x2B2B2B) & 0x7FFFFFFF
+    cases = 200
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "fuzz_parity.py"), "--rules", ALL_RULES, "--domain", str(cases), str(seed)],
+                         capture_output=True, text=True, timeout=2400)
+    assert res.returncode == 0, f"seed {seed}\n" + res.stdout[-3000:] + res.stderr[-3000:]
+    last = res.stdout.strip().splitlines()[-1].split()
+    assert "0 mismatches" in res.stdout and int(last[0]) == cases and "fragment" in res.stdout.strip().splitlines()[-1], res.stdout[-500:]
+    assert int(last[last.index("degenerate,") - 1]) <= cases * 2 // 3, res.stdout[-500:]
+
+
+def test_fuzz_contig_domain_under_the_other_readings():
+    """The --contigs leg under the three non-default readings: loci at contig ends, where the longer slide is clamped, at the
+    case's own critical contig lengths."""
+    seed = (source_seed() ^ 0x4D4D4D) & 0x7FFFFFFF
+    cases = 200
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "fuzz_parity.py"), "--rules", ALL_RULES, "--contigs", str(cases), str(seed)],
+                         capture_output=True, text=True, timeout=2400)
+    assert res.returncode == 0, f"seed {seed}\n" + res.stdout[-3000:] + res.stderr[-3000:]
+    last = res.stdout.strip().splitlines()[-1].split()
+    assert "0 mismatches" in res.stdout and int(last[0]) == cases and "fragment" in res.stdout.strip().splitlines()[-1], res.stdout[-500:]
+    assert int(last[last.index("degenerate,") - 1]) <= cases // 4, res.stdout[-500:]

@@ -138,7 +138,7 @@ def test_forced_paths_under_the_longer_slide(name, tmp_path):
     res = subprocess.run([sys.executable, rc.__file__, "A", "end", str(out)], env=dict(os.environ, **env), capture_output=True, text=True, timeout=600)
     assert res.returncode == 0 and res.stdout.strip().endswith("OK"), res.stdout[-2000:] + res.stderr[-2000:]
     with np.load(out) as z:
-        got = rc.unpack(z, "A")
+        got = rc.unpack(z, rc.inputs("A"))
         repeats, parts = int(z["repeats"]), int(z["parts"])
     rc.assert_same(got[0], rc.expected("A", "end")[0], f"case A under end, {env}", in_parts=name == "events_split")
     if name == "events_retry":

@@ -90,14 +90,7 @@ def test_protein_golden_moves_under_no_reading():
 
 
 # ---- the host arithmetic ------------------------------------------------------------------------------------------------
-def oracle_threshold(olib, s, k, pid, ci):
-    """Smallest shared count whose upper-bound identity passes, by the oracle's doL2Mapping arithmetic (float32 throughout)."""
-    for c in range(s + 1):
-        md = olib.fo_j2md(np.float32(c / s), k)
-        lower = np.float32(olib.fo_md_lower_bound(md, s, k, ci))
-        if np.float32(100) * (np.float32(1) - lower) >= np.float32(pid):
-            return c
-    return s + 1
+oracle_threshold = rc.oracle_threshold
 
 
 @pytest.mark.parametrize("ci", [0.75, 0.9])

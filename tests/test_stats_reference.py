@@ -100,8 +100,10 @@ def check_sketch_size(s, k, cs):
     """identity and upper bound bit for bit at every shared count in `cs` (ascending); the upper bound monotone over them
     from c = 1 on.  c = 0 is the one exception: j2md(0) is defined as 1, while j2md(1 / s) exceeds 1 once 2 / (s + 1) < e^-k
     (k <= 7 in protein mode, s of a few hundred and more), so upper(0) > upper(1) there.  pass_shared (the walk of
-    StatTables::extend) then says "0 fails" although upper(0) >= pid for pid in (upper(1), upper(0)]; that cannot reach a
-    result, because in exactly that range the minimum hit count is at least 2 and no locus has 0 shared records."""
+    StatTables::extend) then says "0 fails" although upper(0) >= pid for pid in (upper(1), upper(0)].  At the 0.9 interval
+    checked here the minimum hit count is at least 2 in exactly that range (asserted below); that alone does not keep a locus
+    from sharing 0 records in its best window, so the library refuses such parameters instead of relying on it
+    (fa_stats.h: stat_zero_passes_alone; tests/test_rules_domain_inputs.py checks the refusal at every interval)."""
     ups = {}
     for c in cs:
         got, want = abi_identity(c, s, k), model_identity(c, s, k)
