@@ -430,10 +430,50 @@ int fa_table_representatives(const fa_cgi_row *rows, int64_t n_rows, int rows_de
  * [1] pairs, [2] present pairs, [3] rounds (those that merged a pair: at most n_genomes - 1; a block of exactly tied genomes
  * merges one pair per round), [4] merges = n_genomes - *n_clusters.  Runs like fa_table_clusters: on the calling thread's
  * current device, on a stream of its own, with memory from the device pool, finished when it returns, FA_ERR_NO_DEVICE
- * without a device.  Only the partition at one cut-off is returned: no merge list, no tree. */
+ * without a device.  Only the partition at one cut-off is returned; fa_table_dendrogram returns the merge list, the tree,
+ * as well. */
 int fa_table_linkage(const fa_cgi_row *rows, int64_t n_rows, int rows_device, int32_t n_genomes, const uint64_t *query_lengths,
                      const uint64_t *reference_lengths, const fa_table_params *p, float missing, int32_t *labels, int labels_device,
                      int32_t *n_clusters, int64_t *stats);
+/* One merge of the sequential walk of step 5. */
+typedef struct fa_merge {
+  int32_t lo, hi;            /* labels of the two clusters before the merge, lo < hi; the merged cluster is labelled lo */
+  int32_t size_lo, size_hi;  /* their sizes before the merge; n = size_lo * size_hi */
+  int64_t s;                 /* S(A,B) of step 3: sum of w + qm * (n - present) */
+  int64_t present;           /* c(A,B): present genome pairs between them, >= 1 */
+} fa_merge;                  /* 32 bytes */
+/* The average-linkage dendrogram of the table: every merge of fa_table_linkage's walk, so that the partition at any cut-off
+ * at or above the one it was built with is had without another pass over the table (fa_dendrogram_cut).  Steps 1-7 of
+ * fa_table_linkage apply word for word, stats[0..4] included.  p->min_identity is the BUILD cut-off: the tree is known down
+ * to it (for the whole tree pass any value just above `missing`).
+ *   merges    receives every merge of the sequential walk, in the order of the walk -- which is the order of step 4 applied
+ *             to {s, size_lo * size_hi, lo, hi}: the walk visits its merges in that order (average linkage is reducible),
+ *             so the merges that pass a cut-off t >= the build cut-off are a prefix of the list, and that prefix is the walk
+ *             of fa_table_linkage at t.  *n_merges (not NULL) is their number, equal to stats[4]; a table has at most
+ *             n_genomes - 1.  merges == NULL only counts.  A `cap` below the number of merges is FA_ERR_INVALID with nothing
+ *             written but *n_merges.
+ *   labels    may be NULL; otherwise [n_genomes], the partition at the build cut-off, byte for byte what fa_table_linkage
+ *             returns for the same arguments.
+ * out_device != 0: `merges` and `labels` are both DEVICE pointers.  n_clusters and stats may be NULL.  The same input gives
+ * the same bytes on every run. */
+int fa_table_dendrogram(const fa_cgi_row *rows, int64_t n_rows, int rows_device, int32_t n_genomes, const uint64_t *query_lengths,
+                        const uint64_t *reference_lengths, const fa_table_params *p, float missing, fa_merge *merges, int64_t cap,
+                        int64_t *n_merges, int32_t *labels, int out_device, int32_t *n_clusters, int64_t *stats);
+/* The partitions of a merge list at n_cuts >= 1 cut-offs.  min_identity is a HOST array of n_cuts values; for cut t, qc is
+ * formed exactly as in fa_table_linkage (rint of the value times 2^20, clamped just above the largest weight), and merge i
+ * applies iff s >= qc * size_lo * size_hi.  labels is laid out [n_cuts][n_genomes] (a DEVICE pointer when labels_device != 0,
+ * as `merges` is when merges_device != 0): labels[t][g] is the root of g in the forest parent[hi] = lo over the applying
+ * merges -- for a list of fa_table_dendrogram the smallest member of g's cluster, as everywhere else.  n_clusters, a HOST
+ * array of n_cuts values, may be NULL.  The call cannot know the cut-off a list was built with: a cut below it returns the
+ * build partition (the list ends there), so keep the build cut-off with the list (pyfastani_amd.clusters.Dendrogram does,
+ * and refuses such a cut).  FA_ERR_INVALID with nothing written: a negative or NaN cut; n_cuts < 1; n_merges outside
+ * [0, max(n_genomes - 1, 0)]; a merge with lo < 0, lo >= hi or hi >= n_genomes; a hi that occurs in two merges; a size
+ * below 1, or two sizes that add up to more than n_genomes; s < 0; present < 1.  More than 2^18 genomes, or more than
+ * 2^31 - 1 labels in all, are FA_ERR_UNSUPPORTED.  Runs like the other reductions: on the calling thread's current device, on
+ * a stream of its own, with memory from the device pool, finished when it returns, FA_ERR_NO_DEVICE without a device.  The
+ * same input gives the same bytes on every run. */
+int fa_dendrogram_cut(const fa_merge *merges, int64_t n_merges, int merges_device, int32_t n_genomes, const float *min_identity,
+                      int32_t n_cuts, int32_t *labels, int labels_device, int32_t *n_clusters);
 /* The order of step 4 on two candidates a and b = {S, |A||B|, lo, hi} (S >= 0, |A||B| >= 1, labels >= 0, else
  * FA_ERR_INVALID): *first = 1 when a comes before b, 0 when b comes before a, 2 when they are equal.  Host only; it calls the
  * comparator the kernels use. */

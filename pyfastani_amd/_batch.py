@@ -27,6 +27,14 @@ PAIR_DTYPE = np.dtype(
 )
 assert PAIR_DTYPE.itemsize == 24
 
+# one merge of an average-linkage dendrogram (``fa_merge``): what `pyfastani_amd.clusters.dendrogram` keeps.  The clusters
+# labelled ``lo < hi`` (their smallest genomes), of ``size_lo`` and ``size_hi`` genomes, merge into ``lo``; ``s`` is the fixed-point
+# sum of the identities over all ``size_lo * size_hi`` genome pairs between them, ``present`` of those pairs have a row
+MERGE_DTYPE = np.dtype(
+    [("lo", "<i4"), ("hi", "<i4"), ("size_lo", "<i4"), ("size_hi", "<i4"), ("s", "<i8"), ("present", "<i8")]
+)
+assert MERGE_DTYPE.itemsize == 32
+
 
 def pass_fragments():
     """Fragments the library maps per pass (``FA_PASS_FRAGMENTS``; 49152 by default, as in ``csrc/fa_knobs.h``).  The library

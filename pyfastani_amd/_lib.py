@@ -84,6 +84,18 @@ class Pair(C.Structure):
     ]
 
 
+class Merge(C.Structure):
+    # fa_merge: one merge of an average-linkage dendrogram (pyfastani_amd._batch.MERGE_DTYPE is the numpy face of it)
+    _fields_ = [
+        ("lo", C.c_int32),
+        ("hi", C.c_int32),
+        ("size_lo", C.c_int32),
+        ("size_hi", C.c_int32),
+        ("s", C.c_int64),
+        ("present", C.c_int64),
+    ]
+
+
 class TableParams(C.Structure):
     # fa_table_params: the filter and the cut-off of fa_table_pairs / fa_table_clusters
     _fields_ = [
@@ -183,6 +195,8 @@ SIGNATURES = {
     "fa_table_clusters": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _P(TableParams), _vp, _i32, _P(_i32), _vp]),
     "fa_table_representatives": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _P(TableParams), _vp, _vp, _vp, _i32, _P(_i32), _vp]),
     "fa_table_linkage": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _P(TableParams), _f32, _vp, _i32, _P(_i32), _vp]),
+    "fa_table_dendrogram": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _P(TableParams), _f32, _vp, _i64, _P(_i64), _vp, _i32, _P(_i32), _vp]),
+    "fa_dendrogram_cut": (_i32, [_vp, _i64, _i32, _i32, _vp, _i32, _vp, _i32, _vp]),
     "fa_debug_linkage_order": (_i32, [_P(_i64), _P(_i64), _P(_i32)]),
     "fa_table_best": (_i32, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _P(BestParams), _vp, _vp, _i64, _P(_i64), _i32, _vp]),
     "fa_screen_tile": (_i32, [_i32, _P(_i32)]),

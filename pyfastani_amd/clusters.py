@@ -1,6 +1,6 @@
 """What an all-vs-all is run for, computed where the hit table already is: the symmetric identity of every genome pair and
 the groups of genomes above a cut-off (species clusters at 95 %, dereplication at 99 %), by ``fa_table_pairs`` /
-``fa_table_clusters`` / ``fa_table_representatives`` / ``fa_table_linkage`` of the library (include/fastani_hip.h has the semantics; upstream's counterpart is the matrix output,
+``fa_table_clusters`` / ``fa_table_representatives`` / ``fa_table_linkage`` / ``fa_table_dendrogram`` of the library (include/fastani_hip.h has the semantics; upstream's counterpart is the matrix output,
 `outputPhylip`, include/fastani/cgi/compute_core_identity.pxd:39-51 of the reference, and whatever the user clusters it with).
 
 The rows are one genome set mapped against itself: ``query_id`` and ``ref_genome_id`` index the same list of ``n`` genomes,
@@ -15,7 +15,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._batch import PAIR_DTYPE, ROW_DTYPE
+from ._batch import MERGE_DTYPE, PAIR_DTYPE, ROW_DTYPE
 from ._lib import TableParams, check, lib
 
 
@@ -112,8 +112,8 @@ def average_linkage(rows, query_lengths, reference_lengths, fragment_length, min
     chain, and unlike `representatives` they do not depend on an order.  Means are compared exactly (fixed point, integers);
     ties go to the pair with the smaller genome numbers.  Returns ``labels``, int32 ``[n]``: the smallest genome number of
     every genome's cluster -- numpy for ``ROW_DTYPE`` rows, a tensor on the rows' device for device rows.  ``stats``, a dict,
-    receives ``rows``, ``pairs``, ``present``, ``rounds``, ``merges`` and ``n_clusters``.  Only this partition is returned:
-    no tree.  A negative or NaN ``min_identity`` or ``missing``, or an identity outside [0, 128], raises ``ValueError``; more
+    receives ``rows``, ``pairs``, ``present``, ``rounds``, ``merges`` and ``n_clusters``.  Only this partition is returned;
+    `dendrogram` returns the tree, to be cut at any higher cut-off.  A negative or NaN ``min_identity`` or ``missing``, or an identity outside [0, 128], raises ``ValueError``; more
     than 2^18 genomes ``NotImplementedError``."""
     t = _Table(rows, query_lengths, reference_lengths, fragment_length, minimum_fraction, min_identity, reciprocal)
     n_clusters, counters = C.c_int32(0), (C.c_int64 * 5)()
@@ -128,6 +128,90 @@ def average_linkage(rows, query_lengths, reference_lengths, fragment_length, min
         stats.update(rows=counters[0], pairs=counters[1], present=counters[2], rounds=counters[3], merges=counters[4],
                      n_clusters=n_clusters.value)
     return labels
+
+
+def _fixed_cutoff(value):
+    """qc as the library forms it from a float32 parameter: rint(value * 2^20), clamped just above the largest weight"""
+    return int(min(np.rint(np.float64(np.float32(value)) * 2.0 ** 20), 128.0 * 2.0 ** 20 + 1.0))
+
+
+class Dendrogram:
+    """An average-linkage tree of ``n`` genomes, as `dendrogram` builds it: ``merges``, the merges of the UPGMA walk in the
+    order of the walk -- ``MERGE_DTYPE`` records, or an int32 ``[n_merges, 8]`` tensor of their words on the rows' device --,
+    ``labels``, the partition at the build cut-off ``min_identity``, and ``missing``.  The tree is known down to
+    ``min_identity``: it is a forest with one tree per cluster of ``labels``."""
+
+    def __init__(self, n, merges, labels, min_identity, missing):
+        self.n, self.merges, self.labels, self.min_identity, self.missing = n, merges, labels, float(min_identity), float(missing)
+
+    def records(self):
+        """``merges`` as ``MERGE_DTYPE`` records on the host"""
+        if _is_tensor(self.merges):
+            return np.ascontiguousarray(self.merges.detach().cpu().numpy()).reshape(-1).view(MERGE_DTYPE)
+        return self.merges
+
+    def identity(self):
+        """The mean identity of every merge, float64 ``s / (size_lo * size_hi) / 2**20``: for display -- nothing is decided by
+        it, the cuts compare integers."""
+        m = self.records()
+        return m["s"] / (m["size_lo"].astype(np.float64) * m["size_hi"]) / 2.0 ** 20
+
+    def cut(self, min_identity):
+        """The partition at ``min_identity`` (``fa_dendrogram_cut``): labels ``[n]`` for a number, ``[len, n]`` for a
+        sequence of them -- what `average_linkage` returns at that cut-off, without another pass over the table.  numpy for
+        host merges, a tensor on their device for device merges.  A cut below the build cut-off (compared in fixed point, as
+        the library compares) raises ``ValueError``: the tree is not known there."""
+        scalar = np.ndim(min_identity) == 0
+        cuts = np.ascontiguousarray(np.atleast_1d(np.asarray(min_identity, dtype=np.float32)))
+        if cuts.ndim != 1 or len(cuts) < 1:
+            raise ValueError("a cut takes one cut-off or a sequence of at least one")
+        if np.any(np.isnan(cuts)) or np.any(cuts < 0):
+            raise ValueError("min_identity must be a number that is not negative")
+        built = _fixed_cutoff(self.min_identity)
+        for value in cuts:
+            if _fixed_cutoff(value) < built:
+                raise ValueError(f"a cut at {float(value)!r} lies below the cut-off the dendrogram was built with, {self.min_identity!r}")
+        n_merges = int(self.merges.shape[0])
+        head = (n_merges, self.n, C.c_void_p(cuts.ctypes.data), len(cuts))
+        if _is_tensor(self.merges) and self.merges.is_cuda:
+            import torch
+            merges = self.merges.contiguous()
+            with torch.cuda.device(merges.device):
+                torch.cuda.synchronize(merges.device)          # the library runs on a stream of its own: torch's writes are done
+                labels = torch.empty((len(cuts), self.n), dtype=torch.int32, device=merges.device)
+                check(lib.fa_dendrogram_cut(C.c_void_p(merges.data_ptr()), head[0], 1, *head[1:], C.c_void_p(labels.data_ptr()), 1, None))
+        else:
+            merges = np.ascontiguousarray(self.records(), dtype=MERGE_DTYPE)
+            labels = np.empty((len(cuts), self.n), dtype=np.int32)
+            check(lib.fa_dendrogram_cut(C.c_void_p(merges.ctypes.data), head[0], 0, *head[1:], C.c_void_p(labels.ctypes.data), 0, None))
+        return labels[0] if scalar else labels
+
+
+def dendrogram(rows, query_lengths, reference_lengths, fragment_length, minimum_fraction=0.2, min_identity=95.0, reciprocal=False,
+               missing=0.0, stats=None):
+    """The average-linkage (UPGMA) tree of the table, built once and cut anywhere (``fa_table_dendrogram``): the arguments, the
+    semantics and ``stats`` of `average_linkage`, ``min_identity`` being the BUILD cut-off -- the lowest identity at which
+    clusters are still merged, so the lowest at which the tree can be cut (for the whole tree: any value just above
+    ``missing``).  Returns a `Dendrogram`; its ``labels`` are those of ``average_linkage`` at ``min_identity``, its ``merges``
+    are sorted by decreasing mean identity, exactly and with the tie rule of the walk, so the partition at a higher cut-off is
+    a prefix of them: ``cut``.  `outputs.linkage_matrix` and `outputs.write_newick` take the merges."""
+    t = _Table(rows, query_lengths, reference_lengths, fragment_length, minimum_fraction, min_identity, reciprocal)
+    n_clusters, n_merges, counters = C.c_int32(0), C.c_int64(0), (C.c_int64 * 5)()
+    cap = max(t.n - 1, 0)
+    with t.on_device():
+        if t.torch:
+            labels = t.torch.empty(t.n, dtype=t.torch.int32, device=t.device)
+            merges = t.torch.empty((cap, 8), dtype=t.torch.int32, device=t.device)
+            out = (C.c_void_p(merges.data_ptr()), cap, C.byref(n_merges), C.c_void_p(labels.data_ptr()), 1)
+        else:
+            labels, merges = np.empty(t.n, dtype=np.int32), np.empty(cap, dtype=MERGE_DTYPE)
+            out = (C.c_void_p(merges.ctypes.data), cap, C.byref(n_merges), C.c_void_p(labels.ctypes.data), 0)
+        check(lib.fa_table_dendrogram(*t.head(), float(missing), *out, C.byref(n_clusters), counters))
+    if stats is not None:
+        stats.update(rows=counters[0], pairs=counters[1], present=counters[2], rounds=counters[3], merges=counters[4],
+                     n_clusters=n_clusters.value)
+    merges = merges[: n_merges.value] if t.torch else merges[: n_merges.value].copy()
+    return Dendrogram(t.n, merges, labels, min_identity, missing)
 
 
 def _order(order, t):

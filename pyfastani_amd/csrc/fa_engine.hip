@@ -525,6 +525,24 @@ int fa_table_linkage(const fa_cgi_row *rows, int64_t n_rows, int rows_device, in
     table_reduce(rows, n_rows, rows_device != 0, n_genomes, query_lengths, reference_lengths, p, want);
   });
 }
+int fa_table_dendrogram(const fa_cgi_row *rows, int64_t n_rows, int rows_device, int32_t n_genomes, const uint64_t *query_lengths,
+                        const uint64_t *reference_lengths, const fa_table_params *p, float missing, fa_merge *merges, int64_t cap,
+                        int64_t *n_merges, int32_t *labels, int out_device, int32_t *n_clusters, int64_t *stats) {
+  return guarded([&] {
+    TableRequest want;
+    want.clusters = want.linkage = want.dendrogram = true;
+    want.missing = missing;
+    want.merges = merges; want.merge_cap = cap; want.n_merges = n_merges;
+    want.labels = labels; want.labels_device = out_device != 0; want.n_clusters = n_clusters; want.stats = stats;
+    table_reduce(rows, n_rows, rows_device != 0, n_genomes, query_lengths, reference_lengths, p, want);
+  });
+}
+int fa_dendrogram_cut(const fa_merge *merges, int64_t n_merges, int merges_device, int32_t n_genomes, const float *min_identity,
+                      int32_t n_cuts, int32_t *labels, int labels_device, int32_t *n_clusters) {
+  return guarded([&] {
+    dendrogram_cut(merges, n_merges, merges_device != 0, n_genomes, min_identity, n_cuts, labels, labels_device != 0, n_clusters);
+  });
+}
 int fa_debug_linkage_order(const int64_t a[4], const int64_t b[4], int *first) {
   return guarded([&] {
     FA_REQUIRE(a && b && first, FA_ERR_INVALID, "null candidate or destination");

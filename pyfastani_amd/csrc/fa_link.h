@@ -68,4 +68,25 @@ FA_LINK_FN bool link_better(const LinkCand &b, const LinkCand &a) {
   return link_order(b, a) == 1;
 }
 
+// ---- the merge list (fa_table_dendrogram, fa_dendrogram_cut): a merge {lo, hi, size_lo, size_hi, s, present} is the
+// candidate {s, size_lo * size_hi, lo, hi} the walk merged, and the list is sorted under link_order
+// whether a record can be a merge of a table of n_genomes <= LINK_MAX_GENOMES genomes: with it size_lo * size_hi <= 2^34, so
+// link_passes does not overflow for any cut-off the drivers pass on (qc <= LINK_MAX_W + 1)
+FA_LINK_FN bool link_merge_ok(int32_t lo, int32_t hi, int32_t size_lo, int32_t size_hi, long long s, long long present,
+                              int32_t n_genomes) {
+  return lo >= 0 && lo < hi && hi < n_genomes && size_lo >= 1 && size_hi >= 1 && (long long)size_lo + (long long)size_hi <= (long long)n_genomes &&
+         s >= 0 && present >= 1;
+}
+
+FA_LINK_FN LinkCand link_merge_cand(int32_t lo, int32_t hi, int32_t size_lo, int32_t size_hi, long long s) {
+  return LinkCand{s, (long long)size_lo * (long long)size_hi, lo, hi};
+}
+
+// the fixed-point cut-off of a float parameter, as fa_table_linkage forms qc: no weight exceeds LINK_MAX_W, so a cut-off above
+// it merges nothing whatever its value, and neither does the clamped one.  value >= 0 (not NaN)
+FA_LINK_FN long long link_cutoff(float value) {
+  const double d = rint((double)value * LINK_SCALE);
+  return d < (double)(LINK_MAX_W + 1) ? (long long)d : LINK_MAX_W + 1;
+}
+
 }  // namespace fa

@@ -1,6 +1,7 @@
 // fa_linkage.hip.h -- average-linkage (UPGMA) clusters of an all-vs-all hit table on the device (fa_table_linkage): rows ->
 // present pairs with a fixed-point weight -> rounds that merge every mutual nearest pair of clusters -> labels.  Nothing
-// here is on the mapping path: the kernels run only under that entry point, on a stream of the call's own.
+// here is on the mapping path: the kernels run only under that entry point, on a stream of the call's own.  The second half of
+// the file keeps the merges of those rounds as a dendrogram (fa_table_dendrogram) and cuts such a list (fa_dendrogram_cut).
 //
 // Semantics (include/fastani_hip.h has them in full; fa_link.h the arithmetic).  A pair of genomes is present iff it exists
 // after the filter of fa_table.hip.h and, with `reciprocal`, has both directions; its weight is w = rint(identity * 2^20).
@@ -47,8 +48,10 @@ struct LinkStatus {
   unsigned int changed;                        // the last round (1-based) in which a pair merged
   unsigned int live;                           // k_link_segments: entries of this round's directed view
   unsigned int unique;                         // reduce-by-key: distinct keys, the dropped one included
-  unsigned int pad;
+  unsigned int merges;                         // k_link_record (fa_table_dendrogram only): merge records taken so far | LINK_LOST
 };
+// in LinkStatus::merges, above any count (at most 2^18 - 1): k_link_record did not find a merging pair's entry in its run
+constexpr unsigned int LINK_LOST = 0x80000000u;
 
 struct LinkArgs {
   const unsigned long long *keys;      // this round's directed view: distinct keys, sorted
@@ -167,6 +170,152 @@ __global__ __launch_bounds__(256) void k_link_relabel(LinkArgs a) {
   const int32_t from = a.parent[key >> a.bits], to = a.parent[key & ((1ULL << a.bits) - 1ULL)];
   a.next_keys[i] = from == to ? link_dropped(a) : (unsigned long long)from << a.bits | (unsigned long long)to;
   a.next_sums[i] = a.sums[i];
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// The merge list (fa_table_dendrogram) and its cuts (fa_dendrogram_cut)
+// ------------------------------------------------------------------------------------------------------------
+// The rounds above compute every merge of the sequential walk; k_link_record, launched between k_link_best and k_link_merge
+// under fa_table_dendrogram only, keeps them.  The thread of the smaller label knows both labels and both sizes before
+// k_link_merge adds them; the pair's (sum, count) of this round is the entry `to == hi` of its run, found by a binary search
+// (the run is sorted by key), so nothing more travels through k_link_best.  A wave takes its output slots with one atomicAdd
+// (ballot, popcount prefix); the slots depend on the order the waves arrive in, the result does not: the driver sorts the
+// records under the order of step 4 (MergeBefore), which is total on them -- every label is absorbed once, so no two records
+// share `hi` -- and which is the order the sequential walk merges in (fastani_hip.h).
+__global__ __launch_bounds__(256) void k_link_record(LinkArgs a, fa_merge *merges, int64_t cap) {
+  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  bool merging = false;
+  fa_merge m;
+  m.lo = m.hi = m.size_lo = m.size_hi = 0; m.s = m.present = 0;
+  if (g < a.n_genomes) {
+    const int32_t b = a.best[g];
+    if (b > (int32_t)g && b < a.n_genomes && a.best[b] == (int32_t)g) {
+      merging = true;
+      const unsigned long long key = (unsigned long long)g << a.bits | (unsigned long long)b;
+      const int32_t end = a.seg_end[g];
+      int32_t lo = a.seg_start[g], hi = end;
+      while (lo < hi) {
+        const int32_t mid = lo + (hi - lo) / 2;
+        if (a.keys[mid] < key) lo = mid + 1; else hi = mid;
+      }
+      m.lo = (int32_t)g; m.hi = b; m.size_lo = a.size[g]; m.size_hi = a.size[b];
+      // (the entry is there: b is g's partner because k_link_best read it.  Were it not, the call fails on LINK_LOST)
+      if (lo < end && a.keys[lo] == key) {
+        m.s = link_s(a.sums[lo], (long long)m.size_lo * (long long)m.size_hi, a.qm);
+        m.present = a.sums[lo].c;
+      } else {
+        atomicOr(&a.status->merges, LINK_LOST);
+      }
+    }
+  }
+  const unsigned long long mask = __ballot(merging);
+  if (!mask) return;                                               // (the whole wave)
+  const int leader = __ffsll((long long)mask) - 1;
+  int base = 0;
+  if (lane == leader) base = (int)(atomicAdd(&a.status->merges, (unsigned int)__popcll(mask)) & ~LINK_LOST);
+  base = __shfl(base, leader);
+  const int64_t slot = (int64_t)base + __popcll(mask & ((1ULL << lane) - 1ULL));
+  if (merging && slot < cap) merges[slot] = m;                     // (always: a table has at most n_genomes - 1 merges)
+}
+
+// "comes before" of step 4 on two merges
+struct MergeBefore {
+  __host__ __device__ bool operator()(const fa_merge &x, const fa_merge &y) const {
+    return link_order(link_merge_cand(x.lo, x.hi, x.size_lo, x.size_hi, x.s), link_merge_cand(y.lo, y.hi, y.size_lo, y.size_hi, y.s)) == 1;
+  }
+};
+// the same on the records' numbers: the sort moves 4-byte keys, not 32-byte records (which cost rocPRIM's sort kernels scratch
+// memory), and k_link_gather brings the records into the order found
+struct MergeIndexBefore {
+  const fa_merge *merges;
+  __host__ __device__ bool operator()(int32_t x, int32_t y) const { return MergeBefore()(merges[x], merges[y]); }
+};
+
+__global__ __launch_bounds__(256) void k_link_gather(const fa_merge *found, const int32_t *order, int64_t n_merges, fa_merge *sorted) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n_merges) sorted[i] = found[order[i]];
+}
+
+// A cut.  The list is checked first (k_cut_check, k_cut_twice: flags, as k_table_count sets them); a `hi` that occurs twice
+// is caught by scattering the merge's index to slot[hi] and reading it back in the next launch -- one of the two finds the
+// other's index.  With every hi unique, slot[] is also the way from a genome to the merge that absorbs its label, so the
+// forest of a cut is gathered, not scattered: parent[t][g] = lo of that merge if it passes cut t, else g (k_cut_parent).  lo <
+// hi: the forest has no cycle, and a chain of parents is at most n_genomes - 1 long (a deep tree: every merge absorbs the
+// label just above).  The roots are resolved by pointer jumping from one buffer into the other, bit_width(n_genomes - 1)
+// rounds: after round r a pointer spans 2^r steps of the chain or ends at the root.  A round reads only what the launch before
+// it wrote, so the bytes are the same on every run.
+constexpr unsigned CUT_BAD_MERGE = 1u, CUT_TWICE = 2u;
+
+struct CutStatus {
+  unsigned int flags;
+  unsigned int pad;
+};
+
+struct CutArgs {
+  const fa_merge *merges;
+  int64_t n_merges;
+  int32_t n_genomes, n_cuts;
+  const long long *qc;                 // [n_cuts]
+  int32_t *slot;                       // [n_genomes] the merge that absorbs a label, -1 for none: all -1 before k_cut_check
+  unsigned int *roots;                 // [n_cuts] zeroed before k_cut_roots
+  CutStatus *status;
+};
+
+__global__ __launch_bounds__(256) void k_cut_check(CutArgs a) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  bool bad = false;
+  if (i < a.n_merges) {
+    const fa_merge m = a.merges[i];
+    bad = !link_merge_ok(m.lo, m.hi, m.size_lo, m.size_hi, m.s, m.present, a.n_genomes);
+    if (!bad) a.slot[m.hi] = (int32_t)i;
+  }
+  const unsigned long long mask = __ballot(bad);
+  if (mask && (int)(threadIdx.x & 63) == __ffsll((long long)mask) - 1) atomicOr(&a.status->flags, CUT_BAD_MERGE);
+}
+
+__global__ __launch_bounds__(256) void k_cut_twice(CutArgs a) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  bool twice = false;
+  if (i < a.n_merges) {
+    const int32_t hi = a.merges[i].hi;
+    twice = hi >= 0 && hi < a.n_genomes && a.slot[hi] != (int32_t)i;       // (a bad merge wrote nothing; it has its own flag)
+  }
+  const unsigned long long mask = __ballot(twice);
+  if (mask && (int)(threadIdx.x & 63) == __ffsll((long long)mask) - 1) atomicOr(&a.status->flags, CUT_TWICE);
+}
+
+// the three kernels below: blockIdx.x over the genomes, blockIdx.y strided over the cuts
+__global__ __launch_bounds__(256) void k_cut_parent(CutArgs a, int32_t *parent) {
+  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= a.n_genomes) return;
+  const int32_t i = a.slot[g];
+  long long s = 0, n = 1;
+  int32_t lo = (int32_t)g;
+  if (i >= 0) {
+    const fa_merge m = a.merges[i];
+    s = m.s; n = (long long)m.size_lo * (long long)m.size_hi; lo = m.lo;
+  }
+  for (int32_t t = (int32_t)blockIdx.y; t < a.n_cuts; t += (int32_t)gridDim.y)
+    parent[(int64_t)t * a.n_genomes + g] = i >= 0 && link_passes(s, n, a.qc[t]) ? lo : (int32_t)g;
+}
+
+__global__ __launch_bounds__(256) void k_cut_jump(const int32_t *in, int32_t *out, int32_t n_genomes, int32_t n_cuts) {
+  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= n_genomes) return;
+  for (int32_t t = (int32_t)blockIdx.y; t < n_cuts; t += (int32_t)gridDim.y) {
+    const int32_t *row = in + (int64_t)t * n_genomes;
+    out[(int64_t)t * n_genomes + g] = row[row[g]];
+  }
+}
+
+__global__ __launch_bounds__(256) void k_cut_roots(CutArgs a, const int32_t *labels) {
+  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  for (int32_t t = (int32_t)blockIdx.y; t < a.n_cuts; t += (int32_t)gridDim.y) {
+    const bool root = g < a.n_genomes && labels[(int64_t)t * a.n_genomes + g] == (int32_t)g;
+    const unsigned long long mask = __ballot(root);
+    if (mask && (threadIdx.x & 63) == 0) atomicAdd(&a.roots[t], (unsigned int)__popcll(mask));
+  }
 }
 
 }  // namespace fa

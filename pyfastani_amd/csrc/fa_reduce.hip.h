@@ -1,5 +1,5 @@
 // fa_reduce.hip.h -- the host drivers of the reductions over results the mapper already holds: a hit table to pairs,
-// clusters, representatives and average-linkage clusters (fa_table.hip.h, fa_represent.hip.h, fa_linkage.hip.h), to every query's k best hits (fa_best.hip.h), the
+// clusters, representatives, average-linkage clusters and their dendrogram with its cuts (fa_table.hip.h, fa_represent.hip.h, fa_linkage.hip.h), to every query's k best hits (fa_best.hip.h), the
 // signature screen (fa_screen.hip.h) and its containment road (fa_contain.hip.h).  They use nothing of the sketch, the mapper or the workspace; fa_engine.hip wraps each
 // in its extern "C" entry point.
 //
@@ -110,10 +110,11 @@ inline unsigned int representatives(const TableEdge *edges, int64_t n_edges, con
 // The average-linkage clusters of the present pairs of a table over n_genomes > 0 genomes (fa_linkage.hip.h): labels (device)
 // receive every genome's smallest cluster member; returns the number of clusters and, in `rounds`, the rounds that merged a
 // pair.  `emit_into(keys, sums)` has k_table_write put the two directed entries of each of the n_pairs present pairs there.
-// `status` is the call's zeroed TableStatus; the stream is synchronised on return.
+// `status` is the call's zeroed TableStatus; the stream is synchronised on return.  With `merges` (device, room for n_genomes - 1:
+// fa_table_dendrogram) every merge is recorded there, in no order, and *n_merges is their number.
 template <typename Emit>
 inline unsigned int linkage(Emit emit_into, int64_t n_pairs, int32_t *labels, int32_t n_genomes, long long qm, long long qc,
-                            TableStatus *status, hipStream_t st, int64_t &rounds) {
+                            TableStatus *status, hipStream_t st, int64_t &rounds, fa_merge *merges = nullptr, int64_t *n_merges = nullptr) {
   FA_REQUIRE(n_pairs <= (int64_t)(1 << 30), FA_ERR_UNSUPPORTED, "more than 2^30 present pairs");
   StatusBlock<LinkStatus> d_link(st);
   DevBuf<unsigned long long> keys[3];         // the entries to sort, sorted, reduced to distinct keys
@@ -150,6 +151,7 @@ inline unsigned int linkage(Emit emit_into, int64_t n_pairs, int32_t *labels, in
       const dim3 entry_grid(ceil_div(n_in, 256));
       hipLaunchKernelGGL(k_link_segments, entry_grid, dim3(256), 0, st, l);
       hipLaunchKernelGGL(k_link_best, genome_grid, dim3(256), 0, st, l);
+      if (merges) hipLaunchKernelGGL(k_link_record, genome_grid, dim3(256), 0, st, l, merges, (int64_t)n_genomes - 1);
       hipLaunchKernelGGL(k_link_merge, genome_grid, dim3(256), 0, st, l);
       hipLaunchKernelGGL(k_link_labels, genome_grid, dim3(256), 0, st, l);
       hipLaunchKernelGGL(k_link_relabel, entry_grid, dim3(256), 0, st, l);
@@ -160,6 +162,11 @@ inline unsigned int linkage(Emit emit_into, int64_t n_pairs, int32_t *labels, in
       FA_REQUIRE(rounds < (int64_t)n_genomes, FA_ERR_INTERNAL, "average linkage merged in more rounds than there are genomes");
       n_in = (int64_t)now.live;
     }
+  }
+  if (merges) {
+    const unsigned int recorded = d_link.read(st).merges;
+    FA_REQUIRE(!(recorded & LINK_LOST), FA_ERR_INTERNAL, "a merging pair of clusters has no entry in its cluster's run");
+    *n_merges = (int64_t)recorded;
   }
   CompArgs c{};
   c.labels = labels; c.n_genomes = n_genomes; c.status = status;
@@ -176,6 +183,9 @@ struct TableRequest {
   bool representatives = false;            // with `clusters`: labels are representatives, not components
   bool linkage = false;                    // with `clusters`: labels are average-linkage clusters, `missing` their missing identity
   float missing = 0.0f;
+  // with `linkage`: the merge list as well (fa_table_dendrogram): labels may be null, and labels_device holds for merges too
+  bool dendrogram = false;
+  fa_merge *merges = nullptr; int64_t merge_cap = 0; int64_t *n_merges = nullptr;
   const int32_t *order = nullptr; double *identity = nullptr;
   fa_pair *pairs = nullptr; int64_t cap = 0; int64_t *n_pairs = nullptr; bool pairs_device = false;
   int32_t *labels = nullptr; bool labels_device = false; int32_t *n_clusters = nullptr; int64_t *stats = nullptr;
@@ -189,7 +199,8 @@ inline void table_reduce(const fa_cgi_row *rows, int64_t n_rows, bool rows_devic
   FA_REQUIRE(n_rows == 0 || rows, FA_ERR_INVALID, "null rows");
   FA_REQUIRE(n_genomes == 0 || (query_lengths && reference_lengths), FA_ERR_INVALID, "null genome lengths");
   FA_REQUIRE(n_rows <= (int64_t)INT32_MAX, FA_ERR_UNSUPPORTED, "a table of more than 2^31 - 1 rows");
-  if (want.clusters) FA_REQUIRE(n_genomes == 0 || want.labels, FA_ERR_INVALID, "null labels");
+  if (want.dendrogram) FA_REQUIRE(want.n_merges && (!want.merges || want.merge_cap >= 0), FA_ERR_INVALID, "null merge count or negative capacity");
+  else if (want.clusters) FA_REQUIRE(n_genomes == 0 || want.labels, FA_ERR_INVALID, "null labels");
   else FA_REQUIRE(want.n_pairs && want.cap >= 0, FA_ERR_INVALID, "null pair count or negative capacity");
   std::vector<int32_t> pos;
   if (want.representatives) {
@@ -204,6 +215,8 @@ inline void table_reduce(const fa_cgi_row *rows, int64_t n_rows, bool rows_devic
     FA_REQUIRE(dm < dc, FA_ERR_INVALID, "missing must lie below min_identity");
     FA_REQUIRE(n_genomes <= LINK_MAX_GENOMES, FA_ERR_UNSUPPORTED, "average linkage over more than 2^18 genomes");
     // no weight exceeds LINK_MAX_W: a cut-off above it merges nothing whatever its value, and neither does the clamped one
+    // (link_cutoff of fa_link.h is this rule for one float: fa_dendrogram_cut forms its qc with it, and clusters._fixed_cutoff
+    // restates it in Python; the three must stay one rule for a cut to give the bytes of this call)
     qc = (long long)std::min(dc, (double)(LINK_MAX_W + 1));
     qm = (long long)std::min(dm, (double)LINK_MAX_W);
   }
@@ -276,12 +289,41 @@ inline void table_reduce(const fa_cgi_row *rows, int64_t n_rows, bool rows_devic
 
   int64_t rounds = 0;
   unsigned int roots = 0;
-  if (n_genomes && want.linkage) {
+  auto emit_into = [&](unsigned long long *link_keys, LinkSum *link_sums) {
+    a.link_keys = link_keys; a.link_sums = link_sums;
+    emit();
+  };
+  if (want.dendrogram) {
+    // everything lands in buffers of the call's own first: a short `cap` leaves the caller's memory as it was
+    int64_t n_merges = 0;
+    DevBuf<int32_t> d_labels;
+    DevBuf<fa_merge> found, sorted;
+    DevBuf<int32_t> order;                     // the records' numbers in the order of the walk
+    if (n_genomes) {
+      d_labels.ensure((size_t)n_genomes);
+      found.ensure((size_t)std::max(n_genomes - 1, 1));
+      roots = linkage(emit_into, n_emit, d_labels.p, n_genomes, qm, qc, d_status.p, st, rounds, found.p, &n_merges);
+      FA_REQUIRE(n_merges == (int64_t)n_genomes - (int64_t)roots, FA_ERR_INTERNAL, "the merge list and the labels disagree on the number of merges");
+    }
+    *want.n_merges = n_merges;
+    FA_REQUIRE(!want.merges || n_merges <= want.merge_cap, FA_ERR_INVALID, "the merge buffer is smaller than the number of merges");
+    const hipMemcpyKind kind = want.labels_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (want.merges && n_merges) {
+      // the order of the walk (fa_linkage.hip.h): total on the records, so the bytes do not depend on the slots they were taken in
+      sorted.ensure((size_t)n_merges);
+      order.ensure((size_t)n_merges);
+      with_temp(temp, [&](void *t, size_t &bytes) {
+        return rocprim::merge_sort(t, bytes, rocprim::counting_iterator<int32_t>(0), order.p, (size_t)n_merges, MergeIndexBefore{found.p}, st);
+      });
+      hipLaunchKernelGGL(k_link_gather, dim3(ceil_div(n_merges, 256)), dim3(256), 0, st, (const fa_merge *)found.p, (const int32_t *)order.p, n_merges,
+                         sorted.p);
+      FA_HIP(hipGetLastError());
+      FA_HIP(hipMemcpyAsync(want.merges, sorted.p, (size_t)n_merges * sizeof(fa_merge), kind, st));
+    }
+    if (want.labels && n_genomes) FA_HIP(hipMemcpyAsync(want.labels, d_labels.p, (size_t)n_genomes * sizeof(int32_t), kind, st));
+    FA_HIP(hipStreamSynchronize(st));
+  } else if (n_genomes && want.linkage) {
     Staged<int32_t> labels(want.labels, want.labels_device, (size_t)n_genomes);
-    auto emit_into = [&](unsigned long long *link_keys, LinkSum *link_sums) {
-      a.link_keys = link_keys; a.link_sums = link_sums;
-      emit();
-    };
     roots = linkage(emit_into, n_emit, labels.dev(), n_genomes, qm, qc, d_status.p, st, rounds);
     labels.finish(st);
     FA_HIP(hipStreamSynchronize(st));
@@ -321,6 +363,80 @@ inline void table_reduce(const fa_cgi_row *rows, int64_t n_rows, bool rows_devic
     want.stats[2] = (int64_t)status.edges; want.stats[3] = rounds;
     if (want.linkage) want.stats[4] = (int64_t)n_genomes - (int64_t)roots;
   }
+}
+
+// The partitions of a merge list at n_cuts cut-offs (fa_dendrogram_cut; fa_linkage.hip.h has the road)
+inline void dendrogram_cut(const fa_merge *merges, int64_t n_merges, bool merges_device, int32_t n_genomes, const float *min_identity,
+                           int32_t n_cuts, int32_t *labels, bool labels_device, int32_t *n_clusters) {
+  FA_REQUIRE(n_cuts >= 1 && min_identity, FA_ERR_INVALID, "a cut needs at least one cut-off");
+  FA_REQUIRE(n_genomes >= 0, FA_ERR_INVALID, "negative number of genomes");
+  FA_REQUIRE(n_merges >= 0 && n_merges <= (int64_t)std::max(n_genomes - 1, 0), FA_ERR_INVALID, "the number of merges lies outside [0, n_genomes - 1]");
+  FA_REQUIRE(n_merges == 0 || merges, FA_ERR_INVALID, "null merges");
+  FA_REQUIRE(n_genomes == 0 || labels, FA_ERR_INVALID, "null labels");
+  std::vector<long long> qc((size_t)n_cuts);
+  for (int32_t t = 0; t < n_cuts; t++) {
+    FA_REQUIRE(min_identity[t] >= 0.0f, FA_ERR_INVALID, "min_identity must be a number that is not negative");          // (false for NaN)
+    qc[(size_t)t] = link_cutoff(min_identity[t]);
+  }
+  FA_REQUIRE(n_genomes <= LINK_MAX_GENOMES, FA_ERR_UNSUPPORTED, "average linkage over more than 2^18 genomes");
+  FA_REQUIRE((int64_t)n_cuts * (int64_t)n_genomes <= (int64_t)INT32_MAX, FA_ERR_UNSUPPORTED, "more than 2^31 - 1 labels");
+  require_device();
+  if (!n_genomes) {
+    if (n_clusters) std::fill(n_clusters, n_clusters + n_cuts, 0);
+    return;
+  }
+  CallStream stream;
+  hipStream_t st = stream.s;
+  StatusBlock<CutStatus> d_status(st);
+  DevBuf<fa_merge> d_merges;
+  DevBuf<long long> d_qc;
+  DevBuf<int32_t> slot, other;
+  DevBuf<unsigned int> d_roots;
+  const size_t n = (size_t)n_genomes, total = n * (size_t)n_cuts;
+
+  CutArgs a{};
+  a.n_merges = n_merges; a.n_genomes = n_genomes; a.n_cuts = n_cuts; a.status = d_status.p;
+  slot.ensure(n);
+  FA_HIP(hipMemsetAsync(slot.p, 0xFF, n * sizeof(int32_t), st));
+  a.slot = slot.p;
+  if (n_merges) {
+    // the verdict on the list is read before an output is touched
+    a.merges = on_device(merges, merges_device, (size_t)n_merges, d_merges, st);
+    const dim3 merge_grid(ceil_div(n_merges, 256));
+    hipLaunchKernelGGL(k_cut_check, merge_grid, dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_cut_twice, merge_grid, dim3(256), 0, st, a);
+    FA_HIP(hipGetLastError());
+    const CutStatus status = d_status.read(st);
+    FA_REQUIRE(!(status.flags & CUT_BAD_MERGE), FA_ERR_INVALID,
+               "a merge is not 0 <= lo < hi < n_genomes with sizes >= 1 that add up to n_genomes at most, s >= 0 and present >= 1");
+    FA_REQUIRE(!(status.flags & CUT_TWICE), FA_ERR_INVALID, "a label is merged away twice: the same hi in two merges");
+  }
+  d_qc.upload(qc, st);
+  a.qc = d_qc.p;
+  // round r reads buffer (r - 1) % 2 and writes buffer r % 2 (k_cut_parent writes buffer 0): the last one is the output
+  const int rounds = (int)bit_width_u64((unsigned long long)(n_genomes - 1));
+  Staged<int32_t> out(labels, labels_device, total);
+  other.ensure(total);
+  int32_t *buffer[2];
+  buffer[rounds % 2] = out.dev();
+  buffer[1 - rounds % 2] = other.p;
+  const dim3 grid((unsigned)ceil_div(n_genomes, 256), (unsigned)std::min(n_cuts, 65535));
+  hipLaunchKernelGGL(k_cut_parent, grid, dim3(256), 0, st, a, buffer[0]);
+  for (int r = 1; r <= rounds; r++)
+    hipLaunchKernelGGL(k_cut_jump, grid, dim3(256), 0, st, (const int32_t *)buffer[(r - 1) % 2], buffer[r % 2], n_genomes, n_cuts);
+  std::vector<unsigned int> roots;
+  if (n_clusters) {
+    d_roots.ensure((size_t)n_cuts);
+    FA_HIP(hipMemsetAsync(d_roots.p, 0, (size_t)n_cuts * sizeof(unsigned int), st));
+    a.roots = d_roots.p;
+    hipLaunchKernelGGL(k_cut_roots, grid, dim3(256), 0, st, a, (const int32_t *)out.dev());
+    roots.resize((size_t)n_cuts);
+    d_roots.download(roots.data(), roots.size(), st);
+  }
+  FA_HIP(hipGetLastError());
+  out.finish(st);
+  FA_HIP(hipStreamSynchronize(st));
+  for (size_t t = 0; t < roots.size(); t++) n_clusters[t] = (int32_t)roots[t];
 }
 
 // ------------------------------------------------------------------------------------------------------------

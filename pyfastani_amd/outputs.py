@@ -67,6 +67,83 @@ def write_representatives(path, names, labels, identity):
             f.write(f"{name}\t{names[int(label)]}\t{float(value):.6g}\n")
 
 
+def _merge_records(merges):
+    """the merges of a `pyfastani_amd.clusters.Dendrogram` -- ``MERGE_DTYPE`` records, or the int32 ``[n_merges, 8]`` tensor of
+    their words -- as records on the host, with every merge's mean identity in float64"""
+    if hasattr(merges, "cpu"):
+        from ._batch import MERGE_DTYPE
+        merges = np.ascontiguousarray(merges.detach().cpu().numpy()).reshape(-1).view(MERGE_DTYPE)
+    merges = np.asarray(merges)
+    identity = merges["s"] / (merges["size_lo"].astype(np.float64) * merges["size_hi"]) / 2.0 ** 20
+    return merges, identity
+
+
+def linkage_matrix(merges, n):
+    """scipy's linkage matrix ``Z``, float64 ``[n - 1, 4]``, of the merges of a dendrogram over ``n`` genomes
+    (`pyfastani_amd.clusters.dendrogram`): row ``i`` holds the ids of the two clusters merge ``i`` joins -- a genome number,
+    or ``n + j`` for the result of merge ``j``; the smaller id first --, their distance ``100 - identity`` and the number of
+    genomes of the result.  `scipy.cluster.hierarchy.fcluster` and `dendrogram` take it.  A list that is not exactly
+    ``n - 1`` merges long is a forest (the tree was built with a cut-off above its root) and raises ``ValueError``."""
+    merges, identity = _merge_records(merges)
+    if n < 1 or len(merges) != n - 1:
+        raise ValueError(f"a linkage matrix of {n} genomes has {n - 1} merges, not {len(merges)}: build the dendrogram with a lower cut-off")
+    z = np.zeros((len(merges), 4), dtype=np.float64)
+    node = np.arange(n)                                             # the id of the cluster a label stands for now
+    for i, m in enumerate(merges):
+        a, b = int(node[m["lo"]]), int(node[m["hi"]])
+        z[i] = (min(a, b), max(a, b), 100.0 - identity[i], int(m["size_lo"]) + int(m["size_hi"]))
+        node[m["lo"]] = n + i
+    return z
+
+
+def _newick_name(name):
+    name = str(name)
+    if any(c.isspace() or c in "()[]':;," for c in name):
+        return "'" + name.replace("'", "''") + "'"
+    return name
+
+
+def write_newick(path, names, merges, n):
+    """The merges of a dendrogram over ``n`` genomes (`pyfastani_amd.clusters.dendrogram`) as Newick: one tree per cluster of
+    the list -- a list built with a cut-off above its root is a forest --, one per line, in the order of the clusters' labels;
+    a genome no merge touches is written ``name;``.  The subtree of the smaller label comes first.  A node's height is
+    ``(100 - identity) / 2``, so two leaves are ``100 - identity`` of the merge that joined them apart; leaves are at 0.
+    Heights are rounded to six decimals and a branch length is the difference of two of them, written with six decimals: the
+    lengths from a node down to every leaf below it add up to the same number.  They are never negative, because the list is
+    sorted.  A name with whitespace or one of ``()[]':;,`` is single-quoted, with ``'`` doubled."""
+    merges, identity = _merge_records(merges)
+    if len(names) != n:
+        raise ValueError("one name per genome")
+    height = [0] * n + [int(round((100.0 - float(v)) / 2.0 * 1e6)) for v in identity]      # in units of 1e-6; leaves, then merges
+    children = {}
+    node = list(range(n))
+    absorbed = [False] * n
+    for i, m in enumerate(merges):
+        lo, hi = int(m["lo"]), int(m["hi"])
+        children[n + i] = (node[lo], node[hi])
+        node[lo] = n + i
+        absorbed[hi] = True
+    with open(path, "w") as f:
+        for label in range(n):
+            if absorbed[label]:
+                continue
+            # depth first without recursion (a tree can be n - 1 deep): a node, or a piece of text to write on the way back
+            text, stack = [], [node[label]]
+            while stack:
+                item = stack.pop()
+                if isinstance(item, str):
+                    text.append(item)
+                elif item < n:
+                    text.append(_newick_name(names[item]))
+                else:
+                    first, second = children[item]
+                    lengths = [height[item] - height[child] for child in (first, second)]
+                    pieces = [f":{d // 1000000}.{d % 1000000:06d}" if d >= 0 else f":-{-d // 1000000}.{-d % 1000000:06d}" for d in lengths]
+                    text.append("(")
+                    stack += [pieces[1] + ")", second, pieces[0] + ",", first]
+            f.write("".join(text) + ";\n")
+
+
 def write_hits(path, query_names, reference_names, rows):
     """FastANI's tabular output: query, reference, ANI, mapped fragments, total query fragments (one line per hit,
     queries in order, hits of a query by decreasing identity)."""

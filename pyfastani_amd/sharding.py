@@ -242,6 +242,14 @@ class ResidentHitTable:
         return _clusters.average_linkage(self._rows_in_place(tables), query_lengths, reference_lengths, fragment_length,
                                          minimum_fraction, min_identity, reciprocal, missing, stats)
 
+    def dendrogram(self, tables, query_lengths, reference_lengths, fragment_length, minimum_fraction=0.2, min_identity=95.0,
+                   reciprocal=False, missing=0.0, stats=None):
+        """`pyfastani_amd.clusters.dendrogram` over an exchanged table (what `step` returns) of an all-vs-all: the tree, its
+        merges and labels where the table is, with the count rows dropped and the ranks joined as for `clusters`."""
+        from . import clusters as _clusters
+        return _clusters.dendrogram(self._rows_in_place(tables), query_lengths, reference_lengths, fragment_length,
+                                    minimum_fraction, min_identity, reciprocal, missing, stats)
+
     def representatives(self, tables, query_lengths, reference_lengths, fragment_length, minimum_fraction=0.2, min_identity=95.0,
                         reciprocal=False, order=None, stats=None):
         """`pyfastani_amd.clusters.representatives` over an exchanged table (what `step` returns) of an all-vs-all:

@@ -5,6 +5,7 @@
 // library admits is 2^18 genomes: two clusters of 2^17, every pair present at identity 128 or every pair missing at the
 // largest `missing`, against the largest cut-off the driver passes on (LINK_MAX_W + 1).  The order is also held against a
 // second comparison that divides instead of multiplying (quotient, then remainders by cross products that fit 128 bits).
+// The merge list of fa_table_dendrogram / fa_dendrogram_cut: what counts as a merge, its candidate and the cut-off of a float.
 #include <cstdint>
 #include <cstdio>
 
@@ -42,6 +43,25 @@ int main() {
   CHECK(link_order(top, tied) == 1 && link_order(tied, top) == 0 && link_order(top, top) == 2, "equal averages: the labels decide");
   const LinkCand nothing{0, 0, 0, 0};
   CHECK(link_better(top, nothing) && !link_better(nothing, top) && !link_better(nothing, nothing) && !link_better(top, top), "none comes last");
+
+  // the merge list (fa_table_dendrogram, fa_dendrogram_cut): what is a merge, its candidate, and the cut-off of a float
+  const int32_t n_max = LINK_MAX_GENOMES;
+  CHECK(link_merge_ok(0, 1, 1, 1, 0, 1, 2) && link_merge_ok(0, n_max - 1, n_max / 2, n_max / 2, s_full, pairs, n_max), "the smallest and the largest merge");
+  CHECK(!link_merge_ok(-1, 1, 1, 1, 0, 1, 2) && !link_merge_ok(1, 1, 1, 1, 0, 1, 2) && !link_merge_ok(2, 1, 1, 1, 0, 1, 3) && !link_merge_ok(0, 2, 1, 1, 0, 1, 2),
+        "labels out of order or out of range");
+  CHECK(!link_merge_ok(0, 1, 0, 1, 0, 1, 2) && !link_merge_ok(0, 1, 1, -1, 0, 1, 2) && !link_merge_ok(0, 1, 2, 1, 0, 1, 2), "sizes below 1 or beyond the genomes");
+  CHECK(!link_merge_ok(0, 1, INT32_MAX, INT32_MAX, 0, 1, n_max) && !link_merge_ok(0, INT32_MAX, 1, 1, 0, 1, INT32_MAX), "the largest int32 in a size or a label");
+  CHECK(!link_merge_ok(0, 1, 1, 1, -1, 1, 2) && !link_merge_ok(0, 1, 1, 1, 0, 0, 2) && !link_merge_ok(0, 1, 1, 1, INT64_MIN, INT64_MIN, 2), "a negative sum, no present pair");
+  CHECK(link_merge_ok(0, 1, 1, 1, INT64_MAX, INT64_MAX, 2), "the largest sum is admitted: the cut compares it, it does not multiply it");
+  const LinkCand widest = link_merge_cand(0, n_max - 1, n_max / 2, n_max / 2, s_full);
+  CHECK(widest.n == pairs && widest.s == s_full && widest.lo == 0 && widest.hi == n_max - 1, "the candidate of the largest merge");
+  CHECK(link_order(top, widest) == 1 && link_order(widest, top) == 0 && link_passes(widest.s, widest.n, link_cutoff(128.0f)) && !link_passes(widest.s, widest.n, link_cutoff(128.5f)),
+        "the largest merge against the largest cut-offs");
+  CHECK(link_passes(INT64_MAX, pairs, link_cutoff(3.0e38f)) && !link_passes(0, pairs, link_cutoff(1.0e-6f)) && link_passes(0, pairs, link_cutoff(0.0f)),
+        "the cut-off test at the ends of s");
+  CHECK(link_cutoff(0.0f) == 0 && link_cutoff(-0.0f) == 0 && link_cutoff(95.0f) == 95LL << 20 && link_cutoff(128.0f) == LINK_MAX_W, "cut-offs of round values");
+  CHECK(link_cutoff(128.00001f) == LINK_MAX_W + 1 && link_cutoff(3.4e38f) == LINK_MAX_W + 1 && link_cutoff(INFINITY) == LINK_MAX_W + 1, "the clamp, infinity included");
+  CHECK(link_cutoff(1.0f) == link_cutoff(1.00000012f), "two float32 with one fixed-point value");
 
   long checked = 0;
   for (int trial = 0; trial < 200000; trial++) {
