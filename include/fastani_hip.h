@@ -661,7 +661,9 @@ int fa_mapper_last_timings(fa_mapper *m, float *ms, int n);
  * [15] slide-event capacity, [16] loci capacity.
  * Last part: [17] k_l1 launches (size classes), [18] [19] [20] their thread counts (0: none), [21] pre-filter on, [22] k_l2_scan
  * over sorted loci, [23] 32-bit slide events, [24] k_query_fused, [25] offset-major k_l2_events order, [26] wide-state scan
- * launched, [27] the sketch bound it ran with, [28] seed slots of its last k_l1 class.  A call that ran no part leaves 17-28 at 0. */
+ * launched, [27] the sketch bound it ran with, [28] seed slots of its last k_l1 class.  A call that ran no part leaves 17-28 at 0.
+ * Both layouts, this one and fa_mapper_last_timings', are generated from the tables of pyfastani_amd/csrc/fa_diag.h, which
+ * names every entry; pyfastani_amd/diagnostics.py reads them by those names. */
 int fa_mapper_debug_spec(fa_mapper *m, int64_t *out, int n);
 /* on != 0: also bracket the L2 stage of every pass with two HIP events (slot [16] above).  Off by default: an event
  * record costs the stream about as much as a small kernel. */

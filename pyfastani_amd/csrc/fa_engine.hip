@@ -834,11 +834,9 @@ int fa_mapper_debug_spec(fa_mapper *m, int64_t *out, int n) {
   const Spec &s = m->spec;
   const Forms &f = m->ws[m->last_ws].last_forms;
   auto ppm = [](float share) { return (int64_t)std::lround((double)share * 1e6); };
-  const int64_t v[] = {s.init, s.smax, s.seed_slots, ppm(s.l1_small_share), ppm(s.l1_mid_share), ppm(s.l1_tiny_share),
-                       s.l1_prefilter, s.l1_no_small, s.l2_loci_last, s.redo, s.part_frags, s.fuse_skip, s.fuse_penalty,
-                       s.smax_misses, (int64_t)s.scratch_words, (int64_t)s.items_cap, s.l_cap,
-                       f.n_l1, f.l1_threads[0], f.l1_threads[1], f.l1_threads[2], f.prefilter, f.scan_sorted, f.wide, f.fused,
-                       f.ordered, f.redo, f.smax, f.seed_slots};
+#define FA_SPEC_VALUE(name, expr) expr,
+  const int64_t v[] = {FA_SPEC_FIELDS(FA_SPEC_VALUE)};
+#undef FA_SPEC_VALUE
   for (int i = 0; i < n; i++) out[i] = i < (int)(sizeof(v) / sizeof(v[0])) ? v[i] : 0;
   return FA_OK;
 }

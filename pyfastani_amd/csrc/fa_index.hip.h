@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "fa_common.h"
+#include "fa_diag.h"
 #include "fa_k1.hip.h"
 #include "fa_knobs.h"
 #include "fa_map.hip.h"
@@ -24,12 +25,7 @@ using namespace fa;
 
 struct fa_genomes;   // (fa_batch.hip.h: a workspace keeps the batch of the one-query call, by pointer)
 
-// The slots of Workspace::last_ms (fa_mapper_last_timings), laid out as include/fastani_hip.h documents: [MS_STAGE + 0..3] sketch,
-// lookup + L1, L2, CGI ms; [MS_HOST + 0..2] the host-side split of fa_mapper_query; also [MS_L1_SORTED] [MS_L1_MERGED] (FA_L1_STATS
-// samples) and [MS_L1_OFF_FAST] (fragments that left k_l1's fast form)
-enum TimingSlot : int { MS_STAGE = 0, MS_TOTAL = 4, MS_RECORDS, MS_LOCI, MS_EVENTS, MS_WIDE, MS_REPEATS, MS_HOST = 10, MS_CALL = 13,
-                        MS_L2_EVENTS = 16, MS_FUSED, MS_UNFUSED, MS_ORDERED, MS_L1_SORTED, MS_L1_MERGED, MS_L1_OFF_FAST, MS_TILE_LEN, MS_SLOTS };
-static_assert(MS_REPEATS == 9 && MS_ORDERED == 19 && MS_TILE_LEN == 23 && MS_SLOTS == 24, "the layout of fa_mapper_last_timings is ABI");
+// (the slots of Workspace::last_ms, TimingSlot, come from the table of fa_diag.h)
 
 // The way of the mapping records to the host: two buffers of `records` fa_hit_mapping in HBM, two in pinned host memory and an
 // event each.  k_map_write fills HBM buffer w & 1 with window w of a pass (fa_mapstream.h), an asynchronous copy takes it to

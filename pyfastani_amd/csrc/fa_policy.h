@@ -354,7 +354,7 @@ inline bool frag_order_gate(bool on, bool one, int genomes, int64_t F) { return 
 struct Verdict {
   enum Kind { ACCEPTED, VOIDED, SHRUNK, FAILED } kind = ACCEPTED;   // SHRUNK: void, and part_frags cut down; FAILED: F == 1 cannot shrink
   const char *what = nullptr;   // SHRUNK / FAILED: what overflowed the 32-bit offsets
-  bool miss = false;            // a speculated size was too small (fa_mapper_last_timings [9])
+  bool miss = false;            // a speculated size was too small (fa_mapper_last_timings [9], repeats)
   bool fuse_overflow = false;   // k_query_fused overflowed: the range runs again through the two kernels (fuse_overflowed)
   uint64_t loci = 0, events = 0, records = 0;   // live loci, slide events, records in the locus ranges
 };

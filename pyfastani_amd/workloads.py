@@ -205,9 +205,8 @@ def all_vs_all(genomes, fam, params=None, chunk=24, timings=True):
     * hits that survive the minimum-fraction filter stay inside the family, and hit membership is symmetric.
 
     Returns a dict of counts, timings and verdicts; the caller asserts the verdicts that apply to its cell."""
-    import ctypes as C
     import pyfastani_amd as pf
-    from ._lib import lib
+    from . import diagnostics
     params = params or {}
     n = len(genomes)
     with warnings.catch_warnings():
@@ -224,17 +223,16 @@ def all_vs_all(genomes, fam, params=None, chunk=24, timings=True):
         batch = mapper.upload_genomes(genomes)
         t_upload = time.time() - t0
         t0 = time.time()
-        rows, retries, phase = [], 0, np.zeros(5)
+        rows, passes = [], []
         for i in range(0, n, chunk):
             rows.append(batch.query_rows(i, min(chunk, n - i)))
-            ms = (C.c_float * 16)()
-            lib.fa_mapper_last_timings(mapper._h, ms, 16)
-            retries += int(ms[9])
-            phase += np.array(list(ms)[:5])
+            passes.append(diagnostics.timings(mapper))
         t_map = time.time() - t0
     rows = np.concatenate(rows)
+    ms = diagnostics.total(passes)
+    phase = (ms.sketch_ms, ms.l1_ms, ms.l2_ms, ms.cgi_ms, ms.total_ms)
     out = row_properties(rows, batch, mapper, genomes, fam)
-    out["repeated_attempts"] = retries
+    out["repeated_attempts"] = int(ms.repeats)
     if timings:
         out.update({"host_pack_s": t_pack, "sketch_index_s": t_index, "upload_queries_s": t_upload, "map_s": t_map,
                     "pairs_per_s_map_only": n * n / t_map if t_map > 0 else None,

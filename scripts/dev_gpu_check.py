@@ -3,7 +3,7 @@ import sys, os, time, ctypes as C
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import pyfastani_amd as pf
-from pyfastani_amd import _lib, synthetic as syn
+from pyfastani_amd import _lib, diagnostics, synthetic as syn
 from pyfastani_amd._lib import lib, check
 from oracle.oracle import OracleSketch
 
@@ -93,7 +93,7 @@ print(f"[{'OK' if ok else 'FAIL'}] L2 mappings gpu {len(gm)} oracle {len(omm)}")
 if not ok:
     sg, so = set(gm), set(omm)
     print("  only gpu", sorted(sg - so)[:5]); print("  only oracle", sorted(so - sg)[:5])
-ms = (C.c_float * 8)(); lib.fa_mapper_last_timings(mapper._h, ms, 8); print("timings ms", list(ms)[:5])
+ms = diagnostics.timings(mapper); print("timings ms", [ms.sketch_ms, ms.l1_ms, ms.l2_ms, ms.cgi_ms, ms.total_ms])
 
 # ---- protein golden ----
 def fasta(p):

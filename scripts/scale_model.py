@@ -18,7 +18,6 @@ draft assemblies of 50 log-normal contigs: uneven fragment counts -- the case th
     python scripts/scale_model.py --out profiles/r06_scale_model.json
 """
 import argparse
-import ctypes as C
 import json
 import os
 import sys
@@ -57,10 +56,8 @@ def one_rank_rccl_latency_ms(torch, n_bytes, reps=50):
 
 
 def run_workload(torch, name, genomes, steps):
-    import numpy as np
     import pyfastani_amd as pf
-    from pyfastani_amd import sharding
-    from pyfastani_amd._lib import lib
+    from pyfastani_amd import diagnostics, sharding
     n = len(genomes)
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
@@ -82,18 +79,16 @@ def run_workload(torch, name, genomes, steps):
             table = sharding.ResidentHitTable(owned, len(owned) * n, 1, collective=False)
             table.step(batch)
             torch.cuda.synchronize()
-            phases = np.zeros(5)
+            passes = []
             t0 = time.perf_counter()
             for _ in range(steps):
                 tables = table.step(batch)
-                ms = (C.c_float * 8)()
-                lib.fa_mapper_last_timings(mapper._h, ms, 8)
-                phases += np.array(list(ms)[:5])
+                passes.append(diagnostics.timings(mapper))
             torch.cuda.synchronize()
             dt = (time.perf_counter() - t0) / steps * 1e3
             rows = int(tables[0, 0, 0].item())
             ranks.append({"rank": r, "genomes": len(owned), "fragments": int(sum(weights[i] for i in owned)), "step_ms": dt,
-                          "device_ms": float(phases[4] / steps), "rows": rows})
+                          "device_ms": diagnostics.total(passes).total_ms / steps, "rows": rows})
             del batch, table, tables
         frs = [x["fragments"] for x in ranks]
         ms = [x["step_ms"] for x in ranks]

@@ -2,7 +2,7 @@
    python scripts/time_mappings.py [steps] [queries] [--stage-mb MB] [--config3 [FAMILIESxMEMBERS]] [--no-launch]
 
 The launch leg: device time per step of a 16-query launch against the 100-reference index of the bench (config 2), with and
-without mappings, the two alternating step by step.  Device time is slot [4] of fa_mapper_last_timings (pass start to
+without mappings, the two alternating step by step.  Device time is slot [4], total_ms, of fa_mapper_last_timings (pass start to
 hand-over, which follows the count, the scan and the first window of the records); the wall clock of the call also holds the
 way of the records to the host, window by window through the mapping stage (--stage-mb: its size per buffer, default the
 library's FA_MAP_STAGE_MB).
@@ -10,12 +10,11 @@ library's FA_MAP_STAGE_MB).
 The config-3 leg (--config3, default 20x50 = BASELINE config 3, 1000 x 1000 genomes of 5 Mb): the whole table's mappings range
 by range through GenomeBatch.iter_mappings, nothing kept but the counts: records, wall time against the plain query_rows
 table, peak RSS and fa_mapper_mapping_memory.  One bounded run, not a benchmark loop."""
-import argparse, sys, os, json, time, resource, ctypes as C
+import argparse, sys, os, json, time, resource
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import pyfastani_amd as pf
-from pyfastani_amd import workloads
-from pyfastani_amd._lib import lib
+from pyfastani_amd import diagnostics, workloads
 
 ap = argparse.ArgumentParser()
 ap.add_argument("steps", nargs="?", type=int, default=10)
@@ -36,9 +35,8 @@ def set_stage(mapper, mb):
 
 
 def device_ms(mapper):
-    ms = (C.c_float * 24)()
-    lib.fa_mapper_last_timings(mapper._h, ms, 24)
-    return ms[4], ms[3]
+    ms = diagnostics.timings(mapper)
+    return ms.total_ms, ms.cgi_ms
 
 
 def memory(mapper):

@@ -24,6 +24,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from pyfastani_amd import synthetic as syn  # noqa: E402
+from rules_cases import call_counters  # noqa: E402
 
 FIELDS = ("query_id", "query_seq_id", "ref_genome_id", "ref_seq_id", "ref_start_pos", "sketch_size", "conserved", "identity")
 
@@ -173,16 +174,6 @@ def expected_draft(case, q=0):
     maps = exp["maps"][q]
     parts = [maps[maps["ref_genome_id"] == name] for name, _, _, _ in exp["hits"][q]]
     return exp["hits"][q], (np.concatenate(parts) if parts else maps[:0])
-
-
-def call_counters(mapper):
-    """(repeated attempts, accepted parts) of the mapper's most recent query call: slots [9] and [17] + [18] of
-    fa_mapper_last_timings (speculation misses; parts whose sketch stage ran fused / as two kernels)."""
-    import ctypes as C
-    from pyfastani_amd._lib import lib, check
-    ms = (C.c_float * 24)()
-    check(lib.fa_mapper_last_timings(mapper._h, ms, 24))
-    return int(ms[9]), int(ms[17] + ms[18])
 
 
 def gpu_results(case, fresh=False):

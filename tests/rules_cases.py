@@ -354,11 +354,11 @@ def unpack(z, cells):
 
 
 def call_counters(mapper):
-    """(repeated attempts, accepted parts) of the mapper's most recent query call (fa_mapper_last_timings [9], [17] + [18])."""
-    from pyfastani_amd._lib import lib, check
-    ms = (C.c_float * 24)()
-    check(lib.fa_mapper_last_timings(mapper._h, ms, 24))
-    return int(ms[9]), int(ms[17] + ms[18])
+    """(repeated attempts, accepted parts) of the mapper's most recent query call: speculation misses; parts whose sketch stage
+    ran fused / as two kernels."""
+    from pyfastani_amd import diagnostics
+    ms = diagnostics.timings(mapper)
+    return int(ms.repeats), int(ms.fused + ms.unfused)
 
 
 if __name__ == "__main__":

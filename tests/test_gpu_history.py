@@ -26,27 +26,9 @@ from conftest import ROOT
 from oracle.oracle import OracleSketch
 from pyfastani_amd import _lib, synthetic as syn
 from pyfastani_amd._lib import lib, check
+from pyfastani_amd.diagnostics import spec, timings
 
 pytestmark = pytest.mark.gpu
-
-# fa_mapper_debug_spec, in the order include/fastani_hip.h documents
-SPEC_FIELDS = ("init", "smax", "seed_slots", "small_ppm", "mid_ppm", "tiny_ppm", "l1_prefilter", "l1_no_small", "l2_loci_last",
-               "redo", "part_frags", "fuse_skip", "fuse_penalty", "smax_misses", "scratch_words", "items_cap", "l_cap",
-               "n_l1", "l1_t0", "l1_t1", "l1_t2", "f_prefilter", "f_scan_sorted", "f_wide", "f_fused", "f_ordered", "f_redo",
-               "f_smax", "f_seed_slots")
-
-
-def spec(mapper):
-    out = (C.c_int64 * 32)()
-    check(lib.fa_mapper_debug_spec(mapper._h, out, 32))
-    assert list(out)[len(SPEC_FIELDS):] == [0, 0, 0]
-    return dict(zip(SPEC_FIELDS, list(out)))
-
-
-def timings(mapper):
-    ms = (C.c_float * 24)()
-    check(lib.fa_mapper_last_timings(mapper._h, ms, 24))
-    return list(ms)
 
 
 def hit_tuples(hits):
@@ -204,8 +186,8 @@ def run_sequence(ix, calls, tmp_path, mapper=None):
         assert hits == fresh_hits, "hits differ from a fresh mapper's, " + where
         if maps is not None and fresh_maps is not None:
             assert maps == fresh_maps, "mappings differ from a fresh mapper's, " + where
-        trace.append(dict(sp, repeats=int(ms[9]), wide_loci=int(ms[8]), left_fast=int(ms[22]), loci=int(ms[6]),
-                          maps=None if maps is None else len(maps)))
+        trace.append(dict(sp._asdict(), repeats=int(ms.repeats), wide_loci=int(ms.wide_loci), left_fast=int(ms.left_fast),
+                          loci=int(ms.loci), maps=None if maps is None else len(maps)))
     return trace
 
 
@@ -329,7 +311,7 @@ def test_event_width_and_sketch_bound(prot, tmp_path):
 def test_wide_state_scan_is_sticky(prot, tmp_path):
     """redo (sticky): a fragment of a two-residue repeat has a sketch of two, and the window of the random protein around its
     islands holds ~516 reference hashes between those two ranks -- a count beyond the one-byte state of k_l2_scan: the locus is
-    redone with the wide state (timings slot 8) and every later pass launches the wide-state scan as well."""
+    redone with the wide state (timings slot 8, wide_loci) and every later pass launches the wide-state scan as well."""
     t = run_sequence(prot, [("draft", "rand"), ("genome", "dinuc"), ("draft", "rand"), ("draft", "tandem"), ("genome", "dinuc")], tmp_path)
     keys = ("redo", "f_redo", "wide_loci", "repeats")
     assert [x["redo"] for x in t] == [0, 1, 1, 1, 1] and [x["f_redo"] for x in t] == [0, 1, 1, 1, 1], show(t, *keys)
@@ -366,7 +348,7 @@ def test_scan_order_follows_the_last_pass(nuc, tmp_path):
 def test_prefilter_is_sticky(scatter, tmp_path):
     """l1_prefilter (sticky): the scattered query's fragments have ~800 seed hits in hundreds of blocks.  A fresh mapper sorts
     them with 4 096 LDS slots, whose block table holds them; the slots then shrink to 1 024 (a third as many blocks), and on the
-    next call both fragments leave k_l1's block sort (timings slot 22) -- more than one in two hundred, so every later pass drops
+    next call both fragments leave k_l1's block sort (timings slot 22, left_fast) -- more than one in two hundred, so every later pass drops
     the hits that cannot belong to a candidate before the sort, the unrelated query's included.
     Not reached on an index of test size: l1_no_small (fold the 256-thread class away once fragments still leave it with the
     pre-filter on and a second class beside it), which needs fragments of more than ~3 300 seed hits and, in the same pass,
@@ -481,7 +463,7 @@ def test_concurrent_histories_on_one_mapper(nuc, prot, tmp_path):
     for th in threads:
         th.join()
     assert not errors, errors
-    assert spec(pmapper)["smax"] >= 511
+    assert spec(pmapper).smax >= 511
 
 
 # ----------------------------------------------------------------------------------------------------------------

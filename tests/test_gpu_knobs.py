@@ -23,7 +23,6 @@ import sys
 import pytest
 
 from conftest import ROOT
-from test_gpu_history import SPEC_FIELDS
 
 pytestmark = pytest.mark.gpu
 
@@ -31,19 +30,14 @@ MAPPING_RECORD_BYTES = 32            # sizeof(fa_hit_mapping), include/fastani_h
 STAGES = ("sketch", "lookup", "l1", "l2 events", "l2 scan", "cgi")      # debug_sync's names, in the order of a pass
 
 CHILD = """
-import ctypes as C, json, sys
+import json, sys
 sys.path.insert(0, {root!r})
 import pyfastani_amd as pf
-from pyfastani_amd import synthetic as syn
-from pyfastani_amd._lib import lib, check
+from pyfastani_amd import diagnostics, synthetic as syn
 
 def read(mapper):
-    out = (C.c_int64 * 32)()
-    check(lib.fa_mapper_debug_spec(mapper._h, out, 32))
-    ms = (C.c_float * 24)()
-    check(lib.fa_mapper_last_timings(mapper._h, ms, 24))
-    got = dict(zip({fields!r}, list(out)))
-    got.update(repeats=int(ms[9]), fused=int(ms[17]), unfused=int(ms[18]), ordered=int(ms[19]), l1_sorted=int(ms[20]), l1_merged=int(ms[21]))
+    got, ms = diagnostics.spec(mapper)._asdict(), diagnostics.timings(mapper)
+    got.update((name, int(getattr(ms, name))) for name in ("repeats", "fused", "unfused", "ordered", "l1_sorted", "l1_merged"))
     return got
 
 g = syn.rng(7300)
@@ -67,7 +61,7 @@ def readout(*env):
     """The child's readout under `env` (pairs): spec + counters after the one-genome query ("one") and after the batch
     ("batch"), the hits, the records per mapping stage buffer, and the child's stderr."""
     clean = {k: v for k, v in os.environ.items() if not (k.startswith("FA_") and not k.startswith("FA_BENCH"))}
-    res = subprocess.run([sys.executable, "-c", CHILD.format(root=ROOT, fields=tuple(SPEC_FIELDS))], env=dict(clean, **dict(env)),
+    res = subprocess.run([sys.executable, "-c", CHILD.format(root=ROOT)], env=dict(clean, **dict(env)),
                          capture_output=True, text=True, timeout=300)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
     out = json.loads(res.stdout.strip().splitlines()[-1])
@@ -136,7 +130,7 @@ def test_knob_takes_effect(env, holds):
 
 def test_l1_stats_sees_the_block_sort():
     """FA_L1_STATS=1 samples one workgroup of k_l1 in 64 (fragments 0 and 64 of the 66) and counts the road it took: block-sorted
-    (timings[20]) by default, merged (timings[21]) under FA_L1_BLOCK_SORT=0; without FA_L1_STATS neither counter moves."""
+    (timings slot 20, l1_sorted) by default, merged (slot 21, l1_merged) under FA_L1_BLOCK_SORT=0; without FA_L1_STATS neither counter moves."""
     on = one(readout(("FA_L1_STATS", "1")))
     off = one(readout(("FA_L1_BLOCK_SORT", "0"), ("FA_L1_STATS", "1")))
     assert (on["l1_sorted"], on["l1_merged"]) == (2, 0), on

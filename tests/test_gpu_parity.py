@@ -18,6 +18,7 @@ from conftest import ROOT, read_fasta
 from oracle.oracle import OracleSketch
 from pyfastani_amd import _lib, synthetic as syn
 from pyfastani_amd._lib import lib, check
+from pyfastani_amd.diagnostics import spec, timings
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
 from make_synthetic_goldens import build_case  # noqa: E402
@@ -263,9 +264,7 @@ def test_small_sketch_against_crowded_window():
     params = {"minimum_fraction": 0.0, "percentage_identity": 68.0}
     mapper, hits, ohits, det = run_both(params, [[syn.to_ascii(ref)]], [bytes(q)], threads=8)
     assert mapper.window_size == 3
-    ms = (C.c_float * 16)()
-    lib.fa_mapper_last_timings(mapper._h, ms, 16)
-    assert ms[8] > 0, "the wide-state redo pass was not exercised"
+    assert timings(mapper).wide_loci > 0, "the wide-state redo pass was not exercised"
     assert len(det["mappings"]["qseq"]) >= 5
     assert gpu_mappings(mapper) == oracle_mappings(det)
     assert hit_tuples(hits) == ohits
@@ -288,10 +287,9 @@ def test_void_redo_attempt_leaves_no_stale_bins():
         q[f * 3000 + 1400: f * 3000 + 1400 + n] = bytes(syn.to_ascii(r[a: a + n]))
     params = {"minimum_fraction": 0.0, "percentage_identity": 68.0}
     mapper, hits, ohits, det = run_both(params, [[syn.to_ascii(r), syn.to_ascii(x)]], [bytes(q)], threads=8)
-    ms = (C.c_float * 16)()
-    lib.fa_mapper_last_timings(mapper._h, ms, 16)
-    assert ms[8] > 0 and ms[9] >= 1, "no locus left the byte state on the first attempt: the case does not test the repeat"
-    assert ms[8] < ms[6], "every locus overflowed: no twin could be left behind"
+    ms = timings(mapper)
+    assert ms.wide_loci > 0 and ms.repeats >= 1, "no locus left the byte state on the first attempt: the case does not test the repeat"
+    assert ms.wide_loci < ms.loci, "every locus overflowed: no twin could be left behind"
     assert gpu_mappings(mapper) == oracle_mappings(det)
     assert hit_tuples(hits) == ohits
     assert hit_tuples(mapper.query_draft([bytes(q)])) == ohits          # and again, now that the wide pass is always launched
@@ -552,11 +550,10 @@ def test_chunked_l1_more_loci_than_its_scratch(n_refs, pieces):
         # fragments with MORE hits than slots only), and the mapper reserved no HBM scratch beyond what a fresh mapper's first
         # attempt asks for -- nothing at 1 894 hits, which fit its 4 096 slots; with more hits that attempt is void, raises
         # SPEC_SCRATCH for the fragment's padded size plus a quarter, and the repeat runs with slots that hold the fragment.
-        from test_gpu_history import spec
         sp = spec(mapper)
         n32 = 1 << (n_hits - 1).bit_length()
-        assert sp["f_seed_slots"] >= n_hits
-        assert sp["scratch_words"] == (0 if n_hits <= 4096 else n32 + n32 // 4)
+        assert sp.f_seed_slots >= n_hits
+        assert sp.scratch_words == (0 if n_hits <= 4096 else n32 + n32 // 4)
 
 
 def test_chunked_l1_switched_off_matches():
@@ -699,9 +696,8 @@ def test_long_locus_and_reference_exceptions():
     other = bytes(syn.to_ascii(syn.mutate_codes(g, ref, 0.06)))
     query = np.concatenate([flank[18_000:20_000]] + [unit] * 4 + [flank[20_000:22_000]] + [unit] * 3)
     mapper, hits, ohits, det = run_both({}, [[bytes(ref_ascii)], [other]], [syn.to_ascii(query)])
-    ms = (C.c_float * 16)()
-    lib.fa_mapper_last_timings(mapper._h, ms, 16)
-    assert ms[7] / max(ms[6], 1) > 2048, "expected loci with more than 2048 slide events"
+    ms = timings(mapper)
+    assert ms.events / max(ms.loci, 1) > 2048, "expected loci with more than 2048 slide events"
     assert gpu_mappings(mapper) == oracle_mappings(det) and len(ohits) == 2
     assert hit_tuples(hits) == ohits
 
@@ -1266,8 +1262,8 @@ def test_parts_of_a_pass_match(part):
         if not os.environ.get("FA_PASS_FRAGMENTS"):      # (the stage getters keep the last part of a pass only)
             assert T.gpu_mappings(mapper) == T.oracle_mappings(det), "mappings"
         assert T.hit_tuples(hits) == ohits and len(ohits) == 4, "hits"
-        ms = (T.C.c_float * 16)(); T.lib.fa_mapper_last_timings(mapper._h, ms, 16)
-        print(json.dumps({"retries": ms[9], "loci": ms[6]}))
+        ms = T.timings(mapper)
+        print(json.dumps({"retries": ms.repeats, "loci": ms.loci}))
     """) % (ROOT, ROOT)
     env = dict(os.environ)
     if part:
@@ -1325,8 +1321,9 @@ def test_workgroup_order_of_multi_genome_passes_changes_nothing(part):
 
 
 def test_stage_times_by_stamps_agree_with_hip_events():
-    # the stage times of a pass come from device stamps of the 100 MHz counter (fa_mapper_last_timings [0..4]); on request
-    # the L2 stage is bracketed by two HIP events on the library's stream as well ([16]): the two clocks must agree
+    # the stage times of a pass come from device stamps of the 100 MHz counter (fa_mapper_last_timings [0..4]: sketch_ms ..
+    # total_ms); on request the L2 stage is bracketed by two HIP events on the library's stream as well ([16], l2_event_ms):
+    # the two clocks must agree
     g = syn.rng(4242)
     anc = syn.random_codes(g, 1_500_000)
     sk = pf.Sketch()
@@ -1340,18 +1337,16 @@ def test_stage_times_by_stamps_agree_with_hip_events():
         l2, ev, total, parts = [], [], [], []
         for _ in range(5):
             assert len(mapper.query_genome(q)) == 4
-            ms = (C.c_float * 24)()
-            check(lib.fa_mapper_last_timings(mapper._h, ms, 24))
-            l2.append(ms[2]); ev.append(ms[16]); total.append(ms[4]); parts.append(sum(ms[0:4]))
+            ms = timings(mapper)
+            l2.append(ms.l2_ms); ev.append(ms.l2_event_ms); total.append(ms.total_ms)
+            parts.append(ms.sketch_ms + ms.l1_ms + ms.l2_ms + ms.cgi_ms)
     finally:
         check(lib.fa_mapper_set_stage_events(mapper._h, 0))
     assert min(l2) > 0.01 and min(ev) > 0.01, (l2, ev)
     assert abs(np.median(l2) - np.median(ev)) <= 0.15 * np.median(l2) + 0.01, (l2, ev)       # ms
     assert abs(np.median(total) - np.median(parts)) <= 0.02 * np.median(total) + 0.005, (total, parts)
-    ms = (C.c_float * 24)()
     mapper.query_genome(q)
-    check(lib.fa_mapper_last_timings(mapper._h, ms, 24))
-    assert ms[16] == 0.0                                                                       # off again
+    assert timings(mapper).l2_event_ms == 0.0                                                  # off again
 
 
 def test_device_memory_is_stable():
@@ -1423,14 +1418,13 @@ def test_fused_query_sketch_overflow_falls_back(monkeypatch):
     query = [syn.to_ascii(syn.mutate_codes(g, anc, 0.04))]
     mapper, hits, ohits, det = run_both({}, refs, query)              # fused (the default where it applies)
     assert gpu_mappings(mapper) == oracle_mappings(det) and hit_tuples(hits) == ohits and len(ohits) == 2
-    ms = (C.c_float * 24)()
 
     def again():
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")
             h = mapper.query_draft(query)
-        lib.fa_mapper_last_timings(mapper._h, ms, 24)
-        return hit_tuples(h), int(ms[9]), (int(ms[17]), int(ms[18]))   # hits, void attempts, parts accepted (fused, two kernels)
+        ms = timings(mapper)
+        return hit_tuples(h), int(ms.repeats), (int(ms.fused), int(ms.unfused))   # hits, void attempts, parts accepted (fused, two kernels)
 
     assert again() == (ohits, 0, (1, 0))                              # (the first call had sized the workspace)
     monkeypatch.setenv("FA_QF_CAP", "100")
@@ -1460,7 +1454,7 @@ def test_fused_query_sketch_overflow_falls_back(monkeypatch):
 def test_fused_sketch_stage_with_bytes_outside_acgt():
     # A query with N runs, IUPAC codes and lower case still takes the one-launch sketch stage: the tiles that touch such bytes
     # are sketched from the byte image by k_sketch_tiles<0, true> first, k_query_fused hashes the plain tiles and takes the
-    # staged records of the others over.  Every mapping and hit as the oracle's; slot [17] of the timings says which form ran.
+    # staged records of the others over.  Every mapping and hit as the oracle's; slot [17] of the timings (fused) says which form ran.
     g = syn.rng(515)
     anc = syn.random_codes(g, 200_000)
     refs = [[syn.to_ascii(syn.mutate_codes(g, anc, d))] for d in (0.01, 0.05, 0.10)]
@@ -1474,9 +1468,8 @@ def test_fused_sketch_stage_with_bytes_outside_acgt():
     query = [bytes(q)]
     mapper, hits, ohits, det = run_both({}, refs, query, threads=4)
     assert gpu_mappings(mapper) == oracle_mappings(det) and hit_tuples(hits) == ohits and len(ohits) == 3
-    ms = (C.c_float * 24)()
-    lib.fa_mapper_last_timings(mapper._h, ms, 24)
-    assert (int(ms[17]), int(ms[18])) == (1, 0), "the query pass should have run k_query_fused"
+    ms = timings(mapper)
+    assert (int(ms.fused), int(ms.unfused)) == (1, 0), "the query pass should have run k_query_fused"
     # the resident-batch road, two genomes of which one is clean
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
@@ -1489,7 +1482,7 @@ def test_batches_of_tiny_genomes_keep_the_identity_workgroup_order():
     # The offset-major workgroup order of k_l2_events deals groups of equal fragment offset to the eight XCDs.  A batch of
     # plasmid-sized genomes (one to three fragments each) has fewer groups than XCDs: the order would put every real workgroup
     # on one or two XCDs behind a grid that is mostly padding, so such passes keep the identity order (slot [19] of the
-    # timings counts the parts that ran ordered); a batch of larger genomes (16 fragments each) is ordered.  Rows equal the oracle's either way.
+    # timings, `ordered`, counts the parts that ran ordered); a batch of larger genomes (16 fragments each) is ordered.  Rows equal the oracle's either way.
     g = syn.rng(4242)
     anc = [syn.random_codes(g, 12_500) for _ in range(6)]
     refs = [[syn.to_ascii(syn.mutate_codes(g, a, 0.03))] for a in anc]
@@ -1499,17 +1492,16 @@ def test_batches_of_tiny_genomes_keep_the_identity_workgroup_order():
     for i, r in enumerate(refs):
         sk.add_draft(i, r); osk.add_draft(i, r)
     mapper = sk.index(); osk.index()
-    ms = (C.c_float * 24)()
     for genomes, ordered in ((tiny, 0), (big, 1)):
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")
             batch = mapper.upload_genomes(genomes)
             assert int(batch.total_fragments.sum()) >= 64
             hits = [hit_tuples(hs) for hs in batch.query()]
-            lib.fa_mapper_last_timings(mapper._h, ms, 24)
+            ms = timings(mapper)
             want = [osk.query_draft(c, threads=8) for c in genomes]
         assert hits == want
-        assert int(ms[19]) == ordered, (ordered, list(ms)[17:20])
+        assert int(ms.ordered) == ordered, (ordered, ms.fused, ms.unfused, ms.ordered)
 
 
 def test_device_pool_keeps_and_returns_memory():

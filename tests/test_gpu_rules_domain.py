@@ -25,6 +25,7 @@ import pytest
 import rules_cases as rc
 import rules_domain as rd
 import pyfastani_amd as pf
+from pyfastani_amd import diagnostics
 from pyfastani_amd._lib import lib, check
 
 pytestmark = pytest.mark.gpu
@@ -95,9 +96,7 @@ def test_event_counts_follow_the_slide_end(name):
 
 
 def redo_loci(mapper):
-    ms = (C.c_float * 24)()
-    check(lib.fa_mapper_last_timings(mapper._h, ms, 24))
-    return ms[8]
+    return diagnostics.timings(mapper).wide_loci
 
 
 def test_wide_state_redo_under_all_three():

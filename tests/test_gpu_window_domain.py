@@ -19,7 +19,7 @@ import pytest
 
 import pyfastani_amd as pf
 from oracle.oracle import OracleSketch, murmur_hash
-from pyfastani_amd import _lib, synthetic as syn
+from pyfastani_amd import _lib, diagnostics, synthetic as syn
 from pyfastani_amd._lib import lib, check
 from test_gpu_parity import gpu_mappings, hit_tuples, oracle_mappings, quiet_sketch, run_both
 
@@ -191,18 +191,6 @@ def test_window_domain_streams_by_definition(w):
 # ----------------------------------------------------------------------------------------------------------------
 # end to end at the extremes of the recommended window
 # ----------------------------------------------------------------------------------------------------------------
-def spec_of(mapper):
-    out = (C.c_int64 * 32)()
-    check(lib.fa_mapper_debug_spec(mapper._h, out, 32))
-    return list(out)
-
-
-def timings_of(mapper):
-    ms = (C.c_float * 24)()
-    check(lib.fa_mapper_last_timings(mapper._h, ms, 24))
-    return list(ms)
-
-
 # (params, expected window): the identities at both ends of the range, the p-value and the reference size
 CELLS = [
     ({"k": 16, "fragment_length": 3000, "percentage_identity": 64.5}, 2),
@@ -242,23 +230,23 @@ def test_window_extremes_end_to_end(params, w):
     assert gpu_mappings(mapper) == oracle_mappings(det)
     assert hit_tuples(hits) == ohits
     assert len(ohits) >= 3, ohits
-    spec, ms = spec_of(mapper), timings_of(mapper)
+    spec, ms = diagnostics.spec(mapper), diagnostics.timings(mapper)
     k, s = params["k"], 2 * frag // (w + 1)
     # the forms: 32-bit slide events for the sketches of hundreds of records and more (the bound must hold slot = rank + 1 in
     # 9 bits); the 512-thread k_l1 classes where fragments hold more than 4 096 seed hits (three relatives x ~2 000-3 300
     # minimizers at w = 2); one 256-thread class and no pre-filter at the tiny sketches; the one-launch sketch stage
     # (k_query_fused) only in the compiled (k, w) cells -- never beyond w = 1000, where K1 takes the general path
     if w <= 4:
-        assert spec[23] == 1, spec
+        assert spec.f_wide == 1, spec
     if s <= 100:
-        assert spec[23] == 0, spec
+        assert spec.f_wide == 0, spec
     if w == 2 and frag >= 3000:
-        assert 512 in spec[18:21], spec
+        assert 512 in (spec.l1_t0, spec.l1_t1, spec.l1_t2), spec
     if s <= 10:
-        assert spec[17] == 1 and spec[18] == 256 and spec[21] == 0, spec
-    assert spec[21] == 0, spec
+        assert spec.n_l1 == 1 and spec.l1_t0 == 256 and spec.f_prefilter == 0, spec
+    assert spec.f_prefilter == 0, spec
     if (k, w) not in FUSED_CELLS:
-        assert ms[17] == 0 and ms[18] > 0, ms
+        assert ms.fused == 0 and ms.unfused > 0, ms
     # the same genomes as one resident batch
     sk, osk = quiet_sketch(pf.Sketch, **params), quiet_sketch(OracleSketch, **params)
     with warnings.catch_warnings():

@@ -12,7 +12,8 @@ from pyfastani_amd import _batch
 CSRC = os.path.join(ROOT, "pyfastani_amd", "csrc")
 ROW = re.compile(r'^\s*X\((\w+),\s*"(FA_[A-Z0-9_]+)",\s*(FLAG|NUM|COUNT|COUNT_IN\([^)]*\)|COUNT_UP\([^)]*\)|TEXT),\s*([^,]+),\s*(ONCE|LIVE),\s*"([^"]+)"\)', re.M)
 # FA_* names that are no knob of the library: variables of the Python layer, of bench.py and of the scripts, error codes and macros
-NOT_KNOBS = {"FA_FORCE_DIST", "FA_ORACLE_DEFINES", "FA_HEAD", "FA_OK", "FA_KW_CELLS", "FA_EV_WAVES", "FA_EV_RPL"}
+NOT_KNOBS = {"FA_FORCE_DIST", "FA_ORACLE_DEFINES", "FA_HEAD", "FA_OK", "FA_KW_CELLS", "FA_EV_WAVES", "FA_EV_RPL",
+             "FA_TIMING_SLOTS", "FA_SPEC_FIELDS"}            # (the last two: the tables of csrc/fa_diag.h)
 NOT_KNOB_PREFIXES = ("FA_BENCH", "FA_PROFILE_", "FA_ERR_")
 
 
