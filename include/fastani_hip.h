@@ -549,6 +549,35 @@ int fa_screen_tile(int32_t s, int32_t *tile);
  * ascending; a contig id outside [0, sbf[n_genomes-1]); sbf not non-decreasing. */
 int fa_screen_signatures(const uint32_t *d_hash, const int32_t *d_seq_id, int64_t n_records, const int32_t *sbf, int32_t n_genomes,
                          int32_t s, uint32_t *d_sig, int32_t *d_count);
+/* The signatures of the genomes [first, first + count) of a resident batch, made of the fragments the batch already holds:
+ * queries are uploaded once, reduced to signatures, compared (fa_screen_pairs / fa_screen_contained /
+ * fa_screen_contained_winner take the result as it is) and mapped.
+ *   Signature.  That of genome g is taken from the query sketches of its fragments [genome_frag_lo[g], genome_frag_lo[g+1])
+ *      -- the sets the mapper itself maps with, readable through fa_mapper_debug_query_sketch.  With d_g the number of
+ *      distinct hashes in the union of those sketches, the signature is the min(s, d_g) smallest of them, ascending as
+ *      unsigned 32-bit; count[g] = min(s, d_g); entries from count[g] up to s are 0.  A genome without fragments -- no
+ *      contig, or only contigs shorter than a fragment -- has count 0.  Layout and the range 1 <= s <= 4096 are those of
+ *      fa_screen_signatures.
+ *   Relation to a sketch's signature.  A batch keeps only the whole fragments of each contig, and its windows do not cross
+ *      fragment seams.  A genome's batch hash set is therefore a SUBSET of the hash set a sketch holds for the same contigs,
+ *      and EQUALS that of a sketch to which every fragment was added as a contig of its own: the two signatures are close,
+ *      not identical.
+ *   Passes.  The fragments of the range are walked in order, in passes of at most pass_fragments fragments (0: the library's
+ *      pass size, FA_PASS_FRAGMENTS), cut anywhere, not only at genome boundaries; a genome's partial signature is carried
+ *      from pass to pass.  Memory beyond the mapper's workspace is bounded by the records of one pass.  The same input gives
+ *      the same bytes on every run, for every pass_fragments.
+ * d_sig ([count][s]) and d_count ([count]) are DEVICE pointers on the mapper's device; count == 0 is valid and writes
+ * nothing.  stats may be NULL: [0] the fragments sketched, [1] the passes run (ceil(fragments / pass size), 0 for none), and,
+ * only after fa_mapper_set_stage_events(m, 1), [2] the device time of the sketch kernel and [3] that of all passes, in
+ * microseconds (0 otherwise).  FA_ERR_INVALID with nothing written: s out of range, a range outside the batch, a negative
+ * pass_fragments, a NULL handle, NULL outputs with count > 0.  FA_ERR_NO_DEVICE without a device.  FA_ERR_UNSUPPORTED: a pass
+ * whose tiles hold 2^31 record slots or more (two million tiles: only a pass_fragments far above the library's gets there).
+ * The call is not a query.  It borrows a workspace of the mapper for the sketch kernel's staging arrays and runs on that
+ * workspace's stream, finished when it returns; later queries give the rows they gave before, fa_mapper_last_timings and
+ * fa_mapper_debug_spec still speak of the last query, and the stage getters (fa_mapper_debug_*) return what they returned
+ * before the call: nothing they read is written here. */
+int fa_genomes_signatures(fa_mapper *m, fa_genomes *g, int32_t first, int32_t count, int32_t s, int64_t pass_fragments,
+                          uint32_t *d_sig, int32_t *d_count, int64_t *stats);
 /* The signature arrays are DEVICE pointers; pairs_device != 0: `pairs` is one too.  triangular != 0 requires the same
  * pointers for both sets and n_a == n_b.  pairs == NULL only counts.  A `cap` below the number of pairs is FA_ERR_INVALID:
  * nothing is written, and *n_pairs holds the number needed.  FA_ERR_INVALID with nothing written, *n_pairs included: a count

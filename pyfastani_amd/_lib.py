@@ -201,6 +201,7 @@ SIGNATURES = {
     "fa_table_best": (_i32, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _P(BestParams), _vp, _vp, _i64, _P(_i64), _i32, _vp]),
     "fa_screen_tile": (_i32, [_i32, _P(_i32)]),
     "fa_screen_signatures": (_i32, [_vp, _vp, _i64, _vp, _i32, _i32, _vp, _vp]),
+    "fa_genomes_signatures": (_i32, [_vp, _vp, _i32, _i32, _i32, _i64, _vp, _vp, _vp]),
     "fa_screen_pairs": (_i32, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _P(_i64), _i32, _vp]),
     "fa_screen_groups": (_i32, [_vp, _i64, _i32, _i32, _vp, _i32, _P(_i32)]),
     "fa_screen_contents": (_i32, [_vp, _vp, _i64, _vp, _i32, _vp, _vp, _i64, _P(_i64)]),

@@ -1,8 +1,8 @@
 // fa_engine.hip -- the C ABI of libfastani_hip.so (include/fastani_hip.h): the error guard, parameter validation and the
 // entry points, each a call into the object it belongs to.  One header per object: the K1 launcher (fa_k1.hip.h), the
 // reference sketch (fa_refsketch.hip.h), the resident batch (fa_batch.hip.h), the index and its workspaces
-// (fa_index.hip.h), the query pass (fa_query.hip.h), the selection drivers (fa_select.hip.h) and the reductions over
-// finished results (fa_reduce.hip.h).  All of it is this one translation unit.
+// (fa_index.hip.h), the query pass (fa_query.hip.h), the selection drivers (fa_select.hip.h), the signatures of a resident
+// batch (fa_batchsig.hip.h) and the reductions over finished results (fa_reduce.hip.h).  All of it is this one translation unit.
 // There is no CPU fallback anywhere in the library: without a HIP device every compute entry point fails.
 #include <cstring>   // (before rocPRIM, whose texture_cache_iterator.hpp calls memset without including it)
 
@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "fa_batch.hip.h"
+#include "fa_batchsig.hip.h"
 #include "fa_common.h"
 #include "fa_fasta.h"
 #include "fa_index.hip.h"
@@ -570,6 +571,10 @@ int fa_screen_tile(int32_t s, int32_t *tile) {
 int fa_screen_signatures(const uint32_t *d_hash, const int32_t *d_seq_id, int64_t n_records, const int32_t *sbf, int32_t n_genomes,
                          int32_t s, uint32_t *d_sig, int32_t *d_count) {
   return guarded([&] { screen_signatures(d_hash, d_seq_id, n_records, sbf, n_genomes, s, d_sig, d_count); });
+}
+int fa_genomes_signatures(fa_mapper *m, fa_genomes *g, int32_t first, int32_t count, int32_t s, int64_t pass_fragments, uint32_t *d_sig,
+                          int32_t *d_count, int64_t *stats) {
+  return guarded([&] { genomes_signatures(m, g, first, count, s, pass_fragments, d_sig, d_count, stats); });
 }
 int fa_screen_pairs(const uint32_t *d_sig_a, const int32_t *d_count_a, int32_t n_a, const uint32_t *d_sig_b, const int32_t *d_count_b,
                     int32_t n_b, int32_t s, int triangular, int32_t jn, int32_t jd, fa_screen_pair *pairs, int64_t cap, int64_t *n_pairs,

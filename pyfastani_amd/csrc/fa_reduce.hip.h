@@ -1,6 +1,7 @@
 // fa_reduce.hip.h -- the host drivers of the reductions over results the mapper already holds: a hit table to pairs,
 // clusters, representatives, average-linkage clusters and their dendrogram with its cuts (fa_table.hip.h, fa_represent.hip.h, fa_linkage.hip.h), to every query's k best hits (fa_best.hip.h), the
-// signature screen (fa_screen.hip.h) and its containment road (fa_contain.hip.h).  They use nothing of the sketch, the mapper or the workspace; fa_engine.hip wraps each
+// signature screen (fa_screen.hip.h) and its containment road (fa_contain.hip.h).  They use nothing of the sketch, the mapper or the workspace -- but for the last one, the
+// signatures of a resident batch (fa_batchsig.hip.h), which borrows a workspace for K1's staging arrays; fa_engine.hip wraps each
 // in its extern "C" entry point.
 //
 // Every driver has the same frame (the pieces are in fa_common.h): it checks its arguments, then require_device(), then
@@ -19,11 +20,14 @@
 #include <climits>
 #include <vector>
 
+#include "fa_batch.hip.h"
+#include "fa_batchsig.hip.h"
 #include "fa_best.hip.h"
 #include "fa_common.h"
 #include "fa_contain.hip.h"
 #include "fa_linkage.hip.h"
 #include "fa_order.h"
+#include "fa_query.hip.h"
 #include "fa_represent.hip.h"
 #include "fa_screen.hip.h"
 #include "fa_table.hip.h"
@@ -873,6 +877,127 @@ inline void screen_contained(const uint32_t *d_sig, const int32_t *d_count, int3
     stats[1] = n_emit;
     stats[2] = (int64_t)status.visited;
     if (winner) stats[3] = (int64_t)status.assigned;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// The bottom-s signatures of a resident batch, pass by pass (fa_batchsig.hip.h has the semantics and the road)
+// ------------------------------------------------------------------------------------------------------------
+// The call is not a query: the workspace it borrows becomes the lease's "most recent" one when it is handed back, and this
+// puts the mapper's own choice back behind it, so that timings, kernel forms and stage getters go on speaking of the last
+// query.  (Declared before the lease: destroyed after it.  A query that another thread finishes while the call runs loses
+// its place to the one before it: "most recent" is a single-caller notion, as it is between two concurrent queries.)
+struct KeepLastWorkspace {
+  fa_mapper &m;
+  int ws;
+  explicit KeepLastWorkspace(fa_mapper &mm) : m(mm) { std::lock_guard<std::mutex> lock(m.mtx); ws = m.last_ws; }
+  ~KeepLastWorkspace() { std::lock_guard<std::mutex> lock(m.mtx); m.last_ws = ws; }
+};
+
+// Of a workspace only K1's staging arrays (Workspace::sk) are written -- no stage getter reads them, every pass of a query
+// fills them anew -- so what the getters return after the call is what they returned before it.
+inline void genomes_signatures(fa_mapper *m, fa_genomes *g, int32_t first, int32_t count, int32_t s, int64_t pass_frags, uint32_t *d_sig,
+                               int32_t *d_count, int64_t *stats) {
+  FA_REQUIRE(m && g, FA_ERR_INVALID, "null mapper or batch");
+  FA_REQUIRE(s >= 1 && s <= SCR_MAX_S, FA_ERR_INVALID, "the signature size must be in [1, 4096]");
+  FA_REQUIRE(first >= 0 && count >= 0 && (int64_t)first + (int64_t)count <= (int64_t)g->n_genomes, FA_ERR_INVALID, "genome range out of bounds");
+  FA_REQUIRE(pass_frags >= 0, FA_ERR_INVALID, "negative number of fragments per pass");
+  FA_REQUIRE(count == 0 || (d_sig && d_count), FA_ERR_INVALID, "null outputs");
+  FA_REQUIRE(g->P.kmer_size == m->P.kmer_size && g->P.window_size == m->P.window_size && g->P.fragment_length == m->P.fragment_length &&
+                 g->P.alphabet_size == m->P.alphabet_size, FA_ERR_INVALID, "the batch was uploaded with other parameters than the mapper's");
+  require_device();
+  const int64_t per_pass = pass_frags ? pass_frags : pass_fragments();
+  const std::vector<int64_t> &lo = g->genome_frag_lo;
+  const int64_t F0 = count ? lo[(size_t)first] : 0, F1 = count ? lo[(size_t)first + (size_t)count] : 0;
+  int64_t passes = 0;
+  double k1_ms = 0, all_ms = 0;
+  if (count) {
+    KeepLastWorkspace keep(*m);
+    WorkspaceLease lease(*m);
+    Workspace &w = *lease.w;
+    hipStream_t st = w.stream;
+    bool timed;
+    { std::lock_guard<std::mutex> lock(m->mtx); timed = m->stage_events; }
+    std::vector<Event> ev;                               // three a pass: its begin, behind K1, its end
+    DevBuf<uint32_t> carry, heads, rank, segs;
+    DevBuf<int32_t> tile_off;
+    DevBuf<unsigned long long> keys, sorted;
+    DevBuf<unsigned char> temp;
+    carry.ensure((size_t)s + 1);
+    FA_HIP(hipMemsetAsync(d_sig, 0, (size_t)count * (size_t)s * sizeof(uint32_t), st));
+    FA_HIP(hipMemsetAsync(d_count, 0, (size_t)count * sizeof(int32_t), st));
+    // the genome that holds fragment f (genomes without fragments hold none)
+    auto genome_of = [&](int64_t f) { return (int32_t)(std::upper_bound(lo.begin(), lo.end(), f) - lo.begin()) - 1; };
+    auto mark = [&] { if (timed) { ev.emplace_back(); FA_HIP(hipEventRecord(ev.back().get(), st)); } };
+    for (int64_t f0 = F0, f1; f0 < F1; f0 = f1, passes++) {
+      f1 = std::min(F1, f0 + per_pass);
+      const int32_t t0 = g->frag_tile_lo[(size_t)f0], ntiles = g->frag_tile_lo[(size_t)f1] - t0;
+      const int32_t g0 = genome_of(f0), g1 = genome_of(f1 - 1);
+      const bool carried = f0 > lo[(size_t)g0], goes_on = lo[(size_t)g1 + 1] > f1;
+      BatchSigArgs a{};
+      a.tiles = g->tiles + t0; a.ntiles = ntiles; a.frag_query = g->d_frag_query; a.f0 = f0; a.f1 = f1;
+      a.g0 = g0; a.n_genomes = g1 - g0 + 1; a.cont = goes_on ? g1 - g0 : -1; a.s = s; a.carry = carry.p;
+      a.sig = d_sig + (size_t)(g0 - first) * (size_t)s; a.count = d_count + (g0 - first);
+      // (the scan below and the ranks of the heads are 32-bit: the slots of a pass and a carried signature stay within them)
+      FA_REQUIRE((int64_t)ntiles * TILE + s <= (int64_t)INT32_MAX, FA_ERR_UNSUPPORTED, "more than 2^31 - 1 record slots in one pass: lower the fragments per pass");
+      mark();
+      w.sk.reserve((size_t)std::max(ntiles, 1));
+      launch_sketch_tiles(m->P, g->store, a.tiles, ntiles, w.sk.stage_hash.p, w.sk.stage_wpos.p, w.sk.tile_count.p, st);
+      mark();
+      tile_off.ensure((size_t)ntiles + 1);
+      FA_HIP(hipMemsetAsync(w.sk.tile_count.p + ntiles, 0, sizeof(int32_t), st));
+      exclusive_sum_i32(temp, w.sk.tile_count.p, tile_off.p, (size_t)ntiles + 1, st);
+      // the sizes of the pass: its staged records, and the carried partial signature of a genome that began before it
+      int32_t n_staged = 0;
+      uint32_t carry_in = 0;
+      FA_HIP(hipMemcpyAsync(&n_staged, tile_off.p + ntiles, sizeof n_staged, hipMemcpyDeviceToHost, st));
+      if (carried) FA_HIP(hipMemcpyAsync(&carry_in, carry.p + s, sizeof carry_in, hipMemcpyDeviceToHost, st));
+      FA_HIP(hipStreamSynchronize(st));
+      FA_REQUIRE(n_staged >= 0 && n_staged <= (int64_t)ntiles * TILE && carry_in <= (uint32_t)s, FA_ERR_INTERNAL, "a tile staged more records than it has slots");
+      const int64_t n_keys = (int64_t)n_staged + (int64_t)carry_in;
+      if (!n_keys) {                                     // (fragments without a record: every genome of the pass keeps count 0)
+        if (goes_on) FA_HIP(hipMemsetAsync(carry.p + s, 0, sizeof(uint32_t), st));
+        mark();
+        continue;
+      }
+      keys.ensure((size_t)n_keys); sorted.ensure((size_t)n_keys); heads.ensure((size_t)n_keys); rank.ensure((size_t)n_keys);
+      segs.ensure((size_t)a.n_genomes * 2);
+      FA_HIP(hipMemsetAsync(segs.p, 0, (size_t)a.n_genomes * 2 * sizeof(uint32_t), st));
+      a.tile_count = w.sk.tile_count.p; a.tile_off = tile_off.p; a.stage_hash = w.sk.stage_hash.p;
+      a.n_staged = n_staged; a.n_keys = n_keys; a.keys = keys.p; a.carry_in = (int32_t)carry_in;
+      hipLaunchKernelGGL(k_bsig_keys, dim3(ceil_div(ntiles, 4)), dim3(256), 0, st, a);
+      if (carry_in) hipLaunchKernelGGL(k_bsig_carry, dim3(ceil_div(carry_in, 256)), dim3(256), 0, st, a);
+      // the bits a key can have set: 32 of the hash and those of the pass's largest genome number
+      const unsigned end_bit = 32u + id_bits(a.n_genomes);
+      with_temp(temp, [&](void *t, size_t &bytes) {
+        return rocprim::radix_sort_keys(t, bytes, keys.p, sorted.p, (size_t)n_keys, 0u, end_bit, st);
+      });
+      SigArgs sa{};                                      // the heads, their ranks and every genome's segment: fa_screen.hip.h's own
+      sa.keys = sorted.p; sa.n_records = n_keys; sa.first = segs.p; sa.last = segs.p + a.n_genomes;
+      const dim3 key_grid(ceil_div(n_keys, 256));
+      hipLaunchKernelGGL(k_sig_heads, key_grid, dim3(256), 0, st, sa, heads.p);
+      with_temp(temp, [&](void *t, size_t &bytes) {
+        return rocprim::exclusive_scan(t, bytes, heads.p, rank.p, 0u, (size_t)n_keys, rocprim::plus<uint32_t>(), st);
+      });
+      sa.rank = rank.p;
+      hipLaunchKernelGGL(k_sig_segments, key_grid, dim3(256), 0, st, sa);
+      a.sorted = sorted.p; a.rank = rank.p; a.first = sa.first; a.last = sa.last;
+      hipLaunchKernelGGL(k_bsig_write, key_grid, dim3(256), 0, st, a);
+      hipLaunchKernelGGL(k_bsig_counts, dim3(ceil_div(a.n_genomes, 256)), dim3(256), 0, st, a);
+      FA_HIP(hipGetLastError());
+      mark();
+    }
+    FA_HIP(hipStreamSynchronize(st));
+    for (size_t i = 0; i + 2 < ev.size(); i += 3) {
+      float k1 = 0, all = 0;
+      FA_HIP(hipEventElapsedTime(&k1, ev[i], ev[i + 1]));
+      FA_HIP(hipEventElapsedTime(&all, ev[i], ev[i + 2]));
+      k1_ms += k1; all_ms += all;
+    }
+  }
+  if (stats) {
+    stats[0] = F1 - F0; stats[1] = passes;
+    stats[2] = (int64_t)std::llround(k1_ms * 1e3); stats[3] = (int64_t)std::llround(all_ms * 1e3);
   }
 }
 

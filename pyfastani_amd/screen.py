@@ -24,8 +24,18 @@ is credited to one genome only -- of those that hold it the one holding the most
 redundant relatives fall to what they alone explain and drop below the cut-off.  The rule is this library's integer
 restatement of ``mash screen -w`` (``fa_screen_contained_winner``); it has not been checked against the Mash program.
 
+Queries need no `Sketch` of their own: a `GenomeBatch` is reduced to signatures from the fragments it already holds in HBM
+(``fa_genomes_signatures``), pass by pass in bounded memory, and is then mapped as it is.
+
+    batch = mapper.upload_genomes(queries)                 # once
+    query_sigs = screen.signatures(batch, size=1000)       # names: the genome numbers, or names=; first= / count= take a range
+    found = screen.contained(query_sigs, contents)         # ... and batch.query() maps the same upload
+
 The signature is that of the genome's *winnowed minimizers*, not of all its k-mers, and so is every statistic here, the
-winner-take-all one included: the distances are Mash-like at the sketch's ``k``, not those of the Mash program.  Everything but `fold` runs on the device; there is no CPU path, and without a HIP device
+winner-take-all one included: the distances are Mash-like at the sketch's ``k``, not those of the Mash program.  A batch's
+signature is one step further away: a batch keeps only the whole fragments of each contig and its windows do not cross fragment
+seams, so a genome's hash set is a *subset* of what a `Sketch` holds for the same contigs (and equals that of a `Sketch` to
+which every fragment was added as a contig of its own): the two signatures are close, not identical.  Everything but `fold` runs on the device; there is no CPU path, and without a HIP device
 the functions raise ``RuntimeError`` like every compute entry point.
 
 Not imported by the package itself (like `clusters` and `classify`): it needs numpy.
@@ -80,12 +90,30 @@ class Signatures:
                           parts[0].k)
 
 
-def signatures(sketch, size=1000, device="cuda"):
-    """The bottom-``size`` signatures of every genome of ``sketch`` (1 <= size <= 4096), from the records
-    `Sketch._export_records` copies HBM to HBM: the sketch is left as it is, un-indexed."""
-    import torch
+def signatures(source, size=1000, device="cuda", names=None, first=0, count=None, pass_fragments=0, stats=None):
+    """The bottom-``size`` signatures (1 <= size <= 4096) of every genome of ``source``.
+
+    A `Sketch`: from the records `Sketch._export_records` copies HBM to HBM; the sketch is left as it is, un-indexed.
+    ``names``, ``first`` and ``count`` belong to the other source and raise ``ValueError`` here.
+
+    A `GenomeBatch`: of its genomes ``[first, first + count)``, from the fragments the batch holds already, pass by pass in
+    bounded memory on the device of the batch's mapper (``fa_genomes_signatures``; ``device`` plays no part) -- queries are
+    uploaded once, screened and mapped.  ``names`` default to the genome numbers as strings, ``k`` is the mapper's.
+    ``pass_fragments`` sets the fragments per pass of this call (0: the library's, ``FA_PASS_FRAGMENTS``); the result does not
+    depend on it.  ``stats``, a dict, receives ``fragments`` and ``passes``, and ``k1_us`` / ``device_us`` (the device time of
+    the sketch kernel and of all passes; 0 unless the mapper's stage events are on).  The call is not a query: the mapper's
+    timings and stage getters go on speaking of its last query."""
     if not 1 <= int(size) <= MAX_SIZE:
         raise ValueError(f"the signature size must be in [1, {MAX_SIZE}]")
+    if hasattr(source, "_export_records"):
+        if names is not None or first != 0 or count is not None:
+            raise ValueError("names, first and count select genomes of a GenomeBatch: a Sketch is taken whole, under its own names")
+        return _sketch_signatures(source, size, device)
+    return _batch_signatures(source, int(size), names, int(first), count, int(pass_fragments), stats)
+
+
+def _sketch_signatures(sketch, size, device):
+    import torch
     rec, (lengths, sbf, counter) = sketch._export_records(device)
     rec = rec.contiguous()
     n, n_records = len(sbf), int(rec.shape[1])
@@ -97,6 +125,31 @@ def signatures(sketch, size=1000, device="cuda"):
         check(lib.fa_screen_signatures(C.c_void_p(rec[0].data_ptr()), C.c_void_p(rec[1].data_ptr()), n_records,
                                        C.c_void_p(sbf.ctypes.data), n, int(size), C.c_void_p(sig.data_ptr()), C.c_void_p(count.data_ptr())))
     return Signatures(sig, count, sketch.names, sketch.k)
+
+
+def _batch_signatures(batch, size, names, first, count, pass_fragments, stats):
+    n = len(batch)
+    count = n - first if count is None else int(count)
+    if first < 0 or count < 0 or first + count > n:
+        raise ValueError("genome range out of bounds")
+    names = [str(g) for g in range(first, first + count)] if names is None else list(names)
+    if len(names) != count:
+        raise ValueError("there is one name per genome of the range")
+    if pass_fragments < 0:
+        raise ValueError("pass_fragments must not be negative")
+    import torch
+    mapper = batch._mapper
+    where = mapper._torch_device()
+    sig = torch.empty((count, size), dtype=torch.int32, device=where)
+    tally = torch.empty(count, dtype=torch.int32, device=where)
+    counters = (C.c_int64 * 4)()
+    torch.cuda.synchronize(where)                        # the library runs on a stream of the mapper's: torch's writes are done
+    with torch.cuda.device(where):
+        check(lib.fa_genomes_signatures(C.c_void_p(mapper._h), C.c_void_p(batch._h), first, count, size, pass_fragments,
+                                        C.c_void_p(sig.data_ptr()) if count else None, C.c_void_p(tally.data_ptr()) if count else None, counters))
+    if stats is not None:
+        stats.update(fragments=counters[0], passes=counters[1], k1_us=counters[2], device_us=counters[3])
+    return Signatures(sig, tally, names, mapper.k)
 
 
 def jaccard_cutoff(max_distance, k):
