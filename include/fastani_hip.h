@@ -478,6 +478,47 @@ int fa_dendrogram_cut(const fa_merge *merges, int64_t n_merges, int merges_devic
  * FA_ERR_INVALID): *first = 1 when a comes before b, 0 when b comes before a, 2 when they are equal.  Host only; it calls the
  * comparator the kernels use. */
 int fa_debug_linkage_order(const int64_t a[4], const int64_t b[4], int *first);
+/* Centrality and medoids of given clusters of the table: for every genome its mean identity to the other members of its
+ * cluster, and for every cluster the member that stands for it (dRep's score = quality + centrality), whichever rule made the
+ * partition.  Several partitions -- the cuts of a dendrogram -- are served by one pass over the table.
+ *   1. Filter, pair, present, weight: steps 1-2 of fa_table_linkage word for word, `reciprocal` included.  w = rint(identity *
+ *      2^20), qm = rint((double)missing * 2^20).  p->min_identity is not read: the labels carry the cut-off.
+ *   2. Labels.  labels is laid out [n_sets][n_genomes], n_sets >= 1.  A set t is valid iff every labels[t][g] lies in
+ *      [0, n_genomes) and labels[t][labels[t][g]] == labels[t][g]: every label is a member of its own cluster, as in what
+ *      fa_table_clusters, fa_table_linkage, fa_dendrogram_cut and fa_table_representatives return.  The cluster of g in set t
+ *      is {h : labels[t][h] == labels[t][g]}; m is its size.
+ *   3. Centrality.  S[t][g] = sum of w(g,h) over the present pairs with h != g in g's cluster + qm * (m - 1 - their number).
+ *      The mean identity of g to its cluster is S / (m - 1); for m == 1, S = 0.  With at most 2^18 genomes S < 2^46.
+ *   4. Bonus.  bonus is a HOST array [n_genomes], NULL meaning all zero: the caller's quality score in identity points.
+ *      qb[g] = rint(bonus[g] * 2^20), |bonus[g]| <= 32768, and T[t][g] = S[t][g] + qb[g] * (m - 1): "mean centrality + bonus",
+ *      compared exactly in int64 (|T| < 2^54).
+ *   5. Medoid.  The medoid of a cluster is its member with the largest T, ties to the smaller genome number.  medoids[t][g] is
+ *      the medoid of g's cluster in set t; n_clusters, a HOST array [n_sets] that may be NULL, counts the g with
+ *      medoids[t][g] == g.
+ *   6. Identity.  identity[t][g] is 100.0 when g is its own medoid; w / 2^20 as float64 for the present pair (g, medoid); NaN
+ *      (0x7ff8000000000000) when that pair is not present -- under average linkage a member need not have a row with its
+ *      medoid.  w / 2^20 equals the pair's symmetric identity whenever that is a multiple of 2^-20, which holds for
+ *      everything FastANI reports at or above 16.
+ *   7. Outputs.  sums and sizes, [n_sets][n_genomes], hold S and m.  medoids, identity, sums and sizes may each be NULL.
+ *      labels and all four outputs are DEVICE pointers when io_device != 0.
+ *   8. stats may be NULL; stats[0] surviving rows, [1] pairs, [2] present pairs, [3] present pairs that lie inside a cluster,
+ *      summed over the sets.
+ *   9. FA_ERR_INVALID with nothing written, the out-parameters included: everything fa_table_clusters rejects; missing
+ *      negative, NaN or above 128; n_sets < 1; null labels with n_genomes > 0; an invalid label set; a bonus that is NaN or
+ *      beyond +-32768; a present pair whose identity is NaN or outside [0, 128].  n_genomes > 2^18, or n_sets * n_genomes >
+ *      2^31 - 1, is FA_ERR_UNSUPPORTED.
+ *  10. Runs like the other reductions: on the calling thread's current device, on a stream of its own, with memory from the
+ *      device pool, finished when it returns, FA_ERR_NO_DEVICE without a device.  The same input gives the same bytes on
+ *      every run. */
+int fa_table_medoids(const fa_cgi_row *rows, int64_t n_rows, int rows_device, int32_t n_genomes, const uint64_t *query_lengths,
+                     const uint64_t *reference_lengths, const fa_table_params *p, float missing, const int32_t *labels, int32_t n_sets,
+                     const double *bonus, int32_t *medoids, double *identity, int64_t *sums, int32_t *sizes, int io_device,
+                     int32_t *n_clusters, int64_t *stats);
+/* Steps 4-5 on two members b and a of one cluster of m genomes (1 <= m <= 2^18; S in [0, 2^46), |bonus| <= 32768, numbers >= 0,
+ * else FA_ERR_INVALID): t[0] = T of b, t[1] = T of a, *better = 1 when b replaces a as the medoid, else 0.  Host only; it calls
+ * the functions the kernels use. */
+int fa_debug_medoid_better(double bonus_b, int64_t s_b, int32_t b, double bonus_a, int64_t s_a, int32_t a, int32_t m, int64_t t[2],
+                           int *better);
 
 /* ---- a query x reference hit table, reduced to every query's k best hits ---- */
 /* What a batch of queries is mapped against a reference database for: per query, the closest references that pass an identity

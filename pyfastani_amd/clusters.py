@@ -1,6 +1,6 @@
 """What an all-vs-all is run for, computed where the hit table already is: the symmetric identity of every genome pair and
 the groups of genomes above a cut-off (species clusters at 95 %, dereplication at 99 %), by ``fa_table_pairs`` /
-``fa_table_clusters`` / ``fa_table_representatives`` / ``fa_table_linkage`` / ``fa_table_dendrogram`` of the library (include/fastani_hip.h has the semantics; upstream's counterpart is the matrix output,
+``fa_table_clusters`` / ``fa_table_representatives`` / ``fa_table_linkage`` / ``fa_table_dendrogram`` / ``fa_table_medoids`` of the library (include/fastani_hip.h has the semantics; upstream's counterpart is the matrix output,
 `outputPhylip`, include/fastani/cgi/compute_core_identity.pxd:39-51 of the reference, and whatever the user clusters it with).
 
 The rows are one genome set mapped against itself: ``query_id`` and ``ref_genome_id`` index the same list of ``n`` genomes,
@@ -11,6 +11,7 @@ CPU path: without a HIP device the functions raise ``RuntimeError``, like every 
 
 Not imported by the package itself (like `outputs`): it needs numpy.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -212,6 +213,71 @@ def dendrogram(rows, query_lengths, reference_lengths, fragment_length, minimum_
                      n_clusters=n_clusters.value)
     merges = merges[: n_merges.value] if t.torch else merges[: n_merges.value].copy()
     return Dendrogram(t.n, merges, labels, min_identity, missing)
+
+
+Medoids = collections.namedtuple("Medoids", "labels identity centrality size")
+
+
+def medoids(rows, query_lengths, reference_lengths, fragment_length, labels, minimum_fraction=0.2, reciprocal=False, missing=0.0,
+            bonus=None, stats=None):
+    """Centrality and medoids of given clusters (``fa_table_medoids``): ``labels`` is a partition as `clusters`,
+    `average_linkage`, `Dendrogram.cut` or `representatives` return it -- int32 ``[n]``, or ``[c, n]`` for ``c`` partitions
+    served by one pass over the table; numpy for ``ROW_DTYPE`` rows, a tensor on the rows' device for device rows (mixing the
+    two raises ``ValueError``).  A genome's centrality is its mean identity to the other members of its cluster, a pair without
+    a row that passes the filter (with ``reciprocal``: in both directions) counting as ``missing``; the medoid of a cluster is
+    the member with the largest ``centrality + bonus`` -- ``bonus``, one value per genome in identity points (dRep:
+    completeness - 5 x contamination ...), ``None`` for none --, compared exactly in fixed point, ties to the smaller genome
+    number.  Returns ``Medoids(labels, identity, centrality, size)``, each of the shape of ``labels``: the medoid of every
+    genome's cluster (int32; a medoid labels itself, so `outputs.write_representatives` takes ``labels`` and ``identity``);
+    the symmetric identity of the genome and its medoid (float64; 100 for a medoid, NaN where the two have no present pair);
+    the centrality (float64, ``sums / (size - 1) / 2**20``, 100 for a cluster of one: for display and for scores the caller
+    forms itself -- nothing is decided by it); the size of the cluster (int32).  ``stats``, a dict, receives ``rows``,
+    ``pairs``, ``present``, ``inside`` (present pairs inside a cluster, over all partitions) and ``n_clusters`` (a list, one
+    per partition).  A label outside ``[0, n)`` or one that is not its own label, a NaN or negative ``missing`` or one above
+    128, a NaN ``bonus`` or one beyond 32768 raise ``ValueError``; more than 2^18 genomes ``NotImplementedError``."""
+    t = _Table(rows, query_lengths, reference_lengths, fragment_length, minimum_fraction, 0.0, reciprocal)
+    if _is_tensor(labels) != t.is_device:
+        raise ValueError("labels are numpy for ROW_DTYPE rows and a tensor on the rows' device for device rows")
+    if t.is_device:
+        if labels.dtype != t.torch.int32 or labels.device != t.device:
+            raise ValueError("device labels are an int32 tensor on the rows' device")
+        labels = labels.contiguous()
+    else:
+        labels = np.ascontiguousarray(labels)
+        if labels.dtype.kind not in "iu":
+            raise ValueError("labels are genome numbers")
+        labels = labels.astype(np.int32, copy=False)
+    shape = tuple(labels.shape)
+    if len(shape) not in (1, 2) or shape[-1] != t.n or (len(shape) == 2 and shape[0] < 1):
+        raise ValueError("labels are [n] or [c, n] with c >= 1 over the n genomes of the length arrays")
+    n_sets = shape[0] if len(shape) == 2 else 1
+    if bonus is not None:
+        bonus = np.ascontiguousarray(bonus.cpu().numpy() if hasattr(bonus, "cpu") else bonus, dtype=np.float64)
+        if bonus.shape != (t.n,):
+            raise ValueError("bonus holds one value per genome")
+    bonus_ptr = C.c_void_p(bonus.ctypes.data) if bonus is not None else None
+    n_clusters, counters = (C.c_int32 * n_sets)(), (C.c_int64 * 4)()
+    with t.on_device():
+        if t.torch:
+            t.torch.cuda.synchronize(t.device)              # (labels may come from torch's own stream)
+            out = [t.torch.empty(shape, dtype=kind, device=t.device) for kind in (t.torch.int32, t.torch.float64, t.torch.int64, t.torch.int32)]
+            ptrs = [C.c_void_p(x.data_ptr()) for x in out]
+            label_ptr = C.c_void_p(labels.data_ptr())
+        else:
+            out = [np.empty(shape, dtype=kind) for kind in (np.int32, np.float64, np.int64, np.int32)]
+            ptrs = [C.c_void_p(x.ctypes.data) for x in out]
+            label_ptr = C.c_void_p(labels.ctypes.data)
+        check(lib.fa_table_medoids(*t.head(), float(missing), label_ptr, n_sets, bonus_ptr, *ptrs, 1 if t.is_device else 0, n_clusters,
+                                   counters))
+    chosen, identity, sums, size = out
+    if t.torch:
+        centrality = sums.to(t.torch.float64) / (size - 1).clamp(min=1).to(t.torch.float64) / 2.0 ** 20
+        centrality = t.torch.where(size == 1, t.torch.full_like(centrality, 100.0), centrality)
+    else:
+        centrality = np.where(size == 1, 100.0, sums / np.maximum(size - 1, 1).astype(np.float64) / 2.0 ** 20)
+    if stats is not None:
+        stats.update(rows=counters[0], pairs=counters[1], present=counters[2], inside=counters[3], n_clusters=list(n_clusters))
+    return Medoids(chosen, identity, centrality, size)
 
 
 def _order(order, t):

@@ -554,6 +554,33 @@ int fa_debug_linkage_order(const int64_t a[4], const int64_t b[4], int *first) {
     *first = link_order(x, y);
   });
 }
+int fa_table_medoids(const fa_cgi_row *rows, int64_t n_rows, int rows_device, int32_t n_genomes, const uint64_t *query_lengths,
+                     const uint64_t *reference_lengths, const fa_table_params *p, float missing, const int32_t *labels, int32_t n_sets,
+                     const double *bonus, int32_t *medoids, double *identity, int64_t *sums, int32_t *sizes, int io_device,
+                     int32_t *n_clusters, int64_t *stats) {
+  return guarded([&] {
+    MedoidRequest m;
+    m.missing = missing; m.labels = labels; m.n_sets = n_sets; m.bonus = bonus;
+    m.medoids = medoids; m.identity = identity; m.sums = sums; m.sizes = sizes; m.io_device = io_device != 0;
+    m.n_clusters = n_clusters;
+    TableRequest want;
+    want.clusters = true;
+    want.medoids = &m; want.stats = stats;
+    table_reduce(rows, n_rows, rows_device != 0, n_genomes, query_lengths, reference_lengths, p, want);
+  });
+}
+int fa_debug_medoid_better(double bonus_b, int64_t s_b, int32_t b, double bonus_a, int64_t s_a, int32_t a, int32_t m, int64_t t[2],
+                           int *better) {
+  return guarded([&] {
+    FA_REQUIRE(t && better, FA_ERR_INVALID, "null destination");
+    FA_REQUIRE(medoid_bonus_ok(bonus_a) && medoid_bonus_ok(bonus_b), FA_ERR_INVALID, "a bonus must be a number in [-32768, 32768]");
+    FA_REQUIRE(m >= 1 && m <= LINK_MAX_GENOMES && a >= 0 && b >= 0, FA_ERR_INVALID, "a cluster has 1 .. 2^18 members with numbers >= 0");
+    FA_REQUIRE(s_a >= 0 && s_b >= 0 && s_a < (1LL << 46) && s_b < (1LL << 46), FA_ERR_INVALID, "a centrality sum lies in [0, 2^46)");
+    t[0] = medoid_t(s_b, medoid_qb(bonus_b), m);
+    t[1] = medoid_t(s_a, medoid_qb(bonus_a), m);
+    *better = medoid_better(t[0], b, t[1], a) ? 1 : 0;
+  });
+}
 int fa_table_best(const fa_cgi_row *rows, int64_t n_rows, int rows_device, int32_t n_queries, int32_t n_references,
                   const uint64_t *query_lengths, const uint64_t *reference_lengths, const fa_best_params *p, fa_cgi_row *best,
                   int64_t *offsets, int64_t cap, int64_t *n_best, int out_device, int64_t *stats) {

@@ -1,5 +1,6 @@
 // fa_link.h -- the integer arithmetic of average-linkage clustering (fa_table_linkage, fa_linkage.hip.h): plain C++, no HIP.
 // The kernels and fa_debug_linkage_order call the same functions, so the exactness of the order is testable without a GPU.
+// The last part holds the same for the medoids of given clusters (fa_table_medoids, fa_medoid.hip.h, fa_debug_medoid_better).
 //
 // Identities are fixed point, 20 fractional bits: w = rint(identity * 2^20), ties to even.  A float32 at or above 16 is a
 // multiple of 2^-19, so the float64 mean of two of them is a multiple of 2^-20 and the conversion is exact for everything
@@ -87,6 +88,34 @@ FA_LINK_FN LinkCand link_merge_cand(int32_t lo, int32_t hi, int32_t size_lo, int
 FA_LINK_FN long long link_cutoff(float value) {
   const double d = rint((double)value * LINK_SCALE);
   return d < (double)(LINK_MAX_W + 1) ? (long long)d : LINK_MAX_W + 1;
+}
+
+// ---- centrality and medoids (fa_table_medoids, fa_medoid.hip.h).  A member g of a cluster of m genomes has
+//     S = sum of w over its present pairs inside the cluster + qm * (m - 1 - their number)           (< 2^46)
+//     T = S + qb * (m - 1),   qb = rint(bonus * 2^20), |bonus| <= 32768                             (|T| < 2^54)
+// so T / (m - 1) is "mean identity to the others + bonus", and within one cluster (one m) the order of T is its order.
+constexpr double MEDOID_MAX_BONUS = 32768.0;
+
+// whether a bonus can be converted at all (false for NaN)
+FA_LINK_FN bool medoid_bonus_ok(double bonus) { return bonus >= -MEDOID_MAX_BONUS && bonus <= MEDOID_MAX_BONUS; }
+
+// rint(bonus * 2^20), ties to even; medoid_bonus_ok(bonus)
+FA_LINK_FN long long medoid_qb(double bonus) { return (long long)rint(bonus * LINK_SCALE); }
+
+// the centrality sum of a member: `w` and `c` are the sum and the number of its present pairs inside its cluster of m >= 1
+FA_LINK_FN long long medoid_s(long long w, long long c, long long m, long long qm) { return w + qm * (m - 1 - c); }
+
+FA_LINK_FN long long medoid_t(long long s, long long qb, long long m) { return s + qb * (m - 1); }
+
+// T as an unsigned key of the same order (the sign bit flipped): what a 64-bit atomicMax can decide.  Never 0 for |T| < 2^63
+FA_LINK_FN unsigned long long medoid_key(long long t) { return (unsigned long long)t ^ 0x8000000000000000ULL; }
+
+// whether member b with T = tb replaces member a with T = ta as the medoid: the larger T, ties to the smaller genome number.
+// The kernels decide the same relation in two order-independent steps: the largest medoid_key of the cluster, then the
+// smallest genome number among the members that reach it
+FA_LINK_FN bool medoid_better(long long tb, int32_t b, long long ta, int32_t a) {
+  const unsigned long long kb = medoid_key(tb), ka = medoid_key(ta);
+  return kb != ka ? kb > ka : b < a;
 }
 
 }  // namespace fa

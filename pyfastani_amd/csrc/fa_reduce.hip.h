@@ -1,5 +1,5 @@
 // fa_reduce.hip.h -- the host drivers of the reductions over results the mapper already holds: a hit table to pairs,
-// clusters, representatives, average-linkage clusters and their dendrogram with its cuts (fa_table.hip.h, fa_represent.hip.h, fa_linkage.hip.h), to every query's k best hits (fa_best.hip.h), the
+// clusters, representatives, average-linkage clusters and their dendrogram with its cuts, and the medoids of given clusters (fa_table.hip.h, fa_represent.hip.h, fa_linkage.hip.h, fa_medoid.hip.h), to every query's k best hits (fa_best.hip.h), the
 // signature screen (fa_screen.hip.h) and its containment road (fa_contain.hip.h).  They use nothing of the sketch, the mapper or the workspace -- but for the last one, the
 // signatures of a resident batch (fa_batchsig.hip.h), which borrows a workspace for K1's staging arrays; fa_engine.hip wraps each
 // in its extern "C" entry point.
@@ -26,6 +26,7 @@
 #include "fa_common.h"
 #include "fa_contain.hip.h"
 #include "fa_linkage.hip.h"
+#include "fa_medoid.hip.h"
 #include "fa_order.h"
 #include "fa_query.hip.h"
 #include "fa_represent.hip.h"
@@ -182,7 +183,94 @@ inline unsigned int linkage(Emit emit_into, int64_t n_pairs, int32_t *labels, in
   return roots;
 }
 
+// what fa_table_medoids brings beyond the table: the label sets, the bonus and the four outputs
+struct MedoidRequest {
+  float missing = 0.0f;
+  const int32_t *labels = nullptr; int32_t n_sets = 0; const double *bonus = nullptr;
+  int32_t *medoids = nullptr; double *identity = nullptr; int64_t *sums = nullptr; int32_t *sizes = nullptr;
+  bool io_device = false;                  // labels and the four outputs
+  int32_t *n_clusters = nullptr;           // host, [n_sets]
+};
+
+// whether one label set is valid: every label in [0, n_genomes) and its own label
+inline bool label_set_ok(const int32_t *labels, int32_t n_genomes) {
+  for (int32_t g = 0; g < n_genomes; g++) {
+    const int32_t l = labels[g];
+    if (l < 0 || l >= n_genomes || labels[l] != l) return false;
+  }
+  return true;
+}
+
+// The medoids of n_sets partitions of n_genomes > 0 genomes over the present pairs of a table (fa_medoid.hip.h): the four
+// outputs of `m` are written once the label sets have passed k_medoid_check; `roots` receives every set's number of medoids and
+// `inside` the present pairs inside a cluster, over all sets.  `emit_into(keys, sums)` has k_table_write put the two directed
+// entries of each of the n_pairs present pairs there.  `qb` is empty for no bonus.  The stream is synchronised on return.
+template <typename Emit>
+inline void medoids(Emit emit_into, int64_t n_pairs, int32_t n_genomes, long long qm, const std::vector<long long> &qb, const MedoidRequest &m,
+                    hipStream_t st, std::vector<unsigned int> &roots, int64_t &inside) {
+  FA_REQUIRE(n_pairs <= (int64_t)(1 << 30), FA_ERR_UNSUPPORTED, "more than 2^30 present pairs");
+  StatusBlock<MedoidStatus> d_status(st);
+  DevBuf<int32_t> d_labels, words;            // words: seg_start, seg_end, then size and who of every (set, genome)
+  DevBuf<unsigned long long> keys[2], best;
+  DevBuf<LinkSum> sums[2];
+  DevBuf<long long> s, d_qb;
+  DevBuf<unsigned int> d_roots;
+  DevBuf<unsigned char> temp;
+  const size_t n = (size_t)n_genomes, total = n * (size_t)m.n_sets;
+  const int64_t n_in = 2 * n_pairs;
+
+  MedoidArgs a{};
+  a.n_entries = n_in; a.n_genomes = n_genomes; a.n_sets = m.n_sets; a.bits = (int32_t)id_bits(n_genomes); a.qm = qm;
+  a.status = d_status.p;
+  a.labels = on_device(m.labels, m.io_device, total, d_labels, st);
+  words.ensure(2 * n + 2 * total);
+  a.seg_start = words.p; a.seg_end = words.p + n; a.size = words.p + 2 * n; a.who = words.p + 2 * n + total;
+  FA_HIP(hipMemsetAsync(words.p, 0, (2 * n + total) * sizeof(int32_t), st));
+  FA_HIP(hipMemsetAsync(a.who, 0x7F, total * sizeof(int32_t), st));            // 0x7F7F7F7F: above every genome number
+  const dim3 grid((unsigned)ceil_div(n_genomes, 256), (unsigned)std::min(m.n_sets, 65535));
+  // the verdict on the labels is read before they index anything and before an output is touched
+  hipLaunchKernelGGL(k_medoid_check, grid, dim3(256), 0, st, a);
+  FA_HIP(hipGetLastError());
+  FA_REQUIRE(!(d_status.read(st).flags & MED_BAD_LABEL), FA_ERR_INVALID,
+             "a label lies outside [0, n_genomes) or is not its own label");
+  if (n_in) {
+    for (int i = 0; i < 2; i++) { keys[i].ensure((size_t)n_in); sums[i].ensure((size_t)n_in); }
+    emit_into(keys[0].p, sums[0].p);
+    // one sort for all the sets; the bits a key can have set: two genome numbers
+    const unsigned end_bit = 2u * (unsigned)a.bits;
+    with_temp(temp, [&](void *t, size_t &bytes) {
+      return rocprim::radix_sort_pairs(t, bytes, keys[0].p, keys[1].p, sums[0].p, sums[1].p, (size_t)n_in, 0u, end_bit, st);
+    });
+    a.keys = keys[1].p; a.sums = sums[1].p;
+    hipLaunchKernelGGL(k_medoid_segments, dim3(ceil_div(n_in, 256)), dim3(256), 0, st, a);
+  }
+  s.ensure(total);
+  a.s = s.p;
+  const dim3 sums_grid(grid.x, (unsigned)std::min(ceil_div(m.n_sets, MED_SETS), 65535));
+  hipLaunchKernelGGL(k_medoid_sums, sums_grid, dim3(256), 0, st, a);
+  if (!qb.empty()) { d_qb.upload(qb, st); a.qb = d_qb.p; }
+  best.ensure(total);
+  FA_HIP(hipMemsetAsync(best.p, 0, total * sizeof(unsigned long long), st));
+  a.best = best.p;
+  hipLaunchKernelGGL(k_medoid_best, grid, dim3(256), 0, st, a);
+  hipLaunchKernelGGL(k_medoid_pick, grid, dim3(256), 0, st, a);
+  d_roots.ensure((size_t)m.n_sets);
+  FA_HIP(hipMemsetAsync(d_roots.p, 0, (size_t)m.n_sets * sizeof(unsigned int), st));
+  a.roots = d_roots.p;
+  Staged<int32_t> out_medoids(m.medoids, m.io_device, total), out_sizes(m.sizes, m.io_device, total);
+  Staged<double> out_identity(m.identity, m.io_device, total);
+  Staged<int64_t> out_sums(m.sums, m.io_device, total);
+  a.medoids = out_medoids.dev(); a.identity = out_identity.dev(); a.sums_out = out_sums.dev(); a.sizes_out = out_sizes.dev();
+  hipLaunchKernelGGL(k_medoid_write, grid, dim3(256), 0, st, a);
+  FA_HIP(hipGetLastError());
+  out_medoids.finish(st); out_identity.finish(st); out_sums.finish(st); out_sizes.finish(st);
+  roots.resize((size_t)m.n_sets);
+  d_roots.download(roots.data(), roots.size(), st);
+  inside = (int64_t)(d_status.read(st).inside / 2ULL);            // (two directed entries a pair; read() synchronises)
+}
+
 struct TableRequest {
+  const MedoidRequest *medoids = nullptr;  // with `clusters`: fa_table_medoids; labels, n_clusters and the rest below are not read
   bool clusters = false;
   bool representatives = false;            // with `clusters`: labels are representatives, not components
   bool linkage = false;                    // with `clusters`: labels are average-linkage clusters, `missing` their missing identity
@@ -203,7 +291,26 @@ inline void table_reduce(const fa_cgi_row *rows, int64_t n_rows, bool rows_devic
   FA_REQUIRE(n_rows == 0 || rows, FA_ERR_INVALID, "null rows");
   FA_REQUIRE(n_genomes == 0 || (query_lengths && reference_lengths), FA_ERR_INVALID, "null genome lengths");
   FA_REQUIRE(n_rows <= (int64_t)INT32_MAX, FA_ERR_UNSUPPORTED, "a table of more than 2^31 - 1 rows");
-  if (want.dendrogram) FA_REQUIRE(want.n_merges && (!want.merges || want.merge_cap >= 0), FA_ERR_INVALID, "null merge count or negative capacity");
+  std::vector<long long> qb;
+  if (const MedoidRequest *m = want.medoids) {
+    FA_REQUIRE(m->missing >= 0.0f && m->missing <= (float)LINK_MAX_IDENTITY, FA_ERR_INVALID, "missing must be a number in [0, 128]");   // (false for NaN)
+    FA_REQUIRE(m->n_sets >= 1, FA_ERR_INVALID, "medoids need at least one label set");
+    FA_REQUIRE(n_genomes == 0 || m->labels, FA_ERR_INVALID, "null labels");
+    FA_REQUIRE(n_genomes <= LINK_MAX_GENOMES, FA_ERR_UNSUPPORTED, "medoids over more than 2^18 genomes");
+    FA_REQUIRE((int64_t)m->n_sets * (int64_t)n_genomes <= (int64_t)INT32_MAX, FA_ERR_UNSUPPORTED, "more than 2^31 - 1 labels");
+    if (m->bonus) {
+      qb.resize((size_t)n_genomes);
+      for (int32_t g = 0; g < n_genomes; g++) {
+        FA_REQUIRE(medoid_bonus_ok(m->bonus[g]), FA_ERR_INVALID, "a bonus must be a number in [-32768, 32768]");
+        qb[(size_t)g] = medoid_qb(m->bonus[g]);
+      }
+    }
+    // (labels on the host are checked here, those in HBM by k_medoid_check -- which sees the host's again)
+    if (!m->io_device)
+      for (int32_t t = 0; t < m->n_sets; t++)
+        FA_REQUIRE(label_set_ok(m->labels + (size_t)t * (size_t)n_genomes, n_genomes), FA_ERR_INVALID,
+                   "a label lies outside [0, n_genomes) or is not its own label");
+  } else if (want.dendrogram) FA_REQUIRE(want.n_merges && (!want.merges || want.merge_cap >= 0), FA_ERR_INVALID, "null merge count or negative capacity");
   else if (want.clusters) FA_REQUIRE(n_genomes == 0 || want.labels, FA_ERR_INVALID, "null labels");
   else FA_REQUIRE(want.n_pairs && want.cap >= 0, FA_ERR_INVALID, "null pair count or negative capacity");
   std::vector<int32_t> pos;
@@ -224,6 +331,7 @@ inline void table_reduce(const fa_cgi_row *rows, int64_t n_rows, bool rows_devic
     qc = (long long)std::min(dc, (double)(LINK_MAX_W + 1));
     qm = (long long)std::min(dm, (double)LINK_MAX_W);
   }
+  if (want.medoids) qm = link_fixed((double)want.medoids->missing);
   require_device();
   CallStream stream;
   hipStream_t st = stream.s;
@@ -240,7 +348,7 @@ inline void table_reduce(const fa_cgi_row *rows, int64_t n_rows, bool rows_devic
   a.n_rows = n_rows; a.n_genomes = n_genomes;
   a.fragment_length = (unsigned long long)p->fragment_length; a.min_fraction = p->min_fraction;
   a.min_identity = (double)p->min_identity; a.reciprocal = p->reciprocal;
-  a.edges_only = want.linkage ? TAB_EMIT_LINK : want.representatives ? TAB_EMIT_WEIGHTED : want.clusters ? TAB_EMIT_EDGES : TAB_EMIT_PAIRS;
+  a.edges_only = want.linkage || want.medoids ? TAB_EMIT_LINK : want.representatives ? TAB_EMIT_WEIGHTED : want.clusters ? TAB_EMIT_EDGES : TAB_EMIT_PAIRS;
   a.link_bits = (int32_t)id_bits(n_genomes);
   a.status = d_status.p;
   a.n_chunks = ceil_div(n_rows, TAB_CHUNK);
@@ -297,6 +405,17 @@ inline void table_reduce(const fa_cgi_row *rows, int64_t n_rows, bool rows_devic
     a.link_keys = link_keys; a.link_sums = link_sums;
     emit();
   };
+  if (const MedoidRequest *m = want.medoids) {
+    std::vector<unsigned int> set_roots((size_t)m->n_sets, 0u);
+    int64_t inside = 0;
+    if (n_genomes) medoids(emit_into, n_emit, n_genomes, qm, qb, *m, st, set_roots, inside);
+    if (m->n_clusters) for (int32_t t = 0; t < m->n_sets; t++) m->n_clusters[t] = (int32_t)set_roots[(size_t)t];
+    if (want.stats) {
+      want.stats[0] = (int64_t)status.survivors; want.stats[1] = (int64_t)status.pairs;
+      want.stats[2] = (int64_t)status.edges; want.stats[3] = inside;
+    }
+    return;
+  }
   if (want.dendrogram) {
     // everything lands in buffers of the call's own first: a short `cap` leaves the caller's memory as it was
     int64_t n_merges = 0;

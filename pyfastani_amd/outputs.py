@@ -57,7 +57,8 @@ def write_clusters(path, names, labels):
 def write_representatives(path, names, labels, identity):
     """The result of `pyfastani_amd.clusters.representatives`: one line per genome, in genome order, with its name, the name
     of its representative and the symmetric identity of the two (100 for a representative itself).  `write_clusters` takes
-    the same labels."""
+    the same labels.  The ``labels`` and ``identity`` of one partition of `pyfastani_amd.clusters.medoids` are written the same
+    way; a member without a row with its medoid has a NaN identity, printed as ``nan``."""
     labels = labels.cpu().numpy() if hasattr(labels, "cpu") else np.asarray(labels)
     identity = identity.cpu().numpy() if hasattr(identity, "cpu") else np.asarray(identity)
     if len(labels) != len(names) or len(identity) != len(names):

@@ -250,6 +250,16 @@ class ResidentHitTable:
         return _clusters.dendrogram(self._rows_in_place(tables), query_lengths, reference_lengths, fragment_length,
                                     minimum_fraction, min_identity, reciprocal, missing, stats)
 
+    def medoids(self, tables, query_lengths, reference_lengths, fragment_length, labels, minimum_fraction=0.2, reciprocal=False,
+                missing=0.0, bonus=None, stats=None):
+        """`pyfastani_amd.clusters.medoids` over an exchanged table (what `step` returns) of an all-vs-all and the labels of
+        `average_linkage`, a `dendrogram`'s ``cut`` or any other partition of its genomes: ``Medoids(labels, identity,
+        centrality, size)`` where the table is, with the count rows dropped and the ranks joined as for `clusters`.  The call
+        runs on one GPU."""
+        from . import clusters as _clusters
+        return _clusters.medoids(self._rows_in_place(tables), query_lengths, reference_lengths, fragment_length, labels,
+                                 minimum_fraction, reciprocal, missing, bonus, stats)
+
     def representatives(self, tables, query_lengths, reference_lengths, fragment_length, minimum_fraction=0.2, min_identity=95.0,
                         reciprocal=False, order=None, stats=None):
         """`pyfastani_amd.clusters.representatives` over an exchanged table (what `step` returns) of an all-vs-all:

@@ -6,6 +6,7 @@
 // largest `missing`, against the largest cut-off the driver passes on (LINK_MAX_W + 1).  The order is also held against a
 // second comparison that divides instead of multiplying (quotient, then remainders by cross products that fit 128 bits).
 // The merge list of fa_table_dendrogram / fa_dendrogram_cut: what counts as a merge, its candidate and the cut-off of a float.
+// The medoids of fa_table_medoids: the bonus, S, T, the key and the relation at the ends of their range.
 #include <cstdint>
 #include <cstdio>
 
@@ -62,6 +63,23 @@ int main() {
   CHECK(link_cutoff(0.0f) == 0 && link_cutoff(-0.0f) == 0 && link_cutoff(95.0f) == 95LL << 20 && link_cutoff(128.0f) == LINK_MAX_W, "cut-offs of round values");
   CHECK(link_cutoff(128.00001f) == LINK_MAX_W + 1 && link_cutoff(3.4e38f) == LINK_MAX_W + 1 && link_cutoff(INFINITY) == LINK_MAX_W + 1, "the clamp, infinity included");
   CHECK(link_cutoff(1.0f) == link_cutoff(1.00000012f), "two float32 with one fixed-point value");
+
+  // centrality and medoids (fa_table_medoids): the bonus, S, T and the relation at the ends of their range -- a cluster of 2^18
+  // genomes, every pair at 128 or every pair missing at 128, the largest bonus of either sign
+  const long long m_max = LINK_MAX_GENOMES;
+  CHECK(medoid_bonus_ok(32768.0) && medoid_bonus_ok(-32768.0) && medoid_bonus_ok(-0.0), "the ends of the bonus range");
+  CHECK(!medoid_bonus_ok(32768.01) && !medoid_bonus_ok(-1e300) && !medoid_bonus_ok(0.0 / 0.0), "outside it, and NaN");
+  CHECK(medoid_qb(32768.0) == 1LL << 35 && medoid_qb(-32768.0) == -(1LL << 35) && medoid_qb(0.5 / LINK_SCALE) == 0 && medoid_qb(1.5 / LINK_SCALE) == 2 &&
+        medoid_qb(-1.5 / LINK_SCALE) == -2, "the fixed-point bonus, ties to even");
+  const long long s_all = medoid_s(LINK_MAX_W * (m_max - 1), m_max - 1, m_max, LINK_MAX_W), s_missing = medoid_s(0, 0, m_max, LINK_MAX_W);
+  CHECK(s_all == LINK_MAX_W * (m_max - 1) && s_missing == s_all && s_all < (1LL << 46) && medoid_s(0, 0, 1, LINK_MAX_W) == 0, "the largest S stays below 2^46");
+  const long long t_top = medoid_t(s_all, medoid_qb(32768.0), m_max), t_bottom = medoid_t(0, medoid_qb(-32768.0), m_max);
+  CHECK(t_top < (1LL << 54) && t_bottom > -(1LL << 54) && medoid_t(s_all, medoid_qb(32768.0), 1) == s_all, "|T| stays below 2^54");
+  CHECK(medoid_key(t_bottom) < medoid_key(-1) && medoid_key(-1) < medoid_key(0) && medoid_key(0) < medoid_key(t_top) && medoid_key(t_bottom) != 0,
+        "the key keeps the order across the sign and is never 0");
+  CHECK(medoid_better(t_top, 5, t_top - 1, 0) && !medoid_better(t_top - 1, 0, t_top, 5) && medoid_better(0, 7, -1, 0) && !medoid_better(t_bottom, 0, 0, 7),
+        "one unit of T decides");
+  CHECK(medoid_better(t_top, 3, t_top, 4) && !medoid_better(t_top, 4, t_top, 3) && !medoid_better(t_top, 3, t_top, 3), "a tie goes to the smaller number");
 
   long checked = 0;
   for (int trial = 0; trial < 200000; trial++) {
