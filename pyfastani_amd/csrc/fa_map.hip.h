@@ -1868,7 +1868,10 @@ struct L2Args {
   // robin): related genomes are largely co-linear, so those workgroups stream the same stretches of the index at the same
   // time and all but the first find them in the XCD's L2 / the memory-side cache instead of HBM.  nullptr: identity.
   const int32_t *frag_order;
-  unsigned long long *stamp;         // stage_stamp: start of the L2 stage
+  // ... and a pass of ONE genome: its `one_frags` fragments in eight runs of `one_run`, workgroup b takes one_genome_frag(b, ...)
+  // -- arithmetic on blockIdx.x, no table.  one_run 0: off (the table, or the identity).
+  uint32_t one_run, one_frags;
+  unsigned long long *stamp;        // stage_stamp: start of the L2 stage
   // k_l2_scan takes its loci through `scan_order` when it is set (round 6): the loci of every region sorted by the length of their
   // event streams, longest first (a counting sort over SCAN_CLASSES classes of `scan_class_div` events: k_l2_events counts,
   // k_l2_order places).  A wave slides 64 loci and lasts as long as the longest; in the numbering of k_l1 a wave holds the loci of
@@ -1939,7 +1942,7 @@ __global__ __launch_bounds__(EV_THREADS, EV_WAVES_PER_SIMD) void k_l2_events(L2A
   __shared__ __align__(8) unsigned char rank_table[OCC_N * 4 + (OCC_N + 1) * 2];
   uint32_t *const OCC = (uint32_t *)rank_table;
   uint16_t *const R0 = (uint16_t *)(rank_table + OCC_N * 4);
-  const int f = a.frag_order ? a.frag_order[blockIdx.x] : (int)blockIdx.x;
+  const int f = a.one_run ? one_genome_frag(blockIdx.x, a.one_run, a.one_frags) : a.frag_order ? a.frag_order[blockIdx.x] : (int)blockIdx.x;
   if (f < 0) return;
   const uint32_t l_lo = a.f_loci_lo[f], l_n = a.f_loci_n[f];
   if (l_n == 0) return;
@@ -2252,6 +2255,10 @@ __global__ __launch_bounds__(EV_THREADS, EV_WAVES_PER_SIMD) void k_l2_events(L2A
 // pivot move changes g by count + 1, and the comparison with the best window so far done on a copy of the shared
 // count that the event's no-eval bit makes negative.
 //
+// Before its first pivot event a wave runs a prologue, kept short for the same reason: every lane clears its slots (clear), the
+// admits of the first super-window are applied to the per-rank state alone (fill), and the pivot, g and the shared count are
+// read off the state (read_pivot: one running sum, and no further than the rank where the last lane of the wave has its pivot).
+//
 // BASE0: the state starts at LDS address 0 (a kernel without static LDS; the kernel checks it), so that with 64
 // one-byte lanes per row the masked event word OR the lane IS the address of the event's slot.
 template <typename T, typename ST, int LNT, bool BASE0>
@@ -2275,6 +2282,8 @@ struct Slide {
     rl = lbase; g = 0; shared = 0; best = -1; beg = opt_s = opt_e = beg0; overflow = 0;
   }
   static constexpr uint32_t EMPTY = 2u;                           // count 0 (biased), not matched
+  // (per lane, its own slots 0 .. s + 1.  Clearing the whole block of the workgroup with 16-byte stores of all lanes instead
+  // removed vector instructions and did not move the stage: profiles/EXPERIMENTS.md, "The first window of the scan")
   __device__ __forceinline__ void clear() { for (int i = 0; i <= s + 1; i++) sto(i * LNB + lbase, EMPTY); }
   // SH: position of the event inside its 32-bit word (a constant after unrolling)
   template <int SH> __device__ __forceinline__ int slot_addr(uint32_t word) const {
@@ -2296,21 +2305,34 @@ struct Slide {
   }
   // pivot of the filled window: r* = min{r : r + sum_{c <= r} cnt[c] >= s} (s if there is none); the comparison after
   // the last admit of the first window (best was -1: it always wins)
-  __device__ __forceinline__ void read_pivot() {
-    int rstar = s, F = s, acc = 0, m_acc = 0;
-    bool hit = false;
-    for (int r = 0; r < s; r++) {
-      const uint32_t v = ld((r + 1) * LNB + lbase);
-      const int c = (int)(v >> 1) - 1, mt = (int)(v & 1u);
-      const bool now = !hit && r + acc + c >= s;
-      rstar = now ? r : rstar;
-      F = now ? r + acc : F;
-      shared = now ? m_acc : shared;
-      hit = hit || now;
-      acc += c; m_acc += mt;
+  // The stored element of rank c is v = (cnt[c] + 1) << 1 | matched, so with u = v >> 1 the test reads sum_{c <= r} u >= s + 1:
+  // ONE running sum `su`, which never falls, so "rank r lies below r*" (`open`: su <= s and r < s) holds for a prefix of the
+  // ranks: r* is their number, r* + sum_{c < r*} cnt[c] the sum at the last of them (s + the whole sum when no rank passes), and
+  // the sum of their v is twice that plus the matched ranks below r*.  The ranks behind r* change nothing, so the wave leaves
+  // the loop when its last lane has passed its r* (tested once per eight ranks; a lane without such a rank keeps it to rank s).
+  // `ranks`: the ranks of the state block (the same in every lane, >= s): the loop is uniform, its reads stay inside the block;
+  // what a lane reads behind its rank s -- slots it never cleared -- is not used (`open` is false from r = s on).
+  __device__ __forceinline__ void read_pivot(int ranks) {
+    int rstar = 0, F = 0, su = 0, addr = LNB + lbase;
+    uint32_t vsum = 0;
+    bool open = true;
+    auto rank = [&](int r) __attribute__((always_inline)) {
+      const uint32_t v = ld(addr);
+      addr += LNB;
+      su += (int)(v >> 1);
+      open = su <= s && r < s;
+      rstar += open ? 1 : 0;
+      F = open ? su : F;
+      vsum += open ? v : 0u;
+    };
+    int r = 0;
+    for (; r + 8 <= ranks; r += 8) {
+#pragma unroll
+      for (int q = 0; q < 8; q++) rank(r + q);
+      if (!__ballot(open)) break;
     }
-    F = hit ? F : s + acc;
-    shared = hit ? shared : m_acc;
+    for (; r < ranks && __ballot(open); r++) rank(r);
+    shared = (int)vsum - 2 * F;
     g = F - s;
     rl = rstar * LNB + lbase;                                     // address of slot r* (= state of rank r*-1)
     best = shared;
@@ -2425,7 +2447,7 @@ __global__ __launch_bounds__(L2_THREADS) void k_l2_scan(L2Args a) {
     }
     cur = nxt;
   }
-  sl.read_pivot();
+  sl.read_pivot(a.cnt_slots - 1);
   if (!fill_groups) sl.best = -1;
   for (uint32_t g = fill_groups; g < ngroups; g++) {
     const uint4 nxt = (g + 1 < ngroups) ? ev[g + 1] : make_uint4(0, 0, 0, 0);   // prefetch: the load is off the chain

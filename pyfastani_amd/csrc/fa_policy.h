@@ -15,6 +15,12 @@
 
 #include "fa_error.h"
 
+#if defined(__HIPCC__)
+#define FA_POLICY_FN __host__ __device__ inline
+#else
+#define FA_POLICY_FN inline
+#endif
+
 namespace fa {
 
 // ------------------------------------------------------------------------------------------------------------
@@ -183,6 +189,26 @@ inline uint32_t lds_seed_cap_max(int smax) {
 // A tri-state knob (-1: unset): the policy's default, or forced off (0) / on (anything else).
 inline bool knob_or(int knob, bool dflt) { return knob < 0 ? dflt : knob != 0; }
 
+// Workgroup order of k_l2_events over the F fragments of a pass that lie in ONE genome (round 5): its fragments in eight
+// contiguous runs of `run` = ceil(F / 8), one per XCD (workgroups go to XCDs round robin, so workgroup b runs on XCD b mod 8 and is
+// the (b / 8)-th of it).  The loci of neighbouring fragments overlap by two thirds on every reference (a locus spans ~2.6 fragment
+// lengths), so the workgroups of a run read the same index stretches -- from their XCD's L2 instead of the memory side, where
+// the identity order (fragment b on XCD b mod 8) had put every neighbour on another XCD.  8 x run workgroups; the fragment
+// (relative to the pass) of workgroup b, or -1: the last run may be short.  Under 64 fragments the identity order stays (run 0).
+FA_POLICY_FN uint32_t one_genome_run(int64_t F) { return F < 64 ? 0u : (uint32_t)((F + 7) / 8); }
+FA_POLICY_FN int32_t one_genome_frag(uint32_t b, uint32_t run, uint32_t F) {
+  const uint32_t i = (b & 7u) * run + (b >> 3);
+  return (b >> 3) < run && i < F ? (int32_t)i : -1;
+}
+FA_POLICY_FN int32_t one_genome_frag(uint32_t b, uint32_t F) { return one_genome_frag(b, (F + 7u) / 8u, F); }
+// do the fragments [f0, f1) lie in one genome?  (genome_frag_lo: the first fragment of every genome of the batch, g0 one at or
+// before f0)
+inline bool frag_range_in_one_genome(const int64_t *genome_frag_lo, int32_t g0, int64_t f0, int64_t f1) {
+  int32_t q = g0;
+  while (genome_frag_lo[q + 1] <= f0) q++;
+  return genome_frag_lo[q + 1] >= f1;
+}
+
 // Workgroup order of k_l2_events over the fragments [f0, f1) of a pass that holds several genomes (genome_frag_lo: the
 // first fragment of every genome of the batch, g0 the first genome of the pass): fragments sorted by their offset inside
 // their genome (then by genome), every group of equal offset dealt to the XCD whose list is the shortest so far
@@ -195,15 +221,13 @@ inline uint32_t build_frag_order(const int64_t *genome_frag_lo, int32_t g0, int6
   out.clear();
   int32_t q = g0;
   while (genome_frag_lo[q + 1] <= f0) q++;
-  if (genome_frag_lo[q + 1] >= f1) {
-    // ONE genome (round 5): its fragments in eight contiguous runs, one per XCD.  The loci of neighbouring fragments overlap by
-    // two thirds on every reference (a locus spans ~2.6 fragment lengths), so the workgroups of a run read the same index
-    // stretches -- from their XCD's L2 instead of the memory side, where the identity order (fragment b on XCD b mod 8)
-    // had put every neighbour on another XCD.
-    if (F < 64) return 0;
-    const int64_t run = (F + 7) / 8;
-    out.assign((size_t)run * 8, -1);
-    for (int64_t i = 0; i < F; i++) out[(size_t)((i % run) * 8 + i / run)] = (int32_t)i;
+  if (frag_range_in_one_genome(genome_frag_lo, g0, f0, f1)) {
+    // ONE genome: the order is arithmetic (one_genome_frag), and a pass takes it from there without a table (QueryPass::
+    // prepare_order); this is the same order as a table, for the callers and the checks that want one
+    const uint32_t run = one_genome_run(F);
+    if (!run) return 0;
+    out.resize((size_t)run * 8);
+    for (uint32_t b = 0; b < run * 8; b++) out[b] = one_genome_frag(b, run, (uint32_t)F);
     return (uint32_t)out.size();
   }
   // offset of every fragment inside its genome, counting sort by it (stable: genomes stay in order inside a group)

@@ -325,6 +325,7 @@ struct QueryPass {
     LociRegions loci{nullptr, 1, 0};          // regions of the locus numbering of this part
     const int32_t *frag_order = nullptr;      // workgroup order of the part (prepare_order), null = identity
     uint32_t order_len = 0;
+    uint32_t order_run = 0;                   // ... or, inside one genome, the run length of the arithmetic order (0: off)
     // into the status block of the part (launch_part, once the block exists)
     int32_t *d_stats = nullptr;
     uint64_t *d_totals = nullptr;
@@ -396,11 +397,14 @@ struct QueryPass {
     launch_cgi_stage_and_hand_over(r, p);
   }
 
-  // The workgroup order of k_l2_events (frag_order_gate, build_frag_order), built on the host, cached per (batch, fragment
-  // range) and uploaded behind K1.
+  // The workgroup order of k_l2_events (frag_order_gate).  A part inside ONE genome -- a caller that maps genome after genome
+  // out of a resident batch changes the range with every call -- takes it as arithmetic on the workgroup number (one_genome_run,
+  // one_genome_frag): nothing is built, cached or uploaded.  A part of several genomes takes a table (build_frag_order), built
+  // on the host, cached per (batch, fragment range) and uploaded behind K1.
   void prepare_order(Part &p) {
     // (FA_FRAG_ORDER_ONE: the A/B of the one-genome order)
     if (!frag_order_gate(knob::frag_order() != 0, knob::frag_order_one() != 0, NQ, p.F)) return;
+    if (frag_range_in_one_genome(g.genome_frag_lo.data(), g0, p.f0, p.f1)) { p.order_run = one_genome_run(p.F); return; }
     if (w.order_batch != g.serial || w.order_f0 != p.f0 || w.order_f1 != p.f1) {
       std::vector<int32_t> ord;
       w.order_len = build_frag_order(g.genome_frag_lo.data(), g0, p.f0, p.f1, ord);       // 0: the lists cannot be balanced, identity order
@@ -551,9 +555,11 @@ struct QueryPass {
       a.slide_end = w.rules.slide_end; a.tie = TieKey::of(w.rules.cgi_ties);
       a.f_loci_lo = w.f_loci_lo.p; a.f_loci_n = w.f_loci_n.p;
       // several genomes in the pass: the workgroups of k_l2_events in offset-major order (prepare_order)
+      // (one genome: the same order as arithmetic, 8 runs of order_run workgroups)
       a.frag_order = p.frag_order;
-      const uint32_t ev_grid = p.frag_order ? p.order_len : (uint32_t)F;
-      if (p.frag_order) r.ordered = true;
+      a.one_run = p.order_run; a.one_frags = (uint32_t)F;
+      const uint32_t ev_grid = p.order_run ? 8u * p.order_run : p.frag_order ? p.order_len : (uint32_t)F;
+      if (p.frag_order || p.order_run) r.ordered = true;
       a.ev_stage = lds.ev_stage;
       const size_t ev_lds = lds.events;
       FA_REQUIRE(ev_lds <= 150 * 1024, FA_ERR_UNSUPPORTED, "query sketch too large for the LDS-staged event kernel");
