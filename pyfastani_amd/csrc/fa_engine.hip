@@ -489,53 +489,39 @@ int fa_table_pairs(const fa_cgi_row *rows, int64_t n_rows, int rows_device, int3
                    const uint64_t *reference_lengths, const fa_table_params *p, fa_pair *pairs, int64_t cap, int64_t *n_pairs,
                    int pairs_device) {
   return guarded([&] {
-    TableRequest want;
-    want.pairs = pairs; want.cap = cap; want.n_pairs = n_pairs; want.pairs_device = pairs_device != 0;
-    table_reduce(rows, n_rows, rows_device != 0, n_genomes, query_lengths, reference_lengths, p, want);
+    table_pairs({rows, n_rows, rows_device != 0, n_genomes, query_lengths, reference_lengths, p}, pairs, cap, n_pairs, pairs_device != 0);
   });
 }
 int fa_table_clusters(const fa_cgi_row *rows, int64_t n_rows, int rows_device, int32_t n_genomes, const uint64_t *query_lengths,
                       const uint64_t *reference_lengths, const fa_table_params *p, int32_t *labels, int labels_device,
                       int32_t *n_clusters, int64_t *stats) {
   return guarded([&] {
-    TableRequest want;
-    want.clusters = true;
-    want.labels = labels; want.labels_device = labels_device != 0; want.n_clusters = n_clusters; want.stats = stats;
-    table_reduce(rows, n_rows, rows_device != 0, n_genomes, query_lengths, reference_lengths, p, want);
+    table_clusters({rows, n_rows, rows_device != 0, n_genomes, query_lengths, reference_lengths, p},
+                   labels, labels_device != 0, n_clusters, stats);
   });
 }
 int fa_table_representatives(const fa_cgi_row *rows, int64_t n_rows, int rows_device, int32_t n_genomes, const uint64_t *query_lengths,
                              const uint64_t *reference_lengths, const fa_table_params *p, const int32_t *order, int32_t *labels,
                              double *identity, int out_device, int32_t *n_representatives, int64_t *stats) {
   return guarded([&] {
-    TableRequest want;
-    want.clusters = want.representatives = true;
-    want.order = order; want.labels = labels; want.identity = identity; want.labels_device = out_device != 0;
-    want.n_clusters = n_representatives; want.stats = stats;
-    table_reduce(rows, n_rows, rows_device != 0, n_genomes, query_lengths, reference_lengths, p, want);
+    table_representatives({rows, n_rows, rows_device != 0, n_genomes, query_lengths, reference_lengths, p},
+                          order, labels, identity, out_device != 0, n_representatives, stats);
   });
 }
 int fa_table_linkage(const fa_cgi_row *rows, int64_t n_rows, int rows_device, int32_t n_genomes, const uint64_t *query_lengths,
                      const uint64_t *reference_lengths, const fa_table_params *p, float missing, int32_t *labels, int labels_device,
                      int32_t *n_clusters, int64_t *stats) {
   return guarded([&] {
-    TableRequest want;
-    want.clusters = want.linkage = true;
-    want.missing = missing;
-    want.labels = labels; want.labels_device = labels_device != 0; want.n_clusters = n_clusters; want.stats = stats;
-    table_reduce(rows, n_rows, rows_device != 0, n_genomes, query_lengths, reference_lengths, p, want);
+    table_linkage({rows, n_rows, rows_device != 0, n_genomes, query_lengths, reference_lengths, p},
+                  missing, labels, labels_device != 0, n_clusters, stats);
   });
 }
 int fa_table_dendrogram(const fa_cgi_row *rows, int64_t n_rows, int rows_device, int32_t n_genomes, const uint64_t *query_lengths,
                         const uint64_t *reference_lengths, const fa_table_params *p, float missing, fa_merge *merges, int64_t cap,
                         int64_t *n_merges, int32_t *labels, int out_device, int32_t *n_clusters, int64_t *stats) {
   return guarded([&] {
-    TableRequest want;
-    want.clusters = want.linkage = want.dendrogram = true;
-    want.missing = missing;
-    want.merges = merges; want.merge_cap = cap; want.n_merges = n_merges;
-    want.labels = labels; want.labels_device = out_device != 0; want.n_clusters = n_clusters; want.stats = stats;
-    table_reduce(rows, n_rows, rows_device != 0, n_genomes, query_lengths, reference_lengths, p, want);
+    table_dendrogram({rows, n_rows, rows_device != 0, n_genomes, query_lengths, reference_lengths, p},
+                     missing, merges, cap, n_merges, labels, out_device != 0, n_clusters, stats);
   });
 }
 int fa_dendrogram_cut(const fa_merge *merges, int64_t n_merges, int merges_device, int32_t n_genomes, const float *min_identity,
@@ -559,14 +545,8 @@ int fa_table_medoids(const fa_cgi_row *rows, int64_t n_rows, int rows_device, in
                      const double *bonus, int32_t *medoids, double *identity, int64_t *sums, int32_t *sizes, int io_device,
                      int32_t *n_clusters, int64_t *stats) {
   return guarded([&] {
-    MedoidRequest m;
-    m.missing = missing; m.labels = labels; m.n_sets = n_sets; m.bonus = bonus;
-    m.medoids = medoids; m.identity = identity; m.sums = sums; m.sizes = sizes; m.io_device = io_device != 0;
-    m.n_clusters = n_clusters;
-    TableRequest want;
-    want.clusters = true;
-    want.medoids = &m; want.stats = stats;
-    table_reduce(rows, n_rows, rows_device != 0, n_genomes, query_lengths, reference_lengths, p, want);
+    table_medoids({rows, n_rows, rows_device != 0, n_genomes, query_lengths, reference_lengths, p},
+                  missing, labels, n_sets, bonus, medoids, identity, sums, sizes, io_device != 0, n_clusters, stats);
   });
 }
 int fa_debug_medoid_better(double bonus_b, int64_t s_b, int32_t b, double bonus_a, int64_t s_a, int32_t a, int32_t m, int64_t t[2],

@@ -14,10 +14,10 @@
 // entries, key from << bits | to, value (w, 1).  A round is
 //   radix sort of the entries by key, reduce-by-key (sums of w and of the count: integers, so the order of the additions
 //     does not matter) -- every (cluster, neighbour) once, a cluster's neighbours contiguous;
-//   k_link_segments  the run of every cluster, and the number of live entries (the one key of dropped entries sorts last);
-//   k_link_best      every cluster's first candidate under the exact order: one lane per run of at most LINK_SHORT
-//                    entries; a longer run -- a hub -- is walked by the whole wave, 64 entries a step, and reduced
-//                    across the lanes.  The partner is kept only if the candidate passes the cut-off;
+//   k_link_segments  the run of every cluster (run_ends), and the number of live entries (the one key of dropped entries
+//                    sorts last);
+//   k_link_best      every cluster's first candidate under the exact order, over its run as walk_runs walks it.  The
+//                    partner is kept only if the candidate passes the cut-off;
 //   k_link_merge     a pair that is each other's partner merges: parent[hi] = lo, the sizes add;
 //   k_link_labels    label[g] = parent[label[g]];
 //   k_link_relabel   both ends of every entry through parent[]; an entry inside a cluster gets the dropped key.
@@ -42,6 +42,56 @@
 namespace fa {
 
 constexpr int LINK_SHORT = 32;                 // entries of a run one lane walks alone
+
+// ---- the runs of a directed view (shared with fa_medoid.hip.h) -------------------------------------------------------------
+// A directed view is `live` entries sorted by key = from << bits | to: the entries of one `from` are its run.
+// Entry i < live writes its run's ends into seg_start / seg_end [n_genomes] (zeroed before) where it is the first or the last.
+__device__ __forceinline__ void run_ends(const unsigned long long *keys, int32_t bits, int32_t n_genomes, int64_t i, int64_t live,
+                                         int32_t *seg_start, int32_t *seg_end) {
+  const uint32_t from = (uint32_t)(keys[i] >> bits);
+  if (from >= (uint32_t)n_genomes) return;                          // (never: the ids were checked)
+  if (i == 0 || (uint32_t)(keys[i - 1] >> bits) != from) seg_start[from] = (int32_t)i;
+  if (i == live - 1 || (uint32_t)(keys[i + 1] >> bits) != from) seg_end[from] = (int32_t)(i + 1);
+}
+
+// where `key` is in the run [start, end) (sorted), or -1
+__device__ __forceinline__ int32_t run_find(const unsigned long long *keys, int32_t start, int32_t end, unsigned long long key) {
+  int32_t lo = start, hi = end;
+  while (lo < hi) {
+    const int32_t mid = lo + (hi - lo) / 2;
+    if (keys[mid] < key) lo = mid + 1; else hi = mid;
+  }
+  return lo < end && keys[lo] == key ? lo : -1;
+}
+
+// What the lane's run [start, end) accumulates (an empty run: `zero`), CALLED BY EVERY LANE OF THE WAVE.  A run of at most
+// LINK_SHORT entries is walked by its own lane; the longer ones -- hubs -- one after the other by the whole wave, 64 entries
+// a step, and joined across the lanes by an xor butterfly (the join must not depend on the order).  The caller supplies
+//   own, from(own, owner)   what a visit needs to know of the run's lane, and how every lane gets it from lane `owner`;
+//   visit(of, i, acc)       entry i of the run of a lane whose `own` is `of`, accumulated into acc;
+//   join(acc, d)            acc joined with that of lane ^ d.
+// Every lane reaches every shuffle: nothing in the loop over the hubs is under a lane's own condition but the last line.
+template <typename Own, typename Acc, typename From, typename Visit, typename Join>
+__device__ __forceinline__ Acc walk_runs(int32_t start, int32_t end, const Own &own, const Acc &zero, From from, Visit visit, Join join) {
+  const int lane = threadIdx.x & 63;
+  const bool is_long = end - start > LINK_SHORT;
+  Acc mine = zero;
+  if (!is_long)
+    for (int32_t i = start; i < end; i++) visit(own, i, mine);
+  unsigned long long todo = __ballot(is_long);
+  while (todo) {
+    const int owner = __ffsll((long long)todo) - 1;
+    todo &= todo - 1ULL;
+    const int32_t s0 = __shfl(start, owner), s1 = __shfl(end, owner);
+    const Own of = from(own, owner);
+    Acc acc = zero;
+    for (int32_t i = s0 + lane; i < s1; i += 64) visit(of, i, acc);
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) join(acc, d);
+    if (lane == owner) mine = acc;
+  }
+  return mine;
+}
 
 // one per call, zeroed before the first launch
 struct LinkStatus {
@@ -86,11 +136,7 @@ __global__ __launch_bounds__(256) void k_link_segments(LinkArgs a) {
   const int64_t unique = min((int64_t)a.status->unique, a.bound);
   const int64_t live = unique - (unique > 0 && a.keys[unique - 1] == link_dropped(a) ? 1 : 0);
   if (i == 0) a.status->live = (unsigned int)live;
-  if (i >= live) return;
-  const uint32_t from = (uint32_t)(a.keys[i] >> a.bits);
-  if (from >= (uint32_t)a.n_genomes) return;                        // (never: the ids were checked)
-  if (i == 0 || (uint32_t)(a.keys[i - 1] >> a.bits) != from) a.seg_start[from] = (int32_t)i;
-  if (i == live - 1 || (uint32_t)(a.keys[i + 1] >> a.bits) != from) a.seg_end[from] = (int32_t)(i + 1);
+  if (i < live) run_ends(a.keys, a.bits, a.n_genomes, i, live, a.seg_start, a.seg_end);
 }
 
 // entry i of cluster g's run as a candidate
@@ -108,35 +154,17 @@ __global__ __launch_bounds__(256) void k_link_best(LinkArgs a) {
   const int lane = threadIdx.x & 63;
   int32_t start = 0, end = 0;
   if (g < a.n_genomes) { start = a.seg_start[g]; end = a.seg_end[g]; }
-  LinkCand mine;
-  mine.s = 0; mine.n = 0; mine.lo = 0; mine.hi = 0;
-  const bool is_long = end - start > LINK_SHORT;
-  if (!is_long)
-    for (int32_t i = start; i < end; i++) {
-      const LinkCand c = link_candidate(a, (int32_t)g, i);
-      if (link_better(c, mine)) mine = c;
-    }
-  // the long runs of this wave's clusters, one after the other, by all of its lanes
-  unsigned long long todo = __ballot(is_long);
-  while (todo) {
-    const int owner = __ffsll((long long)todo) - 1;
-    todo &= todo - 1ULL;
-    const int32_t cluster = (int32_t)(g - lane + owner);
-    const int32_t s0 = __shfl(start, owner), s1 = __shfl(end, owner);
-    LinkCand c;
-    c.s = 0; c.n = 0; c.lo = 0; c.hi = 0;
-    for (int32_t i = s0 + lane; i < s1; i += 64) {
-      const LinkCand x = link_candidate(a, cluster, i);
-      if (link_better(x, c)) c = x;
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-      LinkCand x;
-      x.s = __shfl_xor(c.s, d); x.n = __shfl_xor(c.n, d); x.lo = __shfl_xor(c.lo, d); x.hi = __shfl_xor(c.hi, d);
-      if (link_better(x, c)) c = x;
-    }
-    if (lane == owner) mine = c;
-  }
+  const LinkCand none{0, 0, 0, 0};
+  const LinkCand mine = walk_runs(
+      start, end, (int32_t)g, none, [&](int32_t, int owner) { return (int32_t)(g - lane + owner); },
+      [&](int32_t cluster, int32_t i, LinkCand &c) {
+        const LinkCand x = link_candidate(a, cluster, i);
+        if (link_better(x, c)) c = x;
+      },
+      [](LinkCand &c, int d) {
+        const LinkCand x{__shfl_xor(c.s, d), __shfl_xor(c.n, d), __shfl_xor(c.lo, d), __shfl_xor(c.hi, d)};
+        if (link_better(x, c)) c = x;
+      });
   if (g >= a.n_genomes) return;
   int32_t partner = -1;
   if (mine.n != 0 && link_passes(mine.s, mine.n, a.qc)) partner = mine.lo == (int32_t)g ? mine.hi : mine.lo;
@@ -154,8 +182,7 @@ __global__ __launch_bounds__(256) void k_link_merge(LinkArgs a) {
       merged = true;
     }
   }
-  const unsigned long long m = __ballot(merged);                   // one atomicMax per wave that merged a pair
-  if (m && (int)(threadIdx.x & 63) == __ffsll((long long)m) - 1) atomicMax(&a.status->changed, a.round);
+  wave_epoch(&a.status->changed, merged, a.round);
 }
 
 __global__ __launch_bounds__(256) void k_link_labels(LinkArgs a) {
@@ -177,8 +204,8 @@ __global__ __launch_bounds__(256) void k_link_relabel(LinkArgs a) {
 // ------------------------------------------------------------------------------------------------------------
 // The rounds above compute every merge of the sequential walk; k_link_record, launched between k_link_best and k_link_merge
 // under fa_table_dendrogram only, keeps them.  The thread of the smaller label knows both labels and both sizes before
-// k_link_merge adds them; the pair's (sum, count) of this round is the entry `to == hi` of its run, found by a binary search
-// (the run is sorted by key), so nothing more travels through k_link_best.  A wave takes its output slots with one atomicAdd
+// k_link_merge adds them; the pair's (sum, count) of this round is the entry `to == hi` of its run, found by run_find, so
+// nothing more travels through k_link_best.  A wave takes its output slots with one atomicAdd
 // (ballot, popcount prefix); the slots depend on the order the waves arrive in, the result does not: the driver sorts the
 // records under the order of step 4 (MergeBefore), which is total on them -- every label is absorbed once, so no two records
 // share `hi` -- and which is the order the sequential walk merges in (fastani_hip.h).
@@ -193,17 +220,12 @@ __global__ __launch_bounds__(256) void k_link_record(LinkArgs a, fa_merge *merge
     if (b > (int32_t)g && b < a.n_genomes && a.best[b] == (int32_t)g) {
       merging = true;
       const unsigned long long key = (unsigned long long)g << a.bits | (unsigned long long)b;
-      const int32_t end = a.seg_end[g];
-      int32_t lo = a.seg_start[g], hi = end;
-      while (lo < hi) {
-        const int32_t mid = lo + (hi - lo) / 2;
-        if (a.keys[mid] < key) lo = mid + 1; else hi = mid;
-      }
+      const int32_t at = run_find(a.keys, a.seg_start[g], a.seg_end[g], key);
       m.lo = (int32_t)g; m.hi = b; m.size_lo = a.size[g]; m.size_hi = a.size[b];
       // (the entry is there: b is g's partner because k_link_best read it.  Were it not, the call fails on LINK_LOST)
-      if (lo < end && a.keys[lo] == key) {
-        m.s = link_s(a.sums[lo], (long long)m.size_lo * (long long)m.size_hi, a.qm);
-        m.present = a.sums[lo].c;
+      if (at >= 0) {
+        m.s = link_s(a.sums[at], (long long)m.size_lo * (long long)m.size_hi, a.qm);
+        m.present = a.sums[at].c;
       } else {
         atomicOr(&a.status->merges, LINK_LOST);
       }
@@ -270,8 +292,7 @@ __global__ __launch_bounds__(256) void k_cut_check(CutArgs a) {
     bad = !link_merge_ok(m.lo, m.hi, m.size_lo, m.size_hi, m.s, m.present, a.n_genomes);
     if (!bad) a.slot[m.hi] = (int32_t)i;
   }
-  const unsigned long long mask = __ballot(bad);
-  if (mask && (int)(threadIdx.x & 63) == __ffsll((long long)mask) - 1) atomicOr(&a.status->flags, CUT_BAD_MERGE);
+  wave_flag(&a.status->flags, bad, CUT_BAD_MERGE);
 }
 
 __global__ __launch_bounds__(256) void k_cut_twice(CutArgs a) {
@@ -281,8 +302,7 @@ __global__ __launch_bounds__(256) void k_cut_twice(CutArgs a) {
     const int32_t hi = a.merges[i].hi;
     twice = hi >= 0 && hi < a.n_genomes && a.slot[hi] != (int32_t)i;       // (a bad merge wrote nothing; it has its own flag)
   }
-  const unsigned long long mask = __ballot(twice);
-  if (mask && (int)(threadIdx.x & 63) == __ffsll((long long)mask) - 1) atomicOr(&a.status->flags, CUT_TWICE);
+  wave_flag(&a.status->flags, twice, CUT_TWICE);
 }
 
 // the three kernels below: blockIdx.x over the genomes, blockIdx.y strided over the cuts
@@ -311,11 +331,8 @@ __global__ __launch_bounds__(256) void k_cut_jump(const int32_t *in, int32_t *ou
 
 __global__ __launch_bounds__(256) void k_cut_roots(CutArgs a, const int32_t *labels) {
   const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  for (int32_t t = (int32_t)blockIdx.y; t < a.n_cuts; t += (int32_t)gridDim.y) {
-    const bool root = g < a.n_genomes && labels[(int64_t)t * a.n_genomes + g] == (int32_t)g;
-    const unsigned long long mask = __ballot(root);
-    if (mask && (threadIdx.x & 63) == 0) atomicAdd(&a.roots[t], (unsigned int)__popcll(mask));
-  }
+  for (int32_t t = (int32_t)blockIdx.y; t < a.n_cuts; t += (int32_t)gridDim.y)
+    wave_count(&a.roots[t], g < a.n_genomes && labels[(int64_t)t * a.n_genomes + g] == (int32_t)g);
 }
 
 }  // namespace fa

@@ -13,14 +13,13 @@
 //   k_medoid_check     one thread per (set, genome): the label lies in [0, n) and labels itself, else the call's flag; a good
 //                      label's slot counts the genome (atomicAdd): size[t][label] = m;
 //   radix sort of the entries by key, ONCE for all the sets -- a genome's neighbours contiguous and ascending;
-//   k_medoid_segments  the run of every genome;
+//   k_medoid_segments  the run of every genome (run_ends of fa_linkage.hip.h);
 //   k_medoid_sums      every genome's (sum of w, count) over the entries whose other end carries its label, for MED_SETS label
-//                      sets at a time: one lane per run of at most LINK_SHORT entries; a longer run -- a hub -- is walked by
-//                      the whole wave, 64 entries a step, and added up across the lanes.  It writes S;
+//                      sets at a time, over its run as walk_runs (fa_linkage.hip.h) walks it.  It writes S;
 //   k_medoid_best      atomicMax of medoid_key(T) into the slot of the label;
 //   k_medoid_pick      atomicMin of the genome number, among the members whose key is the slot's, into a second slot;
-//   k_medoid_write     the medoid of every genome's cluster, the weight of the entry (g, medoid) found by a binary search in g's
-//                      run -- or NaN --, S and m; a wave counts the genomes that are their own medoid.
+//   k_medoid_write     the medoid of every genome's cluster, the weight of the entry (g, medoid) of g's run (run_find) -- or
+//                      NaN --, S and m; a wave counts the genomes that are their own medoid (wave_count).
 //
 // Why the bytes do not depend on timing.  Every sum is a sum of integers, taken by one lane or one wave in a fixed order.
 // Every cross-workgroup effect is an integer atomicAdd / atomicMax / atomicMin / atomicOr into a slot zeroed (or filled)
@@ -78,19 +77,18 @@ __global__ __launch_bounds__(256) void k_medoid_check(MedoidArgs a) {
       bad = (uint32_t)l >= (uint32_t)a.n_genomes || row[l] != l;
       if (!bad) atomicAdd(a.size + (int64_t)t * a.n_genomes + l, 1);
     }
-    const unsigned long long mask = __ballot(bad);
-    if (mask && (int)(threadIdx.x & 63) == __ffsll((long long)mask) - 1) atomicOr(&a.status->flags, MED_BAD_LABEL);
+    wave_flag(&a.status->flags, bad, MED_BAD_LABEL);
   }
 }
 
 __global__ __launch_bounds__(256) void k_medoid_segments(MedoidArgs a) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= a.n_entries) return;
-  const uint32_t from = (uint32_t)(a.keys[i] >> a.bits);
-  if (from >= (uint32_t)a.n_genomes) return;                        // (never: the ids were checked)
-  if (i == 0 || (uint32_t)(a.keys[i - 1] >> a.bits) != from) a.seg_start[from] = (int32_t)i;
-  if (i == a.n_entries - 1 || (uint32_t)(a.keys[i + 1] >> a.bits) != from) a.seg_end[from] = (int32_t)(i + 1);
+  if (i < a.n_entries) run_ends(a.keys, a.bits, a.n_genomes, i, a.n_entries, a.seg_start, a.seg_end);
 }
+
+// what walk_runs carries for k_medoid_sums: a genome's labels in MED_SETS sets; (sum of w, count) of the entries that match them
+struct MedoidOwn { int32_t label[MED_SETS]; };
+struct MedoidAcc { long long w[MED_SETS] = {}; int32_t c[MED_SETS] = {}; };
 
 // blockIdx.y strided over groups of MED_SETS sets
 __global__ __launch_bounds__(256) void k_medoid_sums(MedoidArgs a) {
@@ -100,56 +98,37 @@ __global__ __launch_bounds__(256) void k_medoid_sums(MedoidArgs a) {
   const int64_t n = a.n_genomes;
   int32_t start = 0, end = 0;
   if (live) { start = a.seg_start[g]; end = a.seg_end[g]; }
-  const bool is_long = end - start > LINK_SHORT;
-  const unsigned long long long_runs = __ballot(is_long);
   const unsigned long long to_mask = (1ULL << a.bits) - 1ULL;
   unsigned long long inside = 0;
   for (int32_t t0 = (int32_t)blockIdx.y * MED_SETS; t0 < a.n_sets; t0 += (int32_t)gridDim.y * MED_SETS) {
-    int32_t own[MED_SETS], c[MED_SETS];
-    long long w[MED_SETS];
+    MedoidOwn own;
+#pragma unroll
+    for (int u = 0; u < MED_SETS; u++)
+      own.label[u] = live && t0 + u < a.n_sets ? a.labels[(int64_t)(t0 + u) * n + g] : -1;      // (-1: no label is negative)
+    const MedoidAcc sum = walk_runs(
+        start, end, own, MedoidAcc{}, [](const MedoidOwn &o, int owner) {
+          MedoidOwn x;
+#pragma unroll
+          for (int u = 0; u < MED_SETS; u++) x.label[u] = __shfl(o.label[u], owner);
+          return x;
+        },
+        [&](const MedoidOwn &of, int32_t i, MedoidAcc &acc) {
+          const int64_t to = (int64_t)(a.keys[i] & to_mask);
+          const long long wi = a.sums[i].w;
+#pragma unroll
+          for (int u = 0; u < MED_SETS; u++)
+            if (t0 + u < a.n_sets && a.labels[(int64_t)(t0 + u) * n + to] == of.label[u]) { acc.w[u] += wi; acc.c[u]++; }
+        },
+        [](MedoidAcc &acc, int d) {
+#pragma unroll
+          for (int u = 0; u < MED_SETS; u++) { acc.w[u] += __shfl_xor(acc.w[u], d); acc.c[u] += __shfl_xor(acc.c[u], d); }
+        });
 #pragma unroll
     for (int u = 0; u < MED_SETS; u++) {
-      own[u] = live && t0 + u < a.n_sets ? a.labels[(int64_t)(t0 + u) * n + g] : -1;      // (-1: no label is negative)
-      w[u] = 0; c[u] = 0;
-    }
-    if (!is_long)
-      for (int32_t i = start; i < end; i++) {
-        const int64_t to = (int64_t)(a.keys[i] & to_mask);
-        const long long wi = a.sums[i].w;
-#pragma unroll
-        for (int u = 0; u < MED_SETS; u++)
-          if (t0 + u < a.n_sets && a.labels[(int64_t)(t0 + u) * n + to] == own[u]) { w[u] += wi; c[u]++; }
-      }
-    // the long runs of this wave's genomes, one after the other, by all of its lanes
-    unsigned long long todo = long_runs;
-    while (todo) {
-      const int owner = __ffsll((long long)todo) - 1;
-      todo &= todo - 1ULL;
-      const int32_t s0 = __shfl(start, owner), s1 = __shfl(end, owner);
-      int32_t label[MED_SETS], cc[MED_SETS];
-      long long ww[MED_SETS];
-#pragma unroll
-      for (int u = 0; u < MED_SETS; u++) { label[u] = __shfl(own[u], owner); ww[u] = 0; cc[u] = 0; }
-      for (int32_t i = s0 + lane; i < s1; i += 64) {
-        const int64_t to = (int64_t)(a.keys[i] & to_mask);
-        const long long wi = a.sums[i].w;
-#pragma unroll
-        for (int u = 0; u < MED_SETS; u++)
-          if (t0 + u < a.n_sets && a.labels[(int64_t)(t0 + u) * n + to] == label[u]) { ww[u] += wi; cc[u]++; }
-      }
-#pragma unroll
-      for (int u = 0; u < MED_SETS; u++) {
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) { ww[u] += __shfl_xor(ww[u], d); cc[u] += __shfl_xor(cc[u], d); }
-        if (lane == owner) { w[u] = ww[u]; c[u] = cc[u]; }
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < MED_SETS; u++) {
-      if (own[u] < 0) continue;
+      if (own.label[u] < 0) continue;
       const int64_t at = (int64_t)(t0 + u) * n;
-      a.s[at + g] = medoid_s(w[u], c[u], a.size[at + own[u]], a.qm);
-      inside += (unsigned long long)c[u];
+      a.s[at + g] = medoid_s(sum.w[u], sum.c[u], a.size[at + own.label[u]], a.qm);
+      inside += (unsigned long long)sum.c[u];
     }
   }
 #pragma unroll
@@ -201,19 +180,13 @@ __global__ __launch_bounds__(256) void k_medoid_write(MedoidArgs a) {
         if (!root) {
           // (medoid < n_genomes: the slot's own genome reaches the slot's largest key at the latest)
           const unsigned long long key = (unsigned long long)g << a.bits | (unsigned long long)(uint32_t)medoid;
-          const int32_t end = a.seg_end[g];
-          int32_t lo = a.seg_start[g], hi = end;
-          while (lo < hi) {
-            const int32_t mid = lo + (hi - lo) / 2;
-            if (a.keys[mid] < key) lo = mid + 1; else hi = mid;
-          }
-          identity = lo < end && a.keys[lo] == key ? (double)a.sums[lo].w / LINK_SCALE : __longlong_as_double((long long)MED_NAN);
+          const int32_t at = run_find(a.keys, a.seg_start[g], a.seg_end[g], key);
+          identity = at >= 0 ? (double)a.sums[at].w / LINK_SCALE : __longlong_as_double((long long)MED_NAN);
         }
         a.identity[at + g] = identity;
       }
     }
-    const unsigned long long mask = __ballot(root);
-    if (mask && (threadIdx.x & 63) == 0) atomicAdd(&a.roots[t], (unsigned int)__popcll(mask));
+    wave_count(&a.roots[t], root);
   }
 }
 

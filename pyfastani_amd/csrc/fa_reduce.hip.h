@@ -12,6 +12,10 @@
 //     device pointer or to a staged copy that is downloaded at the end (Staged);
 //   - sizes its sort keys with bit_width_u64 / id_bits and calls rocPRIM through with_temp;
 //   - is synchronised when it returns: host outputs are complete, device outputs are written.
+//
+// The six reductions of an all-vs-all table share the first half of that frame as code (check_table_args, TableFront); each
+// then has a driver of its own, table_<what>, that reads top to bottom.  What two of them share they share through a function
+// (check_linkage_args, linkage, count_roots), never through a flag: a seventh reduction is a seventh driver.
 #pragma once
 
 #include <rocprim/rocprim.hpp>
@@ -38,6 +42,16 @@ namespace fa {
 // ------------------------------------------------------------------------------------------------------------
 // The hit table of an all-vs-all reduced to pairs and clusters (fa_table.hip.h has the semantics and the road)
 // ------------------------------------------------------------------------------------------------------------
+// the genomes among n > 0 that label themselves (device labels), counted in the call's zeroed `status`; synchronises the stream
+inline unsigned int count_roots(const int32_t *labels, int32_t n, TableStatus *status, hipStream_t st) {
+  unsigned int roots = 0;
+  hipLaunchKernelGGL(k_comp_roots, dim3(ceil_div(n, 256)), dim3(256), 0, st, labels, n, &status->roots);
+  FA_HIP(hipGetLastError());
+  FA_HIP(hipMemcpyAsync(&roots, &status->roots, sizeof roots, hipMemcpyDeviceToHost, st));
+  FA_HIP(hipStreamSynchronize(st));
+  return roots;
+}
+
 // The connected components of an edge list over n_genomes > 0 genomes (fa_table.hip.h): labels (device) receive every genome's
 // smallest group member; returns the number of groups and, in `rounds`, those of the loop.  `status` is the call's zeroed
 // TableStatus; the stream is synchronised on return.
@@ -61,12 +75,7 @@ inline unsigned int components(const int2 *edges, int64_t n_edges, int32_t *labe
       if (changed != c.round) break;
     }
   }
-  unsigned int roots = 0;
-  hipLaunchKernelGGL(k_comp_roots, genome_grid, dim3(256), 0, st, c);
-  FA_HIP(hipGetLastError());
-  FA_HIP(hipMemcpyAsync(&roots, &status->roots, sizeof roots, hipMemcpyDeviceToHost, st));
-  FA_HIP(hipStreamSynchronize(st));
-  return roots;
+  return count_roots(labels, n_genomes, status, st);
 }
 
 // The representatives of a weighted edge list over n_genomes > 0 genomes and every other genome's closest one
@@ -112,14 +121,109 @@ inline unsigned int representatives(const TableEdge *edges, int64_t n_edges, con
   return end.roots;
 }
 
+// the table as all six entry points take it: their first seven arguments
+struct TableIn {
+  const fa_cgi_row *rows; int64_t n_rows; bool rows_device; int32_t n_genomes; const uint64_t *query_lengths, *reference_lengths; const fa_table_params *p;
+};
+// the checks the six share; each driver goes on with its own
+inline void check_table_args(const TableIn &in) {
+  FA_REQUIRE(in.p, FA_ERR_INVALID, "null table parameters");
+  FA_REQUIRE(in.p->fragment_length >= 1, FA_ERR_INVALID, "fragment_length must be strictly positive");
+  FA_REQUIRE(in.n_genomes >= 0 && in.n_rows >= 0, FA_ERR_INVALID, "negative table size");
+  FA_REQUIRE(in.n_rows == 0 || in.rows, FA_ERR_INVALID, "null rows");
+  FA_REQUIRE(in.n_genomes == 0 || (in.query_lengths && in.reference_lengths), FA_ERR_INVALID, "null genome lengths");
+  FA_REQUIRE(in.n_rows <= (int64_t)INT32_MAX, FA_ERR_UNSUPPORTED, "a table of more than 2^31 - 1 rows");
+}
+
+// The front end of the six (fa_table.hip.h): the call's stream and status block, the rows and lengths on the device, the sorted
+// keys, and the count and scan of the records of the call's one form (TAB_EMIT_*: k_table_count depends on it).  Constructed,
+// the table has passed its device checks -- a refused one throws before a driver has touched an output -- and `status` and
+// `n_emit` are read; the driver then has the records written by the emit call of its form.
+struct TableFront {
+  CallStream stream; hipStream_t st;          // the stream first: it outlives the buffers
+  StatusBlock<TableStatus> d_status;          // d_status.p: also the `changed` and `roots` of the loops behind the front end
+  TableStatus status{};                       // its host copy after k_chunk_scan (all zero for a table without rows)
+  int64_t n_emit = 0;                         // records of the call's form
+  DevBuf<unsigned char> temp;                 // rocPRIM's; free for the driver's own sorts afterwards
+
+  TableFront(const TableIn &in, int32_t emit) : st(stream.s), d_status(st) {
+    const int64_t n_rows = in.n_rows; const int32_t n_genomes = in.n_genomes;
+    a.n_rows = n_rows; a.n_genomes = n_genomes;
+    a.fragment_length = (unsigned long long)in.p->fragment_length; a.min_fraction = in.p->min_fraction;
+    a.min_identity = (double)in.p->min_identity; a.reciprocal = in.p->reciprocal;
+    a.emit = emit; a.link_bits = (int32_t)id_bits(n_genomes); a.status = d_status.p;
+    a.n_chunks = ceil_div(n_rows, TAB_CHUNK);
+    if (!n_rows) return;
+    a.rows = on_device(in.rows, in.rows_device, (size_t)n_rows, d_rows, st);
+    d_len.ensure((size_t)n_genomes * 2);
+    FA_HIP(hipMemcpyAsync(d_len.p, in.query_lengths, (size_t)n_genomes * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    FA_HIP(hipMemcpyAsync(d_len.p + n_genomes, in.reference_lengths, (size_t)n_genomes * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    a.query_length = d_len.p; a.reference_length = d_len.p + n_genomes;
+    keys.ensure((size_t)n_rows); keys_sorted.ensure((size_t)n_rows);
+    row_of.ensure((size_t)n_rows); row_of_sorted.ensure((size_t)n_rows);
+    hipLaunchKernelGGL(k_table_keys, dim3(ceil_div(n_rows, 256)), dim3(256), 0, st, a, keys.p, row_of.p);
+    // the bits a key of this table can have set: two flag bits, 31 of b, and those of the largest a
+    const unsigned end_bit = 33u + id_bits(n_genomes);
+    with_temp(temp, [&](void *t, size_t &bytes) {
+      return rocprim::radix_sort_pairs(t, bytes, keys.p, keys_sorted.p, row_of.p, row_of_sorted.p, (size_t)n_rows, 0u, end_bit, st);
+    });
+    a.keys = keys_sorted.p; a.row_of = row_of_sorted.p;
+    chunk_count.ensure((size_t)a.n_chunks); chunk_off.ensure((size_t)a.n_chunks);
+    a.chunk_count = chunk_count.p; a.chunk_off = chunk_off.p;
+    hipLaunchKernelGGL(k_table_count, dim3(ceil_div(a.n_chunks, 4)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_chunk_scan, dim3(1), dim3(1024), 0, st, a.chunk_count, a.chunk_off, a.n_chunks, &d_status.p->emitted);
+    FA_HIP(hipGetLastError());
+    status = d_status.read(st);
+    FA_REQUIRE(!(status.flags & TAB_BAD_ID), FA_ERR_INVALID, "a row names a genome outside [0, n_genomes)");
+    FA_REQUIRE(!(status.flags & TAB_DUPLICATE), FA_ERR_INVALID, "the table holds the same (query, reference) twice");
+    FA_REQUIRE(!(status.flags & TAB_BAD_IDENTITY), FA_ERR_INVALID, "a present pair has an identity that is NaN or outside [0, 128]");
+    n_emit = (int64_t)status.emitted;
+  }
+  // the n_emit records into room for as many (link: for 2 * n_emit directed entries); nothing is launched for none
+  void emit_pairs(fa_pair *pairs) { a.pairs = pairs; emit(TAB_EMIT_PAIRS); }
+  void emit_edges(int2 *edges) { a.edges = edges; emit(TAB_EMIT_EDGES); }
+  void emit_weighted(TableEdge *edges) { a.weighted = edges; emit(TAB_EMIT_WEIGHTED); }
+  void emit_link(unsigned long long *link_keys, LinkSum *link_sums) { a.link_keys = link_keys; a.link_sums = link_sums; emit(TAB_EMIT_LINK); }
+  // slots 0-3 of an entry point's stats (null: none): survivors, pairs, edges, and the entry point's own fourth
+  void write_stats(int64_t *stats, int64_t fourth) const {
+    if (stats) { stats[0] = (int64_t)status.survivors; stats[1] = (int64_t)status.pairs; stats[2] = (int64_t)status.edges; stats[3] = fourth; }
+  }
+
+ private:
+  DevBuf<fa_cgi_row> d_rows; DevBuf<uint64_t> d_len;
+  DevBuf<unsigned long long> keys, keys_sorted;
+  DevBuf<uint32_t> row_of, row_of_sorted;
+  DevBuf<int32_t> chunk_count; DevBuf<int64_t> chunk_off;
+  TableArgs a{};
+  void emit(int32_t form) {
+    FA_REQUIRE(form == a.emit, FA_ERR_INTERNAL, "the front end of a table counted another form than the one asked for");
+    if (!n_emit) return;
+    a.cap = n_emit;
+    hipLaunchKernelGGL(k_table_write, dim3(ceil_div(a.n_chunks, 4)), dim3(256), 0, st, a);
+  }
+};
+
+// `missing` and `min_identity` of fa_table_linkage and fa_table_dendrogram, checked and in fixed point (fa_link.h)
+struct LinkCutoffs { long long qm, qc; };
+inline LinkCutoffs check_linkage_args(const fa_table_params *p, float missing, int32_t n_genomes) {
+  FA_REQUIRE(p->min_identity >= 0.0f, FA_ERR_INVALID, "min_identity must be a number that is not negative");          // (false for NaN)
+  FA_REQUIRE(missing >= 0.0f, FA_ERR_INVALID, "missing must be a number that is not negative");
+  const double dm = rint((double)missing * LINK_SCALE), dc = rint((double)p->min_identity * LINK_SCALE);
+  FA_REQUIRE(dm < dc, FA_ERR_INVALID, "missing must lie below min_identity");
+  FA_REQUIRE(n_genomes <= LINK_MAX_GENOMES, FA_ERR_UNSUPPORTED, "average linkage over more than 2^18 genomes");
+  // no weight exceeds LINK_MAX_W: a cut-off above it merges nothing whatever its value, and neither does the clamped one
+  // (link_cutoff of fa_link.h is this rule for one float: fa_dendrogram_cut forms its qc with it, and clusters._fixed_cutoff
+  // restates it in Python; the three must stay one rule for a cut to give the bytes of this call)
+  return {(long long)std::min(dm, (double)LINK_MAX_W), (long long)std::min(dc, (double)(LINK_MAX_W + 1))};
+}
+
 // The average-linkage clusters of the present pairs of a table over n_genomes > 0 genomes (fa_linkage.hip.h): labels (device)
 // receive every genome's smallest cluster member; returns the number of clusters and, in `rounds`, the rounds that merged a
-// pair.  `emit_into(keys, sums)` has k_table_write put the two directed entries of each of the n_pairs present pairs there.
-// `status` is the call's zeroed TableStatus; the stream is synchronised on return.  With `merges` (device, room for n_genomes - 1:
-// fa_table_dendrogram) every merge is recorded there, in no order, and *n_merges is their number.
-template <typename Emit>
-inline unsigned int linkage(Emit emit_into, int64_t n_pairs, int32_t *labels, int32_t n_genomes, long long qm, long long qc,
-                            TableStatus *status, hipStream_t st, int64_t &rounds, fa_merge *merges = nullptr, int64_t *n_merges = nullptr) {
+// pair.  The front end's form is TAB_EMIT_LINK; its stream is synchronised on return.  With `merges` (device, room for
+// n_genomes - 1: fa_table_dendrogram) every merge is recorded there, in no order, and *n_merges is their number.
+inline unsigned int linkage(TableFront &front, int32_t *labels, int32_t n_genomes, LinkCutoffs q, int64_t &rounds, fa_merge *merges = nullptr,
+                            int64_t *n_merges = nullptr) {
+  const int64_t n_pairs = front.n_emit; const hipStream_t st = front.st;
   FA_REQUIRE(n_pairs <= (int64_t)(1 << 30), FA_ERR_UNSUPPORTED, "more than 2^30 present pairs");
   StatusBlock<LinkStatus> d_link(st);
   DevBuf<unsigned long long> keys[3];         // the entries to sort, sorted, reduced to distinct keys
@@ -129,7 +233,7 @@ inline unsigned int linkage(Emit emit_into, int64_t n_pairs, int32_t *labels, in
   const size_t n = (size_t)n_genomes;
   words.ensure(n * 5);
   LinkArgs l{};
-  l.n_genomes = n_genomes; l.bits = (int32_t)id_bits(n_genomes); l.qm = qm; l.qc = qc;
+  l.n_genomes = n_genomes; l.bits = (int32_t)id_bits(n_genomes); l.qm = q.qm; l.qc = q.qc;
   l.seg_start = words.p; l.seg_end = words.p + n; l.size = words.p + 2 * n; l.parent = words.p + 3 * n; l.best = words.p + 4 * n;
   l.labels = labels; l.status = d_link.p;
   const dim3 genome_grid(ceil_div(n_genomes, 256));
@@ -138,7 +242,7 @@ inline unsigned int linkage(Emit emit_into, int64_t n_pairs, int32_t *labels, in
   int64_t n_in = 2 * n_pairs;
   if (n_in) {
     for (int i = 0; i < 3; i++) { keys[i].ensure((size_t)n_in); sums[i].ensure((size_t)n_in); }
-    emit_into(keys[0].p, sums[0].p);
+    front.emit_link(keys[0].p, sums[0].p);
     l.keys = keys[2].p; l.sums = sums[2].p; l.next_keys = keys[0].p; l.next_sums = sums[0].p;
     // the bits a key can have set: two genome numbers and, above them, the bit of a dropped entry
     const unsigned end_bit = 2u * (unsigned)l.bits + 1u;
@@ -173,24 +277,8 @@ inline unsigned int linkage(Emit emit_into, int64_t n_pairs, int32_t *labels, in
     FA_REQUIRE(!(recorded & LINK_LOST), FA_ERR_INTERNAL, "a merging pair of clusters has no entry in its cluster's run");
     *n_merges = (int64_t)recorded;
   }
-  CompArgs c{};
-  c.labels = labels; c.n_genomes = n_genomes; c.status = status;
-  unsigned int roots = 0;
-  hipLaunchKernelGGL(k_comp_roots, genome_grid, dim3(256), 0, st, c);
-  FA_HIP(hipGetLastError());
-  FA_HIP(hipMemcpyAsync(&roots, &status->roots, sizeof roots, hipMemcpyDeviceToHost, st));
-  FA_HIP(hipStreamSynchronize(st));
-  return roots;
+  return count_roots(labels, n_genomes, front.d_status.p, st);
 }
-
-// what fa_table_medoids brings beyond the table: the label sets, the bonus and the four outputs
-struct MedoidRequest {
-  float missing = 0.0f;
-  const int32_t *labels = nullptr; int32_t n_sets = 0; const double *bonus = nullptr;
-  int32_t *medoids = nullptr; double *identity = nullptr; int64_t *sums = nullptr; int32_t *sizes = nullptr;
-  bool io_device = false;                  // labels and the four outputs
-  int32_t *n_clusters = nullptr;           // host, [n_sets]
-};
 
 // whether one label set is valid: every label in [0, n_genomes) and its own label
 inline bool label_set_ok(const int32_t *labels, int32_t n_genomes) {
@@ -201,52 +289,201 @@ inline bool label_set_ok(const int32_t *labels, int32_t n_genomes) {
   return true;
 }
 
-// The medoids of n_sets partitions of n_genomes > 0 genomes over the present pairs of a table (fa_medoid.hip.h): the four
-// outputs of `m` are written once the label sets have passed k_medoid_check; `roots` receives every set's number of medoids and
-// `inside` the present pairs inside a cluster, over all sets.  `emit_into(keys, sums)` has k_table_write put the two directed
-// entries of each of the n_pairs present pairs there.  `qb` is empty for no bonus.  The stream is synchronised on return.
-template <typename Emit>
-inline void medoids(Emit emit_into, int64_t n_pairs, int32_t n_genomes, long long qm, const std::vector<long long> &qb, const MedoidRequest &m,
-                    hipStream_t st, std::vector<unsigned int> &roots, int64_t &inside) {
-  FA_REQUIRE(n_pairs <= (int64_t)(1 << 30), FA_ERR_UNSUPPORTED, "more than 2^30 present pairs");
+// The six drivers.  Each reads top to bottom in one order: check_table_args, its own checks, require_device(), the front end
+// in its form, its own tail.  A table the front end refuses has therefore touched no output of any of them.
+inline void table_pairs(const TableIn &in, fa_pair *pairs, int64_t cap, int64_t *n_pairs, bool pairs_device) {
+  check_table_args(in);
+  FA_REQUIRE(n_pairs && cap >= 0, FA_ERR_INVALID, "null pair count or negative capacity");
+  require_device();
+  TableFront front(in, TAB_EMIT_PAIRS);
+  *n_pairs = (int64_t)front.status.pairs;                         // (before the capacity check: a caller sizes its buffer by it)
+  if (!pairs) return;
+  FA_REQUIRE(front.n_emit <= cap, FA_ERR_INVALID, "the pair buffer is smaller than the number of pairs");
+  if (!front.n_emit) return;
+  Staged<fa_pair> out(pairs, pairs_device, (size_t)front.n_emit);
+  front.emit_pairs(out.dev());
+  FA_HIP(hipGetLastError());
+  out.finish(front.st); FA_HIP(hipStreamSynchronize(front.st));
+}
+
+inline void table_clusters(const TableIn &in, int32_t *labels, bool labels_device, int32_t *n_clusters, int64_t *stats) {
+  check_table_args(in);
+  const int32_t n_genomes = in.n_genomes;
+  FA_REQUIRE(n_genomes == 0 || labels, FA_ERR_INVALID, "null labels");
+  require_device();
+  TableFront front(in, TAB_EMIT_EDGES);
+  int64_t rounds = 0; unsigned int roots = 0;
+  if (n_genomes) {
+    DevBuf<int2> d_edges;
+    Staged<int32_t> out(labels, labels_device, (size_t)n_genomes);
+    d_edges.ensure((size_t)front.n_emit);
+    front.emit_edges(d_edges.p);
+    roots = components(d_edges.p, front.n_emit, out.dev(), n_genomes, front.d_status.p, front.st, rounds);
+    out.finish(front.st); FA_HIP(hipStreamSynchronize(front.st));
+  }
+  if (n_clusters) *n_clusters = (int32_t)roots;
+  front.write_stats(stats, rounds);
+}
+
+inline void table_representatives(const TableIn &in, const int32_t *order, int32_t *labels, double *identity, bool out_device,
+                                  int32_t *n_representatives, int64_t *stats) {
+  check_table_args(in);
+  const int32_t n_genomes = in.n_genomes;
+  FA_REQUIRE(n_genomes == 0 || labels, FA_ERR_INVALID, "null labels");
+  FA_REQUIRE(in.p->min_identity >= 0.0f, FA_ERR_INVALID, "min_identity must be a number that is not negative");          // (false for NaN)
+  std::vector<int32_t> both;                  // pos, then order
+  FA_REQUIRE(order_positions(order, n_genomes, both), FA_ERR_INVALID, "order is not a permutation of the genome numbers");
+  require_device();
+  TableFront front(in, TAB_EMIT_WEIGHTED);
+  int64_t rounds = 0; unsigned int roots = 0;
+  if (n_genomes) {
+    DevBuf<TableEdge> d_edges; DevBuf<int32_t> d_order;
+    both.resize((size_t)n_genomes * 2);
+    for (int32_t g = 0; g < n_genomes; g++) both[(size_t)n_genomes + (size_t)both[(size_t)g]] = g;
+    d_order.upload(both, front.st);
+    Staged<int32_t> out(labels, out_device, (size_t)n_genomes);
+    Staged<double> out_identity(identity, out_device, (size_t)n_genomes);
+    d_edges.ensure((size_t)front.n_emit);
+    front.emit_weighted(d_edges.p);
+    roots = representatives(d_edges.p, front.n_emit, d_order.p, d_order.p + n_genomes, out.dev(), out_identity.dev(), n_genomes,
+                            front.d_status.p, front.st, rounds);
+    out.finish(front.st); out_identity.finish(front.st);
+    FA_HIP(hipStreamSynchronize(front.st));
+  }
+  if (n_representatives) *n_representatives = (int32_t)roots;
+  front.write_stats(stats, rounds);
+}
+
+inline void table_linkage(const TableIn &in, float missing, int32_t *labels, bool labels_device, int32_t *n_clusters, int64_t *stats) {
+  check_table_args(in);
+  const int32_t n_genomes = in.n_genomes;
+  FA_REQUIRE(n_genomes == 0 || labels, FA_ERR_INVALID, "null labels");
+  const LinkCutoffs q = check_linkage_args(in.p, missing, n_genomes);
+  require_device();
+  TableFront front(in, TAB_EMIT_LINK);
+  int64_t rounds = 0; unsigned int roots = 0;
+  if (n_genomes) {
+    Staged<int32_t> out(labels, labels_device, (size_t)n_genomes);
+    roots = linkage(front, out.dev(), n_genomes, q, rounds);
+    out.finish(front.st); FA_HIP(hipStreamSynchronize(front.st));
+  }
+  if (n_clusters) *n_clusters = (int32_t)roots;
+  front.write_stats(stats, rounds);
+  if (stats) stats[4] = (int64_t)n_genomes - (int64_t)roots;
+}
+
+// fa_table_dendrogram: `labels` may be null, and out_device holds for merges and labels
+inline void table_dendrogram(const TableIn &in, float missing, fa_merge *merges, int64_t cap, int64_t *n_merges, int32_t *labels, bool out_device,
+                             int32_t *n_clusters, int64_t *stats) {
+  check_table_args(in);
+  const int32_t n_genomes = in.n_genomes;
+  FA_REQUIRE(n_merges && (!merges || cap >= 0), FA_ERR_INVALID, "null merge count or negative capacity");
+  const LinkCutoffs q = check_linkage_args(in.p, missing, n_genomes);
+  require_device();
+  TableFront front(in, TAB_EMIT_LINK);
+  const hipStream_t st = front.st;
+  // everything lands in buffers of the call's own first: a short `cap` leaves the caller's memory as it was
+  int64_t rounds = 0, n_found = 0; unsigned int roots = 0;
+  DevBuf<int32_t> d_labels, order;             // order: the records' numbers in the order of the walk
+  DevBuf<fa_merge> found, sorted;
+  if (n_genomes) {
+    d_labels.ensure((size_t)n_genomes);
+    found.ensure((size_t)std::max(n_genomes - 1, 1));
+    roots = linkage(front, d_labels.p, n_genomes, q, rounds, found.p, &n_found);
+    FA_REQUIRE(n_found == (int64_t)n_genomes - (int64_t)roots, FA_ERR_INTERNAL, "the merge list and the labels disagree on the number of merges");
+  }
+  *n_merges = n_found;                                            // (before the capacity check, as fa_table_pairs)
+  FA_REQUIRE(!merges || n_found <= cap, FA_ERR_INVALID, "the merge buffer is smaller than the number of merges");
+  const hipMemcpyKind kind = out_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  if (merges && n_found) {
+    // the order of the walk (fa_linkage.hip.h): total on the records, so the bytes do not depend on the slots they were taken in
+    sorted.ensure((size_t)n_found); order.ensure((size_t)n_found);
+    with_temp(front.temp, [&](void *t, size_t &bytes) {
+      return rocprim::merge_sort(t, bytes, rocprim::counting_iterator<int32_t>(0), order.p, (size_t)n_found, MergeIndexBefore{found.p}, st);
+    });
+    hipLaunchKernelGGL(k_link_gather, dim3(ceil_div(n_found, 256)), dim3(256), 0, st, (const fa_merge *)found.p, (const int32_t *)order.p, n_found,
+                       sorted.p);
+    FA_HIP(hipGetLastError());
+    FA_HIP(hipMemcpyAsync(merges, sorted.p, (size_t)n_found * sizeof(fa_merge), kind, st));
+  }
+  if (labels && n_genomes) FA_HIP(hipMemcpyAsync(labels, d_labels.p, (size_t)n_genomes * sizeof(int32_t), kind, st));
+  FA_HIP(hipStreamSynchronize(st));
+  if (n_clusters) *n_clusters = (int32_t)roots;
+  front.write_stats(stats, rounds);
+  if (stats) stats[4] = (int64_t)n_genomes - (int64_t)roots;
+}
+
+// fa_table_medoids (fa_medoid.hip.h): labels and the four outputs, each [n_sets][n_genomes], are the caller's device pointers
+// with io_device; n_clusters [n_sets] is host memory
+inline void table_medoids(const TableIn &in, float missing, const int32_t *labels, int32_t n_sets, const double *bonus, int32_t *medoids,
+                          double *identity, int64_t *sums, int32_t *sizes, bool io_device, int32_t *n_clusters, int64_t *stats) {
+  check_table_args(in);
+  const int32_t n_genomes = in.n_genomes;
+  FA_REQUIRE(missing >= 0.0f && missing <= (float)LINK_MAX_IDENTITY, FA_ERR_INVALID, "missing must be a number in [0, 128]");   // (false for NaN)
+  FA_REQUIRE(n_sets >= 1, FA_ERR_INVALID, "medoids need at least one label set");
+  FA_REQUIRE(n_genomes == 0 || labels, FA_ERR_INVALID, "null labels");
+  FA_REQUIRE(n_genomes <= LINK_MAX_GENOMES, FA_ERR_UNSUPPORTED, "medoids over more than 2^18 genomes");
+  FA_REQUIRE((int64_t)n_sets * (int64_t)n_genomes <= (int64_t)INT32_MAX, FA_ERR_UNSUPPORTED, "more than 2^31 - 1 labels");
+  std::vector<long long> qb;                   // empty for no bonus
+  if (bonus) {
+    qb.resize((size_t)n_genomes);
+    for (int32_t g = 0; g < n_genomes; g++) {
+      FA_REQUIRE(medoid_bonus_ok(bonus[g]), FA_ERR_INVALID, "a bonus must be a number in [-32768, 32768]");
+      qb[(size_t)g] = medoid_qb(bonus[g]);
+    }
+  }
+  // (labels on the host are checked here, those in HBM by k_medoid_check -- which sees the host's again)
+  if (!io_device)
+    for (int32_t t = 0; t < n_sets; t++)
+      FA_REQUIRE(label_set_ok(labels + (size_t)t * (size_t)n_genomes, n_genomes), FA_ERR_INVALID,
+                 "a label lies outside [0, n_genomes) or is not its own label");
+  require_device();
+  TableFront front(in, TAB_EMIT_LINK);
+  const hipStream_t st = front.st;
+  if (!n_genomes) {
+    if (n_clusters) std::fill(n_clusters, n_clusters + n_sets, 0);
+    front.write_stats(stats, 0);
+    return;
+  }
+  FA_REQUIRE(front.n_emit <= (int64_t)(1 << 30), FA_ERR_UNSUPPORTED, "more than 2^30 present pairs");
   StatusBlock<MedoidStatus> d_status(st);
   DevBuf<int32_t> d_labels, words;            // words: seg_start, seg_end, then size and who of every (set, genome)
   DevBuf<unsigned long long> keys[2], best;
-  DevBuf<LinkSum> sums[2];
+  DevBuf<LinkSum> entry_sums[2];
   DevBuf<long long> s, d_qb;
   DevBuf<unsigned int> d_roots;
   DevBuf<unsigned char> temp;
-  const size_t n = (size_t)n_genomes, total = n * (size_t)m.n_sets;
-  const int64_t n_in = 2 * n_pairs;
+  const size_t n = (size_t)n_genomes, total = n * (size_t)n_sets;
+  const int64_t n_in = 2 * front.n_emit;
 
   MedoidArgs a{};
-  a.n_entries = n_in; a.n_genomes = n_genomes; a.n_sets = m.n_sets; a.bits = (int32_t)id_bits(n_genomes); a.qm = qm;
+  a.n_entries = n_in; a.n_genomes = n_genomes; a.n_sets = n_sets; a.bits = (int32_t)id_bits(n_genomes); a.qm = link_fixed((double)missing);
   a.status = d_status.p;
-  a.labels = on_device(m.labels, m.io_device, total, d_labels, st);
+  a.labels = on_device(labels, io_device, total, d_labels, st);
   words.ensure(2 * n + 2 * total);
   a.seg_start = words.p; a.seg_end = words.p + n; a.size = words.p + 2 * n; a.who = words.p + 2 * n + total;
   FA_HIP(hipMemsetAsync(words.p, 0, (2 * n + total) * sizeof(int32_t), st));
   FA_HIP(hipMemsetAsync(a.who, 0x7F, total * sizeof(int32_t), st));            // 0x7F7F7F7F: above every genome number
-  const dim3 grid((unsigned)ceil_div(n_genomes, 256), (unsigned)std::min(m.n_sets, 65535));
+  const dim3 grid((unsigned)ceil_div(n_genomes, 256), (unsigned)std::min(n_sets, 65535));
   // the verdict on the labels is read before they index anything and before an output is touched
   hipLaunchKernelGGL(k_medoid_check, grid, dim3(256), 0, st, a);
   FA_HIP(hipGetLastError());
   FA_REQUIRE(!(d_status.read(st).flags & MED_BAD_LABEL), FA_ERR_INVALID,
              "a label lies outside [0, n_genomes) or is not its own label");
   if (n_in) {
-    for (int i = 0; i < 2; i++) { keys[i].ensure((size_t)n_in); sums[i].ensure((size_t)n_in); }
-    emit_into(keys[0].p, sums[0].p);
+    for (int i = 0; i < 2; i++) { keys[i].ensure((size_t)n_in); entry_sums[i].ensure((size_t)n_in); }
+    front.emit_link(keys[0].p, entry_sums[0].p);
     // one sort for all the sets; the bits a key can have set: two genome numbers
     const unsigned end_bit = 2u * (unsigned)a.bits;
     with_temp(temp, [&](void *t, size_t &bytes) {
-      return rocprim::radix_sort_pairs(t, bytes, keys[0].p, keys[1].p, sums[0].p, sums[1].p, (size_t)n_in, 0u, end_bit, st);
+      return rocprim::radix_sort_pairs(t, bytes, keys[0].p, keys[1].p, entry_sums[0].p, entry_sums[1].p, (size_t)n_in, 0u, end_bit, st);
     });
-    a.keys = keys[1].p; a.sums = sums[1].p;
+    a.keys = keys[1].p; a.sums = entry_sums[1].p;
     hipLaunchKernelGGL(k_medoid_segments, dim3(ceil_div(n_in, 256)), dim3(256), 0, st, a);
   }
   s.ensure(total);
   a.s = s.p;
-  const dim3 sums_grid(grid.x, (unsigned)std::min(ceil_div(m.n_sets, MED_SETS), 65535));
+  const dim3 sums_grid(grid.x, (unsigned)std::min(ceil_div(n_sets, MED_SETS), 65535));
   hipLaunchKernelGGL(k_medoid_sums, sums_grid, dim3(256), 0, st, a);
   if (!qb.empty()) { d_qb.upload(qb, st); a.qb = d_qb.p; }
   best.ensure(total);
@@ -254,238 +491,21 @@ inline void medoids(Emit emit_into, int64_t n_pairs, int32_t n_genomes, long lon
   a.best = best.p;
   hipLaunchKernelGGL(k_medoid_best, grid, dim3(256), 0, st, a);
   hipLaunchKernelGGL(k_medoid_pick, grid, dim3(256), 0, st, a);
-  d_roots.ensure((size_t)m.n_sets);
-  FA_HIP(hipMemsetAsync(d_roots.p, 0, (size_t)m.n_sets * sizeof(unsigned int), st));
+  d_roots.ensure((size_t)n_sets);
+  FA_HIP(hipMemsetAsync(d_roots.p, 0, (size_t)n_sets * sizeof(unsigned int), st));
   a.roots = d_roots.p;
-  Staged<int32_t> out_medoids(m.medoids, m.io_device, total), out_sizes(m.sizes, m.io_device, total);
-  Staged<double> out_identity(m.identity, m.io_device, total);
-  Staged<int64_t> out_sums(m.sums, m.io_device, total);
+  Staged<int32_t> out_medoids(medoids, io_device, total), out_sizes(sizes, io_device, total);
+  Staged<double> out_identity(identity, io_device, total);
+  Staged<int64_t> out_sums(sums, io_device, total);
   a.medoids = out_medoids.dev(); a.identity = out_identity.dev(); a.sums_out = out_sums.dev(); a.sizes_out = out_sizes.dev();
   hipLaunchKernelGGL(k_medoid_write, grid, dim3(256), 0, st, a);
   FA_HIP(hipGetLastError());
   out_medoids.finish(st); out_identity.finish(st); out_sums.finish(st); out_sizes.finish(st);
-  roots.resize((size_t)m.n_sets);
+  std::vector<unsigned int> roots((size_t)n_sets, 0u);
   d_roots.download(roots.data(), roots.size(), st);
-  inside = (int64_t)(d_status.read(st).inside / 2ULL);            // (two directed entries a pair; read() synchronises)
-}
-
-struct TableRequest {
-  const MedoidRequest *medoids = nullptr;  // with `clusters`: fa_table_medoids; labels, n_clusters and the rest below are not read
-  bool clusters = false;
-  bool representatives = false;            // with `clusters`: labels are representatives, not components
-  bool linkage = false;                    // with `clusters`: labels are average-linkage clusters, `missing` their missing identity
-  float missing = 0.0f;
-  // with `linkage`: the merge list as well (fa_table_dendrogram): labels may be null, and labels_device holds for merges too
-  bool dendrogram = false;
-  fa_merge *merges = nullptr; int64_t merge_cap = 0; int64_t *n_merges = nullptr;
-  const int32_t *order = nullptr; double *identity = nullptr;
-  fa_pair *pairs = nullptr; int64_t cap = 0; int64_t *n_pairs = nullptr; bool pairs_device = false;
-  int32_t *labels = nullptr; bool labels_device = false; int32_t *n_clusters = nullptr; int64_t *stats = nullptr;
-};
-
-inline void table_reduce(const fa_cgi_row *rows, int64_t n_rows, bool rows_device, int32_t n_genomes, const uint64_t *query_lengths,
-                         const uint64_t *reference_lengths, const fa_table_params *p, const TableRequest &want) {
-  FA_REQUIRE(p, FA_ERR_INVALID, "null table parameters");
-  FA_REQUIRE(p->fragment_length >= 1, FA_ERR_INVALID, "fragment_length must be strictly positive");
-  FA_REQUIRE(n_genomes >= 0 && n_rows >= 0, FA_ERR_INVALID, "negative table size");
-  FA_REQUIRE(n_rows == 0 || rows, FA_ERR_INVALID, "null rows");
-  FA_REQUIRE(n_genomes == 0 || (query_lengths && reference_lengths), FA_ERR_INVALID, "null genome lengths");
-  FA_REQUIRE(n_rows <= (int64_t)INT32_MAX, FA_ERR_UNSUPPORTED, "a table of more than 2^31 - 1 rows");
-  std::vector<long long> qb;
-  if (const MedoidRequest *m = want.medoids) {
-    FA_REQUIRE(m->missing >= 0.0f && m->missing <= (float)LINK_MAX_IDENTITY, FA_ERR_INVALID, "missing must be a number in [0, 128]");   // (false for NaN)
-    FA_REQUIRE(m->n_sets >= 1, FA_ERR_INVALID, "medoids need at least one label set");
-    FA_REQUIRE(n_genomes == 0 || m->labels, FA_ERR_INVALID, "null labels");
-    FA_REQUIRE(n_genomes <= LINK_MAX_GENOMES, FA_ERR_UNSUPPORTED, "medoids over more than 2^18 genomes");
-    FA_REQUIRE((int64_t)m->n_sets * (int64_t)n_genomes <= (int64_t)INT32_MAX, FA_ERR_UNSUPPORTED, "more than 2^31 - 1 labels");
-    if (m->bonus) {
-      qb.resize((size_t)n_genomes);
-      for (int32_t g = 0; g < n_genomes; g++) {
-        FA_REQUIRE(medoid_bonus_ok(m->bonus[g]), FA_ERR_INVALID, "a bonus must be a number in [-32768, 32768]");
-        qb[(size_t)g] = medoid_qb(m->bonus[g]);
-      }
-    }
-    // (labels on the host are checked here, those in HBM by k_medoid_check -- which sees the host's again)
-    if (!m->io_device)
-      for (int32_t t = 0; t < m->n_sets; t++)
-        FA_REQUIRE(label_set_ok(m->labels + (size_t)t * (size_t)n_genomes, n_genomes), FA_ERR_INVALID,
-                   "a label lies outside [0, n_genomes) or is not its own label");
-  } else if (want.dendrogram) FA_REQUIRE(want.n_merges && (!want.merges || want.merge_cap >= 0), FA_ERR_INVALID, "null merge count or negative capacity");
-  else if (want.clusters) FA_REQUIRE(n_genomes == 0 || want.labels, FA_ERR_INVALID, "null labels");
-  else FA_REQUIRE(want.n_pairs && want.cap >= 0, FA_ERR_INVALID, "null pair count or negative capacity");
-  std::vector<int32_t> pos;
-  if (want.representatives) {
-    FA_REQUIRE(p->min_identity >= 0.0f, FA_ERR_INVALID, "min_identity must be a number that is not negative");          // (false for NaN)
-    FA_REQUIRE(order_positions(want.order, n_genomes, pos), FA_ERR_INVALID, "order is not a permutation of the genome numbers");
-  }
-  long long qm = 0, qc = 0;
-  if (want.linkage) {
-    FA_REQUIRE(p->min_identity >= 0.0f, FA_ERR_INVALID, "min_identity must be a number that is not negative");          // (false for NaN)
-    FA_REQUIRE(want.missing >= 0.0f, FA_ERR_INVALID, "missing must be a number that is not negative");
-    const double dm = rint((double)want.missing * LINK_SCALE), dc = rint((double)p->min_identity * LINK_SCALE);
-    FA_REQUIRE(dm < dc, FA_ERR_INVALID, "missing must lie below min_identity");
-    FA_REQUIRE(n_genomes <= LINK_MAX_GENOMES, FA_ERR_UNSUPPORTED, "average linkage over more than 2^18 genomes");
-    // no weight exceeds LINK_MAX_W: a cut-off above it merges nothing whatever its value, and neither does the clamped one
-    // (link_cutoff of fa_link.h is this rule for one float: fa_dendrogram_cut forms its qc with it, and clusters._fixed_cutoff
-    // restates it in Python; the three must stay one rule for a cut to give the bytes of this call)
-    qc = (long long)std::min(dc, (double)(LINK_MAX_W + 1));
-    qm = (long long)std::min(dm, (double)LINK_MAX_W);
-  }
-  if (want.medoids) qm = link_fixed((double)want.medoids->missing);
-  require_device();
-  CallStream stream;
-  hipStream_t st = stream.s;
-  StatusBlock<TableStatus> d_status(st);
-  DevBuf<fa_cgi_row> d_rows;
-  DevBuf<uint64_t> d_len;
-  DevBuf<unsigned long long> keys, keys_sorted;
-  DevBuf<uint32_t> row_of, row_of_sorted;
-  DevBuf<unsigned char> temp;
-  DevBuf<int32_t> chunk_count;
-  DevBuf<int64_t> chunk_off;
-
-  TableArgs a{};
-  a.n_rows = n_rows; a.n_genomes = n_genomes;
-  a.fragment_length = (unsigned long long)p->fragment_length; a.min_fraction = p->min_fraction;
-  a.min_identity = (double)p->min_identity; a.reciprocal = p->reciprocal;
-  a.edges_only = want.linkage || want.medoids ? TAB_EMIT_LINK : want.representatives ? TAB_EMIT_WEIGHTED : want.clusters ? TAB_EMIT_EDGES : TAB_EMIT_PAIRS;
-  a.link_bits = (int32_t)id_bits(n_genomes);
-  a.status = d_status.p;
-  a.n_chunks = ceil_div(n_rows, TAB_CHUNK);
-  TableStatus status{};
-  if (n_rows) {
-    a.rows = on_device(rows, rows_device, (size_t)n_rows, d_rows, st);
-    d_len.ensure((size_t)n_genomes * 2);
-    FA_HIP(hipMemcpyAsync(d_len.p, query_lengths, (size_t)n_genomes * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    FA_HIP(hipMemcpyAsync(d_len.p + n_genomes, reference_lengths, (size_t)n_genomes * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    a.query_length = d_len.p; a.reference_length = d_len.p + n_genomes;
-    keys.ensure((size_t)n_rows); keys_sorted.ensure((size_t)n_rows);
-    row_of.ensure((size_t)n_rows); row_of_sorted.ensure((size_t)n_rows);
-    hipLaunchKernelGGL(k_table_keys, dim3(ceil_div(n_rows, 256)), dim3(256), 0, st, a, keys.p, row_of.p);
-    // the bits a key of this table can have set: two flag bits, 31 of b, and those of the largest a
-    const unsigned end_bit = 33u + id_bits(n_genomes);
-    with_temp(temp, [&](void *t, size_t &bytes) {
-      return rocprim::radix_sort_pairs(t, bytes, keys.p, keys_sorted.p, row_of.p, row_of_sorted.p, (size_t)n_rows, 0u, end_bit, st);
-    });
-    a.keys = keys_sorted.p; a.row_of = row_of_sorted.p;
-    chunk_count.ensure((size_t)a.n_chunks); chunk_off.ensure((size_t)a.n_chunks);
-    a.chunk_count = chunk_count.p; a.chunk_off = chunk_off.p;
-    hipLaunchKernelGGL(k_table_count, dim3(ceil_div(a.n_chunks, 4)), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_chunk_scan, dim3(1), dim3(1024), 0, st, a.chunk_count, a.chunk_off, a.n_chunks, &d_status.p->emitted);
-    FA_HIP(hipGetLastError());
-    status = d_status.read(st);
-    FA_REQUIRE(!(status.flags & TAB_BAD_ID), FA_ERR_INVALID, "a row names a genome outside [0, n_genomes)");
-    FA_REQUIRE(!(status.flags & TAB_DUPLICATE), FA_ERR_INVALID, "the table holds the same (query, reference) twice");
-    FA_REQUIRE(!(status.flags & TAB_BAD_IDENTITY), FA_ERR_INVALID, "a present pair has an identity that is NaN or outside [0, 128]");
-  }
-  const int64_t n_emit = (int64_t)status.emitted;
-  // the n_emit records of the call's form (a.edges_only), once their destination is set in `a`
-  auto emit = [&] {
-    a.cap = n_emit;
-    hipLaunchKernelGGL(k_table_write, dim3(ceil_div(a.n_chunks, 4)), dim3(256), 0, st, a);
-  };
-
-  if (!want.clusters) {
-    *want.n_pairs = (int64_t)status.pairs;
-    if (!want.pairs) return;
-    FA_REQUIRE(n_emit <= want.cap, FA_ERR_INVALID, "the pair buffer is smaller than the number of pairs");
-    if (!n_emit) return;
-    Staged<fa_pair> pairs(want.pairs, want.pairs_device, (size_t)n_emit);
-    a.pairs = pairs.dev();
-    emit();
-    FA_HIP(hipGetLastError());
-    pairs.finish(st);
-    FA_HIP(hipStreamSynchronize(st));
-    return;
-  }
-
-  int64_t rounds = 0;
-  unsigned int roots = 0;
-  auto emit_into = [&](unsigned long long *link_keys, LinkSum *link_sums) {
-    a.link_keys = link_keys; a.link_sums = link_sums;
-    emit();
-  };
-  if (const MedoidRequest *m = want.medoids) {
-    std::vector<unsigned int> set_roots((size_t)m->n_sets, 0u);
-    int64_t inside = 0;
-    if (n_genomes) medoids(emit_into, n_emit, n_genomes, qm, qb, *m, st, set_roots, inside);
-    if (m->n_clusters) for (int32_t t = 0; t < m->n_sets; t++) m->n_clusters[t] = (int32_t)set_roots[(size_t)t];
-    if (want.stats) {
-      want.stats[0] = (int64_t)status.survivors; want.stats[1] = (int64_t)status.pairs;
-      want.stats[2] = (int64_t)status.edges; want.stats[3] = inside;
-    }
-    return;
-  }
-  if (want.dendrogram) {
-    // everything lands in buffers of the call's own first: a short `cap` leaves the caller's memory as it was
-    int64_t n_merges = 0;
-    DevBuf<int32_t> d_labels;
-    DevBuf<fa_merge> found, sorted;
-    DevBuf<int32_t> order;                     // the records' numbers in the order of the walk
-    if (n_genomes) {
-      d_labels.ensure((size_t)n_genomes);
-      found.ensure((size_t)std::max(n_genomes - 1, 1));
-      roots = linkage(emit_into, n_emit, d_labels.p, n_genomes, qm, qc, d_status.p, st, rounds, found.p, &n_merges);
-      FA_REQUIRE(n_merges == (int64_t)n_genomes - (int64_t)roots, FA_ERR_INTERNAL, "the merge list and the labels disagree on the number of merges");
-    }
-    *want.n_merges = n_merges;
-    FA_REQUIRE(!want.merges || n_merges <= want.merge_cap, FA_ERR_INVALID, "the merge buffer is smaller than the number of merges");
-    const hipMemcpyKind kind = want.labels_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    if (want.merges && n_merges) {
-      // the order of the walk (fa_linkage.hip.h): total on the records, so the bytes do not depend on the slots they were taken in
-      sorted.ensure((size_t)n_merges);
-      order.ensure((size_t)n_merges);
-      with_temp(temp, [&](void *t, size_t &bytes) {
-        return rocprim::merge_sort(t, bytes, rocprim::counting_iterator<int32_t>(0), order.p, (size_t)n_merges, MergeIndexBefore{found.p}, st);
-      });
-      hipLaunchKernelGGL(k_link_gather, dim3(ceil_div(n_merges, 256)), dim3(256), 0, st, (const fa_merge *)found.p, (const int32_t *)order.p, n_merges,
-                         sorted.p);
-      FA_HIP(hipGetLastError());
-      FA_HIP(hipMemcpyAsync(want.merges, sorted.p, (size_t)n_merges * sizeof(fa_merge), kind, st));
-    }
-    if (want.labels && n_genomes) FA_HIP(hipMemcpyAsync(want.labels, d_labels.p, (size_t)n_genomes * sizeof(int32_t), kind, st));
-    FA_HIP(hipStreamSynchronize(st));
-  } else if (n_genomes && want.linkage) {
-    Staged<int32_t> labels(want.labels, want.labels_device, (size_t)n_genomes);
-    roots = linkage(emit_into, n_emit, labels.dev(), n_genomes, qm, qc, d_status.p, st, rounds);
-    labels.finish(st);
-    FA_HIP(hipStreamSynchronize(st));
-  } else if (n_genomes && want.representatives) {
-    DevBuf<TableEdge> d_edges;
-    DevBuf<int32_t> d_order;                   // pos, then order
-    std::vector<int32_t> both(pos);
-    both.resize((size_t)n_genomes * 2);
-    for (int32_t g = 0; g < n_genomes; g++) both[(size_t)n_genomes + (size_t)pos[(size_t)g]] = g;
-    d_order.upload(both, st);
-    Staged<int32_t> labels(want.labels, want.labels_device, (size_t)n_genomes);
-    Staged<double> identity(want.identity, want.labels_device, (size_t)n_genomes);
-    if (n_emit) {
-      d_edges.ensure((size_t)n_emit);
-      a.weighted = d_edges.p;
-      emit();
-    }
-    roots = representatives(d_edges.p, n_emit, d_order.p, d_order.p + n_genomes, labels.dev(), identity.dev(), n_genomes, d_status.p, st, rounds);
-    labels.finish(st);
-    identity.finish(st);
-    FA_HIP(hipStreamSynchronize(st));
-  } else if (n_genomes) {
-    DevBuf<int2> d_edges;
-    Staged<int32_t> labels(want.labels, want.labels_device, (size_t)n_genomes);
-    if (n_emit) {
-      d_edges.ensure((size_t)n_emit);
-      a.edges = d_edges.p;
-      emit();
-    }
-    roots = components(d_edges.p, n_emit, labels.dev(), n_genomes, d_status.p, st, rounds);
-    labels.finish(st);
-    FA_HIP(hipStreamSynchronize(st));
-  }
-  if (want.n_clusters) *want.n_clusters = (int32_t)roots;
-  if (want.stats) {
-    want.stats[0] = (int64_t)status.survivors; want.stats[1] = (int64_t)status.pairs;
-    want.stats[2] = (int64_t)status.edges; want.stats[3] = rounds;
-    if (want.linkage) want.stats[4] = (int64_t)n_genomes - (int64_t)roots;
-  }
+  const int64_t inside = (int64_t)(d_status.read(st).inside / 2ULL);            // (two directed entries a pair; read() synchronises)
+  if (n_clusters) for (int32_t t = 0; t < n_sets; t++) n_clusters[t] = (int32_t)roots[(size_t)t];
+  front.write_stats(stats, inside);
 }
 
 // The partitions of a merge list at n_cuts cut-offs (fa_dendrogram_cut; fa_linkage.hip.h has the road)

@@ -33,7 +33,7 @@
 // The undecided genome of smallest pos has only decided earlier neighbours: a round makes it a member or a representative.
 // So every round decides at least one genome and the loop ends within n rounds (a path walked in its own order needs about
 // that many); the host caps it there.  It reads the 4-byte `changed` epoch once per round: the last round after which a genome
-// was still undecided.
+// was still undecided (wave_epoch; the representatives are counted with wave_count: fa_table.hip.h has both).
 //
 // Assignment is two passes over the edges with one end a representative and the other a member: an atomicMax of the identity's
 // bit pattern per member (non-negative doubles order like their bits), then an atomicMin of the representative's pos over the
@@ -97,8 +97,7 @@ __global__ __launch_bounds__(256) void k_rep_decide(RepArgs r) {
     if (r.blocked[g] != r.round) r.state[g] = REP_CHOSEN;
     else pending = true;
   }
-  const unsigned long long m = __ballot(pending);                  // one atomicMax per wave that leaves a genome undecided
-  if (m && (int)(threadIdx.x & 63) == __ffsll((long long)m) - 1) atomicMax(&r.status->changed, r.round);
+  wave_epoch(&r.status->changed, pending, r.round);                // the last round that leaves a genome undecided
 }
 
 // the member and the representative of an edge that joins one of each (the only edges the assignment looks at)
@@ -140,8 +139,7 @@ __global__ __launch_bounds__(256) void k_rep_write(RepArgs r) {
     r.labels[g] = label;
     if (r.identity) r.identity[g] = chosen ? 100.0 : __longlong_as_double((long long)r.best[g]);
   }
-  const unsigned long long m = __ballot(chosen);
-  if (m && (threadIdx.x & 63) == 0) atomicAdd(&r.status->roots, (unsigned int)__popcll(m));
+  wave_count(&r.status->roots, chosen);
 }
 
 }  // namespace fa

@@ -36,6 +36,8 @@
 // cross-workgroup effect is an agent-scope atomicMin / atomicMax / atomicAdd / atomicOr, whose outcome does not depend
 // on order.  A round that lowered nothing wrote nothing, so all its reads were current: every edge joins equal labels and
 // every label is a root, which is the answer.  The host reads the 4-byte `changed` epoch once per round.
+// What a kernel reports to the host -- a flag, the epoch of a round, a count -- it reports once per wave, through wave_flag,
+// wave_epoch and wave_count below; the kernels of fa_represent.hip.h, fa_linkage.hip.h and fa_medoid.hip.h use the same three.
 #pragma once
 
 #include "fa_common.h"
@@ -48,6 +50,22 @@ constexpr int TAB_ITERS = 8, TAB_CHUNK = 64 * TAB_ITERS;          // rows per wa
 constexpr unsigned TAB_BAD_ID = 1u, TAB_DUPLICATE = 2u;
 constexpr unsigned TAB_BAD_IDENTITY = 64u;      // (TAB_EMIT_LINK) a present pair whose identity is NaN or outside [0, 128]
 constexpr unsigned long long TAB_KEY_NONE = ~0ULL;
+
+// ---- one report per wave ---------------------------------------------------------------------------------------------
+// What a kernel of the reductions tells the host goes through one of these three, each CALLED BY EVERY LANE OF THE WAVE (they
+// ballot): a wave with something to report issues one atomic, whose result does not depend on the order of the operands.
+__device__ __forceinline__ void wave_flag(unsigned int *flags, bool raise, unsigned int flag) {      // *flags |= flag, if any lane says so
+  const unsigned long long m = __ballot(raise);
+  if (m && (int)(threadIdx.x & 63) == __ffsll((long long)m) - 1) atomicOr(flags, flag);
+}
+__device__ __forceinline__ void wave_epoch(unsigned int *epoch, bool report, unsigned int round) {   // *epoch = the last round a lane reports
+  const unsigned long long m = __ballot(report);
+  if (m && (int)(threadIdx.x & 63) == __ffsll((long long)m) - 1) atomicMax(epoch, round);
+}
+__device__ __forceinline__ void wave_count(unsigned int *count, bool counted) {                      // *count += the lanes that say so
+  const unsigned long long m = __ballot(counted);
+  if (m && (threadIdx.x & 63) == 0) atomicAdd(count, (unsigned int)__popcll(m));
+}
 
 // one per call, zeroed before the first launch
 struct TableStatus {
@@ -79,7 +97,7 @@ struct TableArgs {
   const unsigned long long *keys;      // sorted
   const uint32_t *row_of;              // row number of every sorted key
   int32_t n_chunks;
-  int32_t edges_only;                  // TAB_EMIT_*: the pairs as records, the edges as (a, b), the edges as (a, b, identity),
+  int32_t emit;                        // TAB_EMIT_*: the pairs as records, the edges as (a, b), the edges as (a, b, identity),
                                        // the present pairs as directed entries
   int32_t link_bits;                   // (TAB_EMIT_LINK) a directed entry's key is from << link_bits | to
   int32_t *chunk_count;                // [n_chunks]
@@ -146,7 +164,7 @@ __device__ __forceinline__ TableItem table_item(const TableArgs &a, int64_t i) {
   }
   t.identity = both ? ((double)t.ab + (double)t.ba) / 2.0 : (double)own;
   // (TAB_EMIT_LINK: a pair is present whatever its identity)
-  t.edge = (a.edges_only == TAB_EMIT_LINK || t.identity >= a.min_identity) && (both || a.reciprocal == 0);
+  t.edge = (a.emit == TAB_EMIT_LINK || t.identity >= a.min_identity) && (both || a.reciprocal == 0);
   return t;
 }
 
@@ -164,12 +182,12 @@ __global__ __launch_bounds__(256) void k_table_count(TableArgs a) {
     pairs += __popcll(__ballot(t.head));
     edges += __popcll(__ballot(t.edge));
     duplicate |= t.duplicate;
-    bad_identity |= a.edges_only == TAB_EMIT_LINK && t.edge && !link_identity_ok(t.identity);
+    bad_identity |= a.emit == TAB_EMIT_LINK && t.edge && !link_identity_ok(t.identity);
   }
   if (__any(duplicate) && lane == 0) atomicOr(&a.status->flags, TAB_DUPLICATE);
   if (__any(bad_identity) && lane == 0) atomicOr(&a.status->flags, TAB_BAD_IDENTITY);
   if (lane != 0) return;
-  a.chunk_count[chunk] = a.edges_only ? edges : pairs;
+  a.chunk_count[chunk] = a.emit != TAB_EMIT_PAIRS ? edges : pairs;
   if (survivors) atomicAdd(&a.status->survivors, (unsigned long long)survivors);
   if (pairs) atomicAdd(&a.status->pairs, (unsigned long long)pairs);
   if (edges) atomicAdd(&a.status->edges, (unsigned long long)edges);
@@ -185,22 +203,22 @@ __global__ __launch_bounds__(256) void k_table_write(TableArgs a) {
 #pragma unroll
   for (int u = 0; u < TAB_ITERS; u++) {
     const TableItem t = table_item(a, base + 64 * u);
-    const bool emit = a.edges_only ? t.edge : t.head;
+    const bool emit = a.emit != TAB_EMIT_PAIRS ? t.edge : t.head;
     const unsigned long long mask = __ballot(emit);
     const int64_t o = off + __popcll(mask & below);
     off += __popcll(mask);
     if (!emit || o >= a.cap) continue;
-    if (a.edges_only == TAB_EMIT_LINK) {
+    if (a.emit == TAB_EMIT_LINK) {
       const LinkSum one{link_fixed(t.identity), 1};
       a.link_keys[2 * o] = (unsigned long long)t.a << a.link_bits | (unsigned long long)t.b;
       a.link_keys[2 * o + 1] = (unsigned long long)t.b << a.link_bits | (unsigned long long)t.a;
       a.link_sums[2 * o] = one;
       a.link_sums[2 * o + 1] = one;
-    } else if (a.edges_only == TAB_EMIT_WEIGHTED) {
+    } else if (a.emit == TAB_EMIT_WEIGHTED) {
       TableEdge e;
       e.a = t.a; e.b = t.b; e.identity = t.identity == 0.0 ? 0.0 : t.identity;
       a.weighted[o] = e;
-    } else if (a.edges_only) a.edges[o] = make_int2(t.a, t.b);
+    } else if (a.emit == TAB_EMIT_EDGES) a.edges[o] = make_int2(t.a, t.b);
     else {
       fa_pair p;
       p.a = t.a; p.b = t.b; p.identity_ab = t.ab; p.identity_ba = t.ba; p.identity = t.identity;
@@ -229,11 +247,6 @@ __device__ __forceinline__ int32_t comp_label(const int32_t *labels, int32_t g) 
   return __hip_atomic_load(labels + g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// one atomicMax per wave that lowered a label
-__device__ __forceinline__ void comp_report(const CompArgs &c, bool lowered) {
-  const unsigned long long m = __ballot(lowered);
-  if (m && (int)(threadIdx.x & 63) == __ffsll((long long)m) - 1) atomicMax(&c.status->changed, c.round);
-}
 
 __global__ __launch_bounds__(256) void k_comp_edges(CompArgs c) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -247,7 +260,7 @@ __global__ __launch_bounds__(256) void k_comp_edges(CompArgs c) {
       lowered |= atomicMin(c.labels + carrier, lo) > lo;
     }
   }
-  comp_report(c, lowered);
+  wave_epoch(&c.status->changed, lowered, c.round);
 }
 
 __global__ __launch_bounds__(256) void k_comp_jump(CompArgs c) {
@@ -263,14 +276,13 @@ __global__ __launch_bounds__(256) void k_comp_jump(CompArgs c) {
     }
     if (l < first) lowered = atomicMin(c.labels + g, l) > l;
   }
-  comp_report(c, lowered);
+  wave_epoch(&c.status->changed, lowered, c.round);
 }
 
-__global__ __launch_bounds__(256) void k_comp_roots(CompArgs c) {
+// the genomes that label themselves, added to *roots (of any labels, not only those of the components)
+__global__ __launch_bounds__(256) void k_comp_roots(const int32_t *labels, int32_t n, unsigned int *roots) {
   const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const bool root = g < c.n_genomes && c.labels[g] == (int32_t)g;
-  const unsigned long long m = __ballot(root);
-  if (m && (threadIdx.x & 63) == 0) atomicAdd(&c.status->roots, (unsigned int)__popcll(m));
+  wave_count(roots, g < n && labels[g] == (int32_t)g);
 }
 
 }  // namespace fa

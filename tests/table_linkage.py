@@ -184,6 +184,26 @@ def hubs():
     return make_case(table(np.where(flip, b, a), np.where(flip, a, b), identity), HUB_N, seed=16)
 
 
+RUN_HUBS = np.arange(60, 69)                                           # they straddle a wave boundary: several long runs in one wave
+RUN_DEGREES = (31, 32, 33, 63, 64, 65, 95, 96, 97)                    # one below, at and above 32 (a run one lane walks alone) and each multiple of 64
+RUN_N = 69 + sum(RUN_DEGREES)                                         # 645
+
+
+def run_edges():
+    """nine hubs whose runs in the directed view are exactly RUN_DEGREES long: every leaf is a genome of its own, numbered from
+    69 upwards hub by hub, with no other pair.  Identities are distinct multiples of 1/64 in [90, 100) (exact float32): they ascend
+    with the leaf's number, and the nine largest of all go to each hub's LAST leaf -- the one a walk that drops the tail of a run
+    loses -- so at 99 every hub merges with that leaf and with nothing else; rows in a random direction"""
+    g = np.random.default_rng(69)
+    hub = np.repeat(RUN_HUBS, RUN_DEGREES)
+    leaf = np.arange(69, RUN_N)
+    step = np.arange(len(leaf))                                      # 90.0 .. 98.984375
+    last = np.cumsum(RUN_DEGREES) - 1
+    step[last] = 640 - len(RUN_HUBS) + np.arange(len(RUN_HUBS))      # 99.859375 .. 99.984375
+    flip = g.random(len(leaf)) < 0.5
+    return make_case(table(np.where(flip, leaf, hub), np.where(flip, hub, leaf), 90.0 + step / 64.0), RUN_N, seed=69)
+
+
 BLOCKS = (150, 150, 149)
 BLOCK_CROSS = np.float32(96.0)
 
@@ -220,6 +240,7 @@ def cases():
     out["chain_renumbered"] = chain((1, 2, 0))                       # (the pairs are (1, 2) and (0, 2): now B-C comes first)
     out["block_65"] = identical_block(65)
     out["hubs"] = hubs()
+    out["run_edges"] = run_edges()
     out["three_blocks"] = three_blocks()
     out["missing_matters"] = missing_matters()
     return out

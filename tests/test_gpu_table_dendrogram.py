@@ -128,6 +128,14 @@ def test_every_combination_of_pointers(name):
             check_build(name, reciprocal, 95.0, missing, rows_device=rows_device, out_device=out_device)
 
 
+def test_runs_of_every_length_around_the_steps_of_the_walk():
+    """run_edges: nine runs of 31 .. 97 entries in two waves, each with its best candidate last; built at a cut at which every hub
+    merges and at one at which none does"""
+    for cut, merges in ((99.0, 9), (100.0, 0)):
+        for missing in td.MISSING:
+            assert len(check_build("run_edges", False, cut, missing, rows_device=True, out_device=True)) == merges
+
+
 def library_partition(name, reciprocal, at, missing):
     case = CASES[name]
     stats = {}

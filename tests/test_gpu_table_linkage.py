@@ -118,6 +118,15 @@ def test_hubs_with_long_runs():
     run("hubs", False, 80.0, 70.0)                                                     # many leaves above the cut
 
 
+def test_runs_of_every_length_around_the_steps_of_the_walk():
+    """run_edges: nine runs of 31 .. 97 entries in two waves, each with its best candidate last; a cut at which every hub merges
+    and one at which none does"""
+    for cut, merges in ((99.0, 9), (100.0, 0)):
+        for missing in (0.0, 80.0):
+            code, labels, count, stats = run("run_edges", False, cut, missing, rows_device=True, labels_device=True)
+            assert stats[4] == merges
+
+
 def test_three_blocks_that_differ_in_the_last_unit():
     code, labels, count, stats = run("three_blocks", False, rows_device=True)
     n0 = tl.BLOCKS[0]

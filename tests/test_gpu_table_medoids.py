@@ -161,6 +161,14 @@ def test_hubs_in_one_cluster_walk_long_runs():
     run("hubs", False, both, 80.0)
 
 
+def test_runs_of_every_length_around_the_steps_of_the_walk():
+    """run_edges: nine runs of 31 .. 97 entries in two waves, summed under two label sets at once"""
+    both = np.stack([np.zeros(tl.RUN_N, dtype=np.int32), tm.linkage_labels("run_edges", False, 95.0, 0.0)])
+    for missing in (0.0, 80.0):
+        code, out, n_clusters, stats = run("run_edges", False, both, missing, rows_device=True, io_device=True)
+        assert n_clusters[0] == 1 and out[3][0, 0] == tl.RUN_N
+
+
 def test_three_blocks_that_differ_by_four_units():
     labels = tm.linkage_labels("three_blocks", False, 95.0, 0.0)
     code, out, n_clusters, stats = run("three_blocks", False, labels, rows_device=True)

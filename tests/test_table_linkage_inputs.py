@@ -180,6 +180,22 @@ def test_the_hubs_have_long_runs():
     assert 1 <= merges <= 8 and labels[tl.SECOND_HUB] != tl.SECOND_HUB and np.sum(labels == 0) > 1
 
 
+def test_the_run_edges_have_a_run_of_every_length_at_a_boundary():
+    a, b, w, counts = tl.pairs_of("run_edges", False)
+    runs = np.bincount(np.concatenate([a, b]), minlength=tl.RUN_N)  # the directed view holds a -> b and b -> a
+    assert runs[60:69].tolist() == [31, 32, 33, 63, 64, 65, 95, 96, 97]       # around 32 and around every multiple of 64
+    assert not runs[:60].any() and np.all(runs[69:] == 1)
+    assert len(np.unique(w)) == len(w) and not np.any(w % (tl.SCALE // 64)) and tl.fixed(90.0) <= w.min() and w.max() < tl.fixed(100.0)
+    last = 68 + np.cumsum(tl.RUN_DEGREES)                           # every hub's leaf of largest number has its largest identity
+    for hub, leaf in zip(tl.RUN_HUBS.tolist(), last.tolist()):
+        mine = a == hub
+        assert b[mine].max() == leaf and b[mine][np.argmax(w[mine])] == leaf and w[mine].max() >= tl.fixed(99.0)
+    for missing in (0.0, 80.0):
+        labels, n_clusters, _, merges = tl.expected("run_edges", False, 99.0, missing)       # every hub merges, with that leaf alone
+        assert merges == 9 and labels[last].tolist() == tl.RUN_HUBS.tolist()
+        assert tl.expected("run_edges", False, 100.0, missing)[3] == 0                      # and none does
+
+
 def test_the_three_blocks_differ_in_the_last_unit():
     a, b, w, counts = tl.pairs_of("three_blocks", False)
     n0, n1, n2 = tl.BLOCKS
