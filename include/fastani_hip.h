@@ -520,6 +520,58 @@ int fa_table_medoids(const fa_cgi_row *rows, int64_t n_rows, int rows_device, in
 int fa_debug_medoid_better(double bonus_b, int64_t s_b, int32_t b, double bonus_a, int64_t s_a, int32_t a, int32_t m, int64_t t[2],
                            int *better);
 
+/* ---- the fragment mappings behind a hit table, reduced to a per-fragment profile ---- */
+/* What a mapping table is read for: which parts of a genome are shared with its relatives, and how well -- the per-fragment
+ * reading of core-genome identity.  The records (fa_hit_mapping, left in HBM by fa_mapper_query_genomes_mappings with
+ * maps_device) are accumulated call by call into one entry per query fragment, and the entries reduced per genome.
+ *   1. Profile.  Over a batch of n_queries query genomes, fragment_offsets [n_queries + 1] is the prefix sum of the genomes'
+ *      fragment numbers (fa_genomes_info's total_fragments), fragment_offsets[0] == 0; fragment f (= query_seq_id) of query q
+ *      is entry fragment_offsets[q] + f.  An entry holds count (int32), the number of counted records; sum (int64), the sum
+ *      of their identities in fixed point, rint(identity * 2^20), ties to even; lowest (float32), the smallest identity among
+ *      them, +inf while count == 0.  The three arrays are the caller's DEVICE memory, fragment_offsets[n_queries] entries
+ *      each, initialised by the caller (0, 0, +inf) and owned by it across calls.
+ *   2. Counted.  A record (q, f, r, identity) is counted iff identity >= min_identity in float32 (equality counts), and,
+ *      with labels, query_labels[q] == reference_labels[r], and, with self_reference, self_reference[q] != r:
+ *      self_reference[q] is the reference number that is query q itself, -1 for none -- how an all-vs-all drops its diagonal
+ *      and a chunked batch says which global genome each query is.  query_labels [n_queries], reference_labels
+ *      [n_references] and self_reference [n_queries] are HOST arrays, each NULL for none; the two label arrays go together.
+ *   3. Order.  All three accumulators are integers, or the orderable bit pattern of a non-negative float: the result does
+ *      not depend on the order of the records, on how they are split over calls, or on the road the kernel takes.
+ *      Accumulating one pass and then the next gives the bytes of one call over both.
+ *   4. stats may be NULL; [0] records counted, [1] records at or above min_identity that labels or self dropped, [2] records
+ *      below min_identity, [3] workgroups of the accumulate kernel that summed on chip before touching HBM.
+ *   5. FA_ERR_INVALID with the accumulators untouched: a query_id outside [0, n_queries); a query_seq_id outside [0, the
+ *      fragments of its query); a ref_genome_id outside [0, n_references); an identity that is NaN, has its sign bit set
+ *      (-0.0 included: the minimum is taken on the bit pattern) or lies above 128; offsets that do not start at 0 or that
+ *      decrease; a negative count; one label array without the other; a NaN min_identity; NULL accumulators with a fragment
+ *      to hold.  n_maps == 0 is valid and touches nothing.
+ *   6. Not checked: the same (query, fragment, reference) in two records.  The mapper never emits that, and across calls it
+ *      cannot be seen; such a record counts twice.
+ *   7. What the records are.  They are the mappings computeCGI KEPT: the best of a query fragment per reference genome, then
+ *      the best per reference bin.  A fragment that lost its reference bin to a neighbour is absent from that reference's
+ *      records: count is "references whose hit counts this fragment", not "references where it would map".
+ * `maps` is a DEVICE pointer when maps_device != 0.  Runs like the table reductions: on the calling thread's current device,
+ * on a stream of its own, with memory from the device pool, finished when it returns, FA_ERR_NO_DEVICE without a device. */
+int fa_mappings_profile(const fa_hit_mapping *maps, int64_t n_maps, int maps_device, int32_t n_queries, const int64_t *fragment_offsets,
+                        int32_t n_references, const int32_t *query_labels, const int32_t *reference_labels, const int32_t *self_reference,
+                        float min_identity, int32_t *d_count, int64_t *d_sum, float *d_lowest, int64_t *stats);
+/* The summary of a profile.  min_count is a HOST array [n_sets][n_queries], every value >= 0, n_sets >= 1.  For every
+ * (set, q), over the fragments of q with count >= min_count[set][q]: fragments, how many there are; hits, the sum of their
+ * counts; sum, the sum of their fixed-point sums.  From these and the genome's fragment number the caller forms the core
+ * fraction at a presence threshold, the whole presence curve (one set per threshold) and the mean identity of the core,
+ * sum / hits / 2^20.  A genome without fragments gives zeros.  d_count and d_sum are DEVICE pointers; the three outputs, each
+ * [n_sets][n_queries] and each of which may be NULL, are DEVICE pointers when out_device != 0.  FA_ERR_INVALID with nothing
+ * written: n_sets < 1, a negative min_count, bad offsets as above, NULL min_count or accumulators where there is something
+ * to read.  n_sets * n_queries > 2^31 - 1 is FA_ERR_UNSUPPORTED. */
+int fa_profile_summary(const int32_t *d_count, const int64_t *d_sum, int32_t n_queries, const int64_t *fragment_offsets,
+                       const int32_t *min_count, int32_t n_sets, int64_t *fragments, int64_t *hits, int64_t *sum, int out_device);
+/* The two constants of the accumulate kernel: the records a workgroup takes, and the most fragments a query may have for a
+ * workgroup whose records all belong to it to sum on chip; host only. */
+int fa_profile_chunk(int32_t *records_per_workgroup, int32_t *lds_fragments);
+/* development: the road of the accumulate kernel for the process -- 0 the policy, 1 always global atomics, 2 on chip wherever
+ * it fits; the results do not depend on it (scripts/time_fragment_profile.py times both); host only */
+int fa_debug_profile_road(int32_t road);
+
 /* ---- a query x reference hit table, reduced to every query's k best hits ---- */
 /* What a batch of queries is mapped against a reference database for: per query, the closest references that pass an identity
  * and an aligned-fraction cut-off (species assignment: ANI >= 95 with AF >= 0.5; over one genome set with exclude_self, every

@@ -1832,6 +1832,47 @@ cdef class GenomeBatch:
             rows, maps = self.query_mappings(lo, n)
             yield lo, n, rows, maps
 
+    def iter_mappings_device(self, int first=0, count=None, max_records=None):
+        """`iter_mappings` with the records left in HBM: a generator of ``(first_genome, n_genomes, rows, maps)`` over the
+        ranges of `pyfastani_amd._batch.plan_ranges`.  ``rows`` is the range's ``ROW_DTYPE`` array; ``maps`` is an int32
+        ``[n, 8]`` torch tensor of the words of the range's records (`pyfastani_amd._batch.MAPPING_DTYPE`) on the mapper's
+        device -- a view into ONE buffer that is reused from range to range, so valid until the generator is advanced.
+        The buffer holds ``max_records`` records, or the safe bound: the fragments of the largest range times the number of
+        references.  A range with more records than the buffer holds raises ``ValueError``, as the entry point does.  The
+        records are complete when a step returns (the library writes them on a stream of its own and synchronises it).
+        `pyfastani_amd.conservation.all_vs_all` is the loop that reduces them where they lie."""
+        import numpy as np
+        import torch
+        from ._batch import plan_ranges, pass_fragments
+        cdef int c = self.n_genomes - first if count is None else count
+        cdef int64_t n_ref = max(1, len(self._mapper._names))
+        cdef int64_t cap, map_cap, n_rows = 0, n_maps = 0
+        cdef int code, lo, n
+        cdef uintptr_t p, pm
+        if first < 0 or c < 0 or first + c > self.n_genomes:
+            raise ValueError("genome range out of bounds")
+        ranges = plan_ranges(self.total_fragments, pass_fragments(), first, c)
+        if max_records is None:
+            map_cap = max([int(self.total_fragments[g0:g0 + k].sum()) for g0, k in ranges] + [0]) * n_ref
+        else:
+            map_cap = max_records
+            if map_cap < 0:
+                raise ValueError("max_records must not be negative")
+        device = self._mapper._torch_device()
+        buffer = torch.empty((max(map_cap, 1), 8), dtype=torch.int32, device=device)
+        torch.cuda.synchronize(device)
+        pm = buffer.data_ptr()
+        for lo, n in ranges:
+            cap = max(1, <int64_t> n * n_ref)
+            rows = np.zeros(cap, dtype=_row_dtype())
+            p = rows.ctypes.data
+            n_rows = n_maps = 0
+            with nogil:
+                code = hip.fa_mapper_query_genomes_mappings(self._mapper._hm, self._hg, lo, n, <hip.fa_cgi_row*> p, cap, &n_rows, 0,
+                                                            <hip.fa_hit_mapping*> pm, map_cap, &n_maps, 1)
+            _check(code)
+            yield lo, n, rows[:n_rows], buffer[:n_maps]
+
     def query_rows_device(self, int first, int count, uintptr_t device_ptr, int64_t cap):
         """Same, but the rows are written to a caller-owned DEVICE buffer (e.g. a torch tensor feeding an RCCL all-gather).
         The library writes on its own stream: whatever the caller queued on the buffer (its allocation's memset, say)

@@ -200,6 +200,10 @@ SIGNATURES = {
     "fa_debug_linkage_order": (_i32, [_P(_i64), _P(_i64), _P(_i32)]),
     "fa_table_medoids": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _P(TableParams), _f32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
     "fa_debug_medoid_better": (_i32, [_f64, _i64, _i32, _f64, _i64, _i32, _i32, _P(_i64), _P(_i32)]),
+    "fa_mappings_profile": (_i32, [_vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp]),
+    "fa_profile_summary": (_i32, [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _i32]),
+    "fa_profile_chunk": (_i32, [_P(_i32), _P(_i32)]),
+    "fa_debug_profile_road": (_i32, [_i32]),
     "fa_table_best": (_i32, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _P(BestParams), _vp, _vp, _i64, _P(_i64), _i32, _vp]),
     "fa_screen_tile": (_i32, [_i32, _P(_i32)]),
     "fa_screen_signatures": (_i32, [_vp, _vp, _i64, _vp, _i32, _i32, _vp, _vp]),

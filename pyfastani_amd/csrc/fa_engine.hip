@@ -561,6 +561,33 @@ int fa_debug_medoid_better(double bonus_b, int64_t s_b, int32_t b, double bonus_
     *better = medoid_better(t[0], b, t[1], a) ? 1 : 0;
   });
 }
+int fa_mappings_profile(const fa_hit_mapping *maps, int64_t n_maps, int maps_device, int32_t n_queries, const int64_t *fragment_offsets,
+                        int32_t n_references, const int32_t *query_labels, const int32_t *reference_labels, const int32_t *self_reference,
+                        float min_identity, int32_t *d_count, int64_t *d_sum, float *d_lowest, int64_t *stats) {
+  return guarded([&] {
+    mappings_profile(maps, n_maps, maps_device != 0, n_queries, fragment_offsets, n_references, query_labels, reference_labels, self_reference,
+                     min_identity, d_count, d_sum, d_lowest, stats);
+  });
+}
+int fa_profile_summary(const int32_t *d_count, const int64_t *d_sum, int32_t n_queries, const int64_t *fragment_offsets,
+                       const int32_t *min_count, int32_t n_sets, int64_t *fragments, int64_t *hits, int64_t *sum, int out_device) {
+  return guarded([&] {
+    profile_summary(d_count, d_sum, n_queries, fragment_offsets, min_count, n_sets, fragments, hits, sum, out_device != 0);
+  });
+}
+int fa_profile_chunk(int32_t *records_per_workgroup, int32_t *lds_fragments) {
+  return guarded([&] {
+    FA_REQUIRE(records_per_workgroup && lds_fragments, FA_ERR_INVALID, "null destination");
+    *records_per_workgroup = PROF_CHUNK;
+    *lds_fragments = PROF_LDS_FRAGMENTS;
+  });
+}
+int fa_debug_profile_road(int32_t road) {
+  return guarded([&] {
+    FA_REQUIRE(road >= 0 && road <= 2, FA_ERR_INVALID, "road 0 (the policy), 1 (global atomics) or 2 (on chip wherever it fits)");
+    g_profile_road.store(road);
+  });
+}
 int fa_table_best(const fa_cgi_row *rows, int64_t n_rows, int rows_device, int32_t n_queries, int32_t n_references,
                   const uint64_t *query_lengths, const uint64_t *reference_lengths, const fa_best_params *p, fa_cgi_row *best,
                   int64_t *offsets, int64_t cap, int64_t *n_best, int out_device, int64_t *stats) {

@@ -1,5 +1,6 @@
 // fa_reduce.hip.h -- the host drivers of the reductions over results the mapper already holds: a hit table to pairs,
 // clusters, representatives, average-linkage clusters and their dendrogram with its cuts, and the medoids of given clusters (fa_table.hip.h, fa_represent.hip.h, fa_linkage.hip.h, fa_medoid.hip.h), to every query's k best hits (fa_best.hip.h), the
+// fragment mappings behind a table to a per-fragment conservation profile and its per-genome summary (fa_profile.hip.h), the
 // signature screen (fa_screen.hip.h) and its containment road (fa_contain.hip.h).  They use nothing of the sketch, the mapper or the workspace -- but for the last one, the
 // signatures of a resident batch (fa_batchsig.hip.h), which borrows a workspace for K1's staging arrays; fa_engine.hip wraps each
 // in its extern "C" entry point.
@@ -32,6 +33,7 @@
 #include "fa_linkage.hip.h"
 #include "fa_medoid.hip.h"
 #include "fa_order.h"
+#include "fa_profile.hip.h"
 #include "fa_query.hip.h"
 #include "fa_represent.hip.h"
 #include "fa_screen.hip.h"
@@ -580,6 +582,113 @@ inline void dendrogram_cut(const fa_merge *merges, int64_t n_merges, bool merges
   out.finish(st);
   FA_HIP(hipStreamSynchronize(st));
   for (size_t t = 0; t < roots.size(); t++) n_clusters[t] = (int32_t)roots[t];
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// The fragment mappings behind a hit table reduced to a per-fragment profile (fa_profile.hip.h has the semantics and the road)
+// ------------------------------------------------------------------------------------------------------------
+// the road of k_profile_add: 0 the policy, 1 global atomics only, 2 on chip wherever it fits (fa_debug_profile_road)
+inline std::atomic<int> g_profile_road{0};
+
+// fragment_offsets as both calls take it: [n_queries + 1], from 0, never decreasing
+inline void check_fragment_offsets(int32_t n_queries, const int64_t *fragment_offsets) {
+  FA_REQUIRE(n_queries >= 0, FA_ERR_INVALID, "negative number of queries");
+  FA_REQUIRE(fragment_offsets, FA_ERR_INVALID, "null fragment offsets");
+  FA_REQUIRE(fragment_offsets[0] == 0, FA_ERR_INVALID, "fragment_offsets must start at 0");
+  for (int32_t q = 0; q < n_queries; q++)
+    FA_REQUIRE(fragment_offsets[q + 1] >= fragment_offsets[q], FA_ERR_INVALID, "fragment_offsets must not decrease");
+}
+
+// fa_mappings_profile: the three accumulators are the caller's device arrays; offsets, labels and self_reference host arrays
+inline void mappings_profile(const fa_hit_mapping *maps, int64_t n_maps, bool maps_device, int32_t n_queries, const int64_t *fragment_offsets,
+                             int32_t n_references, const int32_t *query_labels, const int32_t *reference_labels, const int32_t *self_reference,
+                             float min_identity, int32_t *d_count, int64_t *d_sum, float *d_lowest, int64_t *stats) {
+  FA_REQUIRE(n_maps >= 0 && n_references >= 0, FA_ERR_INVALID, "negative number of records or references");
+  check_fragment_offsets(n_queries, fragment_offsets);
+  FA_REQUIRE(n_maps == 0 || maps, FA_ERR_INVALID, "null records");
+  FA_REQUIRE((query_labels != nullptr) == (reference_labels != nullptr), FA_ERR_INVALID, "query_labels and reference_labels go together");
+  FA_REQUIRE(min_identity == min_identity, FA_ERR_INVALID, "min_identity must be a number");
+  const int64_t total = fragment_offsets[n_queries];
+  FA_REQUIRE(total == 0 || (d_count && d_sum && d_lowest), FA_ERR_INVALID, "null accumulators");
+  const int64_t n_chunks = (n_maps + PROF_CHUNK - 1) / PROF_CHUNK;
+  FA_REQUIRE(n_chunks <= (int64_t)INT32_MAX, FA_ERR_UNSUPPORTED, "more than 2^31 - 1 chunks of records");
+  require_device();
+  if (!n_maps) {
+    if (stats) std::fill(stats, stats + 4, (int64_t)0);
+    return;
+  }
+  CallStream stream;
+  hipStream_t st = stream.s;
+  StatusBlock<ProfileStatus> d_status(st);
+  DevBuf<fa_hit_mapping> d_maps;
+  DevBuf<int64_t> d_offsets;
+  DevBuf<int32_t> words, chunk_query;          // words: query_labels, reference_labels, self_reference
+
+  ProfileArgs a{};
+  a.maps = reinterpret_cast<const int4 *>(on_device(maps, maps_device, (size_t)n_maps, d_maps, st));
+  a.n_maps = n_maps; a.n_queries = n_queries; a.n_references = n_references; a.min_identity = min_identity;
+  d_offsets.upload(fragment_offsets, (size_t)n_queries + 1, st);
+  a.offsets = d_offsets.p;
+  const size_t nq = (size_t)n_queries, nr = (size_t)n_references;
+  words.ensure(2 * nq + nr);
+  if (query_labels) {
+    if (nq) FA_HIP(hipMemcpyAsync(words.p, query_labels, nq * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (nr) FA_HIP(hipMemcpyAsync(words.p + nq, reference_labels, nr * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    a.query_labels = words.p; a.reference_labels = words.p + nq;
+  }
+  if (self_reference) {
+    if (nq) FA_HIP(hipMemcpyAsync(words.p + nq + nr, self_reference, nq * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    a.self_reference = words.p + nq + nr;
+  }
+  chunk_query.ensure((size_t)n_chunks);
+  a.chunk_query = chunk_query.p;
+  a.count = d_count; a.sum = reinterpret_cast<unsigned long long *>(d_sum); a.lowest = reinterpret_cast<unsigned int *>(d_lowest);
+  a.status = d_status.p;
+  const int road = g_profile_road.load();
+  a.road = road ? road : (PROF_POLICY_ON_CHIP ? 2 : 1);
+  // the verdict on the records is read before an accumulator is touched
+  hipLaunchKernelGGL(k_profile_check, dim3((unsigned)n_chunks), dim3(PROF_THREADS), 0, st, a);
+  FA_HIP(hipGetLastError());
+  const ProfileStatus checked = d_status.read(st);
+  FA_REQUIRE(!(checked.flags & PROF_BAD_QUERY), FA_ERR_INVALID, "a record names a query outside [0, n_queries)");
+  FA_REQUIRE(!(checked.flags & PROF_BAD_FRAGMENT), FA_ERR_INVALID, "a record names a fragment outside its query's fragments");
+  FA_REQUIRE(!(checked.flags & PROF_BAD_REFERENCE), FA_ERR_INVALID, "a record names a reference outside [0, n_references)");
+  FA_REQUIRE(!(checked.flags & PROF_BAD_IDENTITY), FA_ERR_INVALID, "a record's identity is NaN, negative (-0.0 included) or above 128");
+  hipLaunchKernelGGL(k_profile_add, dim3((unsigned)n_chunks), dim3(PROF_THREADS), 0, st, a);
+  FA_HIP(hipGetLastError());
+  const ProfileStatus end = d_status.read(st);
+  if (stats) { stats[0] = (int64_t)end.counted; stats[1] = (int64_t)end.skipped; stats[2] = (int64_t)end.below; stats[3] = (int64_t)end.on_chip; }
+}
+
+// fa_profile_summary: d_count and d_sum are device arrays; min_count [n_sets][n_queries] is host memory; the three outputs,
+// each [n_sets][n_queries] or null, are device pointers with out_device
+inline void profile_summary(const int32_t *d_count, const int64_t *d_sum, int32_t n_queries, const int64_t *fragment_offsets,
+                            const int32_t *min_count, int32_t n_sets, int64_t *fragments, int64_t *hits, int64_t *sum, bool out_device) {
+  check_fragment_offsets(n_queries, fragment_offsets);
+  FA_REQUIRE(n_sets >= 1, FA_ERR_INVALID, "a summary needs at least one threshold set");
+  FA_REQUIRE(n_queries == 0 || min_count, FA_ERR_INVALID, "null min_count");
+  FA_REQUIRE(fragment_offsets[n_queries] == 0 || (d_count && d_sum), FA_ERR_INVALID, "null accumulators");
+  FA_REQUIRE((int64_t)n_sets * (int64_t)n_queries <= (int64_t)INT32_MAX, FA_ERR_UNSUPPORTED, "more than 2^31 - 1 thresholds");
+  const size_t total = (size_t)n_sets * (size_t)n_queries;
+  for (size_t i = 0; i < total; i++) FA_REQUIRE(min_count[i] >= 0, FA_ERR_INVALID, "min_count must not be negative");
+  require_device();
+  if (!n_queries) return;
+  CallStream stream;
+  hipStream_t st = stream.s;
+  DevBuf<int64_t> d_offsets;
+  DevBuf<int32_t> d_min;
+  d_offsets.upload(fragment_offsets, (size_t)n_queries + 1, st);
+  d_min.upload(min_count, total, st);
+  Staged<int64_t> out_fragments(fragments, out_device, total), out_hits(hits, out_device, total), out_sum(sum, out_device, total);
+  SummaryArgs a{};
+  a.count = d_count; a.sum = reinterpret_cast<const long long *>(d_sum); a.offsets = d_offsets.p; a.min_count = d_min.p;
+  a.n_queries = n_queries; a.n_sets = n_sets;
+  a.fragments = out_fragments.dev(); a.hits = out_hits.dev(); a.sums = out_sum.dev();
+  const dim3 grid((unsigned)n_queries, (unsigned)std::min(ceil_div(n_sets, PROF_SETS), 65535));
+  hipLaunchKernelGGL(k_profile_summary, grid, dim3(PROF_THREADS), 0, st, a);
+  FA_HIP(hipGetLastError());
+  out_fragments.finish(st); out_hits.finish(st); out_sum.finish(st);
+  FA_HIP(hipStreamSynchronize(st));
 }
 
 // ------------------------------------------------------------------------------------------------------------

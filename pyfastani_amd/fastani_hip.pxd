@@ -171,6 +171,16 @@ cdef extern from "fastani_hip.h" nogil:
                                  const int32_t* order, int32_t* labels, double* identity, int out_device,
                                  int32_t* n_representatives, int64_t* stats)
 
+    # the fragment mappings behind a hit table reduced to a per-fragment profile (pyfastani_amd.conservation)
+    int fa_mappings_profile(const fa_hit_mapping* maps, int64_t n_maps, int maps_device, int32_t n_queries,
+                            const int64_t* fragment_offsets, int32_t n_references, const int32_t* query_labels,
+                            const int32_t* reference_labels, const int32_t* self_reference, float min_identity, int32_t* d_count,
+                            int64_t* d_sum, float* d_lowest, int64_t* stats)
+    int fa_profile_summary(const int32_t* d_count, const int64_t* d_sum, int32_t n_queries, const int64_t* fragment_offsets,
+                           const int32_t* min_count, int32_t n_sets, int64_t* fragments, int64_t* hits, int64_t* sum, int out_device)
+    int fa_profile_chunk(int32_t* records_per_workgroup, int32_t* lds_fragments)
+    int fa_debug_profile_road(int32_t road)
+
     # a query x reference hit table reduced to every query's k best hits (pyfastani_amd.classify)
     ctypedef struct fa_best_params:
         float min_fraction

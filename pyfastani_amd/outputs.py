@@ -235,3 +235,30 @@ def write_mappings(path, query_names, reference_names, mappings, query_contig_le
                 where = (int(contig[frag]), int(offset[frag]), int(offset[frag]) + int(fragment_length))
             f.write(f"{query_names[q]}\t{frag}\t{where[0]}\t{where[1]}\t{where[2]}\t{reference_names[r['ref_genome_id']]}\t"
                     f"{r['ref_seq_id']}\t{r['ref_start_pos']}\t{r['identity']:.6g}\t{r['conserved']}\t{r['sketch_size']}\n")
+
+
+PROFILE_COLUMNS = ("genome", "contig", "start", "end", "count", "mean_identity", "lowest_identity")
+
+
+def write_fragment_profile(path, names, count, sum, lowest, contig_lengths, fragment_length):
+    """A `pyfastani_amd.conservation.FragmentProfile` as a tab-separated table, one line per query fragment in profile order
+    under a header line naming the columns (`PROFILE_COLUMNS`): the genome, the fragment's contig (its index into the
+    genome's ``contig_lengths`` as given, short contigs included), start and end on it (`fragment_coordinates`), the number of
+    counted records, and their mean (``sum / count / 2**20``) and lowest identity -- ``NA`` for both where the count is 0.
+    ``count``, ``sum`` and ``lowest`` are the profile's three arrays (numpy or tensors); ``contig_lengths`` holds one sequence
+    of contig lengths per genome, in the order of ``names``."""
+    count, sum, lowest = (x.cpu().numpy() if hasattr(x, "cpu") else np.asarray(x) for x in (count, sum, lowest))
+    if len(names) != len(contig_lengths):
+        raise ValueError("one sequence of contig lengths per genome name")
+    coords = [fragment_coordinates(lengths, fragment_length) for lengths in contig_lengths]
+    if not (len(count) == len(sum) == len(lowest) == int(np.sum([len(c) for c, _ in coords], dtype=np.int64))):
+        raise ValueError("the profile holds one entry per fragment of the genomes")
+    at = 0
+    with open(path, "w") as f:
+        f.write("\t".join(PROFILE_COLUMNS) + "\n")
+        for name, (contig, offset) in zip(names, coords):
+            for k in range(len(contig)):
+                c = int(count[at])
+                values = (f"{int(sum[at]) / c / 2.0 ** 20:.6g}", f"{float(lowest[at]):.6g}") if c else ("NA", "NA")
+                f.write(f"{name}\t{int(contig[k])}\t{int(offset[k])}\t{int(offset[k]) + int(fragment_length)}\t{c}\t{values[0]}\t{values[1]}\n")
+                at += 1
