@@ -213,6 +213,14 @@ int fa_mapper_num_minimizers(fa_mapper *m, int64_t *n);
 int fa_mapper_get_minimizers(fa_mapper *m, uint32_t *hash, int32_t *seq_id, int32_t *wpos);
 int fa_mapper_num_genomes(fa_mapper *m, int64_t *n);
 int fa_mapper_get_state(fa_mapper *m, uint64_t *lengths, int32_t *sequences_by_file);
+/* The numbering of the reference bins computeCGI keeps one mapping per (query genome, reference genome) for: *bin_length =
+ * max(fragment_length - 20, 1), *n_contigs the contigs of the index, contig_bin [n_contigs + 1] the first bin of every contig
+ * and contig_genome [n_contigs] its reference genome -- the index's own arrays, downloaded.  A mapping on contig c at
+ * ref_start_pos p lies in bin contig_bin[c] + p / bin_length; contig_bin[n_contigs] is the number of bins of the index.  A
+ * contig has the bins up to that of its last minimizer window, so a contig WITHOUT minimizer records (shorter than a window)
+ * has NO bins: contig_bin[c + 1] == contig_bin[c].  The two arrays may be NULL to ask for the sizes only; bin_length and
+ * n_contigs may not. */
+int fa_mapper_reference_bins(fa_mapper *m, int32_t *bin_length, int64_t *n_contigs, int32_t *contig_bin, int32_t *contig_genome);
 
 /* Mapper._query_draft up to and including computeCGI, _fastani.pyx:1006-1118, for ONE query genome given as
  * host buffers.  rows receive one cgi::CGI_Results per reference genome with at least one mapping, in
@@ -571,6 +579,72 @@ int fa_profile_chunk(int32_t *records_per_workgroup, int32_t *lds_fragments);
 /* development: the road of the accumulate kernel for the process -- 0 the policy, 1 always global atomics, 2 on chip wherever
  * it fits; the results do not depend on it (scripts/time_fragment_profile.py times both); host only */
 int fa_debug_profile_road(int32_t road);
+
+/* ---- the same records, reduced by reference position; and the regions of either profile ---- */
+/* The other half of the reading: which parts of a REFERENCE the queries share, and where its islands are.  The key space is
+ * the mapper's own (fa_mapper_reference_bins): one entry per reference bin.
+ *   1. Profile.  A record goes to entry contig_bin[ref_seq_id] + ref_start_pos / bin_length, the bin computeCGI kept it for.
+ *      An entry holds count (int32), sum (int64, rint(identity * 2^20), ties to even) and lowest (float32, +inf while count
+ *      == 0), as in fa_mappings_profile.  The three arrays are the caller's DEVICE memory, contig_bin[n_contigs] entries each,
+ *      initialised by the caller (0, 0, +inf) and owned by it across calls.  contig_bin [n_contigs + 1] and contig_genome
+ *      [n_contigs] are HOST arrays.
+ *   2. Counted.  Exactly the rules of fa_mappings_profile: identity >= min_identity in float32 is asked first (equality
+ *      counts), then, with labels, query_labels[q] == reference_labels[r], then, with self_reference, self_reference[q] != r.
+ *      The three are HOST arrays, each NULL for none; the two label arrays go together.
+ *   3. Order.  Every accumulator is an integer atomic -- the minimum on the bit pattern of a non-negative float --, and there
+ *      is no float atomic: the bytes do not depend on the order of the records, on how they are split over calls, or on
+ *      timing.
+ *   4. stats may be NULL; [0] records counted, [1] records at or above min_identity that labels or self dropped, [2] records
+ *      below min_identity.
+ *   5. FA_ERR_INVALID with the accumulators untouched: everything fa_mappings_profile refuses about query_id, ref_genome_id,
+ *      identity, the labels and min_identity; a ref_seq_id outside [0, n_contigs); contig_genome[ref_seq_id] != ref_genome_id;
+ *      ref_start_pos < 0, or its bin not below the contig's number of bins, contig_bin[c + 1] - contig_bin[c]; bin_length
+ *      < 1; a contig_bin that does not start at 0 or that decreases; a contig_genome that decreases or leaves [0,
+ *      n_references); a negative count; NULL accumulators with a bin to hold.  n_maps == 0 is valid and touches nothing.
+ *   6. Not read and not checked: query_seq_id.  Not checked: the same (query, reference genome, bin) in two records; the
+ *      mapper never emits that, and such a record counts twice.
+ *   7. What count means.  The mapper emits at most one record per (query genome, reference genome, bin), so count[bin] is
+ *      the number of query genomes whose hit counts a mapping that STARTS in that bin.  Three properties of FastANI's
+ *      binning follow, none of them of this code.  (a) Bins are 20 bases shorter than fragments: with identical coordinates
+ *      about one bin in fragment_length / 20 holds no fragment start.  (b) A start can slip across a bin boundary: an indel
+ *      moves a mapping's start a few bases into the neighbouring bin, which then holds two candidates and keeps one, and the
+ *      bin beside it stays empty for that query.  (c) The last bin of a contig never receives a start, because no whole
+ *      fragment fits there.  ONE empty bin is therefore no evidence of absence; a run of two or more is, which is what the
+ *      min_length of fa_profile_regions is for.
+ * `maps` is a DEVICE pointer when maps_device != 0.  Runs like fa_mappings_profile. */
+int fa_mappings_reference_profile(const fa_hit_mapping *maps, int64_t n_maps, int maps_device, int32_t n_queries, int32_t n_references,
+                                  int32_t n_contigs, const int32_t *contig_bin, const int32_t *contig_genome, int32_t bin_length,
+                                  const int32_t *query_labels, const int32_t *reference_labels, const int32_t *self_reference,
+                                  float min_identity, int32_t *d_count, int64_t *d_sum, float *d_lowest, int64_t *stats /* [3] */);
+/* The records a workgroup of the reference profile's kernels takes; host only. */
+int fa_reference_profile_chunk(int32_t *records_per_workgroup);
+
+/* The regions of a profile, of either side: the maximal runs of entries that hold.  A segment is a contig: segment_offsets
+ * [n_segments + 1], a HOST array from 0 that never decreases, delimits the entries of every segment -- contig_bin on the
+ * reference side; on the query side the prefix sum of contig_length / fragment_length over the contigs of every genome.
+ * Entry i of segment s HOLDS iff count[i] >= need[s]; with below != 0, iff count[i] < need[s].  need [n_segments] is a HOST
+ * array, every value >= 0.  A region is a maximal run of holding entries inside ONE segment: runs never join across a
+ * segment boundary, and runs of fewer than min_length (>= 1) entries are dropped.  A record gives the segment, the run's
+ * first entry relative to the segment's start, its length, hits, the sum of count over the run, and sum, the sum of the
+ * fixed-point sums over it (0 with d_sum == NULL); reserved is 0.  Records come out in (segment, first) order; the same
+ * input gives the same bytes on every run.  d_count and d_sum are DEVICE pointers; `regions` is one when out_device != 0.
+ * regions == NULL only counts; n_regions may be NULL.  A `cap` below the number of records is FA_ERR_INVALID: nothing is
+ * written to regions and *n_regions holds the number needed.  FA_ERR_INVALID with nothing written anywhere: n_segments < 0,
+ * offsets that do not start at 0 or that decrease, a negative need, min_length < 1, a negative cap, NULL need or d_count
+ * where there is something to read.  More than 2^31 - 1 entries is FA_ERR_UNSUPPORTED.  Runs like fa_table_best. */
+typedef struct fa_profile_region {
+  int32_t segment;          /* the contig, as segment_offsets numbers it */
+  int32_t first;            /* first entry of the run, relative to the segment's start */
+  int32_t length;           /* entries of the run, >= min_length */
+  int32_t reserved;         /* 0 */
+  int64_t hits;             /* sum of count over the run */
+  int64_t sum;              /* sum of the fixed-point sums over the run */
+} fa_profile_region;        /* 32 bytes */
+int fa_profile_regions(const int32_t *d_count, const int64_t *d_sum, int32_t n_segments, const int64_t *segment_offsets,
+                       const int32_t *need, int below, int32_t min_length, fa_profile_region *regions, int64_t cap,
+                       int64_t *n_regions, int out_device);
+/* The entries a workgroup of the regions' kernels takes; host only. */
+int fa_profile_regions_chunk(int32_t *entries_per_workgroup);
 
 /* ---- a query x reference hit table, reduced to every query's k best hits ---- */
 /* What a batch of queries is mapped against a reference database for: per query, the closest references that pass an identity

@@ -35,6 +35,14 @@ MERGE_DTYPE = np.dtype(
 )
 assert MERGE_DTYPE.itemsize == 32
 
+# one region of a conservation profile (``fa_profile_region``): what `conservation.ReferenceProfile.regions` and
+# `conservation.FragmentProfile.regions` return.  A maximal run of ``length`` entries of contig ``segment`` from its entry
+# ``first`` on; ``hits`` is the sum of their counts, ``sum`` that of their fixed-point identity sums
+REGION_DTYPE = np.dtype(
+    [("segment", "<i4"), ("first", "<i4"), ("length", "<i4"), ("reserved", "<i4"), ("hits", "<i8"), ("sum", "<i8")]
+)
+assert REGION_DTYPE.itemsize == 32
+
 
 def pass_fragments():
     """Fragments the library maps per pass (``FA_PASS_FRAGMENTS``; 49152 by default, as in ``csrc/fa_knobs.h``).  The library

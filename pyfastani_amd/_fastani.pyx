@@ -1187,6 +1187,22 @@ cdef class Mapper(_Parameterized):
             _check(hip.fa_mapper_get_minimizers(self._hm, <uint32_t*> ph, <int32_t*> ps, <int32_t*> pw))
         return h, s, w
 
+    def reference_bins(self):
+        """``(bin_length, contig_bin, contig_genome)``: the numbering of the reference bins the mapper keeps one mapping per
+        (query genome, reference genome) for.  A mapping on contig ``c`` (``ref_seq_id``) at ``ref_start_pos`` lies in bin
+        ``contig_bin[c] + ref_start_pos // bin_length``; ``contig_bin`` is int32 ``[n_contigs + 1]`` and its last entry the
+        number of bins, ``contig_genome`` int32 ``[n_contigs]`` the reference genome of every contig.  A contig without
+        minimizer records has no bins.  What `conservation.ReferenceProfile` is keyed by."""
+        import numpy as np
+        cdef int32_t bin_length = 0
+        cdef int64_t n = 0
+        _check(hip.fa_mapper_reference_bins(self._hm, &bin_length, &n, NULL, NULL))
+        contig_bin = np.zeros(n + 1, np.int32)
+        contig_genome = np.zeros(n, np.int32)
+        cdef uintptr_t pb = contig_bin.ctypes.data, pg = contig_genome.ctypes.data
+        _check(hip.fa_mapper_reference_bins(self._hm, &bin_length, &n, <int32_t*> pb, <int32_t*> pg))
+        return int(bin_length), contig_bin, contig_genome
+
     def _state_arrays(self):
         import numpy as np
         cdef int64_t n = 0

@@ -204,6 +204,11 @@ SIGNATURES = {
     "fa_profile_summary": (_i32, [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _i32]),
     "fa_profile_chunk": (_i32, [_P(_i32), _P(_i32)]),
     "fa_debug_profile_road": (_i32, [_i32]),
+    "fa_mapper_reference_bins": (_i32, [_vp, _P(_i32), _P(_i64), _vp, _vp]),
+    "fa_mappings_reference_profile": (_i32, [_vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp]),
+    "fa_reference_profile_chunk": (_i32, [_P(_i32)]),
+    "fa_profile_regions": (_i32, [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _i64, _P(_i64), _i32]),
+    "fa_profile_regions_chunk": (_i32, [_P(_i32)]),
     "fa_table_best": (_i32, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _P(BestParams), _vp, _vp, _i64, _P(_i64), _i32, _vp]),
     "fa_screen_tile": (_i32, [_i32, _P(_i32)]),
     "fa_screen_signatures": (_i32, [_vp, _vp, _i64, _vp, _i32, _i32, _vp, _vp]),

@@ -420,6 +420,19 @@ int fa_mapper_get_minimizers(fa_mapper *m, uint32_t *hash, int32_t *seq_id, int3
     FA_HIP(hipStreamSynchronize(m->stream));
   });
 }
+int fa_mapper_reference_bins(fa_mapper *m, int32_t *bin_length, int64_t *n_contigs, int32_t *contig_bin, int32_t *contig_genome) {
+  return guarded([&] {
+    FA_REQUIRE(m && bin_length && n_contigs, FA_ERR_INVALID, "null mapper or destination");
+    std::lock_guard<std::mutex> lock(m->mtx);
+    *bin_length = std::max(m->P.fragment_length - 20, 1);                    // (build_index)
+    *n_contigs = m->C;
+    if (!contig_bin && !contig_genome) return;
+    bind_device(m->device);
+    if (contig_bin) m->contig_bin.download(contig_bin, (size_t)m->C + 1, m->stream);
+    if (contig_genome) m->contig_genome.download(contig_genome, (size_t)m->C, m->stream);
+    FA_HIP(hipStreamSynchronize(m->stream));
+  });
+}
 int fa_mapper_num_genomes(fa_mapper *m, int64_t *n) { *n = (int64_t)m->lengths.size(); return FA_OK; }
 int fa_mapper_get_state(fa_mapper *m, uint64_t *lengths, int32_t *sbf) {
   for (size_t i = 0; i < m->lengths.size(); i++) { lengths[i] = m->lengths[i]; sbf[i] = m->seqs_by_file[i]; }
@@ -586,6 +599,34 @@ int fa_debug_profile_road(int32_t road) {
   return guarded([&] {
     FA_REQUIRE(road >= 0 && road <= 2, FA_ERR_INVALID, "road 0 (the policy), 1 (global atomics) or 2 (on chip wherever it fits)");
     g_profile_road.store(road);
+  });
+}
+int fa_mappings_reference_profile(const fa_hit_mapping *maps, int64_t n_maps, int maps_device, int32_t n_queries, int32_t n_references,
+                                  int32_t n_contigs, const int32_t *contig_bin, const int32_t *contig_genome, int32_t bin_length,
+                                  const int32_t *query_labels, const int32_t *reference_labels, const int32_t *self_reference,
+                                  float min_identity, int32_t *d_count, int64_t *d_sum, float *d_lowest, int64_t *stats) {
+  return guarded([&] {
+    mappings_reference_profile(maps, n_maps, maps_device != 0, n_queries, n_references, n_contigs, contig_bin, contig_genome, bin_length,
+                               query_labels, reference_labels, self_reference, min_identity, d_count, d_sum, d_lowest, stats);
+  });
+}
+int fa_reference_profile_chunk(int32_t *records_per_workgroup) {
+  return guarded([&] {
+    FA_REQUIRE(records_per_workgroup, FA_ERR_INVALID, "null destination");
+    *records_per_workgroup = REFPROF_CHUNK;
+  });
+}
+int fa_profile_regions(const int32_t *d_count, const int64_t *d_sum, int32_t n_segments, const int64_t *segment_offsets,
+                       const int32_t *need, int below, int32_t min_length, fa_profile_region *regions, int64_t cap,
+                       int64_t *n_regions, int out_device) {
+  return guarded([&] {
+    profile_regions(d_count, d_sum, n_segments, segment_offsets, need, below != 0, min_length, regions, cap, n_regions, out_device != 0);
+  });
+}
+int fa_profile_regions_chunk(int32_t *entries_per_workgroup) {
+  return guarded([&] {
+    FA_REQUIRE(entries_per_workgroup, FA_ERR_INVALID, "null destination");
+    *entries_per_workgroup = REG_CHUNK;
   });
 }
 int fa_table_best(const fa_cgi_row *rows, int64_t n_rows, int rows_device, int32_t n_queries, int32_t n_references,

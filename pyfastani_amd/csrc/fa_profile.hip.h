@@ -74,8 +74,22 @@ __device__ __forceinline__ ProfileRecord profile_record(const int4 *maps, int64_
   return ProfileRecord{head.x, head.y, head.z, __int_as_float(tail.w)};
 }
 
+// What both profiles ask of a record -- this one and the reference-side one of fa_refprofile.hip.h, whose argument block has
+// the same n_queries, n_references, labels, self_reference and min_identity -- is written once, in the two functions below.
+// PROF_BAD_QUERY, PROF_BAD_REFERENCE and PROF_BAD_IDENTITY of a record, 0 for none
+template <typename Args>
+__device__ __forceinline__ unsigned int profile_faults(const Args &a, const ProfileRecord &m) {
+  unsigned int bad = 0;
+  if ((uint32_t)m.q >= (uint32_t)a.n_queries) bad |= PROF_BAD_QUERY;
+  if ((uint32_t)m.r >= (uint32_t)a.n_references) bad |= PROF_BAD_REFERENCE;
+  // a number in [+0, 128]: the bits of such a float are at most those of 128 (a set sign bit and every NaN lie above)
+  if ((uint32_t)__float_as_int(m.identity) > 0x43000000u) bad |= PROF_BAD_IDENTITY;
+  return bad;
+}
+
 // 0 counted, 1 dropped by labels or self, 2 below min_identity (which is asked first); the ids of `m` are in range
-__device__ __forceinline__ int profile_outcome(const ProfileArgs &a, const ProfileRecord &m) {
+template <typename Args>
+__device__ __forceinline__ int profile_outcome(const Args &a, const ProfileRecord &m) {
   if (!(m.identity >= a.min_identity)) return 2;
   if (a.query_labels && a.query_labels[m.q] != a.reference_labels[m.r]) return 1;
   if (a.self_reference && a.self_reference[m.q] == m.r) return 1;
@@ -99,12 +113,8 @@ __global__ __launch_bounds__(PROF_THREADS) void k_profile_check(ProfileArgs a) {
   for (int64_t i = lo + threadIdx.x; i < hi; i += PROF_THREADS) {
     const ProfileRecord m = profile_record(a.maps, i);
     other |= m.q != q0;
-    unsigned int bad = 0;
-    if ((uint32_t)m.q >= (uint32_t)a.n_queries) bad |= PROF_BAD_QUERY;
-    else if (m.f < 0 || (int64_t)m.f >= a.offsets[m.q + 1] - a.offsets[m.q]) bad |= PROF_BAD_FRAGMENT;
-    if ((uint32_t)m.r >= (uint32_t)a.n_references) bad |= PROF_BAD_REFERENCE;
-    // a number in [+0, 128]: the bits of such a float are at most those of 128 (a set sign bit and every NaN lie above)
-    if ((uint32_t)__float_as_int(m.identity) > 0x43000000u) bad |= PROF_BAD_IDENTITY;
+    unsigned int bad = profile_faults(a, m);
+    if (!(bad & PROF_BAD_QUERY) && (m.f < 0 || (int64_t)m.f >= a.offsets[m.q + 1] - a.offsets[m.q])) bad |= PROF_BAD_FRAGMENT;
     flags |= bad;
     if (!bad) {
       const int o = profile_outcome(a, m);

@@ -1,6 +1,7 @@
 // fa_reduce.hip.h -- the host drivers of the reductions over results the mapper already holds: a hit table to pairs,
 // clusters, representatives, average-linkage clusters and their dendrogram with its cuts, and the medoids of given clusters (fa_table.hip.h, fa_represent.hip.h, fa_linkage.hip.h, fa_medoid.hip.h), to every query's k best hits (fa_best.hip.h), the
 // fragment mappings behind a table to a per-fragment conservation profile and its per-genome summary (fa_profile.hip.h), the
+// same records to a profile by reference bin and either profile to its regions (fa_refprofile.hip.h), the
 // signature screen (fa_screen.hip.h) and its containment road (fa_contain.hip.h).  They use nothing of the sketch, the mapper or the workspace -- but for the last one, the
 // signatures of a resident batch (fa_batchsig.hip.h), which borrows a workspace for K1's staging arrays; fa_engine.hip wraps each
 // in its extern "C" entry point.
@@ -35,6 +36,7 @@
 #include "fa_order.h"
 #include "fa_profile.hip.h"
 #include "fa_query.hip.h"
+#include "fa_refprofile.hip.h"
 #include "fa_represent.hip.h"
 #include "fa_screen.hip.h"
 #include "fa_table.hip.h"
@@ -688,6 +690,155 @@ inline void profile_summary(const int32_t *d_count, const int64_t *d_sum, int32_
   hipLaunchKernelGGL(k_profile_summary, grid, dim3(PROF_THREADS), 0, st, a);
   FA_HIP(hipGetLastError());
   out_fragments.finish(st); out_hits.finish(st); out_sum.finish(st);
+  FA_HIP(hipStreamSynchronize(st));
+}
+
+// fa_mappings_reference_profile: the three accumulators are the caller's device arrays; contig_bin, contig_genome, labels and
+// self_reference host arrays (fa_refprofile.hip.h has the semantics and the road)
+inline void mappings_reference_profile(const fa_hit_mapping *maps, int64_t n_maps, bool maps_device, int32_t n_queries, int32_t n_references,
+                                       int32_t n_contigs, const int32_t *contig_bin, const int32_t *contig_genome, int32_t bin_length,
+                                       const int32_t *query_labels, const int32_t *reference_labels, const int32_t *self_reference,
+                                       float min_identity, int32_t *d_count, int64_t *d_sum, float *d_lowest, int64_t *stats) {
+  FA_REQUIRE(n_maps >= 0 && n_references >= 0 && n_queries >= 0 && n_contigs >= 0, FA_ERR_INVALID,
+             "negative number of records, queries, references or contigs");
+  FA_REQUIRE(bin_length >= 1, FA_ERR_INVALID, "bin_length must be at least 1");
+  FA_REQUIRE(contig_bin && (n_contigs == 0 || contig_genome), FA_ERR_INVALID, "null contig_bin or contig_genome");
+  FA_REQUIRE(contig_bin[0] == 0, FA_ERR_INVALID, "contig_bin must start at 0");
+  for (int32_t c = 0; c < n_contigs; c++) {
+    FA_REQUIRE(contig_bin[c + 1] >= contig_bin[c], FA_ERR_INVALID, "contig_bin must not decrease");
+    FA_REQUIRE(contig_genome[c] >= (c ? contig_genome[c - 1] : 0) && contig_genome[c] < n_references, FA_ERR_INVALID,
+               "contig_genome must not decrease and must stay inside [0, n_references)");
+  }
+  FA_REQUIRE(n_maps == 0 || maps, FA_ERR_INVALID, "null records");
+  FA_REQUIRE((query_labels != nullptr) == (reference_labels != nullptr), FA_ERR_INVALID, "query_labels and reference_labels go together");
+  FA_REQUIRE(min_identity == min_identity, FA_ERR_INVALID, "min_identity must be a number");
+  FA_REQUIRE(contig_bin[n_contigs] == 0 || (d_count && d_sum && d_lowest), FA_ERR_INVALID, "null accumulators");
+  const int64_t n_chunks = (n_maps + REFPROF_CHUNK - 1) / REFPROF_CHUNK;
+  FA_REQUIRE(n_chunks <= (int64_t)INT32_MAX, FA_ERR_UNSUPPORTED, "more than 2^31 - 1 chunks of records");
+  require_device();
+  if (!n_maps) {
+    if (stats) std::fill(stats, stats + 3, (int64_t)0);
+    return;
+  }
+  CallStream stream;
+  hipStream_t st = stream.s;
+  StatusBlock<ProfileStatus> d_status(st);
+  DevBuf<fa_hit_mapping> d_maps;
+  DevBuf<int32_t> words;          // contig_bin, contig_genome, query_labels, reference_labels, self_reference
+
+  RefProfileArgs a{};
+  a.maps = reinterpret_cast<const int4 *>(on_device(maps, maps_device, (size_t)n_maps, d_maps, st));
+  a.n_maps = n_maps; a.n_queries = n_queries; a.n_references = n_references; a.n_contigs = n_contigs;
+  a.bin_length = bin_length; a.min_identity = min_identity;
+  const size_t nq = (size_t)n_queries, nr = (size_t)n_references, nc = (size_t)n_contigs;
+  words.ensure(2 * nc + 1 + 2 * nq + nr);
+  int32_t *at = words.p;
+  const auto put = [&](const int32_t *host, size_t n) {
+    int32_t *where = at;
+    if (n) FA_HIP(hipMemcpyAsync(where, host, n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    at += n;
+    return where;
+  };
+  a.contig_bin = put(contig_bin, nc + 1);
+  a.contig_genome = put(contig_genome, nc);
+  if (query_labels) { a.query_labels = put(query_labels, nq); a.reference_labels = put(reference_labels, nr); }
+  if (self_reference) a.self_reference = put(self_reference, nq);
+  a.count = d_count; a.sum = reinterpret_cast<unsigned long long *>(d_sum); a.lowest = reinterpret_cast<unsigned int *>(d_lowest);
+  a.status = d_status.p;
+  // the verdict on the records is read before an accumulator is touched
+  hipLaunchKernelGGL(k_refprofile_check, dim3((unsigned)n_chunks), dim3(REFPROF_THREADS), 0, st, a);
+  FA_HIP(hipGetLastError());
+  const ProfileStatus checked = d_status.read(st);
+  FA_REQUIRE(!(checked.flags & PROF_BAD_QUERY), FA_ERR_INVALID, "a record names a query outside [0, n_queries)");
+  FA_REQUIRE(!(checked.flags & PROF_BAD_REFERENCE), FA_ERR_INVALID, "a record names a reference outside [0, n_references)");
+  FA_REQUIRE(!(checked.flags & PROF_BAD_CONTIG), FA_ERR_INVALID, "a record names a contig outside [0, n_contigs)");
+  FA_REQUIRE(!(checked.flags & PROF_BAD_CONTIG_GENOME), FA_ERR_INVALID, "a record's contig belongs to another reference genome");
+  FA_REQUIRE(!(checked.flags & PROF_BAD_POSITION), FA_ERR_INVALID, "a record's position is negative or outside the bins of its contig");
+  FA_REQUIRE(!(checked.flags & PROF_BAD_IDENTITY), FA_ERR_INVALID, "a record's identity is NaN, negative (-0.0 included) or above 128");
+  hipLaunchKernelGGL(k_refprofile_add, dim3((unsigned)n_chunks), dim3(REFPROF_THREADS), 0, st, a);
+  FA_HIP(hipGetLastError());
+  FA_HIP(hipStreamSynchronize(st));
+  if (stats) { stats[0] = (int64_t)checked.counted; stats[1] = (int64_t)checked.skipped; stats[2] = (int64_t)checked.below; }
+}
+
+// fa_profile_regions: d_count and d_sum are device arrays; segment_offsets and need host arrays; `regions` is a device pointer
+// with out_device
+inline void profile_regions(const int32_t *d_count, const int64_t *d_sum, int32_t n_segments, const int64_t *segment_offsets,
+                            const int32_t *need, bool below, int32_t min_length, fa_profile_region *regions, int64_t cap,
+                            int64_t *n_regions, bool out_device) {
+  check_fragment_offsets(n_segments, segment_offsets);
+  FA_REQUIRE(min_length >= 1, FA_ERR_INVALID, "min_length must be at least 1");
+  FA_REQUIRE(n_segments == 0 || need, FA_ERR_INVALID, "null need");
+  for (int32_t s = 0; s < n_segments; s++) FA_REQUIRE(need[s] >= 0, FA_ERR_INVALID, "need must not be negative");
+  const int64_t total = segment_offsets[n_segments];
+  FA_REQUIRE(total == 0 || d_count, FA_ERR_INVALID, "null count");
+  FA_REQUIRE(!regions || cap >= 0, FA_ERR_INVALID, "negative capacity");
+  FA_REQUIRE(total <= (int64_t)INT32_MAX, FA_ERR_UNSUPPORTED, "a profile of more than 2^31 - 1 entries");
+  require_device();
+  if (!total) {
+    if (n_regions) *n_regions = 0;
+    return;
+  }
+  CallStream stream;
+  hipStream_t st = stream.s;
+  StatusBlock<RegionStatus> d_status(st);
+  DevBuf<int64_t> d_offsets, offs;
+  DevBuf<int32_t> d_need, counts, runs;
+  DevBuf<unsigned long long> before;
+  DevBuf<unsigned char> temp;
+
+  RegionArgs a{};
+  a.count = d_count; a.sum = reinterpret_cast<const unsigned long long *>(d_sum);
+  d_offsets.upload(segment_offsets, (size_t)n_segments + 1, st);
+  d_need.upload(need, (size_t)n_segments, st);
+  a.offsets = d_offsets.p; a.need = d_need.p;
+  a.n_segments = n_segments; a.total = (int32_t)total; a.below = below ? 1 : 0; a.min_length = min_length;
+  const int32_t n_chunks = (int32_t)ceil_div(total, (int64_t)REG_CHUNK);
+  counts.ensure(2 * (size_t)n_chunks); offs.ensure(2 * (size_t)n_chunks);
+  a.chunk_starts = counts.p; a.chunk_ends = counts.p + n_chunks;
+  a.start_off = offs.p; a.end_off = offs.p + n_chunks;
+  hipLaunchKernelGGL(k_region_runs<false>, dim3((unsigned)n_chunks), dim3(REG_THREADS), 0, st, a);
+  hipLaunchKernelGGL(k_chunk_scan, dim3(1), dim3(1024), 0, st, a.chunk_starts, a.start_off, n_chunks, &d_status.p->starts);
+  hipLaunchKernelGGL(k_chunk_scan, dim3(1), dim3(1024), 0, st, a.chunk_ends, a.end_off, n_chunks, &d_status.p->ends);
+  FA_HIP(hipGetLastError());
+  const RegionStatus found = d_status.read(st);
+  FA_REQUIRE(found.starts == found.ends, FA_ERR_INTERNAL, "the starts and the ends of the runs do not pair up");
+  a.n_runs = found.starts;
+  int64_t n_records = 0;
+  DevBuf<int32_t> kept;
+  DevBuf<int64_t> kept_off;
+  const int32_t n_run_chunks = (int32_t)ceil_div(a.n_runs, (int64_t)REG_CHUNK);
+  if (a.n_runs) {
+    runs.ensure(3 * (size_t)a.n_runs);
+    a.run_segment = runs.p; a.run_first = runs.p + a.n_runs; a.run_last = runs.p + 2 * a.n_runs;
+    hipLaunchKernelGGL(k_region_runs<true>, dim3((unsigned)n_chunks), dim3(REG_THREADS), 0, st, a);
+    kept.ensure((size_t)n_run_chunks); kept_off.ensure((size_t)n_run_chunks);
+    a.chunk_kept = kept.p; a.kept_off = kept_off.p;
+    hipLaunchKernelGGL(k_region_emit<false>, dim3((unsigned)n_run_chunks), dim3(REG_THREADS), 0, st, a);
+    hipLaunchKernelGGL(k_chunk_scan, dim3(1), dim3(1024), 0, st, a.chunk_kept, a.kept_off, n_run_chunks, &d_status.p->regions);
+    FA_HIP(hipGetLastError());
+    n_records = d_status.read(st).regions;
+  }
+  if (n_regions) *n_regions = n_records;
+  FA_REQUIRE(!regions || n_records <= cap, FA_ERR_INVALID, "the region buffer is smaller than the number of regions");
+  if (!regions || !n_records) return;
+  // hits and sum of a run: differences of the exclusive sums of count and of sum over the whole profile
+  before.ensure(2 * (size_t)total);
+  unsigned long long *count_before = before.p, *sum_before = before.p + total;
+  with_temp(temp, [&](void *t, size_t &bytes) {
+    return rocprim::exclusive_scan(t, bytes, rocprim::make_transform_iterator(d_count, CountAsU64()), count_before, 0ULL, (size_t)total,
+                                   rocprim::plus<unsigned long long>(), st);
+  });
+  if (a.sum)
+    with_temp(temp, [&](void *t, size_t &bytes) {
+      return rocprim::exclusive_scan(t, bytes, a.sum, sum_before, 0ULL, (size_t)total, rocprim::plus<unsigned long long>(), st);
+    });
+  a.count_before = count_before; a.sum_before = sum_before;
+  Staged<fa_profile_region> out(regions, out_device, (size_t)n_records);
+  a.regions = reinterpret_cast<RegionRecord *>(out.dev());
+  hipLaunchKernelGGL(k_region_emit<true>, dim3((unsigned)n_run_chunks), dim3(REG_THREADS), 0, st, a);
+  FA_HIP(hipGetLastError());
+  out.finish(st);
   FA_HIP(hipStreamSynchronize(st));
 }
 

@@ -181,6 +181,27 @@ cdef extern from "fastani_hip.h" nogil:
     int fa_profile_chunk(int32_t* records_per_workgroup, int32_t* lds_fragments)
     int fa_debug_profile_road(int32_t road)
 
+    # the same records reduced by reference bin, and the regions of either profile (pyfastani_amd.conservation)
+    ctypedef struct fa_profile_region:
+        int32_t segment
+        int32_t first
+        int32_t length
+        int32_t reserved
+        int64_t hits
+        int64_t sum
+
+    int fa_mapper_reference_bins(fa_mapper* m, int32_t* bin_length, int64_t* n_contigs, int32_t* contig_bin, int32_t* contig_genome)
+    int fa_mappings_reference_profile(const fa_hit_mapping* maps, int64_t n_maps, int maps_device, int32_t n_queries,
+                                      int32_t n_references, int32_t n_contigs, const int32_t* contig_bin,
+                                      const int32_t* contig_genome, int32_t bin_length, const int32_t* query_labels,
+                                      const int32_t* reference_labels, const int32_t* self_reference, float min_identity,
+                                      int32_t* d_count, int64_t* d_sum, float* d_lowest, int64_t* stats)
+    int fa_reference_profile_chunk(int32_t* records_per_workgroup)
+    int fa_profile_regions(const int32_t* d_count, const int64_t* d_sum, int32_t n_segments, const int64_t* segment_offsets,
+                           const int32_t* need, int below, int32_t min_length, fa_profile_region* regions, int64_t cap,
+                           int64_t* n_regions, int out_device)
+    int fa_profile_regions_chunk(int32_t* entries_per_workgroup)
+
     # a query x reference hit table reduced to every query's k best hits (pyfastani_amd.classify)
     ctypedef struct fa_best_params:
         float min_fraction

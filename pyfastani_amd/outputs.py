@@ -262,3 +262,52 @@ def write_fragment_profile(path, names, count, sum, lowest, contig_lengths, frag
                 values = (f"{int(sum[at]) / c / 2.0 ** 20:.6g}", f"{float(lowest[at]):.6g}") if c else ("NA", "NA")
                 f.write(f"{name}\t{int(contig[k])}\t{int(offset[k])}\t{int(offset[k]) + int(fragment_length)}\t{c}\t{values[0]}\t{values[1]}\n")
                 at += 1
+
+
+def write_reference_profile(path, names, profile):
+    """A `pyfastani_amd.conservation.ReferenceProfile` as a tab-separated table, one line per reference bin in profile order
+    under a header line naming the columns (`PROFILE_COLUMNS`): the reference genome, the bin's contig numbered inside its
+    genome, start (``bin * bin_length``) and end (start + ``bin_length``) on it, the number of counted records, and their mean
+    (``sum / count / 2**20``) and lowest identity -- ``NA`` for both where the count is 0.  ``profile`` is anything with
+    ``bin_length``, ``contig_bin``, ``contig_genome``, ``count``, ``sum`` and ``lowest`` (numpy or tensors)."""
+    count, sum, lowest = (x.cpu().numpy() if hasattr(x, "cpu") else np.asarray(x) for x in (profile.count, profile.sum, profile.lowest))
+    contig_bin, contig_genome = np.asarray(profile.contig_bin, dtype=np.int64), np.asarray(profile.contig_genome, dtype=np.int64)
+    bin_length = int(profile.bin_length)
+    if len(contig_bin) != len(contig_genome) + 1 or not (len(count) == len(sum) == len(lowest) == int(contig_bin[-1])):
+        raise ValueError("the profile holds one entry per bin of the contigs")
+    if len(contig_genome) and not 0 <= int(contig_genome.min()) <= int(contig_genome.max()) < len(names):
+        raise ValueError("one name per reference genome")
+    first_contig = np.searchsorted(contig_genome, np.arange(len(names)))       # the first contig of every genome
+    with open(path, "w") as f:
+        f.write("\t".join(PROFILE_COLUMNS) + "\n")
+        for c, genome in enumerate(contig_genome.tolist()):
+            for at in range(int(contig_bin[c]), int(contig_bin[c + 1])):
+                n, start = int(count[at]), (at - int(contig_bin[c])) * bin_length
+                values = (f"{int(sum[at]) / n / 2.0 ** 20:.6g}", f"{float(lowest[at]):.6g}") if n else ("NA", "NA")
+                f.write(f"{names[genome]}\t{c - int(first_contig[genome])}\t{start}\t{start + bin_length}\t{n}\t{values[0]}\t{values[1]}\n")
+
+
+REGION_COLUMNS = ("genome", "contig", "start", "end", "entries", "hits", "mean_identity")
+
+
+def write_regions(path, names, regions, segment_genome, segment_contig, unit, offset=0):
+    """The regions of a profile (`conservation.ReferenceProfile.regions`, `conservation.FragmentProfile.regions`) as a
+    BED-like tab-separated table, one line per region in the order given under a header line naming the columns
+    (`REGION_COLUMNS`).  ``segment_genome[s]`` and ``segment_contig[s]`` are the genome (an index into ``names``) and the
+    contig's number inside it of segment ``s``; ``unit`` is the length of an entry in bases -- ``bin_length`` on the reference
+    side, the fragment length on the query side --, so a region covers ``[offset + first * unit, offset + (first + length) *
+    unit)`` of its contig, half open.  ``entries`` is the region's length in entries, ``hits`` the sum of their counts, and
+    ``mean_identity`` ``sum / hits / 2**20``, ``NA`` where ``hits`` is 0 (a region of absence)."""
+    if int(unit) < 1:
+        raise ValueError("unit must be positive")
+    if len(segment_genome) != len(segment_contig):
+        raise ValueError("one genome and one contig number per segment")
+    with open(path, "w") as f:
+        f.write("\t".join(REGION_COLUMNS) + "\n")
+        for r in regions:
+            s, first, length, hits = int(r["segment"]), int(r["first"]), int(r["length"]), int(r["hits"])
+            if not 0 <= s < len(segment_genome):
+                raise ValueError("a region names a segment outside the segments given")
+            start = int(offset) + first * int(unit)
+            mean = f"{int(r['sum']) / hits / 2.0 ** 20:.6g}" if hits else "NA"
+            f.write(f"{names[int(segment_genome[s])]}\t{int(segment_contig[s])}\t{start}\t{start + length * int(unit)}\t{length}\t{hits}\t{mean}\n")
