@@ -1812,7 +1812,9 @@ __global__ __launch_bounds__(L1_BIG_THREADS) void k_l1_big(L1Args a) {
 //   k_l2_events one workgroup per fragment.  Prologue, one lane per locus: searchIndex(rangeStart) as a bounded binary
 //               search, the other two searchIndex() calls as rec_fwd lookups, the event count; the workgroup reserves
 //               its slice of the event buffer with one atomicAdd (the order of fragments is irrelevant).  Then one
-//               wave per locus: every reference record is reduced to its rank in the query sketch (bucket table + 2-3
+//               wave per locus, the loci handed to the waves in order from a counter in LDS and their ranges taken from
+//               LDS where the prologue left them:
+//               every reference record is reduced to its rank in the query sketch (bucket table + 2-3
 //               LDS probes, sketch staged once per fragment) and written as one or two *events* (admit / drop) at
 //               its position in the time-ordered event stream, which is plain arithmetic on rec_bwd / rec_fwd;
 //   k_l2_scan   one lane per locus: the sequential slide is a fixed-trip, branch-free loop over the event stream (one
@@ -1954,15 +1956,21 @@ __global__ __launch_bounds__(EV_THREADS, EV_WAVES_PER_SIMD) void k_l2_events(L2A
   // ---- record range of every locus (the three searchIndex calls of computeL2MappedRegions) and its event count ----
   __shared__ uint32_t sh_wave[EV_THREADS / 64];
   __shared__ uint32_t sh_run, sh_base, sh_ok;
+  __shared__ uint32_t sh_next;                                         // the next locus of the fragment to hand to a wave (the locus loop)
+  // descriptors of the first EV_LOCI_LDS loci, kept for the locus loop: (beg, end0, last, ndrop) and the offset of the locus inside
+  // the fragment's events -- what the global arrays hold too (k_l2_order, k_l2_scan and the diagnostics read those)
+  __shared__ __align__(16) int4 sh_locus[EV_LOCI_LDS];
+  __shared__ uint32_t sh_rel[EV_LOCI_LDS];
   __shared__ unsigned long long sh_records;
   __shared__ uint32_t sh_class[SCAN_CLASSES];                          // loci of this fragment per length class (scan_order)
-  if (threadIdx.x == 0) { sh_run = 0; sh_records = 0; }
+  if (threadIdx.x == 0) { sh_run = 0; sh_records = 0; sh_next = 0; }
   if (threadIdx.x < SCAN_CLASSES) sh_class[threadIdx.x] = 0;
   __syncthreads();
   const int32_t *wpos = a.ix.rec_wpos;
   for (uint32_t c0 = 0; c0 < l_n; c0 += EV_THREADS) {
     const uint32_t l = l_lo + c0 + threadIdx.x;
     uint32_t nev = 0, records = 0;
+    int4 desc = make_int4(0, 0, 0, 0);
     if (c0 + threadIdx.x < l_n) {
       const int lo = a.ix.contig_rec[a.l_seq[l]];
       // searchIndex(seqId, rangeStartPos): rangeStartPos <= wpos of the first seed and wpos is strictly increasing, so
@@ -1993,6 +2001,7 @@ __global__ __launch_bounds__(EV_THREADS, EV_WAVES_PER_SIMD) void k_l2_events(L2A
       // the slide stops at the window position where the last record is admitted; the records dropped by then are
       // the ones before the record active at that position
       const int ndrop = last > end0 ? a.ix.rec_bwd[last - 1] - beg : 0;
+      desc = make_int4(beg, end0, last, ndrop);
       a.l_beg[l] = beg; a.l_end0[l] = end0; a.l_last[l] = last; a.l_ndrop[l] = ndrop;
       // the first super-window is padded to whole 8-event groups: k_l2_scan applies it in bulk, without the pivot logic
       nev = (uint32_t)((((end0 - beg + 7) & ~7) + (last - end0) + ndrop + 7) & ~7);
@@ -2010,7 +2019,10 @@ __global__ __launch_bounds__(EV_THREADS, EV_WAVES_PER_SIMD) void k_l2_events(L2A
     __syncthreads();
     uint32_t off = sh_run + incl - nev;
     for (int q = 0; q < wv; q++) off += sh_wave[q];
-    if (c0 + threadIdx.x < l_n) a.l_ioff[l] = off;           // relative to the fragment for now
+    if (c0 + threadIdx.x < l_n) {
+      a.l_ioff[l] = off;                                     // relative to the fragment for now
+      if (c0 + threadIdx.x < (uint32_t)EV_LOCI_LDS) { sh_locus[c0 + threadIdx.x] = desc; sh_rel[c0 + threadIdx.x] = off; }
+    }
     __syncthreads();
     if (threadIdx.x == 0) { uint32_t tot = 0; for (int q = 0; q < EV_THREADS / 64; q++) tot += sh_wave[q]; sh_run += tot; }
     __syncthreads();
@@ -2042,14 +2054,17 @@ __global__ __launch_bounds__(EV_THREADS, EV_WAVES_PER_SIMD) void k_l2_events(L2A
     for (uint32_t i = threadIdx.x; i < l_n; i += EV_THREADS) a.l_nev[l_lo + i] = 0;
     return;
   }
-  // The waves of the workgroup take the loci of the fragment round-robin; a wave goes through a locus in *trips* of
-  // 64 x EV_RPL records (EV_RPL per lane): first the records of the first super-window, then the later ones, then the
-  // stream is copied out.  (Measured and left out: issuing the reads of the next trip before working on the current one,
+  // The waves of the workgroup take the loci of the fragment one at a time from a counter in LDS (sh_next): whichever wave is
+  // free takes the next one, so the workgroup does not wait for the wave that a fixed deal (l += 4) had given the longest streams
+  // or a locus more than the others.  In numbering order, not longest first: the neighbouring workgroups stream the same
+  // stretches of the index at the same time (frag_order, one_genome_frag), and in order they stay together.  The descriptor of
+  // a locus comes from LDS, where the head left it (the first EV_LOCI_LDS loci; the global arrays behind them): no trip to the
+  // L2 cache in front of every locus.  A wave goes through a locus in *trips* of 64 x EV_RPL records (EV_RPL per lane): first
+  // the records of the first super-window, then the later ones, then the stream is copied out.
+  // (Measured and left out: issuing the reads of the next trip before working on the current one,
   // two register sets swapping roles, and fetching the ranges of the next locus a locus ahead -- 187 -> 187..195 us; the
   // kernel was held to be HBM-bound then; it is bound by its vector issue slots, profiles/EXPERIMENTS.md.)
-  const uint32_t l_end = l_lo + l_n;
-  uint32_t l = l_lo + wv;
-  if (l >= l_end) return;                                            // (no workgroup barrier below this line)
+  const uint32_t l_end = l_lo + l_n;                                 // (no workgroup barrier below this line)
   struct Locus { int beg, end0, last, ndrop; uint32_t ioff; };
   auto fetch_locus = [&](uint32_t lx) __attribute__((always_inline)) {        // unconditional loads from a clamped index
     const uint32_t lc = min(lx, l_end - 1);
@@ -2211,9 +2226,20 @@ __global__ __launch_bounds__(EV_THREADS, EV_WAVES_PER_SIMD) void k_l2_events(L2A
     }
   };
 
-  for (; l < l_end; l += EV_THREADS / 64) {
-    const Locus cur = uniform(fetch_locus(l));
-    __builtin_amdgcn_wave_barrier();                                 // (the relative offset has been read: begin_locus overwrites it)
+  for (;;) {
+    uint32_t li = 0;
+    if (lane == 0) li = atomicAdd(&sh_next, 1u);                     // (a wave that finds none left just ends: nothing waits for it)
+    li = (uint32_t)__builtin_amdgcn_readfirstlane((int)li);
+    if (li >= l_n) break;
+    const uint32_t l = l_lo + li;
+    Locus cur;
+    if (li < (uint32_t)EV_LOCI_LDS) {
+      const int4 d = sh_locus[li];
+      cur = uniform(Locus{d.x, d.y, d.z, d.w, sh_rel[li]});
+    } else {
+      cur = uniform(fetch_locus(l));
+      __builtin_amdgcn_wave_barrier();                               // (the relative offset has been read: begin_locus overwrites it)
+    }
     const Stream st = begin_locus(cur, l);
     auto run = [&](auto store) __attribute__((always_inline)) {
       Trip t;

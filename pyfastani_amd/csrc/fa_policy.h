@@ -39,6 +39,9 @@ constexpr int LOCI_REGIONS = 64;
 constexpr int EV_REGIONS = 64;
 // rank bits of the 16-bit slide event (EvBits<uint16_t>): sketches up to 510 minimizers; larger ones take the wide events
 constexpr int EV_RANK16 = 9;
+// loci of one fragment whose descriptors (record range, drops, offset in the fragment's events) k_l2_events keeps in LDS between
+// its head and its locus loop; the loci behind them are read back from the global arrays (the bench: about 55 per fragment)
+constexpr int EV_LOCI_LDS = 64;
 
 // Pass-level speculation.  A query pass is launched without intermediate host synchronisation, sized by what earlier
 // passes needed (largest sketch, LDS seed slots, HBM seed scratch, loci and event capacities).  Kernels check those

@@ -33,6 +33,7 @@ PATTERNS = [
     (r"slide_chain.*\.txt$|slide_occupancy\.txt$", "bash scripts/run_ubench.sh; scripts/ubench/slide_chain <events> <sketch>", "the slide on synthetic event streams (cycles per event; at 2-6 resident waves per SIMD)"),
     (r"config5_cells\.json$|config[34].*\.json$", "python scripts/run_config45.py / run_config5_cells.py", "BASELINE configs 3-5 by the stand-alone runners"),
     (r"scan_first_window\.txt$", "—", "raw bench lines, kernel averages and `SQ_INSTS_VALU` behind \"The first window of the scan\" (profiles/EXPERIMENTS.md)"),
+    (r"events_head\.txt$", "—", "raw bench lines, kernel averages and counters behind \"The head and the locus loop of k_l2_events\" (profiles/EXPERIMENTS.md)"),
     (r"table_drivers_timing\.json$", "python scripts/time_table_drivers.py <out> <parent run> <branch run> <parent run> <branch run>", "scripts/time_{clusters,representatives,linkage,dendrogram,medoids}.py on the parent commit and on the commit that split the table drivers, alternating: every median, and each branch median against the parent's two widened by their spread"),
     (r"concurrent_clients\.json$|query_draft\.json$|many_relatives.*|two_streams\.json$|boundary_zero_copy\.txt$", "scripts/time_*.py", "one-off timings named by the file"),
 ]
