@@ -1,6 +1,6 @@
 """Differential fuzzing of the HIP path against the CPU oracle: random genomes with planted repeats, tandem
 duplications, inversions, N runs and low-complexity stretches; random parameters.  Every L2 mapping and every hit must
-match.  Usage: python scripts/fuzz_parity.py [--rules l2_confidence=0.75,slide_end=fragment,cgi_ties=largest] [--history | --domain | --contigs] [cases] [seed] [seconds] [default-cell]   (stops after `seconds` if given: a
+match.  Usage: python scripts/fuzz_parity.py [--rules l2_confidence=0.75,slide_end=fragment,cgi_ties=largest] [--history | --domain | --contigs | --kmers] [cases] [seed] [seconds] [default-cell]   (stops after `seconds` if given: a
 time box; a fourth argument keeps every nucleotide case in the default cell k = 16 / fragment 3000 / 80 % with queries of plain
 ACGT -- the cell whose query passes run K1 and the fragment sketch as ONE launch, k_query_fused).  --history: one index per
 case, then 4-8 queries drawn from the generators (plain, tandem, drafts, N / IUPAC, batches) on the SAME mapper, each through
@@ -9,7 +9,10 @@ oracle: a mapper's speculation record carries the sizes and kernel forms of one 
 the window range -- percentage_identity from 64.5-70 (w = 2-4) and 96-100 (sketches of a handful of records), p_value from
 1e-1 to 1e-12, k from 5 to 33.  --contigs: references and queries cut into 1-400 contigs by tests/contig_domain.py's cut_at at the
 case's own critical lengths (0, 1, k - 1 ... k + w + 1, cmw, fragment - 1 / + 0 / + 1, two fragments, the tile seams), half of the genomes with repeats inside
-their contigs (plant_repeats), with a 30 % chance each of a genome without a contig and of a genome of contigs too short for a record; batches as in the default mode."""
+their contigs (plant_repeats), with a 30 % chance each of a genome without a contig and of a genome of contigs too short for a record; batches as in the default mode.
+--kmers: k from the critical list of tests/kmer_domain.py (KS, 1 to 2048) and from 1..64, an EXPLICIT window from its WS (one per form of K1; the recommended
+window is the fragment itself from about k = 22 on), genomes by the rules of that module's end-to-end cells: 12 kb within 0.4 % up to k = 7, 40 kb
+within 0.4 % up to k = 100, 40 kb within 0.03 % beyond, where the fragment grows to 5000 once k + w leaves fewer than 500 windows in 3000."""
 import sys, os, ctypes as C, warnings, time, tempfile
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -90,6 +93,11 @@ if contig_mode:
     # the generator lives beside the tests that share it; the other modes do not need it
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
     import contig_domain as cd
+kmer_mode = "--kmers" in sys.argv
+if kmer_mode:
+    sys.argv.remove("--kmers")
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import kmer_domain as kd
 cases = int(sys.argv[1]) if len(sys.argv) > 1 else 50
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 time_box = float(sys.argv[3]) if len(sys.argv) > 3 else 0.0
@@ -266,6 +274,46 @@ def contigs_case(g, case):
         print("   only gpu", sorted(sg - so)[:4], "only oracle", sorted(so - sg)[:4])
     return ok
 
+def kmers_case(g, case):
+    """One (k, w) with an explicit window; one query through query_draft (hits, every L2 mapping, index size, threshold) or,
+    every fourth case, two queries as a resident batch.  None: the oracle maps nothing."""
+    k = int(g.choice(kd.KS)) if g.random() < 0.5 else int(g.integers(1, 65))
+    # (windows 1 and 2 at small k: every fragment would gather more than 8 192 seed hits inside one contig, the oversized-seed
+    # road that tests/kmer_domain.py keeps its cells away from)
+    w = int(g.choice([x for x in kd.WS if x >= (4 if k < 10 else 1)]))
+    frag = 3000 if k + w + 500 <= 3000 else 5000
+    length = 12_000 if k <= 7 else 40_000
+    divergences = [0.001, 0.004, 0.002] if k <= 100 else [0.0, 0.0001, 0.0003]
+    sk, osk = kd.sketch_pair(k, w, frag, float(g.choice([0.0, 0.2])), rules=RULES)
+    anc = syn.random_codes(g, length)
+    refs = [[bytes(x) for x in syn.split_contigs(g, syn.to_ascii(syn.mutate_codes(g, anc, d)), int(g.integers(1, 4)))] for d in divergences[: int(g.integers(1, 4))]]
+    if g.random() < 0.5:
+        refs.append([bytes(syn.to_ascii(syn.random_codes(g, length // 2)))])
+    for i, contigs in enumerate(refs):
+        sk.add_draft(i, contigs); osk.add_draft(i, contigs)
+    mapper = sk.index(); osk.index()
+    ok = len(mapper.lookup_index) == osk.index_size and mapper.occurences_threshold == osk.freq_threshold
+    dq = divergences[1] if k > 100 else 0.003
+    queries = [[bytes(x) for x in syn.split_contigs(g, syn.to_ascii(syn.mutate_codes(g, anc, dq)), int(g.integers(1, 4)))] for _ in range(2 if case % 4 == 0 else 1)]
+    if len(queries) > 1:
+        got = [hit_list(hs) for hs in mapper.upload_genomes(queries).query()]
+        want = [osk.query_draft(q, threads=8) for q in queries]
+        if not (ok and got == want):
+            print(f"MISMATCH kmers batch case {case} seed {seed} k {k} w {w} fragment {frag}: {got} vs {want}")
+            return False
+        return True if any(want) else None
+    hits = hit_list(mapper.query_draft(queries[0]))
+    ohits, det = osk.query_draft(queries[0], threads=8, details=True)
+    om = det["mappings"]
+    omm = sorted(zip(om["qseq"].tolist(), om["rseq"].tolist(), om["rstart"].tolist(), om["sketch"].tolist(), om["shared"].tolist()))
+    gm = mappings(mapper)
+    if not (ok and hits == ohits and gm == omm):
+        print(f"MISMATCH kmers case {case} seed {seed} k {k} w {w} fragment {frag}: hits {hits} vs {ohits}; mappings gpu {len(gm)} oracle {len(omm)}")
+        sg, so = set(gm), set(omm)
+        print("   only gpu", sorted(sg - so)[:4], "only oracle", sorted(so - sg)[:4])
+        return False
+    return True if ohits else None
+
 for case in range(cases):
     if time_box and time.time() - t0 > time_box:
         break
@@ -279,6 +327,13 @@ for case in range(cases):
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")
             res = contigs_case(g, case)
+        degenerate += res is None
+        bad += res is False
+        continue
+    if kmer_mode:
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            res = kmers_case(g, case)
         degenerate += res is None
         bad += res is False
         continue
