@@ -76,6 +76,8 @@ def lib():
         L.fo_num_minimizers.restype = i64
         L.fo_num_minimizers.argtypes = [vp]
         L.fo_get_minimizers.argtypes = [vp, vp, vp, vp]
+        L.fo_set_state.restype = None
+        L.fo_set_state.argtypes = [vp, i64, vp, vp, i64, i64, vp, vp, vp]
         L.fo_sketch_sequence.restype = i64
         L.fo_sketch_sequence.argtypes = [vp, vp, i64, i32, vp, vp, i64]
         L.fo_index.argtypes = [vp]
@@ -179,6 +181,21 @@ class OracleSketch:
         w = np.empty(n, np.int32)
         lib().fo_get_minimizers(self._h, h.ctypes.data, s.ctypes.data, w.ctypes.data)
         return h, s, w
+
+    def set_state(self, names, lengths, sequences_by_file, counter, hashes, seq_ids, wpos):
+        """Replace the content of the sketch by a saved state -- what `pyfastani_amd.Sketch.__setstate__` takes, as arrays:
+        genome names and lengths, `sequencesByFileInfo`, the contig counter and the minimizer records.  `index()` and
+        everything behind it then work as after `add_draft`."""
+        lengths = np.ascontiguousarray(lengths, dtype=np.uint64)
+        sbf = np.ascontiguousarray(sequences_by_file, dtype=np.int32)
+        h = np.ascontiguousarray(hashes, dtype=np.uint32)
+        s = np.ascontiguousarray(seq_ids, dtype=np.int32)
+        w = np.ascontiguousarray(wpos, dtype=np.int32)
+        assert len(lengths) == len(sbf) == len(names) and len(h) == len(s) == len(w)
+        lib().fo_set_state(self._h, len(lengths), lengths.ctypes.data, sbf.ctypes.data, int(counter), len(h), h.ctypes.data,
+                           s.ctypes.data, w.ctypes.data)
+        self.names = list(names)
+        return self
 
     def sketch_sequence(self, seq):
         b = _as_bytes(seq)

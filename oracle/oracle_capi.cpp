@@ -63,6 +63,24 @@ void fo_get_minimizers(void *hh, uint32_t *hash, int32_t *seq, int32_t *wpos) {
   const auto &v = ((OracleHandle *)hh)->sk.minimizerIndex;
   for (size_t i = 0; i < v.size(); i++) { hash[i] = v[i].hash; seq[i] = v[i].seqId; wpos[i] = v[i].wpos; }
 }
+// the saved state of a sketch replaces its content (the pickled state of the reference's Sketch, _fastani.pyx:572-591): records
+// that came from no sequence -- tests/planted.py -- go in this way.  The lookup index is cleared and the threshold reset: fo_index
+void fo_set_state(void *hh, int64_t n_genomes, const uint64_t *lengths, const int32_t *sequences_by_file, int64_t counter, int64_t n,
+                  const uint32_t *hash, const int32_t *seq, const int32_t *wpos) {
+  OracleHandle *h = (OracleHandle *)hh;
+  Sketch &sk = h->sk;
+  sk.minimizerIndex.resize((size_t)n);
+  for (int64_t i = 0; i < n; i++) sk.minimizerIndex[(size_t)i] = MinimizerInfo{hash[i], seq[i], wpos[i]};
+  sk.lengths.assign(lengths, lengths + n_genomes);
+  sk.sequencesByFileInfo.assign(sequences_by_file, sequences_by_file + n_genomes);
+  sk.counter = (size_t)counter;
+  sk.cur_total = 0;
+  sk.minimizerPosLookupIndex.clear();
+  sk.minimizerFreqHistogram.clear();
+  sk.freqThreshold = INT_MAX;
+  h->indexed = false;
+  h->last_hits.clear(); h->last_mappings.clear(); h->last_rows.clear();
+}
 // minimizers of one stand-alone sequence (query-fragment mode: seqId 0, fresh output)
 int64_t fo_sketch_sequence(void *hh, const void *data, int64_t len, int width, uint32_t *hash, int32_t *wpos, int64_t cap) {
   const Parameters &p = ((OracleHandle *)hh)->sk.param;
